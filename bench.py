@@ -21,10 +21,19 @@ q-tile windows of whole workgroup rounds and the all-gather of window i's rows r
 (liteattention_amd/parallel.py); --overlap-windows 1 is the plain "kernel, then one all-gather" step.
 
 `value` = executed TFLOP/s of the whole job = FLOPs of the LISTED tiles (4*rows*cols*D per tile, summed
-over all ranks) / step time; skipped tiles are never counted as work. The same JSON line carries the
-1-GPU sparsity sweep (0/21/42/57/77 %: ms, executed and dense-equivalent TFLOP/s, t(s)/t(0)), the MFMA
-roofline of the forward kernel (HIP-event kernel time) and the CPU baseline (the oracle port timed on the
-host cores on a bounded sample of the same workload).
+over all ranks) / step time; skipped tiles are never counted as work. The line also carries the MFMA roofline
+of the forward kernel (HIP-event kernel time of the timed steps).
+
+A plain run sets up, runs the W warm-up steps, times the K steps and prints the line; nothing else. With
+--full the same line also carries everything measured or checked beside the headline: the sampled-row check
+of the timed configuration (`verified`), the power / clock sample, the 1-GPU sparsity sweep (0/21/42/57/77 %:
+ms, executed and dense-equivalent TFLOP/s, t(s)/t(0)), the fp8 / other-head-dim / dense / 50-step / half-vote /
+text + video sub-records and the CPU baseline (the oracle port timed on the host cores on a bounded sample of
+the same workload); the --no-* options switch single parts of --full off.
+
+--dump-outputs DIR writes the output the last timed step returned to its caller (B, S, H, D) as DIR/out.npy in
+float32; above 64 MB it is a fixed, seeded sample of whole query rows, whose indices go to DIR/out_rows.npy.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -232,17 +241,21 @@ def agree_on_overlapped_form(att, qkv, dist, dev, sync):
     return None
 
 
-def timed_steps(att, qkv, n_steps, n_warmup, barrier, dist, dev, make_event):
+def timed_steps(att, qkv, n_steps, n_warmup, barrier, dist, dev, make_event, keep_last=None):
     """W untimed steps, then exactly K steps between two barriers (+ device sync inside `barrier`); MAX over ranks of the wall time.
-    Returns (seconds per step, kernel seconds per step by events on the launch stream)."""
+    Returns (seconds per step, kernel seconds per step by events on the launch stream). `keep_last`: a list that receives what the
+    last timed step returned."""
     for _ in range(n_warmup):
         att(*qkv)
     ev = [(make_event(), make_event()) for _ in range(n_steps)]
     barrier()
     t0 = time.perf_counter()
-    for i in range(n_steps):
+    for i in range(n_steps - 1):
         att(*qkv, _kernel_events=ev[i])
+    out = att(*qkv, _kernel_events=ev[-1])     # only the last result is kept: every step reuses the block its predecessor freed
     barrier()
+    if keep_last is not None:
+        keep_last.append(out)
     dt = time.perf_counter() - t0
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / n_steps
     if dist is not None:
@@ -250,6 +263,29 @@ def timed_steps(att, qkv, n_steps, n_warmup, barrier, dist, dev, make_event):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     return dt / n_steps, kern_ms / 1e3
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname, budget=DUMP_BYTES):
+    """--dump-outputs: `out` (B, S, H, D), what the last timed step gave its caller, as DIR/out.npy in float32. Above `budget` (3/4 of it
+    with headroom for the index file) a fixed sample of whole query rows is written instead: rows drawn by a seed-0 CPU generator, so
+    the sample is the same in every run of the same arguments; their indices go to DIR/out_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    B, S, H, D = out.shape
+    for name in ("out.npy", "out_rows.npy"):                      # nothing of an earlier run with other arguments stays beside it
+        if os.path.exists(os.path.join(dirname, name)):
+            os.remove(os.path.join(dirname, name))
+    if out.numel() * 4 <= budget:
+        np.save(os.path.join(dirname, "out.npy"), out.float().cpu().numpy())
+        return
+    n = max(1, min(S, (budget * 3 // 4) // (B * H * D * 4)))
+    rows = torch.randperm(S, generator=torch.Generator().manual_seed(0))[:n].sort().values
+    sample = out.index_select(1, rows.to(out.device))
+    np.save(os.path.join(dirname, "out.npy"), sample.float().cpu().numpy())
+    np.save(os.path.join(dirname, "out_rows.npy"), rows.double().numpy())
 
 
 def multi_gpu_record(dist, dev, kern_s, att, q, out_bytes_per_elem=2):
@@ -583,13 +619,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seqlen", type=int, default=75600)
     ap.add_argument("--heads", type=int, default=40)
-    ap.add_argument("--no-sweep", action="store_true", help="skip the 1-GPU sparsity sweep")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp8", action="store_true", help="skip the fp8 (configs[4]) sub-record of the 1-GPU bf16 line")
-    ap.add_argument("--no-verify", action="store_true", help="skip the sampled-row check after the timed loop")
-    ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi power / clock sample")
-    ap.add_argument("--no-head-dims", action="store_true", help="skip the head_dim 64 / 96 / 192 / 256 sub-record of the 1-GPU bf16 line")
-    ap.add_argument("--no-denoise", action="store_true", help="skip the 50-step denoising run (BASELINE.json configs[2]) of the 1-GPU bf16 line")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every check and sub-record of the line (sampled-row check, power sample, sparsity sweep, "
+                         "fp8, other head dims, dense S=32768, 50-step runs, half vote, text + video recipe, CPU baseline); off: the plain "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/out.npy (float32; a fixed, seeded sample "
+                         "of whole query rows above 64 MB, their indices in DIR/out_rows.npy)")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip the 1-GPU sparsity sweep")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fp8", action="store_true", help="--full: skip the fp8 (configs[4]) sub-record of the 1-GPU bf16 line")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the sampled-row check after the timed loop")
+    ap.add_argument("--no-power", action="store_true", help="--full: skip the rocm-smi power / clock sample")
+    ap.add_argument("--no-head-dims", action="store_true", help="--full: skip the head_dim 64 / 96 / 192 / 256 sub-record of the 1-GPU bf16 line")
+    ap.add_argument("--no-denoise", action="store_true", help="--full: skip the 50-step denoising run (BASELINE.json configs[2]) of the 1-GPU bf16 line")
     ap.add_argument("--prewarm-steps", type=int, default=0,
                     help="untimed steps of the timed configuration BEFORE the W warm-up steps (outside the contract's warm-up and timed region): the socket is at "
                          "its power cap and the clock the first steps after start-up run at is 1-3 %% below the sustained one (round 5: the 20 steps after 3 warm-ups "
@@ -600,6 +643,7 @@ def main():
     ap.add_argument("--dtype", choices=["bf16", "fp16", "fp8"], default="bf16",
                     help="bf16 = headline (BASELINE.json configs[2,3]); fp8 = configs[4] (e4m3 Q/K/V, bf16 out)")
     args = ap.parse_args()
+    full = args.full
 
     # LA_BENCH_FORCE_DIST=1: run the N > 1 code path (process group, trial step, overlapped all-gather, agreement
     # all-reduce) on ONE rank too - a 1-rank RCCL all-gather is a copy on RCCL's stream. For exercising this file on a 1-GPU box.
@@ -649,8 +693,9 @@ def main():
             dist.barrier()
         device_sync()
 
-    def run_dtype(dtype_name, steps, warmup, sweep, distributed):
-        """Headline measurement (+ optional sparsity sweep, + verification) for one input dtype on this rank's heads."""
+    def run_dtype(dtype_name, steps, warmup, sweep, distributed, keep_last=None):
+        """Headline measurement (+ with --full: verification, power sample, optional sparsity sweep) for one input dtype on this rank's
+        heads. `keep_last`: a list that receives what the last timed step returned."""
         fp8 = dtype_name == "fp8"
         peak = MFMA_FP8_PEAK_TFLOPS if fp8 else MFMA_BF16_PEAK_TFLOPS
         q, k, v = [x.to(torch.float8_e4m3fn) for x in qkv_bf16] if fp8 else ([x.half() for x in qkv_bf16] if dtype_name == "fp16" else qkv_bf16)
@@ -674,8 +719,8 @@ def main():
             impose_lists(att.local, rows)
             return rows
 
-        def timed(n_steps, n_warmup):
-            return timed_steps(att, (q, k, v), n_steps, n_warmup, barrier, use_dist, dev, new_event)
+        def timed(n_steps, n_warmup, keep_last=None):
+            return timed_steps(att, (q, k, v), n_steps, n_warmup, barrier, use_dist, dev, new_event, keep_last)
 
         # ---- headline: 42 % imposed sparsity
         rows = set_sparsity(HEADLINE_SPARSITY)
@@ -685,7 +730,7 @@ def main():
         flops_rank = executed_flops(rows, Hl, B, S, S, bm, bn, D)
         for _ in range(max(0, args.prewarm_steps)):          # the same number on every rank (the step may hold a collective)
             att(q, k, v)
-        step_s, kern_s = timed(steps, warmup)
+        step_s, kern_s = timed(steps, warmup, keep_last)
         flops_job = flops_rank * world
         listed_frac = listed_tiles_of_rows(rows) / (q_tiles * k_tiles)
         kernel_name = ("la_prep_v_fp8_kernel + la_fwd_x64_fp8_kernel<true>" if fp8 else
@@ -727,7 +772,7 @@ def main():
             res["multi_gpu"] = multi_gpu_record(dist, dev, kern_s, att, q)
 
         # ---- correctness gate on the timed configuration: sampled rows vs an fp32 torch reference with the same block mask
-        if not args.no_verify:
+        if full and not args.no_verify:
             try:
                 rows42 = set_sparsity(HEADLINE_SPARSITY)
                 read_list = att.local._skip_list[att.local._phase].clone()
@@ -752,7 +797,7 @@ def main():
             res["verified"] = ver
 
         # ---- package power / clock under the timed configuration (1 GPU only; about a second)
-        if use_dist is None and seam is None and not args.no_power:
+        if full and use_dist is None and seam is None and not args.no_power:
             try:
                 set_sparsity(HEADLINE_SPARSITY)
                 n_q = max(8, int(1.2 / max(step_s, 1e-4)))
@@ -788,9 +833,16 @@ def main():
         return res
 
     # (the stand-in seam of the CPU tests has no device: the 1-GPU sub-records - sweep, fp8, head dims, 50-step run, CPU baseline - stay out of its line)
-    main_res = run_dtype(args.dtype, args.steps, args.warmup, sweep=(world == 1 and seam is None and not args.no_sweep), distributed=True)
+    last = []
+    main_res = run_dtype(args.dtype, args.steps, args.warmup, sweep=(full and world == 1 and seam is None and not args.no_sweep), distributed=True,
+                         keep_last=last)
     bm, bn, q_tiles, k_tiles = main_res.pop("_bm_bn_tiles")
     headline_again = main_res.pop("_headline_again")
+    if args.dump_outputs and rank == 0:
+        out = last[0] if isinstance(last[0], torch.Tensor) and last[0].dim() == 4 else HeadShardedLiteAttention.to_bshd(last[0])
+        dump_outputs(out, args.dump_outputs)
+        del out
+    del last
 
     result = {
         "metric": "self-attn TFLOPS + ms/step @ seq=75k d=128 bf16, sparsity 0->77%; 1/2/4/8 GPU",
@@ -817,7 +869,7 @@ def main():
             result[key] = main_res[key]
 
     # ---- BASELINE.json configs[4] beside the headline: the same workload with e4m3 Q/K/V (bf16 out), a few extra seconds
-    if world == 1 and seam is None and args.dtype == "bf16" and not args.no_fp8:
+    if full and world == 1 and seam is None and args.dtype == "bf16" and not args.no_fp8:
         try:
             f8 = run_dtype("fp8", max(5, args.steps // 2), 2, sweep=False, distributed=False)
             f8.pop("_bm_bn_tiles"); f8.pop("_headline_again")
@@ -846,14 +898,14 @@ def main():
             result["fp8"] = {"value": None, "error": repr(e)}
 
     # ---- BASELINE.json configs[1]: dense S=32768 H=40 (well under a second)
-    if world == 1 and seam is None and args.dtype == "bf16" and not args.no_head_dims:
+    if full and world == 1 and seam is None and args.dtype == "bf16" and not args.no_head_dims:
         try:
             result["config1_dense_s32768"] = config1_dense(L, dev)
         except Exception as e:  # noqa: BLE001
             result["config1_dense_s32768"] = {"error": repr(e)}
 
     # ---- the reference's other default head sizes beside the headline 128 (about a second)
-    if world == 1 and seam is None and args.dtype == "bf16" and not args.no_head_dims:
+    if full and world == 1 and seam is None and args.dtype == "bf16" and not args.no_head_dims:
         try:
             result["other_head_dims"] = other_head_dims(L, dev)
         except Exception as e:  # noqa: BLE001
@@ -861,7 +913,7 @@ def main():
 
     # ---- BASELINE.json configs[2]: 50 synthetic denoising steps with REAL (fragmented, per-head) skip lists at fixed thresholds
     # (selfcheck.DENOISE_THRESHOLDS: bisected on all 40 heads for 21 / 42 / 57 / 77 % +- 1 % last-step sparsity, tools/calibrate_denoise.py)
-    if world == 1 and seam is None and args.dtype == "bf16" and not args.no_denoise and S == 75600 and H == 40:
+    if full and world == 1 and seam is None and args.dtype == "bf16" and not args.no_denoise and S == 75600 and H == 40:
         try:
             sw0 = result.get("sweep", [{}])[0].get("kernel_ms")
             result["denoise50"] = denoise50(L, dev, sweep0_ms=sw0, random_qkv=qkv_bf16 if world == 1 else None,
@@ -873,7 +925,7 @@ def main():
             result["denoise50"] = {"error": repr(e)}
 
     # ---- round 6 sub-records: the 128-row vote beside the default, the generator SURVEY.md 8(d) pins, the reference's text + video recipe
-    extra = world == 1 and seam is None and args.dtype == "bf16" and S == 75600 and H == 40
+    extra = full and world == 1 and seam is None and args.dtype == "bf16" and S == 75600 and H == 40
     if extra and not args.no_denoise and "runs" in result.get("denoise50", {}):
         try:
             result["half_vote"] = half_vote_record(L, dev, qkv_bf16, result["denoise50"]["runs"])
@@ -923,7 +975,7 @@ def main():
     except Exception as e:  # noqa: BLE001
         result["summary_keys_error"] = repr(e)
 
-    if world == 1 and seam is None and rank == 0 and not args.no_cpu_baseline and args.dtype == "bf16":
+    if full and world == 1 and seam is None and rank == 0 and not args.no_cpu_baseline and args.dtype == "bf16":
         try:
             result["cpu_baseline"] = cpu_baseline(S, D, bm, bn, banded_rows(q_tiles, k_tiles, bm, bn, HEADLINE_SPARSITY))
         except Exception as e:  # the baseline is a reported number, never the measured path

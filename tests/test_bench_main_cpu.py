@@ -22,9 +22,9 @@ def _clean_env(**extra):
     return env
 
 
-def _bench(args, **env_extra):
+def _bench(args, full=True, **env_extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--seqlen", "1000", "--heads", "4", "--steps", "2", "--warmup", "1", "--prewarm-steps", "1",
-           "--no-cpu-baseline", "--no-power"] + args
+           "--no-cpu-baseline", "--no-power"] + (["--full"] if full else []) + args
     return subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_clean_env(**env_extra), cwd=ROOT)
 
 
@@ -62,7 +62,7 @@ def test_the_plain_all_gather_form_and_the_external_launcher_form():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--seqlen", "1000", "--heads", "4", "--steps", "2",
-           "--warmup", "1", "--prewarm-steps", "1", "--no-cpu-baseline", "--no-power"]
+           "--warmup", "1", "--prewarm-steps", "1", "--no-cpu-baseline", "--no-power", "--full"]
     r = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_clean_env(), cwd=ROOT))
     assert r["n_gpus"] == 2 and r["config"]["launcher"].startswith("external launcher") and r["multi_gpu"]["rccl_world_size"] == 2
 
@@ -77,3 +77,37 @@ def test_a_world_that_is_not_gpus_wide_is_refused():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], capture_output=True, text=True, timeout=300,
                          env=_clean_env(RANK="0", WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="1"), cwd=ROOT)
     assert res.returncode != 0 and "WORLD_SIZE=2" in res.stderr and not res.stdout.strip()
+
+
+FULL_ONLY = ("verified", "power", "sweep", "fp8", "config1_dense_s32768", "other_head_dims", "denoise50", "denoise50_survey", "half_vote",
+             "joint_recipe", "cpu_baseline")
+
+
+def test_a_plain_run_is_the_headline_alone_and_dumps_what_its_last_step_returned(tmp_path):
+    """Without --full the line is the headline and nothing beside it; --dump-outputs writes the output of the last timed step, the same
+    in every run of the same arguments, and the same output the --full run's sampled-row check passes on."""
+    import numpy as np
+    plain = _line(_bench(["--gpus", "1", "--dump-outputs", str(tmp_path / "a")], full=False))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["higher_is_better"] is True
+    assert not [k for k in FULL_ONLY if k in plain]
+    a = np.load(tmp_path / "a" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 1000, 4, 128) and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert not (tmp_path / "a" / "out_rows.npy").exists()                     # 2 MB: the whole output, no sample
+    _line(_bench(["--gpus", "1", "--dump-outputs", str(tmp_path / "b")], full=False))
+    assert np.array_equal(a, np.load(tmp_path / "b" / "out.npy"))
+    full = _line(_bench(["--gpus", "1", "--dump-outputs", str(tmp_path / "c")]))
+    assert full["verified"]["ok"] and full["verified"]["lists_fixed_point"]
+    assert np.array_equal(a, np.load(tmp_path / "c" / "out.npy"))
+
+
+def test_the_dump_of_an_all_gathered_step_is_the_whole_output(tmp_path):
+    """N > 1: rank 0 writes the all-gathered output of its last step in (B, S, H, D), from the overlapped per-window blocks as well."""
+    import numpy as np
+    for windows in ("3", "1"):
+        r = _line(_bench(["--gpus", "2", "--overlap-windows", windows, "--dump-outputs", str(tmp_path / windows)], full=False))
+        assert r["multi_gpu"]["overlapped_form_kept"] is (windows == "3") and "verified" not in r
+        a = np.load(tmp_path / windows / "out.npy")
+        assert a.dtype == np.float32 and a.shape == (1, 1000, 4, 128) and np.isfinite(a).all()
+    assert np.array_equal(np.load(tmp_path / "3" / "out.npy"), np.load(tmp_path / "1" / "out.npy"))

@@ -20,11 +20,11 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _run_bench(extra, env_extra):
+def _run_bench(extra, env_extra, full=True):
     env = dict(os.environ, **env_extra)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--seqlen", "8192", "--heads", "8", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-denoise", "--no-head-dims", "--no-fp8", "--no-power"] + extra
+           "--no-cpu-baseline", "--no-denoise", "--no-head-dims", "--no-fp8", "--no-power"] + (["--full"] if full else []) + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -55,7 +55,7 @@ def test_bench_self_launches_its_ranks_when_no_launcher_did():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LA_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--seqlen", "8192", "--heads", "8", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-denoise", "--no-head-dims", "--no-fp8", "--no-power"]
+           "--no-cpu-baseline", "--no-denoise", "--no-head-dims", "--no-fp8", "--no-power", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -73,3 +73,20 @@ def test_bench_single_process_line_has_the_contract_fields():
         assert key in r, key
     assert "multi_gpu" not in r and r["dtype"] == "bf16" and r["config"]["workload"].startswith("QK-Skip")
     assert r["verified"]["ok"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_the_verified_output(tmp_path):
+    """Without --full the line is the headline alone; --dump-outputs writes what the last timed step returned, identical in a second
+    plain run and in a --full run whose sampled-row check passes on the same configuration."""
+    import numpy as np
+    plain = _run_bench(["--dump-outputs", str(tmp_path / "a")], {}, full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in plain, key
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["dtype"] == "bf16"
+    assert not [k for k in ("verified", "power", "sweep", "fp8", "other_head_dims", "denoise50", "cpu_baseline") if k in plain]
+    a = np.load(tmp_path / "a" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 8192, 8, 128) and np.isfinite(a).all()
+    _run_bench(["--dump-outputs", str(tmp_path / "b")], {}, full=False)
+    full = _run_bench(["--no-sweep", "--dump-outputs", str(tmp_path / "c")], {})
+    assert full["verified"]["ok"]
+    assert np.array_equal(a, np.load(tmp_path / "b" / "out.npy")) and np.array_equal(a, np.load(tmp_path / "c" / "out.npy"))

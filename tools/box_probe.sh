@@ -7,7 +7,7 @@ TAG=${1:-box}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-sweep --no-cpu-baseline --no-fp8 --no-denoise --no-head-dims"
+B="python $R/bench.py --full --no-sweep --no-cpu-baseline --no-fp8 --no-denoise --no-head-dims"
 { hostname; rocm-smi --showserial --showuniqueid 2>/dev/null | grep -iE "serial|unique"; rocm-smi --showmaxpower --showtemp 2>/dev/null | grep -iE "power|junction|edge"; } > $OUT/box_id.txt 2>&1
 $B --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --kernel-include-regex "la_fwd" --output-format csv -d $OUT/pmc -o p -- $B --no-verify --no-power --steps 5 --warmup 2 > $OUT/pmc.log 2>&1

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --no-sweep --no-cpu-baseline --steps 3 --warmup 1 $*"
+BENCH="python $R/bench.py --full --no-sweep --no-cpu-baseline --steps 3 --warmup 1 $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- $BENCH > $OUT/kt.log 2>&1
 run_pmc() { # name counters...
   local name=$1; shift

@@ -29,7 +29,7 @@ for l in open(os.path.join(src, "kt.log")):
     if l.startswith('{"metric"'):
         bench = json.loads(l)
 if bench:
-    lines += ["Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-sweep "
+    lines += ["Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-sweep "
               "--no-cpu-baseline --steps 3 --warmup 1` (tools/profile.sh); PMC in separate `--pmc` passes.", "",
               f"bench line under the profiler: value={bench['value']} {bench['unit']}, ms_per_step={bench['ms_per_step']}, "
               f"kernel_ms(HIP events)={bench['roofline']['kernel_ms']}", ""]
