@@ -106,8 +106,9 @@ def build_m16_variant(force: bool = False, verbose: bool = False) -> str:
     on it (tests/test_gpu_m16.py, in a subprocess with LITEATTENTION_AMD_LIB). Never the product: its record says variant=1."""
     rec = _buildinfo.record_in_file(M16_VARIANT) if os.path.exists(M16_VARIANT) else None
     fresh = rec is not None and rec["src"] == _buildinfo.source_hash() and rec["variant"] == "1" and "m16" in rec["opts"] and rec["wrong_results"] == "0"
-    # its own generator is hashed into no record (an edit to the A/B body must not invalidate the PRODUCT library): compare times
-    fresh = fresh and os.path.getmtime(os.path.join(CSRC, X64_M16_GEN)) <= os.path.getmtime(M16_VARIANT)
+    # its own generator is hashed into no record (an edit to the A/B body must not invalidate the PRODUCT library): compare times (of the
+    # assembler core it shares too)
+    fresh = fresh and all(os.path.getmtime(os.path.join(CSRC, g)) <= os.path.getmtime(M16_VARIANT) for g in (X64_M16_GEN, "gen_asm.py"))
     if fresh and not force:
         return M16_VARIANT
     os.makedirs(os.path.dirname(M16_VARIANT), exist_ok=True)

@@ -1,4 +1,5 @@
-"""Shared by gen_fwd_x64.py and gen_fwd_x64_fp8.py: the in-register epilogue of the 64-rows-per-wave kernels.
+"""Shared by gen_fwd_x64.py and gen_fwd_x64_fp8.py: the in-register epilogue of the 64-rows-per-wave kernels (gen_fwd_x64_m16.py
+reads its parameter words with ``read_epilogue_params``).
 
 finalize (softmax.h:275-296) + store (epilogue_fwd.hpp:214-403) straight from the accumulators: every lane owns ONE query row
 (column lane & 31 of the 32x32 accumulator; lanes l and l ^ 32 split the head dim), so 1/l is lane-local after one half-wave
@@ -13,19 +14,14 @@ Parameter words read here (LDS parameter block, 16-byte aligned groups; written 
     [28] [29]  &lse[row 0 of this (batch, head)] or 0             [30]  O scale (bf16: 1; fp8: v_descale)
     [31]       added to the LSE: ln of the factor P carried (bf16: 0; fp8: ln 2^-(8 - tau))
 """
+from gen_asm import S_EXEC, S_PARAM, S_SEQLENQ, S_T0, S_T1, S_T2, S_T3, S_T64, S_TB, S_VB, emit, label, new_label, s, sr, v, vr
+
+# the loop's DMA-base registers are dead here: O base, LSE base and the scalars live in them
+S_OBASE, S_LSEB, S_ORS, S_CLN2, S_OSCALE, S_LSEADD = S_TB, S_VB, S_T0, S_T1, S_T2, S_T3
 
 
-def store_epilogue(g, o_reg):
-    """g: the generator's globals (emit, v, s, sr, vr, label, new_label and its register map); o_reg(qb, db) -> first AGPR."""
-    emit, v, s, sr, vr, label, new_label = g["emit"], g["v"], g["s"], g["sr"], g["vr"], g["label"], g["new_label"]
-    T, L0, L1, MREF, NEGINF, HH4, QROW = g["T"], g["L0"], g["L1"], g["MREF"], g["NEGINF"], g["HH4"], g["QROW"]
-    S_PARAM, S_SEQLENQ, S_EXEC, S_T64 = g["S_PARAM"], g["S_SEQLENQ"], g["S_EXEC"], g["S_T64"]
-    # the loop's DMA-base registers are dead here: O base, LSE base and the scalars live in them
-    S_OBASE, S_LSEB, S_ORS, S_CLN2, S_OSCALE, S_LSEADD = g["S_TB"], g["S_VB"], g["S_T0"], g["S_T1"], g["S_T2"], g["S_T3"]
-    cvt = g.get("CVT_OP", "v_cvt_pk_bf16_f32")                 # the 16-bit output type follows the inputs (fp8 inputs: bf16)
-    n_qb, n_db = g.get("NQB", 2), g.get("DB", 4)               # q-blocks per wave, 32-wide d-blocks (head_dim 256: 1 and 8)
-    HH16 = g["MLOC"][0]                                        # dead after the loop: hh * 16 bytes
-    emit("; ---- finalize + store O (bf16) and LSE straight from the accumulators")
+def read_epilogue_params(T):
+    """Parameter words 24-31 -> S_OBASE ... S_LSEADD (T: the generator's temporaries; T[0] and T[4..11] are overwritten)."""
     emit(f"v_mov_b32 {v(T[0])}, {s(S_PARAM)}")
     emit(f"ds_read_b128 {vr(T[4], 4)}, {v(T[0])} offset:96")
     emit(f"ds_read_b128 {vr(T[8], 4)}, {v(T[0])} offset:112")
@@ -34,6 +30,16 @@ def store_epilogue(g, o_reg):
                      (S_OSCALE, T[10]), (S_LSEADD, T[11])):
         emit(f"v_readfirstlane_b32 {s(dst)}, {v(src)}")
     emit("s_nop 4")
+
+
+def store_epilogue(g, o_reg):
+    """g: the generator's globals (its register map); o_reg(qb, db) -> first AGPR."""
+    T, L0, L1, MREF, NEGINF, HH4, QROW = g["T"], g["L0"], g["L1"], g["MREF"], g["NEGINF"], g["HH4"], g["QROW"]
+    cvt = g.get("CVT_OP", "v_cvt_pk_bf16_f32")                 # the 16-bit output type follows the inputs (fp8 inputs: bf16)
+    n_qb, n_db = g.get("NQB", 2), g.get("DB", 4)               # q-blocks per wave, 32-wide d-blocks (head_dim 256: 1 and 8)
+    HH16 = g["MLOC"][0]                                        # dead after the loop: hh * 16 bytes
+    emit("; ---- finalize + store O (bf16) and LSE straight from the accumulators")
+    read_epilogue_params(T)
     emit(f"v_lshlrev_b32 {v(HH16)}, 2, {v(HH4)}")
     for qb in range(n_qb):
         # l = sum over the two half-waves; inv = oscale / l (0 for l == 0 or NaN); lse = m_ref c ln2 + ln l + lse_add

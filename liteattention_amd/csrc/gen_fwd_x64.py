@@ -32,29 +32,13 @@ it has grown by more than `tau` (log2 units); P stays <= 2^tau. The skip vote us
 import os
 import sys
 
+from gen_asm import *
 from gen_epilogue import store_epilogue
 
-OPT = set(x for x in os.environ.get("LA_X64_OPT", "").split(",") if x)
-
-
-def opt_val(key, default):
-    for o in OPT:
-        if o.startswith(key + ":"):
-            return o[len(key) + 1:]
-    return default
-
-
-# Options that only MOVE instructions (placement, split points, cache policy, code alignment): the body computes the same results bit
-# for bit. Every other option drops work or changes the arithmetic - pricing experiments (tools/asm_variants.py). The first line of a
-# generated body says which kind went in; liteattention_amd/build.py refuses the latter for the product library and records both in
-# la_build_info() for A/B builds (--out=).
+set_label_prefix(".LX")
+OPT = options("LA_X64_OPT")
+# Options that only MOVE instructions (placement, split points, cache policy, code alignment): see gen_asm.option_tag.
 SCHEDULE_ONLY = {"snake", "x", "cap1", "cap2", "dmagaps", "dmapol", "align", "pad4", "pad4b", "e64", "wp2", "wp2b", "wc2", "kearly", "klate", "klate2", "expblock", "norot", "w2", "pk"}
-
-
-def option_tag():
-    wrong = sorted(o for o in OPT if o.split(":")[0] not in SCHEDULE_ONLY)
-    return (f"// la_body_options: {','.join(sorted(OPT)) or '-'}; wrong_results={1 if wrong else 0}"
-            + (f" (PRICING ONLY, results are wrong: {','.join(wrong)})" if wrong else ""))
 
 
 # 16-bit element type of Q / K / V / P / O: "bf16" (default) or "f16" (LA_X64_DTYPE; the build generates one body per type). Only the
@@ -117,8 +101,8 @@ PW = (64 // NW) * ROW // 1024             # 1-KiB DMA pieces per wave per tile (
 # (+1.4 %), head_dim 192 1111 -> 1107 (24 + 24 KiB there: nothing to balance) - small, because these forms sit at the power limit
 # too (1.8-1.9 GHz). Default: 256 only; `kearly` / `klate2` force it on / off for A/B.
 K_EARLY = NQB == 1 and (D == 256 or "kearly" in OPT) and "klate2" not in OPT
-XPAIRS = int(opt_val("x", {64: "4", 256: "6"}.get(D, "5")))   # pair-groups (of 16; one group = the same pair of both q-blocks) done in phase 2 (head_dim 64: 4 since round 4,
-                                                      # +1.8-2.2 % over round 3's 8 on two boxes; 1 / 2 / 3 / 6 / 10 / 12 lose to it; head_dim 256: 6, +1 % over 5; 96 / 192: 5 stays)
+XPAIRS = int(opt_val(OPT, "x", {64: "4", 256: "6"}.get(D, "5")))   # pair-groups (of 16; one group = the same pair of both q-blocks) done in phase 2 (head_dim 64: 4 since round 4,
+                                                           # +1.8-2.2 % over round 3's 8 on two boxes; 1 / 2 / 3 / 6 / 10 / 12 lose to it; head_dim 256: 6, +1 % over 5; 96 / 192: 5 stays)
 # `snake` (A/B): the q-block order of a fragment's two MFMAs flips with the fragment's parity, so that every MFMA shares an operand register
 # with its predecessor inside a group - (K0,Q0) (K0,Q1) (K1,Q1) (K1,Q0) instead of (K0,Q0) (K0,Q1) (K1,Q0) (K1,Q1). The matrix pipe
 # ALONE gains 0.9 % from it on N(0,1) data (tools/debug/mfma_order_bench.py: operand toggling is what an MFMA's energy depends on).
@@ -131,9 +115,9 @@ def qb_of(t):
     return pos ^ (f & 1) if SNAKE and NQB == 2 else pos
 
 
-CAP1 = int(opt_val("cap1", "0"))          # fillers per MFMA gap the distributor may place (0 = balance evenly)
-CAP2 = int(opt_val("cap2", "0"))
-DMA_GAPS = [int(x) for x in opt_val("dmagaps", {128: "1,2,4,6,8,10,11,13,15,17", 96: "0,1,3,4,6,7,8,9,11,12", 64: "1,2,4,8,9,11"}[D] if DL <= 128 else
+CAP1 = int(opt_val(OPT, "cap1", "0"))     # fillers per MFMA gap the distributor may place (0 = balance evenly)
+CAP2 = int(opt_val(OPT, "cap2", "0"))
+DMA_GAPS = [int(x) for x in opt_val(OPT, "dmagaps", {128: "1,2,4,6,8,10,11,13,15,17", 96: "0,1,3,4,6,7,8,9,11,12", 64: "1,2,4,8,9,11"}[D] if DL <= 128 else
                                     "1,2,3,4,5,7,8,9,10,11,13,14,15,16,17,19,20,21,22,23").replace(".", ",").split(",")]   # m0K,K0..3,m0V,V0..3 (phase 1)
 assert W2 or max(DMA_GAPS) < NG          # (step_w2 places its DMA pieces itself)
 
@@ -188,82 +172,16 @@ if W2:                                    # 90 VGPRs: S v[0:31] (one buffer), V^
     ALPHA, MLOC2 = [84], [85]
     LANE, RIPROW, RAGK, RAGV = 86, 87, 88, 89
 
-# ---------------------------------------------------------------- SGPR map (s32-s34 are ABI-reserved: unused)
-S_KBASE, S_VBASE, S_QBASE = 36, 38, 40    # 64-bit
-S_TB, S_VB, S_EXEC, S_T64, S_T64B = 42, 44, 46, 48, 50   # 64-bit temps
-(S_KRS, S_VRS, S_LASTROW, S_NTILES, S_C, S_THR, S_TAILVALID, S_FIRSTLAST, S_TAB, S_DOFLAGS, S_WAVE, S_I, S_DOMASK,
- S_FREE0, S_FREE1, S_FREE2, S_LDS, S_T0, S_T1, S_T2, S_T3, S_NM1, S_QRS, S_QROW0, S_SEQLENQ, S_EXPORT, S_PARAM, S_DOWORD, S_NEGC,
- S_FREE3, S_DMAW, S_FREE4, S_TAU, S_RESC, S_FREE5) = range(52, 87)
-S_FREE6, S_TB2, S_VB2, S_BIT = 87, 88, 90, 92
+# ---------------------------------------------------------------- SGPR aliases of this generator (the map: gen_asm.py)
 S_STATE = S_FREE3         # HALF: the form of the NEXT step, computed in front of the drain: (a(i), a(i+1)) as bits 0, 1, or 4 = the walk is over
 S_ACT, S_ACTPTR, S_HSTRIDE = S_T64B, S_FREE1, S_FREE2    # HALF: s[50:51] = activity window (bit k = a(i + k)), LDS address of the next activity word, bytes between the halves' flag blocks
-S_ONES = S_FREE0                                 # packed (1.0, 1.0) of the element type: src0 of the row-sum dot (dotsum)    # second set of DMA bases (the loop is unrolled by two); the rotating vote bit
+S_ONES = S_FREE0                                 # packed (1.0, 1.0) of the element type: src0 of the row-sum dot (dotsum)
 S_CC = 94                                        # s[94:95] = (c, c): scalar operand of v_pk_fma_f32
-TBS, VBS = [S_TB, S_TB2], [S_VB, S_VB2]
 
 KV_TILE = 64 * ROW
 V_REGION = 2 * KV_TILE
-DMA_POLICY = {"": "", "nt": " nt", "sc0": " sc0", "sc1": " sc1"}[opt_val("dmapol", "")]    # cache-policy experiments on the K/V stream
+DMA_POLICY = {"": "", "nt": " nt", "sc0": " sc0", "sc1": " sc1"}[opt_val(OPT, "dmapol", "")]  # cache-policy experiments on the K/V stream
 DMA_BIAS = 3072           # S_KBASE / S_VBASE hold (tensor base - DMA_BIAS); LK / LV[j] hold (+DMA_BIAS - 1024 j): see dma_ops
-
-out = []          # IR: str | ("LDS", str, tag) | ("WAIT", tag) | ("DRAIN",)
-
-
-def emit(x):
-    out.append(x if isinstance(x, tuple) else "    " + x)
-
-
-def label(s):
-    out.append(s + ":")
-
-
-def v(i):
-    return f"v{i}"
-
-
-def vr(a, n):
-    return f"v[{a}:{a + n - 1}]"
-
-
-def ar(a, n):
-    return f"a[{a}:{a + n - 1}]"
-
-
-def s(i):
-    return f"s{i}"
-
-
-def sr(a, n=2):
-    return f"s[{a}:{a + n - 1}]"
-
-
-uid = [0]
-
-
-def new_label(prefix):
-    uid[0] += 1
-    return f".LX{prefix}_{uid[0]}_%="
-
-
-def finalize(items):
-    """Counted lgkmcnt waits: LDS operations of one wave return in order."""
-    lines, q = [], []
-    for it in items:
-        if isinstance(it, str):
-            lines.append(it)
-        elif it[0] == "LDS":
-            lines.append("    " + it[1])
-            q.append(it[2])
-        elif it[0] == "WAIT":
-            if it[1] in q:
-                idx = max(i for i, t in enumerate(q) if t == it[1])
-                lines.append(f"    s_waitcnt lgkmcnt({min(len(q) - 1 - idx, 15)})")
-                q = q[idx + 1:]
-        elif it[0] == "DRAIN":
-            lines.append("    s_waitcnt lgkmcnt(0)" if "nowaitvm" in OPT else "    s_waitcnt vmcnt(0) lgkmcnt(0)")
-            q = []
-    return lines
-
 
 # ---------------------------------------------------------------- building blocks (return item lists)
 def k_read(kbuf_imm, j):
@@ -290,7 +208,7 @@ def v_read(slot, vbuf_imm, m):
 # PRICING ONLY (wrong results; profiles/r04_power_ceiling.md): every 32x32x16 MFMA replaced by TWO 16x16x32 MFMAs on the same operand
 # registers (the same FLOPs, 4-register accumulators taken round-robin from the 16 of the original) - what the matrix pipe costs in the
 # other shape, inside the real loop with its real operand data. `mfma16:qk` / `mfma16:pv` / `mfma16:both`.
-MFMA16 = opt_val("mfma16", "")
+MFMA16 = opt_val(OPT, "mfma16", "")
 MFMA16_OP = {"bf16": "v_mfma_f32_16x16x32_bf16", "f16": "v_mfma_f32_16x16x32_f16"}[DTYPE]
 
 
@@ -550,7 +468,7 @@ def inval_block(lbl, back):
 def flush_block(flush_label, back_label):
     """Out of line: doflags word |= domask by one lane; next word, domask = 0, bit = 1. Drains lgkmcnt (keeps counted waits valid)."""
     label(flush_label)
-    flush_domask()
+    flush_domask(T[4], T[5])
     emit(f"s_add_u32 {s(S_DOWORD)}, {s(S_DOWORD)}, 4")
     emit(f"s_mov_b32 {s(S_BIT)}, 1")
     if HALF:
@@ -568,16 +486,6 @@ def flush_block(flush_label, back_label):
     else:
         emit("s_waitcnt lgkmcnt(0)")
     emit(f"s_branch {back_label}")
-
-
-def flush_domask():
-    emit(f"v_mov_b32 {v(T[4])}, {s(S_DOWORD)}")
-    emit(f"v_mov_b32 {v(T[5])}, {s(S_DOMASK)}")
-    emit(f"s_mov_b64 {sr(S_EXEC)}, exec")
-    emit("s_mov_b64 exec, 1")
-    emit(f"ds_or_b32 {v(T[4])}, {v(T[5])}")
-    emit(f"s_mov_b64 exec, {sr(S_EXEC)}")
-    emit(f"s_mov_b32 {s(S_DOMASK)}, 0")
 
 
 def rescale_o_block(lbl, back):
@@ -623,34 +531,6 @@ def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
     return o
 
 
-def weight(it):
-    """Issue cost in quad-cycles as measured (PMC: SQ_ACTIVE_INST_VALU): a transcendental takes two slots, labels none."""
-    if isinstance(it, str):
-        if it.endswith(":"):
-            return 0
-        if "v_exp_f32" in it:
-            return 2
-    return 1
-
-
-def n_fill(items):
-    return sum(weight(it) for it in items)
-
-
-def distribute(queue, post, start, cap):
-    """Append the ops of `queue` (order kept) to post[start..NG-1], topping every gap up to `cap` fillers."""
-    q = list(queue)
-    if cap <= 0:
-        total = sum(n_fill(post[t]) for t in range(start, NG)) + n_fill(q)
-        cap = -(-total // (NG - start))
-    for t in range(start, NG):
-        while q and n_fill(post[t]) < cap:
-            post[t].append(q.pop(0))
-            while q and isinstance(q[0], str) and q[0].endswith(":"):      # a label sticks to the op before it
-                post[t].append(q.pop(0))
-    post[NG - 1] += q
-
-
 def emit_gaps(pre, mf, post):
     """One phase: per gap the pre items, the MFMA, the fillers. Pricing variant mfma16 (two 16x16x32 MFMAs per gap): with `spread` the
     second MFMA of a gap sits behind the first half of the gap's fillers instead of right behind the first (a 16x16x32 MFMA holds the
@@ -664,9 +544,6 @@ def emit_gaps(pre, mf, post):
         else:
             for it in pre[t] + [mf[t]] + post[t]:
                 out.append(it)
-
-
-deferred = []     # out-of-line blocks emitted after the loop: callables
 
 
 def widen_last(n, since):
@@ -683,29 +560,24 @@ def widen_last(n, since):
     assert n == 0, "not enough 4-byte instructions to widen"
 
 
-HALFSKIP = int(opt_val("halfskip", "0"))     # PRICING ONLY: every wave sits out one step in HALFSKIP (no MFMA, no softmax, no fragment reads)
+HALFSKIP = int(opt_val(OPT, "halfskip", "0"))  # PRICING ONLY: every wave sits out one step in HALFSKIP (no MFMA, no softmax, no fragment reads)
 
 
-def step(variant, light=False, a_cur=True, a_nxt=True):
-    if light:                             # the step of a wave whose 128-row half does not list this tile: it still stages its DMA pieces,
-        saved = set(OPT)                  # follows the tile-address table and meets the barrier
-        OPT.update({"nomfma1", "nomfma2", "nosoftmax", "norowmax", "novread", "nokread", "nowaitv"})
-        try:
-            return _step(variant)
-        finally:
-            OPT.clear()
-            OPT.update(saved)
-    return _step(variant, a_cur, a_nxt)
+# What a wave leaves out of a step when it sits the tile out (HALFSKIP): it still stages its DMA pieces, follows the tile-address table
+# and meets the barrier
+LIGHT = frozenset({"nomfma1", "nomfma2", "nosoftmax", "norowmax", "novread", "nokread", "nowaitv"})
 
 
-def _step(variant, a_cur=True, a_nxt=True):
+def step(variant, a_cur=True, a_nxt=True, drop=frozenset()):
     """One pipeline step; variant = parity of i: S_cur = S set `variant`, K(i+2)/V(i) in LDS buffer `variant`, DMA bases
     in SGPR set `variant` (computed during the previous step). Nothing but the drain, the barrier and the loop test sits
     between the last MFMA of a step and the first of the next.
     HALF: a_cur / a_nxt = this wave's half lists tile i / tile i + 1. Tile i's work of the step (rest of softmax(i), V^T reads, PV(i))
     is there iff a_cur; tile i + 1's (QK(i+1), row max / vote / running max, first part of softmax(i+1)) iff a_nxt. The DMA issue, the
     table reads, the vote-bit / table-pointer bookkeeping, the drain and the barrier are in every form. K(i+2) fragments: read beside
-    the PV MFMAs when a_cur (whatever a(i+2): the gaps cannot branch), else in a block of their own iff a(i+2)."""
+    the PV MFMAs when a_cur (whatever a(i+2): the gaps cannot branch), else in a block of their own iff a(i+2).
+    drop: work left out as if these options were set (LIGHT)."""
+    opt = OPT | drop
     cur, nxt = variant, variant ^ 1
     kbuf_read = cur * KV_TILE                # K(i+2)
     kbuf_stage = nxt * KV_TILE               # K(i+3) goes where K(i+1) was
@@ -720,22 +592,22 @@ def _step(variant, a_cur=True, a_nxt=True):
     post = [[] for _ in range(NG)]
     mf = []
     for t in range(NG):
-        mf.append(mfma_qk(nxt, ord1[t // NQB], qb_of(t)) if ("nomfma1" not in OPT and a_nxt) else "    s_nop 0")
+        mf.append(mfma_qk(nxt, ord1[t // NQB], qb_of(t)) if ("nomfma1" not in opt and a_nxt) else "    s_nop 0")
     for g, op in zip(DMA_GAPS, dma_ops(kbuf_stage, vbuf_stage, st=variant)):
         post[g].append(op)
-    if K_EARLY and "nokread" not in OPT:
+    if K_EARLY and "nokread" not in opt:
         for t in range(NG):
             if t % NQB == NQB - 1:                           # the last MFMA that reads fragment ord1[t // NQB] has issued
                 post[t].append(k_read(kbuf_read, ord1[t // NQB]))
-    if "novread" not in OPT and a_cur:
+    if "novread" not in opt and a_cur:
         for f in range(8):                                   # the first 8 V^T fragments, spread over the second half of the phase
             post[NG // 2 + f * (NG // 2) // 8] += v_read(f, vbuf_cur, ord2[f])
-    vq = softmax_stream(cur, list(range(XPAIRS, 16))) if a_cur else []
+    vq = softmax_stream(cur, list(range(XPAIRS, 16))) if a_cur and "nosoftmax" not in opt else []
     distribute(vq, post, 0, CAP1)
     mark = len(out)
     emit_gaps(pre, mf, post)
     if full:
-        widen_last(int(opt_val("wp2", "0")) if variant == 0 else int(opt_val("wp2b", opt_val("wp2", "0"))), mark)      # shift phase 2 (copy 0 / copy 1 of the step)
+        widen_last(int(opt_val(OPT, "wp2", "0")) if variant == 0 else int(opt_val(OPT, "wp2b", opt_val(OPT, "wp2", "0"))), mark)  # shift phase 2 (copy 0 / copy 1 of the step)
     if a_nxt and not a_cur:
         # no PV MFMAs stand between the QK MFMAs and the first VALU read of their results (the row max): the MFMA results are
         # readable 18 wait states after the last one issued
@@ -749,14 +621,14 @@ def _step(variant, a_cur=True, a_nxt=True):
     mf = []
     for t in range(NG):
         f, qb = t // NQB, t % NQB
-        if qb == 0 and "novread" not in OPT and "nowaitv" not in OPT and a_cur:
+        if qb == 0 and "novread" not in opt and "nowaitv" not in opt and a_cur:
             pre[t].append(("WAIT", ("v", ord2[f], 1)))
-        mf.append(mfma_pv(cur, f % 8, ord2[f], qb_of(t)) if ("nomfma2" not in OPT and a_cur) else "    s_nop 0")
-        if qb == NQB - 1 and f + 8 < NVF and "novread" not in OPT and a_cur:
+        mf.append(mfma_pv(cur, f % 8, ord2[f], qb_of(t)) if ("nomfma2" not in opt and a_cur) else "    s_nop 0")
+        if qb == NQB - 1 and f + 8 < NVF and "novread" not in opt and a_cur:
             post[t] += v_read(f % 8, vbuf_cur, ord2[f + 8])
-        if "nokread" not in OPT and not K_EARLY and a_cur and (t < NKF if "klate" not in OPT else (t & 1) == 0):
-            post[t].append(k_read(kbuf_read, ord1[t if "klate" not in OPT else f]))
-    if "mfmasum" in OPT:
+        if "nokread" not in opt and not K_EARLY and a_cur and (t < NKF if "klate" not in opt else (t & 1) == 0):
+            post[t].append(k_read(kbuf_read, ord1[t if "klate" not in opt else f]))
+    if "mfmasum" in opt:
         # PRICING ONLY: the 64 v_add_f32 of the row sums are gone and one more MFMA per (q-block, 16-key group)
         # stands for "ones x P^T" - 8 per step. No 32 accumulator registers are free in this register map, so the stand-in
         # accumulates into O^T (finite garbage) with a Q fragment as its A operand (real data: prices the energy conservatively).
@@ -773,7 +645,7 @@ def _step(variant, a_cur=True, a_nxt=True):
     vq = [("LDS", f"ds_read_b64 {vr(T[4], 2)}, {v(TABV)} offset:8", "tabv"),
           ("LDS", f"ds_read_b64 {vr(T[6], 2)}, {v(TABV)} offset:32", "tabk")]
     n_head = len(vq)
-    if "norowmax" not in OPT and a_nxt:
+    if "norowmax" not in opt and a_nxt:
         rm = row_max_ops(nxt)
     else:
         rm = []
@@ -793,7 +665,7 @@ def _step(variant, a_cur=True, a_nxt=True):
     if not a_nxt:
         vq += stats_bookkeeping(fl, flback)
         deferred.append(lambda: flush_block(fl, flback))
-    elif "notail" not in OPT:
+    elif "notail" not in opt:
         # (HALF: positions past the end of the walk have a = 0, so a form with statistics never runs at i == n - 1 and the test below never
         # fires there; it stays so that the hot loop is instruction for instruction - gap for gap - the tuned schedule of the form
         # without activity bits)
@@ -802,7 +674,7 @@ def _step(variant, a_cur=True, a_nxt=True):
         deferred.append(lambda: inval_block(inv, invback))
         deferred.append(lambda: rare_rescale_block(rare, back))
         deferred.append(lambda: flush_block(fl, flback))
-    if a_nxt:
+    if a_nxt and "nosoftmax" not in opt:
         vq += softmax_stream(nxt, list(range(XPAIRS)))
     # the first two gaps may only hold ops that do not read S_nxt (MFMA -> VALU read hazard): the SALU / seq part
     distribute(vq[:n_head], post, 0, CAP2 if CAP2 > 0 else 6)
@@ -822,8 +694,8 @@ def _step(variant, a_cur=True, a_nxt=True):
         # shift the second copy of the step against the first (code-placement experiments). HALF: a step is four scalar instructions (16
         # bytes: five in the PV gaps, one fewer behind the barrier) longer than the tuned form's; four widened encodings more put the second
         # copy of the step back at the fetch phase it was tuned at (profiles/r05_code_placement.md: period 32 bytes)
-        widen_last(int(opt_val("wc2", "4" if HALF else "0")), mark)
-    if HALF and not a_cur and "nokread" not in OPT:
+        widen_last(int(opt_val(OPT, "wc2", "4" if HALF else "0")), mark)
+    if HALF and not a_cur and "nokread" not in opt:
         # K(i+2) fragments iff this half lists tile i + 2 (bit 2 of the window). Behind every counted LDS wait of the step and in front
         # of the drain: a conditional LDS operation between a counted wait and its target would break the count.
         nok = new_label("nokfrag")
@@ -844,7 +716,7 @@ def _step(variant, a_cur=True, a_nxt=True):
         for op in state_ops():
             out.append(op)
     emit(("DRAIN",))
-    if "nobarrier" not in OPT:
+    if "nobarrier" not in opt:
         emit("s_barrier")
     if not HALF:
         emit(f"s_add_u32 {s(S_I)}, {s(S_I)}, 1")
@@ -1081,22 +953,7 @@ def step_w2(p, group):
 
 def prologue():
     stamp(0)
-    emit("; ---- lane id, parameter block -> SGPRs")
-    emit(f"v_mbcnt_lo_u32_b32 {v(LANE)}, -1, 0")
-    emit(f"v_mbcnt_hi_u32_b32 {v(LANE)}, -1, {v(LANE)}")
-    emit(f"s_mov_b32 {s(S_WAVE)}, %0")
-    emit(f"s_mov_b32 {s(S_PARAM)}, %1")
-    emit(f"v_mov_b32 {v(T[0])}, {s(S_PARAM)}")
-    for q in range(6):
-        emit(f"ds_read_b128 {vr(4 * q, 4)}, {v(T[0])} offset:{16 * q}")
-    emit("s_waitcnt lgkmcnt(0)")
-    plist = [S_KBASE, S_KBASE + 1, S_VBASE, S_VBASE + 1, S_KRS, S_VRS, S_LASTROW, S_NTILES, S_C, S_THR, S_TAILVALID,
-             S_FIRSTLAST, S_TAB, S_DOFLAGS, S_QBASE, S_QBASE + 1, S_QRS, S_QROW0, S_SEQLENQ, S_EXPORT, S_LDS, S_NEGC, S_TAU]
-    if HALF:
-        plist.append(S_HSTRIDE)            # [23]: bytes between the two halves' flag blocks; [19] (S_EXPORT) = LDS address of half 0's activity words
-    for idx, sg in enumerate(plist):
-        emit(f"v_readfirstlane_b32 {s(sg)}, {v(idx)}")
-    emit("s_nop 4")
+    read_params(LANE, T[0], [S_HSTRIDE] if HALF else [])     # HALF: word 23; word 19 (S_EXPORT) = LDS address of half 0's activity words
     if HALF:
         emit("; ---- half = wave >> 1: its vote words, its activity words; the window starts as positions [0, 64)")
         emit(f"s_lshr_b32 {s(S_T0)}, {s(S_WAVE)}, 1")
@@ -1357,7 +1214,7 @@ def epilogue():
     nofl = new_label("nolastflush")
     emit(f"s_cmp_eq_u32 {s(S_DOMASK)}, 0")
     emit(f"s_cbranch_scc1 {nofl}")
-    flush_domask()
+    flush_domask(T[4], T[5])
     label(nofl)
     emit("s_nop 15")                                           # the last PV MFMAs have written the accumulators
     emit("s_nop 15")
@@ -1399,10 +1256,10 @@ def main():
     # the asm statement happened to leave: an edit to the list writer moved the headline kernel from phase 8 to phase 16 and cost 0.8 %.
     # The head is now pinned: .p2align 5, then PHASE / 4 s_nop (executed once per item), per body the best measured phase.
     # `align:N` / `pad4:N` override it for experiments.
-    if opt_val("align", "") or opt_val("pad4", ""):
-        if opt_val("align", ""):
-            out.append(f".p2align {opt_val('align', '')}")
-        for _ in range(int(opt_val("pad4", "0"))):
+    if opt_val(OPT, "align", "") or opt_val(OPT, "pad4", ""):
+        if opt_val(OPT, "align", ""):
+            out.append(f".p2align {opt_val(OPT, 'align', '')}")
+        for _ in range(int(opt_val(OPT, "pad4", "0"))):
             emit("s_nop 0")
     else:
         out.append(".p2align 5")
@@ -1412,7 +1269,7 @@ def main():
     label(loop)
     for variant in (0, 1):
         if variant == 1:
-            for _ in range(int(opt_val("pad4b", "0"))):        # code-placement experiments: the second copy of the step against the first
+            for _ in range(int(opt_val(OPT, "pad4b", "0"))):   # code-placement experiments: the second copy of the step against the first
                 emit("s_nop 0")
         if not HALF:
             emit(f"s_cmp_lt_u32 {s(S_I)}, {s(S_NTILES)}")
@@ -1457,7 +1314,7 @@ def main():
             emit(f"s_cbranch_scc1 {lbl}")
             step(variant)
             label(after)
-            deferred.append(lambda lbl=lbl, after=after, variant=variant: (label(lbl), step(variant, light=True), emit(f"s_branch {after}")))
+            deferred.append(lambda lbl=lbl, after=after, variant=variant: (label(lbl), step(variant, drop=LIGHT), emit(f"s_branch {after}")))
         else:                            # (the W2 body has its own loops and returned above)
             step(variant)
     emit(f"s_branch {loop}")
@@ -1475,20 +1332,15 @@ E64_OPS = ("v_exp_f32", "v_add_f32", "v_mul_f32", "v_sub_f32", "v_max_f32", "v_m
 
 
 def write_out():
-    lines = finalize(out)
+    lines = finalize(OPT)
     if "e64" in OPT:       # code-placement experiment: every 4-byte VOP1 / VOP2 of the body in its 8-byte VOP3 encoding (same operation, same issue cost)
         import re
         pat = re.compile(r"^(\s*)(" + "|".join(E64_OPS) + r")(\s+[vs]\d+(?:,\s*-?[vs]\d+)+\s*)$")      # register operands only: VOP3 takes no literals on gfx9
         lines = [pat.sub(lambda m: m.group(1) + m.group(2) + "_e64" + m.group(3), ln) for ln in lines]
-    text = "\n".join(lines)
-    path = sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_body.inc"
-    with open(path, "w") as f:
-        f.write("// GENERATED by gen_fwd_x64.py — do not edit. Inline-asm body of la_fwd_x64_kernel.\n" if D == 128 and not HALF else
-                f"// GENERATED by gen_fwd_x64.py (LA_X64_D={D} LA_X64_FORM=half) — do not edit. Inline-asm body of la_fwd_x64_kernel<.., {D}, true>.\n" if HALF else
-                f"// GENERATED by gen_fwd_x64.py (LA_X64_D={D}) — do not edit. Inline-asm body of la_fwd_bf16_x64_kernel<.., {D}>.\n")
-        f.write(option_tag() + "\n")
-        f.write('R"ASM(\n' + text + '\n)ASM"\n')
-    print(f"wrote {path}: {len(lines)} lines, {text.count('v_mfma')} MFMAs")
+    header = ("// GENERATED by gen_fwd_x64.py — do not edit. Inline-asm body of la_fwd_x64_kernel." if D == 128 and not HALF else
+              f"// GENERATED by gen_fwd_x64.py (LA_X64_D={D} LA_X64_FORM=half) — do not edit. Inline-asm body of la_fwd_x64_kernel<.., {D}, true>." if HALF else
+              f"// GENERATED by gen_fwd_x64.py (LA_X64_D={D}) — do not edit. Inline-asm body of la_fwd_bf16_x64_kernel<.., {D}>.")
+    write_body(sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_body.inc", header, option_tag(OPT, SCHEDULE_ONLY), lines)
 
 
 if __name__ == "__main__":

@@ -32,28 +32,14 @@ results equal the offset-8 ones except for P < 2^-12 (absolute 2.4e-4 of a weigh
 import os
 import sys
 
+from gen_asm import *
 from gen_epilogue import store_epilogue
 
-OPT = set(x for x in os.environ.get("LA_X64F8_OPT", "").split(",") if x)
-
-
-def opt_val(key, default):
-    for o in OPT:
-        if o.startswith(key + ":"):
-            return o[len(key) + 1:]
-    return default
-
-
+set_label_prefix(".LF")
+OPT = options("LA_X64F8_OPT")
 # Options that only move instructions or select one of the three product bodies (exp / lvalu): same results bit for bit as the body of
-# that name. Everything else is a pricing experiment; the first line of a generated body says which kind went in (see gen_fwd_x64.py).
+# that name (gen_asm.option_tag).
 SCHEDULE_ONLY = {"x", "dmagaps", "align", "pad4", "smstart", "klate", "pk", "exp", "lvalu", "vspread"}
-
-
-def option_tag():
-    wrong = sorted(o for o in OPT if o.split(":")[0] not in SCHEDULE_ONLY)
-    return (f"// la_body_options: {','.join(sorted(OPT)) or '-'}; wrong_results={1 if wrong else 0}"
-            + (f" (PRICING ONLY, results are wrong: {','.join(wrong)})" if wrong else ""))
-
 
 
 # Head dim (round 6): 128, or 64 = the same step with ONE 64-wide contraction per score block and two 32-wide d-blocks of O^T: 4 QK + 4 PV
@@ -77,7 +63,7 @@ DB = ND                                   # gen_epilogue.py: d-blocks to store
 PIECES_K = 4 if WIDE else (D + 63) // 64  # 1 KiB LDS-DMA pieces per wave and K tile (WIDE: the 16 KiB image of 256-byte rows)
 PIECES_V = (D + 63) // 64                 # ... and prepared V^T tile (64 D bytes; 96: padded to 8 KiB)
 ROWSUM = 99                               # "d-block" index of the row-sum MFMA in PV_ORDER
-XPAIRS = int(opt_val("x", {128: {"lin": "8", "exp": "4", "lvalu": "4"}, 64: {"lin": "12", "exp": "2", "lvalu": "6"}, 96: {"lin": "8", "exp": "4", "lvalu": "4"},
+XPAIRS = int(opt_val(OPT, "x", {128: {"lin": "8", "exp": "4", "lvalu": "4"}, 64: {"lin": "12", "exp": "2", "lvalu": "6"}, 96: {"lin": "8", "exp": "4", "lvalu": "4"},
                                 192: {"lin": "8", "exp": "8", "lvalu": "8"}, 256: {"lin": "8", "exp": "8", "lvalu": "8"}}[D]
                         ["lvalu" if "lvalu" in OPT else "exp" if "exp" in OPT else "lin"]))          # pair-groups (of 16) done in phase 2. EVEN: two pair-groups share one packed-e4m3 destination register
                                           # (lo / hi half by op_sel); an odd split leaves a half-written register across the phase boundary
@@ -127,10 +113,10 @@ NG2 = NQB * ND + (NQB if LMFMA else 0)    # MFMAs (gaps) of phase 2: PV + the ro
 # the row maximum does, so the lazy rescale only guards the fp32 accumulators: TAU = 32, i.e. never on real data. Cost: 8 vector
 # instructions per step (exponent, scale byte and encoding offset for both q-blocks).
 MX = LIN and "nomx" not in OPT
-TAU = float(opt_val("tau", "32" if MX else ("1" if LIN else "2")))
+TAU = float(opt_val(OPT, "tau", "32" if MX else ("1" if LIN else "2")))
 P_CEIL = 8.75 if LIN else 8.0
 P_OFFSET = 7.0 if MX else P_CEIL - TAU
-DMA_GAPS = [int(x) for x in opt_val("dmagaps", {64: "0,1,2,3", 96: "0,1,1,2,3,3", 128: "0,1,1,2,3,3", 192: "0,1,1,2,2,3,4,4,5", 256: "0,1,1,2,2,3,4,4,5,5"}[D]).replace(".", ",").split(",")]   # m0K,K0,K1,m0V,V0,V1 (phase 1 gaps; an M0 write is never adjacent to its first use)
+DMA_GAPS = [int(x) for x in opt_val(OPT, "dmagaps", {64: "0,1,2,3", 96: "0,1,1,2,3,3", 128: "0,1,1,2,3,3", 192: "0,1,1,2,2,3,4,4,5", 256: "0,1,1,2,2,3,4,4,5,5"}[D]).replace(".", ",").split(",")]  # m0K,K0,K1,m0V,V0,V1 (phase 1 gaps; an M0 write is never adjacent to its first use)
 
 
 # ---------------------------------------------------------------- AGPR map
@@ -173,78 +159,12 @@ TABV = 222                                # LDS address of tab[i + 2], the tile-
 NMR, NMSB, SCB = [178, 179], [186, 187], [[188, 189], [215, 218]]      # (L0 / L1 are unused with the matrix-pipe row sums)
 MXT = [T[10], T[11]]
 
-# ---------------------------------------------------------------- SGPR map (s32-s34 are ABI-reserved: unused)
-S_KBASE, S_VBASE, S_QBASE = 36, 38, 40
-S_TB, S_VB, S_EXEC, S_T64, S_T64B = 42, 44, 46, 48, 50
-(S_KRS, S_VRS, S_LASTROW, S_NTILES, S_C, S_THR, S_TAILVALID, S_FIRSTLAST, S_TAB, S_DOFLAGS, S_WAVE, S_I, S_DOMASK,
- S_FREE0, S_FREE1, S_FREE2, S_LDS, S_T0, S_T1, S_T2, S_T3, S_NM1, S_QRS, S_QROW0, S_SEQLENQ, S_EXPORT, S_PARAM, S_DOWORD, S_NEGC,
- S_FREE3, S_DMAW, S_FREE4, S_TAU, S_RESC, S_FREE5) = range(52, 87)
+# ---------------------------------------------------------------- SGPR aliases of this generator (the map: gen_asm.py)
 S_C8, S_NEGC8, S_M8 = S_FREE0, S_FREE1, S_FREE2   # lin: 8 c and -8 c; mx: -8.0
-S_FREE6, S_TB2, S_VB2, S_BIT = 87, 88, 90, 92     # second set of DMA bases (the loop is unrolled by two); the rotating vote bit
 S_DMAWV = S_FREE4 if PIECES_V != PIECES_K else S_DMAW   # LDS-DMA destination of this wave's V^T pieces (head_dim 192: 3 pieces against 4 of K)
-TBS, VBS = [S_TB, S_TB2], [S_VB, S_VB2]
 
 KV_TILE = 16384 if WIDE else 8192         # one stage of the K / V^T rings
 V_REGION = 2 * KV_TILE
-
-out = []
-
-
-def emit(x):
-    out.append(x if isinstance(x, tuple) else "    " + x)
-
-
-def label(s):
-    out.append(s + ":")
-
-
-def v(i):
-    return f"v{i}"
-
-
-def vr(a, n):
-    return f"v[{a}:{a + n - 1}]"
-
-
-def ar(a, n):
-    return f"a[{a}:{a + n - 1}]"
-
-
-def s(i):
-    return f"s{i}"
-
-
-def sr(a, n=2):
-    return f"s[{a}:{a + n - 1}]"
-
-
-uid = [0]
-
-
-def new_label(prefix):
-    uid[0] += 1
-    return f".LF{prefix}_{uid[0]}_%="
-
-
-def finalize(items):
-    """Counted lgkmcnt waits: LDS operations of one wave return in order."""
-    lines, q = [], []
-    for it in items:
-        if isinstance(it, str):
-            lines.append(it)
-        elif it[0] == "LDS":
-            lines.append("    " + it[1])
-            q.append(it[2])
-        elif it[0] == "WAIT":
-            if it[1] in q:
-                idx = max(i for i, t in enumerate(q) if t == it[1])
-                lines.append(f"    s_waitcnt lgkmcnt({min(len(q) - 1 - idx, 15)})")
-                q = q[idx + 1:]
-        elif it[0] == "DRAIN":
-            lines.append("    s_waitcnt lgkmcnt(0)" if "nowaitvm" in OPT else "    s_waitcnt vmcnt(0) lgkmcnt(0)")   # nowaitvm: pricing only
-            q = []
-    return lines
-
 
 # ---------------------------------------------------------------- building blocks
 def k_read(kbuf_imm, j, t):
@@ -475,21 +395,11 @@ def inval_block(lbl, back):
 
 def flush_block(flush_label, back_label):
     label(flush_label)
-    flush_domask()
+    flush_domask(T[4], T[5])
     emit(f"s_add_u32 {s(S_DOWORD)}, {s(S_DOWORD)}, 4")
     emit(f"s_mov_b32 {s(S_BIT)}, 1")
     emit("s_waitcnt lgkmcnt(0)")
     emit(f"s_branch {back_label}")
-
-
-def flush_domask():
-    emit(f"v_mov_b32 {v(T[4])}, {s(S_DOWORD)}")
-    emit(f"v_mov_b32 {v(T[5])}, {s(S_DOMASK)}")
-    emit(f"s_mov_b64 {sr(S_EXEC)}, exec")
-    emit("s_mov_b64 exec, 1")
-    emit(f"ds_or_b32 {v(T[4])}, {v(T[5])}")
-    emit(f"s_mov_b64 exec, {sr(S_EXEC)}")
-    emit(f"s_mov_b32 {s(S_DOMASK)}, 0")
 
 
 def rescale_o_block(lbl, back):
@@ -533,34 +443,6 @@ def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
     return o
 
 
-def weight(it):
-    if isinstance(it, str):
-        if it.endswith(":"):
-            return 0
-        if "v_exp_f32" in it:
-            return 2
-    return 1
-
-
-def n_fill(items):
-    return sum(weight(it) for it in items)
-
-
-def distribute(queue, post, start, cap=0):
-    q = list(queue)
-    ng = len(post)
-    if cap <= 0:
-        total = sum(n_fill(post[t]) for t in range(start, ng)) + n_fill(q)
-        cap = -(-total // (ng - start))
-    for t in range(start, ng):
-        while q and n_fill(post[t]) < cap:
-            post[t].append(q.pop(0))
-            while q and isinstance(q[0], str) and q[0].endswith(":"):
-                post[t].append(q.pop(0))
-    post[ng - 1] += q
-
-
-deferred = []
 QK_ORDER = [(sx, kb, qb) for sx in range(NSX) for kb in (0, 1) for qb in QBS]      # dependent pairs are 4 MFMAs apart (one q-block: 2)
 PV_ORDER = [(db, qb) for db in range(ND) for qb in QBS] + ([(ROWSUM, qb) for qb in QBS] if LMFMA else [])
 K_FRAGS = [(NSX * kb + sx, t) for sx in range(NSX) for kb in (0, 1) for t in (0, 1)]  # sx = 0 fragments first
@@ -581,7 +463,7 @@ def step(variant):
     for f, (db, t) in enumerate([(db, t) for db in range(ND) for t in (0, 1)]):
         v0 = 0 if "vspread" in OPT else NG // 2          # vspread (A/B): the V^T fragment reads over the whole of phase 1 instead of its second half
         post[v0 + f * (NG - v0) // (2 * ND)].append(v_read(vbuf_cur, db, t))
-    distribute(softmax_stream(cur, list(range(XPAIRS, 16))), post, int(opt_val("smstart", "0")))
+    distribute(softmax_stream(cur, list(range(XPAIRS, 16))), post, int(opt_val(OPT, "smstart", "0")))
     for t in range(NG):
         out.append(mf[t])
         out.extend(post[t])
@@ -649,20 +531,7 @@ def step(variant):
 
 
 def prologue():
-    emit("; ---- lane id, parameter block -> SGPRs")
-    emit(f"v_mbcnt_lo_u32_b32 {v(LANE)}, -1, 0")
-    emit(f"v_mbcnt_hi_u32_b32 {v(LANE)}, -1, {v(LANE)}")
-    emit(f"s_mov_b32 {s(S_WAVE)}, %0")
-    emit(f"s_mov_b32 {s(S_PARAM)}, %1")
-    emit(f"v_mov_b32 {v(T[0])}, {s(S_PARAM)}")
-    for q in range(6):
-        emit(f"ds_read_b128 {vr(4 * q, 4)}, {v(T[0])} offset:{16 * q}")
-    emit("s_waitcnt lgkmcnt(0)")
-    plist = [S_KBASE, S_KBASE + 1, S_VBASE, S_VBASE + 1, S_KRS, S_VRS, S_LASTROW, S_NTILES, S_C, S_THR, S_TAILVALID,
-             S_FIRSTLAST, S_TAB, S_DOFLAGS, S_QBASE, S_QBASE + 1, S_QRS, S_QROW0, S_SEQLENQ, S_EXPORT, S_LDS, S_NEGC, S_TAU]
-    for idx, sg in enumerate(plist):
-        emit(f"v_readfirstlane_b32 {s(sg)}, {v(idx)}")
-    emit("s_nop 4")
+    read_params(LANE, T[0])
     if LIN:
         emit(f"v_mul_f32 {v(T[0])}, 8.0, {v(8)}")             # v8 / v21 still hold c / -c of the parameter block
         emit(f"v_mul_f32 {v(T[1])}, 8.0, {v(21)}")
@@ -873,7 +742,7 @@ def epilogue():
     nofl = new_label("nolastflush")
     emit(f"s_cmp_eq_u32 {s(S_DOMASK)}, 0")
     emit(f"s_cbranch_scc1 {nofl}")
-    flush_domask()
+    flush_domask(T[4], T[5])
     label(nofl)
     emit("s_nop 15")                                           # the last PV MFMAs (16 passes each) have written the accumulators
     emit("s_nop 15")
@@ -890,10 +759,10 @@ def main():
     loop, done = new_label("loop"), new_label("done")
     # Code placement (round 5; see gen_fwd_x64.py main()): the loop head is pinned at the best measured phase inside a 32-byte window -
     # default form 0, exact-exp 24 (30.65 ms against 31.25 at phases 8 / 16: 2 %), exact-rowsum 8 (flat). `align:N` / `pad4:N` override.
-    if opt_val("align", "") or opt_val("pad4", ""):
-        if opt_val("align", ""):
-            out.append(f".p2align {opt_val('align', '')}")
-        for _ in range(int(opt_val("pad4", "0"))):
+    if opt_val(OPT, "align", "") or opt_val(OPT, "pad4", ""):
+        if opt_val(OPT, "align", ""):
+            out.append(f".p2align {opt_val(OPT, 'align', '')}")
+        for _ in range(int(opt_val(OPT, "pad4", "0"))):
             emit("s_nop 0")
     else:
         out.append(".p2align 5")
@@ -911,8 +780,7 @@ def main():
         blk()
     label(done)
     epilogue()
-    lines = finalize(out)
-    text = "\n".join(lines)
+    lines = finalize(OPT)
     path = sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_fp8_body.inc"
     mode = 2 if not LMFMA else (0 if LIN else 1)               # PMODE of the shell (la_fwd_kernel_x64_fp8.hip)
     # the three bodies of the build are told apart by their FILE NAME in the shell's includes: a body generated under options that belong to
@@ -928,11 +796,8 @@ def main():
         with open(path.replace("_body.inc", "_consts.h"), "w") as f:
             f.write("// GENERATED by gen_fwd_x64_fp8.py together with the body of the same name — do not edit.\n")
             f.write(f"#define LA_X64F8_TAU_{mode} {TAU!r}f\n#define LA_X64F8_OFFSET_{mode} {P_OFFSET!r}f\n")
-    with open(path, "w") as f:
-        f.write("// GENERATED by gen_fwd_x64_fp8.py — do not edit. Inline-asm body of la_fwd_x64_fp8_kernel.\n")
-        f.write(option_tag() + "\n")
-        f.write('R"ASM(\n' + text + '\n)ASM"\n')
-    print(f"wrote {path}: {len(lines)} lines, {text.count('v_mfma')} MFMAs")
+    write_body(path, "// GENERATED by gen_fwd_x64_fp8.py — do not edit. Inline-asm body of la_fwd_x64_fp8_kernel.",
+               option_tag(OPT, SCHEDULE_ONLY), lines)
 
 
 if __name__ == "__main__":

@@ -38,24 +38,12 @@ of the next tile (4 key blocks x 4 k-steps x 4); VGPR v[0:63] / v[64:127] S^T pi
 import os
 import sys
 
-OPT = set(x for x in os.environ.get("LA_X64_OPT", "").split(",") if x)
+from gen_asm import *
+from gen_epilogue import S_CLN2, S_LSEADD, S_LSEB, S_OBASE, S_ORS, S_OSCALE, read_epilogue_params
 
-
-def opt_val(key, default):
-    for o in OPT:
-        if o.startswith(key + ":"):
-            return o[len(key) + 1:]
-    return default
-
-
-SCHEDULE_ONLY = {"x", "dmagaps", "dmapol", "align", "pad4", "safe", "kgaps", "vgap0"}      # see gen_fwd_x64.py: same results bit for bit
-
-
-def option_tag():
-    wrong = sorted(o for o in OPT if o.split(":")[0] not in SCHEDULE_ONLY)
-    return (f"// la_body_options: {','.join(sorted(OPT | {'m16'}))}; wrong_results={1 if wrong else 0}"
-            + (f" (PRICING ONLY, results are wrong: {','.join(wrong)})" if wrong else ""))
-
+set_label_prefix(".LM")
+OPT = options("LA_X64_OPT")
+SCHEDULE_ONLY = {"m16", "x", "dmagaps", "dmapol", "align", "pad4", "safe", "kgaps", "vgap0"}      # see gen_asm.option_tag
 
 DTYPE = os.environ.get("LA_X64_DTYPE", "bf16")
 MFMA_OP = {"bf16": "v_mfma_f32_16x16x32_bf16", "f16": "v_mfma_f32_16x16x32_f16"}[DTYPE]
@@ -69,10 +57,10 @@ ROW, ROW_SHIFT = 256, 8
 KV_TILE = 64 * ROW
 V_REGION = 2 * KV_TILE
 NQUADS = NQB * NKB                                      # softmax units: the 4 scores of one (q-block, key block) accumulator
-XQ = int(opt_val("x", "5"))                             # quads of the NEXT tile done in phase 2 (of 16), the rest in phase 1
-SAFE_GAPS = int(opt_val("safe", "4"))                   # MFMA gaps at the head of phase 2 that hold nothing that reads S_nxt
-DMA_GAPS = [int(x) for x in opt_val("dmagaps", "2.4.8.12.16.20.22.26.30.34").replace(".", ",").split(",")]
-DMA_POLICY = {"": "", "nt": " nt", "sc0": " sc0", "sc1": " sc1"}[opt_val("dmapol", "")]
+XQ = int(opt_val(OPT, "x", "5"))                        # quads of the NEXT tile done in phase 2 (of 16), the rest in phase 1
+SAFE_GAPS = int(opt_val(OPT, "safe", "4"))              # MFMA gaps at the head of phase 2 that hold nothing that reads S_nxt
+DMA_GAPS = [int(x) for x in opt_val(OPT, "dmagaps", "2.4.8.12.16.20.22.26.30.34").replace(".", ",").split(",")]
+DMA_POLICY = {"": "", "nt": " nt", "sc0": " sc0", "sc1": " sc1"}[opt_val(OPT, "dmapol", "")]
 DMA_BIAS = 3072
 
 # ---------------------------------------------------------------- register map
@@ -108,72 +96,6 @@ MTRUE_T, MREF_T, MTHR_T = 192, 193, 194   # transposed state: lane (j, g) = quer
 ALPHA = list(range(195, 199))             # rescale factor per q-block (rare block -> O rescale at the step's tail)
 T = list(range(200, 216))                 # temporaries (T[0] even: 64-bit tuples such as T[4:5] must be even-aligned)
 NEGINF, G4, QROW_T, TABV, LANE, J16, RAGK, RAGV = 199, 216, 217, 218, 219, 220, 221, 222
-
-S_KBASE, S_VBASE, S_QBASE = 36, 38, 40    # 64-bit
-S_TB, S_VB, S_EXEC, S_T64, S_T64B = 42, 44, 46, 48, 50
-(S_KRS, S_VRS, S_LASTROW, S_NTILES, S_C, S_THR, S_TAILVALID, S_FIRSTLAST, S_TAB, S_DOFLAGS, S_WAVE, S_I, S_DOMASK,
- S_FREE0, S_FREE1, S_FREE2, S_LDS, S_T0, S_T1, S_T2, S_T3, S_NM1, S_QRS, S_QROW0, S_SEQLENQ, S_EXPORT, S_PARAM, S_DOWORD, S_NEGC,
- S_FREE3, S_DMAW, S_FREE4, S_TAU, S_RESC, S_FREE5) = range(52, 87)
-S_FREE6, S_TB2, S_VB2, S_BIT = 87, 88, 90, 92
-TBS, VBS = [S_TB, S_TB2], [S_VB, S_VB2]
-
-out = []          # IR: str | ("LDS", str, tag) | ("WAIT", tag) | ("DRAIN",)
-
-
-def emit(x):
-    out.append(x if isinstance(x, tuple) else "    " + x)
-
-
-def label(s_):
-    out.append(s_ + ":")
-
-
-def v(i):
-    return f"v{i}"
-
-
-def vr(a, n):
-    return f"v[{a}:{a + n - 1}]"
-
-
-def ar(a, n):
-    return f"a[{a}:{a + n - 1}]"
-
-
-def s(i):
-    return f"s{i}"
-
-
-def sr(a, n=2):
-    return f"s[{a}:{a + n - 1}]"
-
-
-uid = [0]
-
-
-def new_label(prefix):
-    uid[0] += 1
-    return f".LM{prefix}_{uid[0]}_%="
-
-
-def finalize(items):
-    """Counted lgkmcnt waits: LDS operations of one wave return in order."""
-    lines, q = [], []
-    for it in items:
-        if isinstance(it, str):
-            lines.append(it)
-        elif it[0] == "LDS":
-            lines.append("    " + it[1])
-            q.append(it[2])
-        elif it[0] == "WAIT":
-            if it[1] in q:
-                idx = max(i for i, t in enumerate(q) if t == it[1])
-                lines.append(f"    s_waitcnt lgkmcnt({min(len(q) - 1 - idx, 15)})")
-                q = q[idx + 1:]
-        elif it[0] == "DRAIN":
-            lines.append("    s_waitcnt vmcnt(0) lgkmcnt(0)")
-            q = []
-    return lines
 
 
 # ---------------------------------------------------------------- building blocks
@@ -349,19 +271,9 @@ def inval_block(lbl, back):
     emit(f"s_branch {back}")
 
 
-def flush_domask():
-    emit(f"v_mov_b32 {v(T[4])}, {s(S_DOWORD)}")
-    emit(f"v_mov_b32 {v(T[5])}, {s(S_DOMASK)}")
-    emit(f"s_mov_b64 {sr(S_EXEC)}, exec")
-    emit("s_mov_b64 exec, 1")
-    emit(f"ds_or_b32 {v(T[4])}, {v(T[5])}")
-    emit(f"s_mov_b64 exec, {sr(S_EXEC)}")
-    emit(f"s_mov_b32 {s(S_DOMASK)}, 0")
-
-
 def flush_block(flush_label, back_label):
     label(flush_label)
-    flush_domask()
+    flush_domask(T[4], T[5])
     emit(f"s_add_u32 {s(S_DOWORD)}, {s(S_DOWORD)}, 4")
     emit(f"s_mov_b32 {s(S_BIT)}, 1")
     emit("s_waitcnt lgkmcnt(0)")
@@ -400,40 +312,10 @@ def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
     return o
 
 
-def weight(it):
-    if isinstance(it, str):
-        if it.endswith(":"):
-            return 0
-        if "v_exp_f32" in it:
-            return 2
-    return 1
-
-
-def n_fill(items):
-    return sum(weight(it) for it in items)
-
-
-def distribute(queue, post, start, cap=0, end=NG):
-    """Append the ops of `queue` (order kept) to post[start..end-1], topping every gap up to `cap` fillers (0: balance evenly)."""
-    q = list(queue)
-    if cap <= 0:
-        total = sum(n_fill(post[t]) for t in range(start, end)) + n_fill(q)
-        cap = -(-total // (end - start))
-    for t in range(start, end):
-        while q and n_fill(post[t]) < cap:
-            post[t].append(q.pop(0))
-            while q and isinstance(q[0], str) and q[0].endswith(":"):      # a label sticks to the op before it
-                post[t].append(q.pop(0))
-    post[end - 1] += q
-
-
 def emit_gaps(pre, mf, post):
     for t in range(NG):
         for it in pre[t] + [mf[t]] + post[t]:
             out.append(it)
-
-
-deferred = []
 
 
 def step(variant):
@@ -448,7 +330,7 @@ def step(variant):
     mf = [mfma_qk(nxt, kb, ks, qb) if "nomfma1" not in OPT else "    s_nop 0" for ks, kb, qb in QK_ORDER]
     for g_, op in zip(DMA_GAPS, dma_ops(kbuf_stage, vbuf_stage, st=variant)):
         post[g_].append(op)
-    v0 = int(opt_val("vgap0", "36"))
+    v0 = int(opt_val(OPT, "vgap0", "36"))
     for f in range(8):                                         # key step 0's fragments, spread over the back of the phase
         if "novread" not in OPT:
             post[v0 + f * ((NG - v0) // 8)] += v_read(f, vbuf_cur, 0, f)
@@ -461,7 +343,7 @@ def step(variant):
     post = [[] for _ in range(NG)]
     mf = []
     kq = [(kb, ks) for ks in range(KS) for kb in range(NKB)]                     # the order phase 1 of the next step consumes them
-    kgaps = int(opt_val("kgaps", "2"))                                           # one K fragment read every `kgaps` gaps
+    kgaps = int(opt_val(OPT, "kgaps", "2"))                                      # one K fragment read every `kgaps` gaps
     for t, (kk, db, qb) in enumerate(PV_ORDER):
         f = kk * DB + db
         if qb == 0 and "novread" not in OPT:
@@ -511,20 +393,7 @@ def step(variant):
 
 
 def prologue():
-    emit("; ---- lane id, parameter block -> SGPRs")
-    emit(f"v_mbcnt_lo_u32_b32 {v(LANE)}, -1, 0")
-    emit(f"v_mbcnt_hi_u32_b32 {v(LANE)}, -1, {v(LANE)}")
-    emit(f"s_mov_b32 {s(S_WAVE)}, %0")
-    emit(f"s_mov_b32 {s(S_PARAM)}, %1")
-    emit(f"v_mov_b32 {v(T[0])}, {s(S_PARAM)}")
-    for q in range(6):
-        emit(f"ds_read_b128 {vr(4 * q, 4)}, {v(T[0])} offset:{16 * q}")
-    emit("s_waitcnt lgkmcnt(0)")
-    plist = [S_KBASE, S_KBASE + 1, S_VBASE, S_VBASE + 1, S_KRS, S_VRS, S_LASTROW, S_NTILES, S_C, S_THR, S_TAILVALID,
-             S_FIRSTLAST, S_TAB, S_DOFLAGS, S_QBASE, S_QBASE + 1, S_QRS, S_QROW0, S_SEQLENQ, S_EXPORT, S_LDS, S_NEGC, S_TAU]
-    for idx, sg in enumerate(plist):
-        emit(f"v_readfirstlane_b32 {s(sg)}, {v(idx)}")
-    emit("s_nop 4")
+    read_params(LANE, T[0])
     emit(f"s_sub_u32 {s(S_NM1)}, {s(S_NTILES)}, 1")
     emit(f"s_lshl_b32 {s(S_DMAW)}, {s(S_WAVE)}, {ROW_SHIFT + 4}")          # a wave stages 16 rows = 4 KiB of a tile
     emit(f"s_add_u32 {s(S_DMAW)}, {s(S_DMAW)}, {s(S_LDS)}")
@@ -672,27 +541,18 @@ def prologue():
 
 
 def epilogue():
-    """finalize (softmax.h:275-296) + store (epilogue_fwd.hpp:214-403) straight from the accumulators.
-    Parameter words (LDS block, written by the C++ shell; the same as gen_epilogue.py reads): [24] [25] O row 0 of this (batch, head),
-    [26] O row stride in bytes, [27] c ln 2, [28] [29] &lse[row 0] or 0, [30] O scale, [31] added to the LSE."""
-    S_OBASE, S_LSEB, S_ORS, S_CLN2, S_OSCALE, S_LSEADD = S_TB, S_VB, S_T0, S_T1, S_T2, S_T3
+    """finalize (softmax.h:275-296) + store (epilogue_fwd.hpp:214-403) straight from the accumulators (parameter words 24-31:
+    gen_epilogue.py)."""
     emit("; ---- flush the last (partial) vote word")
     nofl = new_label("nolastflush")
     emit(f"s_cmp_eq_u32 {s(S_DOMASK)}, 0")
     emit(f"s_cbranch_scc1 {nofl}")
-    flush_domask()
+    flush_domask(T[4], T[5])
     label(nofl)
     emit("s_nop 15")                                           # the last PV MFMAs have written the accumulators
     emit("s_nop 15")
     emit("; ---- finalize + store O and LSE straight from the accumulators")
-    emit(f"v_mov_b32 {v(T[0])}, {s(S_PARAM)}")
-    emit(f"ds_read_b128 {vr(T[4], 4)}, {v(T[0])} offset:96")
-    emit(f"ds_read_b128 {vr(T[8], 4)}, {v(T[0])} offset:112")
-    emit("s_waitcnt lgkmcnt(0)")
-    for dst, src in ((S_OBASE, T[4]), (S_OBASE + 1, T[5]), (S_ORS, T[6]), (S_CLN2, T[7]), (S_LSEB, T[8]), (S_LSEB + 1, T[9]),
-                     (S_OSCALE, T[10]), (S_LSEADD, T[11])):
-        emit(f"v_readfirstlane_b32 {s(dst)}, {v(src)}")
-    emit("s_nop 4")
+    read_epilogue_params(T)
     # l of every row, transposed: lane (j, g) = row 16 g + j of the wave = row `lane`
     for op in transposing_reduce(L, "v_add_f32", T[0]):
         out.append(op)
@@ -785,10 +645,10 @@ def epilogue():
 def main():
     prologue()
     loop, done = new_label("loop"), new_label("done")
-    if opt_val("align", "") or opt_val("pad4", ""):           # code placement: see gen_fwd_x64.py main(); this body is pinned at phase 8 (not swept)
-        if opt_val("align", ""):
-            out.append(f".p2align {opt_val('align', '')}")
-        for _ in range(int(opt_val("pad4", "0"))):
+    if opt_val(OPT, "align", "") or opt_val(OPT, "pad4", ""):  # code placement: see gen_fwd_x64.py main(); this body is pinned at phase 8 (not swept)
+        if opt_val(OPT, "align", ""):
+            out.append(f".p2align {opt_val(OPT, 'align', '')}")
+        for _ in range(int(opt_val(OPT, "pad4", "0"))):
             emit("s_nop 0")
     else:
         out.append(".p2align 5")
@@ -804,14 +664,9 @@ def main():
         blk()
     label(done)
     epilogue()
-    lines = finalize(out)
-    text = "\n".join(lines)
-    path = sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_m16_body.inc"
-    with open(path, "w") as f:
-        f.write("// GENERATED by gen_fwd_x64_m16.py — do not edit. Inline-asm body of la_fwd_x64_kernel<.., 128> on v_mfma_f32_16x16x32.\n")
-        f.write(option_tag() + "\n")
-        f.write('R"ASM(\n' + text + '\n)ASM"\n')
-    print(f"wrote {path}: {len(lines)} lines, {text.count('v_mfma')} MFMAs")
+    write_body(sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_m16_body.inc",
+               "// GENERATED by gen_fwd_x64_m16.py — do not edit. Inline-asm body of la_fwd_x64_kernel<.., 128> on v_mfma_f32_16x16x32.",
+               option_tag(OPT | {"m16"}, SCHEDULE_ONLY), finalize(OPT))
 
 
 if __name__ == "__main__":
