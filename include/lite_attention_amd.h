@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 8   /* 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
+#define LA_ABI_VERSION 9   /* 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
 
@@ -56,7 +56,7 @@ typedef enum la_status {
     LA_ERR_LISTS = -8,           /* read list without write list, or vice versa                   */
     LA_ERR_UNSUPPORTED = -9,     /* feature outside the hot path (causal, dv != d, ...)           */
     LA_ERR_LAUNCH = -10,         /* hipLaunchKernel failed; see la_last_hip_error()               */
-    LA_ERR_SEQLEN = -11,         /* sequence too long for the per-workgroup list staging in LDS   */
+    LA_ERR_SEQLEN = -11,         /* sequence too long for the per-workgroup list staging in LDS, or (int16 lists) for an int16 row */
     LA_ERR_WORKSPACE = -12,      /* fp8: workspace missing or smaller than la_fwd_workspace_bytes() */
     LA_ERR_Q_WINDOW = -13        /* q_tile_begin/q_tile_count outside [0, ceil(seqlen_q/block_m)]  */
 } la_status;
@@ -76,6 +76,13 @@ typedef enum la_status {
                                   * q-tile windows: q_tile_begin even, q_tile_count even unless the window reaches the last q-tile. Lists are read
                                   * as SETS of tiles (identical to the literal walk for every well-formed list; a list with overlapping or
                                   * ascending ranges walks each named tile once). */
+#define LA_FLAG_LIST_INT16 128u  /* read_list and write_list point at int16_t rows instead of int32_t ones: the same geometry [B_alloc, H, Qt, Kt+1]
+                                  * contiguous and the same row format, half the bytes (the lists are the only state a caller keeps per layer: 112 -> 56 MB
+                                  * at S = 75 600, H = 40; INTEGRATION.md has the table). A row is 2 * (Kt + 1) bytes and may start on any 2-byte
+                                  * boundary: the kernels touch such lists with 16-bit loads and stores only. Every entry is a tile index below Kt or a
+                                  * count of at most Kt, so int16 holds every well-formed list la_fwd accepts; with Kt + 1 > 32767 the flag is refused
+                                  * (LA_ERR_SEQLEN) before any launch; on a launch without lists it is LA_ERR_UNSUPPORTED. must_do_list stays int32_t. Every kernel that takes lists takes both forms, and
+                                  * o, lse and the written list VALUES are identical to the int32 launch's. */
 #define LA_FLAG_EXACT_RESCALE 8u /* A/B: the hand-scheduled kernels rescale O on EVERY growth of a row maximum (tau = 0) instead of lazily
                                   * (bf16: only after it grew by more than 2^8; results agree to rounding, lists are identical) */
 /* fp8 (e4m3) forms of P. DEFAULT = the reference's arithmetic in full: P = exp2(S c - m c + off) by the transcendental unit, rounded to e4m3 by the
@@ -159,9 +166,9 @@ typedef struct la_fwd_args {
     int64_t k_descale_batch_stride, k_descale_head_stride;
     int64_t v_descale_batch_stride, v_descale_head_stride;
 
-    const int32_t* read_list;    /* QKSkipMaskArgs::attn_read_list   flash.h:13                   */
-    int32_t*       write_list;   /* QKSkipMaskArgs::attn_write_list  flash.h:15                   */
-    const int32_t* must_do_list; /* QKSkipMaskArgs::attn_must_do_list flash.h:14; may be NULL     */
+    const int32_t* read_list;    /* QKSkipMaskArgs::attn_read_list   flash.h:13 (int16_t rows under LA_FLAG_LIST_INT16: cast the pointer) */
+    int32_t*       write_list;   /* QKSkipMaskArgs::attn_write_list  flash.h:15 (the same)        */
+    const int32_t* must_do_list; /* QKSkipMaskArgs::attn_must_do_list flash.h:14; may be NULL; int32_t whatever the flags */
     int32_t        must_do_is_1d;
     float          thr;          /* QKSkipMaskArgs::thr flash.h:17 (log2 domain)                  */
 
@@ -227,6 +234,11 @@ int la_fwd(const la_fwd_args* args, void* stream);
 int la_skip_list_stats(const int32_t* list, int32_t n_batch, int32_t num_heads, int32_t q_tiles,
                        int32_t k_tiles, int64_t* out_counts, void* stream);
 
+/* The same for a list of either element type: `list` holds int32_t (list_elem_size 4) or int16_t (2: the lists of a launch with
+ * LA_FLAG_LIST_INT16). Other element sizes: LA_ERR_DTYPE; element size 2 with k_tiles + 1 > 32767: LA_ERR_SEQLEN. */
+int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles,
+                          int32_t k_tiles, int64_t* out_counts, void* stream);
+
 /* LSE-weighted merge of `num_splits` partial attention results (sequence-parallel K/V splits):
  *   o_partial   [num_splits, B, Sq, H, Dv] contiguous: fp32, or (partial_is_16bit != 0) the element type of o
  *   lse_partial fp32 [num_splits, B, H, Sq] contiguous
@@ -260,12 +272,18 @@ int la_blockmask_to_lists(const uint8_t* blockmask, int64_t mask_batch_stride, i
                           int32_t num_heads, int32_t q_tiles, int32_t k_tiles, const int32_t* q_tiles_valid,
                           const int32_t* k_tiles_valid, int32_t* lists, int32_t* empty_rows, void* stream);
 
+/* The same with rows of either element type: `lists` is int32_t (list_elem_size 4) or int16_t (2) [batch, num_heads, q_tiles, k_tiles + 1],
+ * written with element-wide stores. Other element sizes: LA_ERR_DTYPE; element size 2 with k_tiles + 1 > 32767: LA_ERR_SEQLEN. */
+int la_blockmask_to_lists_ex(const uint8_t* blockmask, int64_t mask_batch_stride, int64_t mask_head_stride, int32_t batch,
+                             int32_t num_heads, int32_t q_tiles, int32_t k_tiles, const int32_t* q_tiles_valid,
+                             const int32_t* k_tiles_valid, void* lists, int32_t list_elem_size, int32_t* empty_rows, void* stream);
+
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)
  * sizes them in whole rounds of this number. No counterpart in the reference (one launch per call). */
 int la_device_slots(int head_dim, int element_size, uint32_t flags, int* compute_units, int* workgroups_per_cu);
 
-/* What this binary was built from: "abi=7;src=<sha256[:16] of the kernel / API sources, generators and this header>;variant=0|1;
+/* What this binary was built from: "abi=9;src=<sha256[:16] of the kernel / API sources, generators and this header>;variant=0|1;
  * wrong_results=0|1;opts=<generator options and -D defines, empty for the product build>". The product build (variant=0) is generated
  * with NO generator option and NO define, whatever the environment of the build held; A/B and pricing builds (python -m
  * liteattention_amd.build --out=...) say variant=1, and wrong_results=1 when an option that changes the arithmetic went in. The Python

@@ -29,7 +29,7 @@ def source_hash() -> Optional[str]:
 
 
 def parse(info: str) -> Dict[str, str]:
-    """"abi=7;src=...;variant=0;wrong_results=0;opts=..." -> dict (opts may itself hold ';'-free text only)."""
+    """"abi=9;src=...;variant=0;wrong_results=0;opts=..." -> dict (opts may itself hold ';'-free text only)."""
     out = {}
     for part in info.split(";"):
         k, _, v = part.partition("=")

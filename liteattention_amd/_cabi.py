@@ -13,7 +13,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # LITEATTENTION_AMD_LIB overrides the in-tree location (deployment / tests of the failure path)
 LIB_PATH = os.environ.get("LITEATTENTION_AMD_LIB") or os.path.join(_PKG_DIR, "libliteattention_amd.so")
 
-LA_ABI_VERSION = 8
+LA_ABI_VERSION = 9
 LA_DTYPE_BF16, LA_DTYPE_FP16, LA_DTYPE_FP8_E4M3, LA_DTYPE_FP32 = 0, 1, 2, 3
 
 LA_OK = 0
@@ -26,6 +26,7 @@ LA_ERR_Q_WINDOW = -13
 EXPORTED_SYMBOLS = (
     "la_abi_version", "la_get_tile_sizes", "la_get_tile_sizes_ex", "la_fwd", "la_fwd_workspace_bytes", "la_skip_list_stats", "la_combine",
     "la_status_string", "la_last_hip_error", "la_blockmask_to_lists", "la_device_slots", "la_build_info", "la_combine_list",
+    "la_skip_list_stats_ex", "la_blockmask_to_lists_ex",
 )
 
 
@@ -64,6 +65,8 @@ LA_FLAG_EXACT_RESCALE = 8
 LA_FLAG_FP8_MFMA_ROWSUM = 16     # fp8: row sums of the ROUNDED P from the matrix pipe (default: fp32 sums of the un-rounded P, the reference's)
 LA_FLAG_FP8_ENCODED_P = 32       # fp8: the block-scaled log-linear byte encoding of P (default: exp2 + hardware e4m3 rounding, the reference's)
 LA_FLAG_HALF_VOTE = 64
+LA_FLAG_LIST_INT16 = 128         # read_list / write_list hold int16 rows (half the list state); set by the host from the dtype of the lists it is given
+LIST_INT16_MAX_ROW = 32767       # ... for rows of at most this many entries (k_tiles + 1): beyond, la_fwd answers LA_ERR_SEQLEN
 GEOMETRY_FLAGS = LA_FLAG_KERNEL_128ROW | LA_FLAG_HALF_VOTE      # the flags that change the q-tile of the skip lists (la_get_tile_sizes_ex)
 
 
@@ -94,6 +97,17 @@ def default_flags() -> int:
     if fp8_p == "encoded":
         f |= LA_FLAG_FP8_ENCODED_P
     return f
+
+
+def default_list_dtype():
+    """Element type of the skip lists a ``LiteAttention`` object allocates when its constructor is not told: LA_LIST_DTYPE=int16 ->
+    ``torch.int16`` (half the per-layer list state), unset / int32 -> ``torch.int32``. Like the switches of ``default_flags()`` this
+    only chooses a host default: the library reads no environment, ``la_fwd`` is told by LA_FLAG_LIST_INT16."""
+    import torch
+    name = os.environ.get("LA_LIST_DTYPE", "")
+    if name not in ("", "int32", "int16"):
+        raise ValueError("LA_LIST_DTYPE: int32 (default) or int16")
+    return torch.int16 if name == "int16" else torch.int32
 
 
 class NativeLibraryError(RuntimeError):
@@ -146,6 +160,13 @@ def load() -> ctypes.CDLL:
     lib.la_blockmask_to_lists.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.la_blockmask_to_lists.restype = ctypes.c_int
+    lib.la_skip_list_stats_ex.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.la_skip_list_stats_ex.restype = ctypes.c_int
+    lib.la_blockmask_to_lists_ex.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                             ctypes.c_void_p]
+    lib.la_blockmask_to_lists_ex.restype = ctypes.c_int
     lib.la_device_slots.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.la_device_slots.restype = ctypes.c_int
     lib.la_status_string.argtypes = [ctypes.c_int]

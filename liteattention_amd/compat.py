@@ -231,8 +231,9 @@ def _blockmask_to_lists_host(blockmask: torch.Tensor, k_tiles_valid: Optional[to
 
 def blockmask_to_lists(blockmask: torch.Tensor, k_tiles_valid: Optional[torch.Tensor] = None, validate: bool = True,
                        q_tiles_valid: Optional[torch.Tensor] = None, batch: Optional[int] = None,
-                       heads: Optional[int] = None) -> torch.Tensor:
+                       heads: Optional[int] = None, dtype: torch.dtype = torch.int32) -> torch.Tensor:
     """0/1 block mask -> int32 read-list rows ``[L, start0, end0, ...]`` (descending ranges, both ends inclusive, zero padded).
+    ``dtype=torch.int16``: int16 rows (``la_blockmask_to_lists_ex``; for rows of at most 32 767 entries), what a launch with int16 lists reads.
 
     A mask on the GPU is converted by the library (``la_blockmask_to_lists``, one wave per row, no host round trip except the optional
     ``validate`` read of the empty-row counter): mask ``[q_tiles, k_tiles]`` (shared), ``[batch, q_tiles, k_tiles]`` or
@@ -244,12 +245,14 @@ def blockmask_to_lists(blockmask: torch.Tensor, k_tiles_valid: Optional[torch.Te
     host or on the device. ``validate=True`` costs one blocking read of a 4-byte counter on the device path (callers on a hot path, such
     as ``flash_blocksparse_attn_qkvpacked_func`` with a mask converted once, pass ``validate=False`` after the first conversion). A mask
     in host memory goes through the tensor-op form (host bookkeeping, like ``init_skip_list``); it has no ``q_tiles_valid``."""
+    from .skip_lists import check_list_dtype
+    check_list_dtype(dtype, blockmask.shape[-1])
     if not blockmask.is_cuda:
         if q_tiles_valid is not None:
             raise NotImplementedError("q_tiles_valid: device masks only")
         if k_tiles_valid is not None and blockmask.dim() >= 3 and torch.as_tensor(k_tiles_valid).numel() != blockmask.shape[0]:
             raise ValueError("k_tiles_valid / q_tiles_valid must hold one entry per batch")       # the device path's rule (ADVICE r4)
-        out = _blockmask_to_lists_host(blockmask, k_tiles_valid, validate)
+        out = _blockmask_to_lists_host(blockmask, k_tiles_valid, validate).to(dtype)
         if batch is not None and heads is not None and out.dim() < 4:
             out = (out[None, None] if out.dim() == 2 else out[:, None]).expand(batch, heads, -1, -1).contiguous()
         return out
@@ -270,7 +273,7 @@ def blockmask_to_lists(blockmask: torch.Tensor, k_tiles_valid: Optional[torch.Te
         raise ValueError("blockmask batch/heads do not match")
     sb = m.stride(0) if len(lead) >= 1 and lead[0] == B and B > 1 else 0
     sh = m.stride(1) if len(lead) == 2 and lead[1] == H and H > 1 else 0
-    lists = torch.empty((B, H, qt, kt + 1), dtype=torch.int32, device=m.device)
+    lists = torch.empty((B, H, qt, kt + 1), dtype=dtype, device=m.device)
     empty = torch.empty(1, dtype=torch.int32, device=m.device) if validate else None
 
     def _valid(t):
@@ -282,10 +285,10 @@ def blockmask_to_lists(blockmask: torch.Tensor, k_tiles_valid: Optional[torch.Te
         return t
     kv, qv = _valid(k_tiles_valid), _valid(q_tiles_valid)
     with torch.cuda.device(m.device):
-        rc = _cabi.load().la_blockmask_to_lists(m.data_ptr(), sb, sh, B, H, qt, kt, qv.data_ptr() if qv is not None else None,
-                                                kv.data_ptr() if kv is not None else None, lists.data_ptr(),
-                                                empty.data_ptr() if empty is not None else None,
-                                                torch.cuda.current_stream(m.device).cuda_stream)
+        rc = _cabi.load().la_blockmask_to_lists_ex(m.data_ptr(), sb, sh, B, H, qt, kt, qv.data_ptr() if qv is not None else None,
+                                                   kv.data_ptr() if kv is not None else None, lists.data_ptr(), lists.element_size(),
+                                                   empty.data_ptr() if empty is not None else None,
+                                                   torch.cuda.current_stream(m.device).cuda_stream)
     if rc != _cabi.LA_OK:
         raise RuntimeError(f"la_blockmask_to_lists: {_cabi.status_string(rc)}")
     if validate and int(empty.item()) != 0:

@@ -25,7 +25,8 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 //   fp8 head_dim 128: x64-fp8. The skip lists are indexed by the selected kernel's tile, so
 //   la_get_tile_sizes_ex and la_fwd must agree on it: both call uses_128row().
 constexpr uint32_t kKnownFlags = LA_FLAG_V_PREPARED | LA_FLAG_STATIC_SCHED | LA_FLAG_KERNEL_128ROW | LA_FLAG_EXACT_RESCALE |
-                                LA_FLAG_FP8_MFMA_ROWSUM | LA_FLAG_FP8_ENCODED_P | LA_FLAG_HALF_VOTE;
+                                LA_FLAG_FP8_MFMA_ROWSUM | LA_FLAG_FP8_ENCODED_P | LA_FLAG_HALF_VOTE | LA_FLAG_LIST_INT16;
+constexpr int kListInt16MaxRow = 32767;           // LA_FLAG_LIST_INT16: a row of k_tiles + 1 entries whose values (tile indices, counts <= k_tiles) fit int16
 bool uses_128row(int head_dim, int element_size, uint32_t flags) {      // the flag changes the q-tile (256 -> 128 rows) at head dims 64 and 128
     return element_size == 2 && (head_dim == 128 || head_dim == 64) && (flags & LA_FLAG_KERNEL_128ROW) != 0;
 }
@@ -94,7 +95,7 @@ const char* la_status_string(int status) {
         case LA_ERR_LISTS: return "attn_read_list and attn_write_list must be given together";
         case LA_ERR_UNSUPPORTED: return "feature outside the QK-Skip hot path (head_dim_v != head_dim, unknown flags, skip lists with cu_seqlens on the 128-row kernels or, for bf16 / fp16, above head_dim 128)";
         case LA_ERR_LAUNCH: return "HIP kernel launch failed (see la_last_hip_error)";
-        case LA_ERR_SEQLEN: return "seqlen_k too long: the expanded skip list does not fit in LDS (dense launches are cut into runs and merged when the workspace of la_fwd_workspace_bytes() is given)";
+        case LA_ERR_SEQLEN: return "seqlen_k too long: the expanded skip list does not fit in LDS (dense launches are cut into runs and merged when the workspace of la_fwd_workspace_bytes() is given)";   // also: LA_FLAG_LIST_INT16 / list_elem_size 2 with k_tiles + 1 > 32767 (the message is pinned by the callers' tests)
         case LA_ERR_WORKSPACE: return "fp8 needs a 16-byte aligned workspace of la_fwd_workspace_bytes() bytes";
         case LA_ERR_Q_WINDOW: return "q_tile_begin/q_tile_count outside the q-tiles of this problem (LA_FLAG_HALF_VOTE: windows start on an even q-tile and hold an even number unless they reach the last)";
         default: return "unknown la_status";
@@ -169,6 +170,8 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     if (a->head_dim % (fp8 ? 16 : 8) != 0) return LA_ERR_HEAD_DIM;                         // flash_api.cpp:854-856
     if (a->head_dim_v != a->head_dim) return LA_ERR_UNSUPPORTED;
     if (a->reserved0 != 0 || (a->flags & ~kKnownFlags) != 0) return LA_ERR_UNSUPPORTED;
+    if ((a->flags & LA_FLAG_LIST_INT16) && a->read_list == nullptr && a->write_list == nullptr)
+        return LA_ERR_UNSUPPORTED;                     // the flag types the list pointers: a launch without lists has nothing it could mean
     int bm = 0, bn = 0;
     const int trc = la_get_tile_sizes_ex(a->head_dim, esize, a->flags, &bm, &bn);
     if (trc != LA_OK) return trc;
@@ -238,6 +241,8 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     p.q_tiles = (a->seqlen_q + bm - 1) / bm;
     p.list_q_tiles = p.q_tiles;
     p.k_tiles = (a->seqlen_k + bn - 1) / bn;
+    if ((a->flags & LA_FLAG_LIST_INT16) && p.k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;    // before any launch
+    p.list_int16 = (a->flags & LA_FLAG_LIST_INT16) ? 1 : 0;
     const bool half_vote = uses_half_vote(a->head_dim, esize, a->flags);
     if (a->q_tile_count == 0) {
         if (a->q_tile_begin != 0) return LA_ERR_Q_WINDOW;
@@ -363,14 +368,37 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     return LA_OK;
 }
 
-int la_skip_list_stats(const int32_t* list, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
-                       int64_t* out_counts, void* stream_) {
+int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
+                          int64_t* out_counts, void* stream_) {
     if (!list || !out_counts) return LA_ERR_NULL_ARG;
+    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
     if (n_batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
+    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
     const int64_t rows = static_cast<int64_t>(n_batch) * num_heads * q_tiles;
     if (rows > 0x7fffffffLL) return LA_ERR_SHAPE;
-    const hipError_t err = la::launch_skip_list_stats(list, static_cast<int>(rows), k_tiles, out_counts,
+    const hipError_t err = la::launch_skip_list_stats(list, list_elem_size, static_cast<int>(rows), k_tiles, out_counts,
                                                       static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
+int la_skip_list_stats(const int32_t* list, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
+                       int64_t* out_counts, void* stream_) {
+    return la_skip_list_stats_ex(list, 4, n_batch, num_heads, q_tiles, k_tiles, out_counts, stream_);
+}
+
+int la_blockmask_to_lists_ex(const uint8_t* blockmask, int64_t mask_batch_stride, int64_t mask_head_stride, int32_t batch,
+                             int32_t num_heads, int32_t q_tiles, int32_t k_tiles, const int32_t* q_tiles_valid,
+                             const int32_t* k_tiles_valid, void* lists, int32_t list_elem_size, int32_t* empty_rows, void* stream_) {
+    if (!blockmask || !lists) return LA_ERR_NULL_ARG;
+    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
+    if (batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
+    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    if (mask_batch_stride < 0 || mask_head_stride < 0) return LA_ERR_STRIDE;
+    if (static_cast<int64_t>(batch) * num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
+    const hipError_t err = la::launch_blockmask_to_lists(blockmask, mask_batch_stride, mask_head_stride, batch, num_heads, q_tiles,
+                                                         k_tiles, q_tiles_valid, k_tiles_valid, lists, list_elem_size, empty_rows,
+                                                         static_cast<hipStream_t>(stream_));
     if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
     return LA_OK;
 }
@@ -378,15 +406,8 @@ int la_skip_list_stats(const int32_t* list, int32_t n_batch, int32_t num_heads, 
 int la_blockmask_to_lists(const uint8_t* blockmask, int64_t mask_batch_stride, int64_t mask_head_stride, int32_t batch,
                           int32_t num_heads, int32_t q_tiles, int32_t k_tiles, const int32_t* q_tiles_valid,
                           const int32_t* k_tiles_valid, int32_t* lists, int32_t* empty_rows, void* stream_) {
-    if (!blockmask || !lists) return LA_ERR_NULL_ARG;
-    if (batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
-    if (mask_batch_stride < 0 || mask_head_stride < 0) return LA_ERR_STRIDE;
-    if (static_cast<int64_t>(batch) * num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
-    const hipError_t err = la::launch_blockmask_to_lists(blockmask, mask_batch_stride, mask_head_stride, batch, num_heads, q_tiles,
-                                                         k_tiles, q_tiles_valid, k_tiles_valid, lists, empty_rows,
-                                                         static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return la_blockmask_to_lists_ex(blockmask, mask_batch_stride, mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid,
+                                    k_tiles_valid, lists, 4, empty_rows, stream_);
 }
 
 int la_device_slots(int head_dim, int element_size, uint32_t flags, int* compute_units, int* workgroups_per_cu) {

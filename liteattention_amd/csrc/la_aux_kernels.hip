@@ -19,7 +19,8 @@
 
 namespace la {
 
-__global__ void __launch_bounds__(256) skip_list_stats_kernel(const int32_t* __restrict__ list, int rows, int k_tiles,
+template <typename ListT>       // int32_t, or int16_t (la_skip_list_stats_ex with list_elem_size 2): element-wide loads only
+__global__ void __launch_bounds__(256) skip_list_stats_kernel(const ListT* __restrict__ list, int rows, int k_tiles,
                                                                unsigned long long* out) {
     // one wave per row; lanes stride over the ranges of the row
     const int lane = threadIdx.x & 63;
@@ -27,7 +28,7 @@ __global__ void __launch_bounds__(256) skip_list_stats_kernel(const int32_t* __r
     const int n_waves = (gridDim.x * blockDim.x) >> 6;
     unsigned long long acc = 0;
     for (int r = wave_in_grid; r < rows; r += n_waves) {
-        const int32_t* row = list + static_cast<int64_t>(r) * (k_tiles + 1);
+        const ListT* row = list + static_cast<int64_t>(r) * (k_tiles + 1);
         int len = row[0];
         if (len < 2) len = 2;   // the reader always walks the first range (mainloop...:93-101)
         if (len > k_tiles) len = k_tiles;
@@ -41,15 +42,19 @@ __global__ void __launch_bounds__(256) skip_list_stats_kernel(const int32_t* __r
     if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = static_cast<unsigned long long>(rows);
 }
 
-hipError_t launch_skip_list_stats(const int32_t* list, int rows, int k_tiles, int64_t* out, hipStream_t stream) {
+hipError_t launch_skip_list_stats(const void* list, int list_elem_size, int rows, int k_tiles, int64_t* out, hipStream_t stream) {
     hipError_t err = hipMemsetAsync(out, 0, 2 * sizeof(int64_t), stream);
     if (err != hipSuccess) return err;
     (void)hipGetLastError();
     int blocks = (rows + 3) / 4;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(skip_list_stats_kernel, dim3(blocks), dim3(256), 0, stream, list, rows, k_tiles,
-                       reinterpret_cast<unsigned long long*>(out));
+    if (list_elem_size == 2)
+        hipLaunchKernelGGL(skip_list_stats_kernel<int16_t>, dim3(blocks), dim3(256), 0, stream, static_cast<const int16_t*>(list), rows, k_tiles,
+                           reinterpret_cast<unsigned long long*>(out));
+    else
+        hipLaunchKernelGGL(skip_list_stats_kernel<int32_t>, dim3(blocks), dim3(256), 0, stream, static_cast<const int32_t*>(list), rows, k_tiles,
+                           reinterpret_cast<unsigned long long*>(out));
     return hipGetLastError();
 }
 
@@ -61,12 +66,13 @@ hipError_t launch_skip_list_stats(const int32_t* list, int rows, int k_tiles, in
 // memory latencies, not 19. STAGED (rows of up to ~4 000 tiles): the pairs are scattered into an LDS copy of the row and the row leaves in
 // coalesced 256-byte wave stores, zero padding included; otherwise they go straight to global memory (partial, scattered stores).
 // Round 4 at the Wan2.1 geometry (11 840 rows x 1 183 ints, 56-70 MB): first form 35-44 us, one load per byte 29-32 us, staged: tools/blockmask_bench.py.
-template <bool STAGED>
+// ListT: the element type of the rows written (int32_t, or int16_t: la_blockmask_to_lists_ex with list_elem_size 2); the LDS stage stays int32.
+template <bool STAGED, typename ListT>
 __global__ void __launch_bounds__(256) blockmask_to_lists_kernel(const uint8_t* __restrict__ mask, int64_t mask_batch_stride,
                                                                   int64_t mask_head_stride, int batch, int num_heads, int q_tiles,
                                                                   int k_tiles, const int32_t* __restrict__ q_tiles_valid,
                                                                   const int32_t* __restrict__ k_tiles_valid,
-                                                                  int32_t* __restrict__ lists, int32_t* __restrict__ empty_rows) {
+                                                                  ListT* __restrict__ lists, int32_t* __restrict__ empty_rows) {
     constexpr int G = 8;                         // chunks of 64 positions whose loads are in flight together
     extern __shared__ int32_t bm_rows[];         // STAGED: 4 waves x (k_tiles + 2) ints
     const int lane = threadIdx.x & 63;
@@ -79,7 +85,7 @@ __global__ void __launch_bounds__(256) blockmask_to_lists_kernel(const uint8_t* 
         const int64_t bh = r / q_tiles;
         const int h = static_cast<int>(bh % num_heads), b = static_cast<int>(bh / num_heads);
         const uint8_t* mrow = mask + b * mask_batch_stride + h * mask_head_stride + static_cast<int64_t>(m) * k_tiles;
-        int32_t* out = lists + r * (k_tiles + 1);
+        ListT* out = lists + r * (k_tiles + 1);
         int kv = k_tiles_valid ? k_tiles_valid[b] : k_tiles;          // tiles >= kv do not exist for this sequence
         kv = kv < 0 ? 0 : (kv > k_tiles ? k_tiles : kv);
         const bool all = q_tiles_valid != nullptr && m >= q_tiles_valid[b];   // a q-tile past the sequence's end: never read; full corner
@@ -103,9 +109,14 @@ __global__ void __launch_bounds__(256) blockmask_to_lists_kernel(const uint8_t* 
                 const bool is_start = keep && !prev, is_end = keep && !next;
                 const unsigned long long sb = __ballot(is_start);
                 const int ridx = runs + __popcll(sb & ((2ull << lane) - 1ull)) - 1;       // the run this position belongs to
-                int32_t* const dst = STAGED ? stage : out;
-                if (is_start && 1 + 2 * ridx <= k_tiles) dst[1 + 2 * ridx] = t;
-                if (is_end && 2 + 2 * ridx <= k_tiles) dst[2 + 2 * ridx] = t;              // a last end behind the row is counted, not stored
+                // (a last end behind the row is counted, not stored)
+                if (STAGED) {
+                    if (is_start && 1 + 2 * ridx <= k_tiles) stage[1 + 2 * ridx] = t;
+                    if (is_end && 2 + 2 * ridx <= k_tiles) stage[2 + 2 * ridx] = t;
+                } else {
+                    if (is_start && 1 + 2 * ridx <= k_tiles) out[1 + 2 * ridx] = static_cast<ListT>(t);
+                    if (is_end && 2 + 2 * ridx <= k_tiles) out[2 + 2 * ridx] = static_cast<ListT>(t);
+                }
                 runs += __popcll(sb);
                 before = kb[c];
             }
@@ -117,12 +128,12 @@ __global__ void __launch_bounds__(256) blockmask_to_lists_kernel(const uint8_t* 
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            for (int i = lane; i <= k_tiles; i += 64) out[i] = i == 0 ? 2 * runs : (i <= 2 * runs ? stage[i] : 0);
+            for (int i = lane; i <= k_tiles; i += 64) out[i] = static_cast<ListT>(i == 0 ? 2 * runs : (i <= 2 * runs ? stage[i] : 0));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         } else {
             for (int i = 2 * runs + 1 + lane; i <= k_tiles; i += 64) out[i] = 0;
-            if (lane == 0) out[0] = 2 * runs;
+            if (lane == 0) out[0] = static_cast<ListT>(2 * runs);
         }
         if (lane == 0 && runs == 0 && empty_rows != nullptr) atomicAdd(empty_rows, 1);
     }
@@ -130,7 +141,7 @@ __global__ void __launch_bounds__(256) blockmask_to_lists_kernel(const uint8_t* 
 
 hipError_t launch_blockmask_to_lists(const uint8_t* mask, int64_t mask_batch_stride, int64_t mask_head_stride, int batch,
                                      int num_heads, int q_tiles, int k_tiles, const int32_t* q_tiles_valid,
-                                     const int32_t* k_tiles_valid, int32_t* lists, int32_t* empty_rows, hipStream_t stream) {
+                                     const int32_t* k_tiles_valid, void* lists, int list_elem_size, int32_t* empty_rows, hipStream_t stream) {
     if (empty_rows != nullptr) {
         const hipError_t err = hipMemsetAsync(empty_rows, 0, sizeof(int32_t), stream);
         if (err != hipSuccess) return err;
@@ -140,12 +151,24 @@ hipError_t launch_blockmask_to_lists(const uint8_t* mask, int64_t mask_batch_str
     if (blocks > 16384) blocks = 16384;      // >> 256 CUs; rows beyond are taken by the grid-stride loop
     (void)hipGetLastError();
     const size_t lds = 4 * (static_cast<size_t>(k_tiles) + 2) * sizeof(int32_t);
-    if (lds <= 64 * 1024)
-        hipLaunchKernelGGL(blockmask_to_lists_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(256), lds, stream, mask, mask_batch_stride,
-                           mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid, k_tiles_valid, lists, empty_rows);
-    else
-        hipLaunchKernelGGL(blockmask_to_lists_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, mask, mask_batch_stride,
-                           mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid, k_tiles_valid, lists, empty_rows);
+    const dim3 grid(static_cast<unsigned>(blocks));
+    if (list_elem_size == 2) {
+        int16_t* const l16 = static_cast<int16_t*>(lists);
+        if (lds <= 64 * 1024)
+            hipLaunchKernelGGL((blockmask_to_lists_kernel<true, int16_t>), grid, dim3(256), lds, stream, mask, mask_batch_stride,
+                               mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid, k_tiles_valid, l16, empty_rows);
+        else
+            hipLaunchKernelGGL((blockmask_to_lists_kernel<false, int16_t>), grid, dim3(256), 0, stream, mask, mask_batch_stride,
+                               mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid, k_tiles_valid, l16, empty_rows);
+    } else {
+        int32_t* const l32 = static_cast<int32_t*>(lists);
+        if (lds <= 64 * 1024)
+            hipLaunchKernelGGL((blockmask_to_lists_kernel<true, int32_t>), grid, dim3(256), lds, stream, mask, mask_batch_stride,
+                               mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid, k_tiles_valid, l32, empty_rows);
+        else
+            hipLaunchKernelGGL((blockmask_to_lists_kernel<false, int32_t>), grid, dim3(256), 0, stream, mask, mask_batch_stride,
+                               mask_head_stride, batch, num_heads, q_tiles, k_tiles, q_tiles_valid, k_tiles_valid, l32, empty_rows);
+    }
     return hipGetLastError();
 }
 

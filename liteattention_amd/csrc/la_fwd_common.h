@@ -74,8 +74,12 @@ struct ListReader {
 // `endflags` (bit p set = position p is the last tile of its read-list range) and the vote bits `doflags` (bit p
 // set = some row of the q-tile voted "do" for position p). No global loads of the read list: real lists hold
 // hundreds of ranges per row and two dependent global loads per range cost more than the tiles they describe.
+// ListT (every list reader / writer below): the element type of the read / write list rows - int32_t, or int16_t under LA_FLAG_LIST_INT16.
+// An entry is a tile index below k_tiles or a count of at most k_tiles (la_fwd refuses the flag when k_tiles + 1 > 32767), every
+// access is one element wide (an int16 row may start on any 2-byte boundary), and the must-do row stays int32 in both forms.
+template <typename ListT>
 __device__ __noinline__ void write_skip_list(const int* seq, const unsigned* endflags, const unsigned* doflags,
-                                             int n_tiles, int* __restrict__ write_row,
+                                             int n_tiles, ListT* __restrict__ write_row,
                                              const int* __restrict__ must_do_row, int k_tiles) {
     ListReader md;
     const bool has_md = must_do_row != nullptr;
@@ -93,23 +97,24 @@ __device__ __noinline__ void write_skip_list(const int* seq, const unsigned* end
             skip = skip && !must_do;
         }
         if (skip != is_skipping) {                                       // :163-168
-            if (w <= k_tiles) write_row[w] = n;
+            if (w <= k_tiles) write_row[w] = static_cast<ListT>(n);
             ++w;
             is_skipping = skip;
         }
         if ((endflags[pos >> 5] >> (pos & 31)) & 1u) {                   // record_range_end :173-181 (raw flag)
             is_skipping = true;
-            if (!raw_skip) { if (w <= k_tiles) write_row[w] = n; ++w; }
+            if (!raw_skip) { if (w <= k_tiles) write_row[w] = static_cast<ListT>(n); ++w; }
         }
     }
-    write_row[0] = min(w - 1, k_tiles);                                  // finalize :185-191
+    write_row[0] = static_cast<ListT>(min(w - 1, k_tiles));                                  // finalize :185-191
 }
 
 // The same over the positions `live` selects (half-vote kernels: bit p set = this list's walk holds position p of the union sequence;
 // the other positions belong to the other half's list only and do not exist for this writer; the first LIVE position is the list's
 // first walked tile).
+template <typename ListT>
 __device__ __forceinline__ void write_skip_list_live(const int* seq, const unsigned* endflags, const unsigned* doflags, const unsigned* live,
-                                                  int n_tiles, int* __restrict__ write_row,
+                                                  int n_tiles, ListT* __restrict__ write_row,
                                                   const int* __restrict__ must_do_row, int k_tiles) {
     ListReader md;
     const bool has_md = must_do_row != nullptr;
@@ -128,16 +133,16 @@ __device__ __forceinline__ void write_skip_list_live(const int* seq, const unsig
             skip = skip && !must_do;
         }
         if (skip != is_skipping) {
-            if (w <= k_tiles) write_row[w] = n;
+            if (w <= k_tiles) write_row[w] = static_cast<ListT>(n);
             ++w;
             is_skipping = skip;
         }
         if ((endflags[pos >> 5] >> (pos & 31)) & 1u) {
             is_skipping = true;
-            if (!raw_skip) { if (w <= k_tiles) write_row[w] = n; ++w; }
+            if (!raw_skip) { if (w <= k_tiles) write_row[w] = static_cast<ListT>(n); ++w; }
         }
     }
-    write_row[0] = min(w - 1, k_tiles);
+    write_row[0] = static_cast<ListT>(min(w - 1, k_tiles));
 }
 
 // Inclusive prefix sum over the 64 lanes of a wave on the DPP datapath (round 5): four row_shr steps scan each 16-lane row, then
@@ -162,8 +167,9 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 // advances at most one range per flagged tile, mainloop...:156-159), but for lists of at most ONE range - the
 // default [0,0] and the single-range case - membership reduces to `n <= start && n > end` whatever the reader
 // state; longer must-do lists take the serial path, which reproduces the state machine literally.
+template <typename ListT>
 __device__ __forceinline__ void write_skip_list_wave(const int* seq, const unsigned* endflags, const unsigned* doflags,
-                                                     int n_tiles, int* __restrict__ write_row,
+                                                     int n_tiles, ListT* __restrict__ write_row,
                                                      const int* __restrict__ must_do_row, int k_tiles, int lane) {
     int md_start = 0, md_end = 0;
     if (must_do_row != nullptr) {
@@ -197,19 +203,20 @@ __device__ __forceinline__ void write_skip_list_wave(const int* seq, const unsig
         const bool e2 = live && is_end && !raw;
         const unsigned long long e1_b = __ballot(e1), e2_b = __ballot(e2);
         int slot = w + __popcll(e1_b & below) + __popcll(e2_b & below);
-        if (e1) { if (slot <= k_tiles) write_row[slot] = n; ++slot; }
-        if (e2) { if (slot <= k_tiles) write_row[slot] = n; }
+        if (e1) { if (slot <= k_tiles) write_row[slot] = static_cast<ListT>(n); ++slot; }
+        if (e2) { if (slot <= k_tiles) write_row[slot] = static_cast<ListT>(n); }
         w += __popcll(e1_b) + __popcll(e2_b);
         carry_skip = static_cast<int>((after_b >> 63) & 1ull);
     }
-    if (lane == 0) write_row[0] = min(w - 1, k_tiles);
+    if (lane == 0) write_row[0] = static_cast<ListT>(min(w - 1, k_tiles));
 }
 
 // The same for ONE HALF of a half-vote workgroup (LA_FLAG_HALF_VOTE): the walk was the union of two lists, `livebits` (bit p = this
 // half's list holds position p) selects this list's positions; the others do not exist for this writer: the state a position sees is
 // the one its nearest LIVE predecessor left, and the first live position is the list's first walked tile (never flagged, :1804-1805).
+template <typename ListT>
 __device__ __forceinline__ void write_skip_list_wave_live(const int* seq, const unsigned* endflags, const unsigned* doflags,
-                                                          const unsigned* livebits, int n_tiles, int* __restrict__ write_row,
+                                                          const unsigned* livebits, int n_tiles, ListT* __restrict__ write_row,
                                                           const int* __restrict__ must_do_row, int k_tiles, int lane) {
     int md_start = 0, md_end = 0;
     if (must_do_row != nullptr) {
@@ -243,15 +250,15 @@ __device__ __forceinline__ void write_skip_list_wave_live(const int* seq, const 
         const bool e2 = live && is_end && !raw;
         const unsigned long long e1_b = __ballot(e1), e2_b = __ballot(e2);
         int slot = w + __popcll(e1_b & below) + __popcll(e2_b & below);
-        if (e1) { if (slot <= k_tiles) write_row[slot] = n; ++slot; }
-        if (e2) { if (slot <= k_tiles) write_row[slot] = n; }
+        if (e1) { if (slot <= k_tiles) write_row[slot] = static_cast<ListT>(n); ++slot; }
+        if (e2) { if (slot <= k_tiles) write_row[slot] = static_cast<ListT>(n); }
         w += __popcll(e1_b) + __popcll(e2_b);
         if (live_b != 0ull) {
             carry_skip = static_cast<int>((after_b >> (63 - __clzll(static_cast<long long>(live_b)))) & 1ull);
             seen = true;
         }
     }
-    if (lane == 0) write_row[0] = min(w - 1, k_tiles);
+    if (lane == 0) write_row[0] = static_cast<ListT>(min(w - 1, k_tiles));
 }
 
 // o = 0, lse = +inf for `nrows` query rows of one (sequence, head) that has no keys (flash_api.cpp:1241-1245), by the whole
@@ -427,20 +434,21 @@ __device__ __forceinline__ int next_work_item(const FwdParams& p, int chunk, int
 // lane writes its own tiles. The first range is walked even when len == 0 (mainloop...:93-101); indices are
 // clamped to [0, k_tiles) and the total to k_tiles (memory safety on malformed lists). `endflags` (zeroed by the
 // caller) gets one bit per range end.
-__device__ __forceinline__ int expand_read_list(const int* __restrict__ row, int* seq, unsigned* endflags, int k_tiles,
+template <typename ListT>
+__device__ __forceinline__ int expand_read_list(const ListT* __restrict__ row, int* seq, unsigned* endflags, int k_tiles,
                                                 int lane) {
-    const int len = max(row[0], 2);
+    const int len = max(static_cast<int>(row[0]), 2);
     const int n_ranges = min(len >> 1, (k_tiles + 1) >> 1);
     int pos = 0;
     for (int base = 0; base < n_ranges; base += 64) {
         const int r = base + lane;
         int start = 0, cnt = 0;
         if (r < n_ranges) {
-            // the row is k_tiles + 1 ints: a pair whose end would lie behind it (odd k_tiles with (k_tiles + 1) / 2 ranges; k_tiles = 1)
+            // the row is k_tiles + 1 entries: a pair whose end would lie behind it (odd k_tiles with (k_tiles + 1) / 2 ranges; k_tiles = 1)
             // reads as (0, 0) - the oracle's reader_load rule - except the first pair, whose start is always in the row
             const bool in_row = 2 + 2 * r <= k_tiles;
-            start = (in_row || r == 0) ? min(max(row[1 + 2 * r], 0), k_tiles - 1) : 0;
-            const int end = in_row ? min(max(row[2 + 2 * r], 0), k_tiles - 1) : 0;
+            start = (in_row || r == 0) ? min(max(static_cast<int>(row[1 + 2 * r]), 0), k_tiles - 1) : 0;
+            const int end = in_row ? min(max(static_cast<int>(row[2 + 2 * r]), 0), k_tiles - 1) : 0;
             cnt = max(start - end + 1, 0);
             if (r == 0) cnt = max(cnt, 1);        // the first tile of the first range is always walked (mainloop...:1614-1660)
         }
@@ -470,22 +478,31 @@ __device__ __forceinline__ int expand_read_list(const int* __restrict__ row, int
     return pos;
 }
 
+// The shells pick ListT per launch by a wave-uniform test (FwdParams::list_int16), not by a kernel template parameter: the statement
+// is compiled once per element type inside one kernel, `ListT` names the type in it.
+#define LA_WITH_LIST_TYPE(is_int16, ...)                              \
+    do {                                                              \
+        if (is_int16) { using ListT = int16_t; __VA_ARGS__; }         \
+        else { using ListT = int32_t; __VA_ARGS__; }                  \
+    } while (0)
+
 // Half-vote kernels: one read-list row -> a bitmap over the key tiles (bit t = the list names tile t) and the bitmap of its range
 // ends. Same clamps as expand_read_list (indices into [0, k_tiles), at most (k_tiles + 1) / 2 ranges, the first tile of the first
 // range always walked); the list is read as a SET - a well-formed list (descending, disjoint ranges: everything a writer, the
 // initial list or a block mask produces) walks exactly its tiles in descending order either way, a malformed one (overlapping or
 // ascending ranges) walks each named tile once. One wave; `in_bits` / `end_bits` zeroed by the caller.
-__device__ __forceinline__ void expand_read_list_bits(const int* __restrict__ row, unsigned* in_bits, unsigned* end_bits, int k_tiles,
+template <typename ListT>
+__device__ __forceinline__ void expand_read_list_bits(const ListT* __restrict__ row, unsigned* in_bits, unsigned* end_bits, int k_tiles,
                                                       int lane) {
-    const int len = max(row[0], 2);
+    const int len = max(static_cast<int>(row[0]), 2);
     const int n_ranges = min(len >> 1, (k_tiles + 1) >> 1);
     for (int base = 0; base < n_ranges; base += 64) {
         const int r = base + lane;
         int hi = 0, cnt = 0;
         if (r < n_ranges) {
             const bool in_row = 2 + 2 * r <= k_tiles;
-            hi = (in_row || r == 0) ? min(max(row[1 + 2 * r], 0), k_tiles - 1) : 0;
-            const int end = in_row ? min(max(row[2 + 2 * r], 0), k_tiles - 1) : 0;
+            hi = (in_row || r == 0) ? min(max(static_cast<int>(row[1 + 2 * r]), 0), k_tiles - 1) : 0;
+            const int end = in_row ? min(max(static_cast<int>(row[2 + 2 * r]), 0), k_tiles - 1) : 0;
             cnt = max(hi - end + 1, 0);
             if (r == 0) cnt = max(cnt, 1);
         }

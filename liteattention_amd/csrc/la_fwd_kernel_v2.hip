@@ -150,7 +150,8 @@ la_fwd_v2_kernel(const FwdParams p) {                   // F16 selects fp16 inst
             if (base + tid < 2 * ((k_tiles + 31) / 32)) doflags[base + tid] = 0u;
         __syncthreads();
         if (wave == 0) {
-            const int n = expand_read_list(p.read_list + list_off, seq, endflags, k_tiles, lane);
+            int n;
+            LA_WITH_LIST_TYPE(p.list_int16, n = expand_read_list(static_cast<const ListT*>(p.read_list) + list_off, seq, endflags, k_tiles, lane));
             if (lane == 0) meta[0] = n;
         }
     }
@@ -416,7 +417,7 @@ la_fwd_v2_kernel(const FwdParams p) {                   // F16 selects fp16 inst
         if (wave == 0 && p.write_list != nullptr) {
             const int* md = p.must_do_list ? (p.must_do_is_1d ? p.must_do_list : p.must_do_list + list_off) : nullptr;
 #ifndef LA_ABL_NOWRITER
-            write_skip_list_wave(seq, endflags, doflags, n_tiles, p.write_list + list_off, md, k_tiles, lane);
+            LA_WITH_LIST_TYPE(p.list_int16, write_skip_list_wave(seq, endflags, doflags, n_tiles, static_cast<ListT*>(p.write_list) + list_off, md, k_tiles, lane));
 #endif
         }
     }

@@ -33,9 +33,9 @@ struct FwdParams {
     float thr;
     unsigned* work_counter; // x64 + lists: zeroed ticket counter in caller workspace -> persistent workgroups take work items
                             // dynamically (skip lists make items unequal); nullptr -> one workgroup per item, static XCD map
-    const int* read_list;
-    int* write_list;
-    const int* must_do_list;
+    const void* read_list;  // rows of int32_t, or of int16_t when list_int16 (LA_FLAG_LIST_INT16): same geometry, offsets in ELEMENTS
+    void* write_list;
+    const int* must_do_list;   // int32 in both forms
     int must_do_is_1d;
     // fp8 only: per-(batch, head) descales, NULL = 1.0 (flash_api.cpp:1003-1022); strides in elements
     const float* q_descale;
@@ -49,6 +49,7 @@ struct FwdParams {
     const int* cu_seqlens_q;
     const int* cu_seqlens_k;
     int64_t total_q;
+    int list_int16;         // 1 = read_list / write_list hold int16_t (wave-uniform: the shells pick the element type of the list readers / writers by it)
 };
 
 // Varlen launches (la_fwd_args.cu_seqlens_*): sequence b's own rows and lengths.
@@ -97,10 +98,10 @@ hipError_t launch_prep_v_fp8(const void* v, int64_t v_batch_stride, int64_t v_ro
                              const int* cu_seqlens_k = nullptr);
 hipError_t launch_empty_k_fill(uint16_t* o, float* lse, int64_t o_batch_stride, int64_t o_row_stride, int64_t o_head_stride,
                                int batch, int seqlen_q, int num_heads, int head_dim_v, hipStream_t stream);
-hipError_t launch_skip_list_stats(const int32_t* list, int rows, int k_tiles, int64_t* out, hipStream_t stream);
+hipError_t launch_skip_list_stats(const void* list, int list_elem_size, int rows, int k_tiles, int64_t* out, hipStream_t stream);
 hipError_t launch_blockmask_to_lists(const uint8_t* mask, int64_t mask_batch_stride, int64_t mask_head_stride, int batch,
                                      int num_heads, int q_tiles, int k_tiles, const int32_t* q_tiles_valid,
-                                     const int32_t* k_tiles_valid, int32_t* lists, int32_t* empty_rows, hipStream_t stream);
+                                     const int32_t* k_tiles_valid, void* lists, int list_elem_size, int32_t* empty_rows, hipStream_t stream);
 hipError_t launch_combine(const void* o_partial, bool partial_is_16bit, bool f16, const float* lse_partial, uint16_t* o,
                           float* lse, int num_splits, int batch, int seqlen_q, int num_heads, int head_dim_v,
                           hipStream_t stream, bool out_f32 = false, int64_t o_batch_stride = 0, int64_t o_row_stride = 0,

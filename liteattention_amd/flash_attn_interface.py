@@ -116,11 +116,28 @@ def q_tiles_per_item(head_dim: int, element_size: int) -> int:
     return 2 if half else 1
 
 
-def _check_list(t: Optional[torch.Tensor], name: str, q: torch.Tensor) -> Optional[int]:
-    """flash_api.cpp:919-963: int32, 4-D, contiguous (same messages)."""
+LIST_DTYPES = (torch.int32, torch.int16)      # element types of read / write lists (int16: LA_FLAG_LIST_INT16); must-do lists are int32
+
+
+def _list_flags(attn_read_list: Optional[torch.Tensor], attn_write_list: Optional[torch.Tensor]) -> int:
+    """Dtype rule of the read / write list pair, checked before anything touches a device: each is int32 or int16 (anything else keeps the
+    reference's message, flash_api.cpp:919-963), and the two share one dtype. Returns the ``la_fwd_args.flags`` bit the pair asks
+    for: LA_FLAG_LIST_INT16 for int16 lists, 0 for int32 lists or none."""
+    for name, t in (("attn_read_list", attn_read_list), ("attn_write_list", attn_write_list)):
+        if t is not None and t.dtype not in LIST_DTYPES:
+            raise RuntimeError(f"{name} must be int32 tensor")
+    if attn_read_list is not None and attn_write_list is not None and attn_read_list.dtype != attn_write_list.dtype:
+        raise RuntimeError(f"attn_read_list and attn_write_list must have the same dtype (int32 or int16), got "
+                           f"{attn_read_list.dtype} and {attn_write_list.dtype}")
+    t = attn_read_list if attn_read_list is not None else attn_write_list
+    return _cabi.LA_FLAG_LIST_INT16 if t is not None and t.dtype == torch.int16 else 0
+
+
+def _check_list(t: Optional[torch.Tensor], name: str, q: torch.Tensor, dtypes=(torch.int32,)) -> Optional[int]:
+    """flash_api.cpp:919-963: int32 (read / write lists: or int16, ``dtypes``), 4-D, contiguous (same messages)."""
     if t is None:
         return None
-    if t.dtype != torch.int32:
+    if t.dtype not in dtypes:
         raise RuntimeError(f"{name} must be int32 tensor")
     if t.dim() != 4:
         raise RuntimeError(f"{name} must be 4D tensor with shape [batch, heads, q_blocks, k_blocks]")
@@ -288,8 +305,9 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     softmax_lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)                  # :887-892
     empty = torch.empty(0, dtype=torch.float32, device=q.device)
 
-    read_ptr = _check_list(attn_read_list, "attn_read_list", q)
-    write_ptr = _check_list(attn_write_list, "attn_write_list", q)
+    list_flags = _list_flags(attn_read_list, attn_write_list)
+    read_ptr = _check_list(attn_read_list, "attn_read_list", q, LIST_DTYPES)
+    write_ptr = _check_list(attn_write_list, "attn_write_list", q, LIST_DTYPES)
     if _must_do_is_1d and attn_must_do_list is not None:
         if attn_must_do_list.dtype != torch.int32 or attn_must_do_list.dim() != 1 or not attn_must_do_list.is_contiguous():
             raise RuntimeError("1-D attn_must_do_list must be a contiguous int32 vector")
@@ -331,7 +349,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     # caller-owned scratch (the C side allocates nothing): fp8 = the pre-transposed V tiles; bf16 with lists = the ticket
     # counter of the dynamic work distribution. Freed after the launch by the caching allocator's stream-ordered reuse.
     workspace = None
-    base_flags = ((host_flags & ~(_cabi.LA_FLAG_KERNEL_128ROW if is_fp8 else 0)) | _flags) & ~_scoped_clear()
+    base_flags = (((host_flags & ~(_cabi.LA_FLAG_KERNEL_128ROW if is_fp8 else 0)) | _flags) & ~_scoped_clear()) | list_flags
     a.flags = base_flags | (_cabi.LA_FLAG_STATIC_SCHED if _static_sched is True else 0)
     need = _cabi.load().la_fwd_workspace_bytes(ctypes.byref(a))
     if need < 0:
@@ -586,13 +604,14 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
             setattr(a, f"{name}_descale_batch_stride", t.stride(0))
             setattr(a, f"{name}_descale_head_stride", t.stride(1))
     workspace = None
+    list_flags = _list_flags(attn_read_list, attn_write_list)
     if attn_read_list is not None:
         q_tiles, k_tiles = -(-int(max_seqlen_q) // block_m), -(-max(int(max_seqlen_k), 0) // block_n)
         for name, t in (("attn_read_list", attn_read_list), ("attn_write_list", attn_write_list),
                         ("attn_must_do_list", None if _must_do_is_1d else attn_must_do_list)):
             if t is None:
                 continue
-            _check_list(t, name, q)
+            _check_list(t, name, q, (torch.int32,) if name == "attn_must_do_list" else LIST_DTYPES)
             if t.shape[0] < B or tuple(t.shape[1:]) != (H, q_tiles, k_tiles + 1):
                 raise RuntimeError(f"{name} must have shape [>=batch, heads, q_blocks, k_blocks + 1] = [>={B}, {H}, {q_tiles}, "
                                    f"{k_tiles + 1}] for max_seqlen ({max_seqlen_q}, {max_seqlen_k}) and tile sizes ({block_m}, {block_n}); "
@@ -616,6 +635,7 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     flags = (flags | _scoped_flags()) & ~_scoped_clear()
     a.flags = flags & ((_cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P | _cabi.LA_FLAG_STATIC_SCHED) if is_fp8 else
                        (_cabi.GEOMETRY_FLAGS | _cabi.LA_FLAG_EXACT_RESCALE | _cabi.LA_FLAG_STATIC_SCHED))
+    a.flags |= list_flags
     a.cu_seqlens_q, a.cu_seqlens_k, a.total_q = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), Tq
     if attn_read_list is not None or is_fp8:      # ticket counters of the dynamic work distribution (as in the fixed-length path); fp8: + the V^T tiles
         need = _cabi.load().la_fwd_workspace_bytes(ctypes.byref(a))
@@ -895,8 +915,8 @@ def flash_attn_combine(out_partial: torch.Tensor, lse_partial: torch.Tensor, out
 
 
 def skip_list_stats(skip_list: torch.Tensor, batch: Optional[int] = None) -> torch.Tensor:
-    """Device-side count of listed tiles: returns int64[2] = (listed tiles, rows). No host sync."""
-    if skip_list.dtype != torch.int32 or skip_list.dim() != 4 or not skip_list.is_contiguous():
+    """Device-side count of listed tiles: returns int64[2] = (listed tiles, rows). No host sync. int32 or int16 lists."""
+    if skip_list.dtype not in LIST_DTYPES or skip_list.dim() != 4 or not skip_list.is_contiguous():
         raise RuntimeError("skip list must be a contiguous int32 tensor [batch, heads, q_blocks, k_blocks + 1]")
     if not skip_list.is_cuda:
         raise RuntimeError("skip_list_stats has no CPU implementation")
@@ -904,8 +924,8 @@ def skip_list_stats(skip_list: torch.Tensor, batch: Optional[int] = None) -> tor
     out = torch.empty(2, dtype=torch.int64, device=skip_list.device)
     with torch.cuda.device(skip_list.device):
         stream = torch.cuda.current_stream(skip_list.device).cuda_stream
-        rc = _cabi.load().la_skip_list_stats(skip_list.data_ptr(), nb, skip_list.shape[1], skip_list.shape[2],
-                                             skip_list.shape[3] - 1, out.data_ptr(), ctypes.c_void_p(stream))
+        rc = _cabi.load().la_skip_list_stats_ex(skip_list.data_ptr(), skip_list.element_size(), nb, skip_list.shape[1], skip_list.shape[2],
+                                                skip_list.shape[3] - 1, out.data_ptr(), ctypes.c_void_p(stream))
     if rc != _cabi.LA_OK:
         raise RuntimeError(f"la_skip_list_stats: {_cabi.status_string(rc)}")
     return out

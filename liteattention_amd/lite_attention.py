@@ -20,6 +20,7 @@ from typing import Optional, Tuple, Union
 
 import torch
 
+from . import _cabi
 from . import skip_lists as _sl
 from .flash_attn_interface import flash_attn_func, get_tile_sizes
 
@@ -36,10 +37,14 @@ class LiteAttention:
     Args mirror the reference (lite_attention.py:36): ``enable_skipping=True``, ``threshold=-10.0``
     (log2 domain, must be negative unless env LITE_ATTENTION_DEBUG is set), ``max_batch_size=4`` (an upper bound: the lists are
     allocated for the batch actually seen and grow up to it, ``_skip_list[2, batch_seen, H, Qt, Kt+1]``).
+    ``list_dtype`` (extension): element type of the lists, ``torch.int32`` or ``torch.int16`` - int16 halves the list state (the only
+    state a layer keeps; INTEGRATION.md has the footprint table) and changes no result; default: LA_LIST_DTYPE in the environment, else int32.
     One instance per attention layer; not thread-safe (README.md:162-172)."""
 
-    def __init__(self, enable_skipping: bool = True, threshold: float = -10.0, max_batch_size: int = 4):
-        self._skip_list: Optional[Tensor] = None   # [2, max_batch, H, Qt, Kt+1] int32
+    def __init__(self, enable_skipping: bool = True, threshold: float = -10.0, max_batch_size: int = 4,
+                 list_dtype: Optional[torch.dtype] = None):
+        self.list_dtype = _sl.check_list_dtype(_cabi.default_list_dtype() if list_dtype is None else list_dtype, 0)
+        self._skip_list: Optional[Tensor] = None   # [2, max_batch, H, Qt, Kt+1] of list_dtype
         self._phase = 0                            # index of the buffer the NEXT call reads
         self._shape_key = None                     # what the lists were built for
         self._must_do_rows = {}                    # (tokens, block_n, row width, device) -> device row (LRU, _MUST_DO_ROWS_MAX)
@@ -70,13 +75,13 @@ class LiteAttention:
 
     @staticmethod
     def init_skip_list(batch, seq_len, heads, head_dim, v_colmajor, dtype, device, must_skip_list=None,
-                       seq_len_k=None) -> Tensor:
+                       seq_len_k=None, list_dtype: torch.dtype = torch.int32) -> Tensor:
         """``[2, batch, heads, q_tiles, k_tiles+1]`` int32, rows ``[2, k_tiles-1, 0, ...]`` (:113-153).
-        ``seq_len_k`` (extension) defaults to ``seq_len``."""
+        ``seq_len_k`` (extension) defaults to ``seq_len``; ``list_dtype`` (extension): ``torch.int16`` for lists of half the bytes."""
         _, bn, qt, kt = _sl.tile_geometry(seq_len, seq_len if seq_len_k is None else seq_len_k, head_dim,
                                           dtype.itemsize)
         row = None if must_skip_list is None else _sl.must_skip_row(must_skip_list, bn, kt)
-        return _sl.new_skip_lists(batch, heads, qt, kt, device, row)
+        return _sl.new_skip_lists(batch, heads, qt, kt, device, row, list_dtype)
 
     @staticmethod
     def _expand_must_do_list(must_do_list, list_shape, query, value):
@@ -92,12 +97,13 @@ class LiteAttention:
         default 4, 13 GB over 40 layers); here the lists cover the batch actually seen and grow on demand up to
         ``max_batch_size`` (``_get_read_write_lists``), so a default-constructed object costs what ``max_batch_size=1`` would."""
         return self.init_skip_list(query.shape[0] if batch is None else batch, query.shape[1], query.shape[2], query.shape[3],
-                                   False, query.dtype, query.device, must_skip_list, seq_len_k=value.shape[1])
+                                   False, query.dtype, query.device, must_skip_list, seq_len_k=value.shape[1],
+                                   list_dtype=self.list_dtype)
 
     def _get_read_write_lists(self, query: Tensor, value: Tensor, must_skip_list: list = None
                               ) -> Tuple[Optional[Tensor], Optional[Tensor]]:
         """(read, write) views for this call; (re)builds the lists when any of seq lengths / heads /
-        head_dim / dtype / device - or the tile geometry of the kernel that will run - changed (:179-200) and flips the
+        head_dim / dtype / device / list element type - or the tile geometry of the kernel that will run - changed (:179-200) and flips the
         ping-pong phase (:203-210). A batch larger than any seen so far (<= max_batch_size) grows the lists: the state of the
         sequences already tracked is kept, the new ones start from "all tiles listed"."""
         if not self.enable_skipping:
@@ -107,7 +113,7 @@ class LiteAttention:
         # the tile sizes belong to the key: LA_FWD_KERNEL=v2 changes the q-tile of head_dim 128 from 256 to 128 rows, and lists
         # built for one geometry are mis-shaped for the other
         key = (query.shape[1], value.shape[1], query.shape[2], query.shape[3], query.dtype, query.device,
-               get_tile_sizes(query.shape[3], query.dtype.itemsize))
+               get_tile_sizes(query.shape[3], query.dtype.itemsize), self.list_dtype)
         if self._skip_list is None or key != self._shape_key:
             self._skip_list = self._init_skip_list(query, value, must_skip_list)
             self._shape_key = key
@@ -134,7 +140,7 @@ class LiteAttention:
         batch = self.max_batch_size if batch is None else batch
         assert batch <= self.max_batch_size, "batch size must be less than or equal to max_batch_size (modify max_batch_size in LiteAttention constructor)"
         key = (query.shape[1], value.shape[1], query.shape[2], query.shape[3], query.dtype, query.device,
-               get_tile_sizes(query.shape[3], query.dtype.itemsize))
+               get_tile_sizes(query.shape[3], query.dtype.itemsize), self.list_dtype)
         if self._skip_list is None or key != self._shape_key:
             self._skip_list = self._init_skip_list(query, value, must_skip_list, batch=batch)
             self._shape_key, self._phase = key, 0
@@ -254,10 +260,12 @@ class LiteAttention:
             "shape_key": None if key is None else (*key[:4], str(key[4]).replace("torch.", "")),
             "device": None if key is None else str(key[5]),
             "tile_sizes": None if key is None else tuple(key[6]),
+            "list_dtype": str(self.list_dtype).replace("torch.", ""),      # of the saved lists (absent before int16 lists existed: int32)
         }
 
     def load_state_dict(self, state: dict, device=None):
-        """Restore ``state_dict()``. The lists go back to the device they were saved from (``state["device"]``) unless
+        """Restore ``state_dict()``. The lists are kept in THIS object's ``list_dtype``: a state saved with the other element type is
+        converted (widening is exact; narrowing to int16 checks that every value fits and raises ``ValueError`` otherwise). The lists go back to the device they were saved from (``state["device"]``) unless
         ``device`` names another one; a state that records no device (round-1 checkpoints) needs ``device=``. The next call
         must present the same shapes / dtype / device, otherwise the lists are rebuilt as on any shape change (:179-200)."""
         self.threshold = state["threshold"]
@@ -282,9 +290,9 @@ class LiteAttention:
                              "(LA_FWD_KERNEL differs?): the lists cannot be reused")
         if tuple(state["skip_list"].shape[3:]) != (_sl.cdiv(sq, tiles[0]), _sl.cdiv(sk, tiles[1]) + 1):
             raise ValueError("the saved lists do not match the tile geometry of the kernel selected now")
-        self._skip_list = state["skip_list"].to(dev).contiguous()
+        self._skip_list = _sl.convert_lists(state["skip_list"], self.list_dtype).to(dev).contiguous()
         self._phase = state["phase"]
-        self._shape_key = (sq, sk, h, d, dtype, dev, tuple(tiles))
+        self._shape_key = (sq, sk, h, d, dtype, dev, tuple(tiles), self.list_dtype)
 
 
 class SeqParallelLiteAttention:
@@ -292,9 +300,10 @@ class SeqParallelLiteAttention:
     The (local Q x split j) tile pattern differs per j, hence one state each. Transport of K/V and the
     LSE merge of the partial results stay with the caller; ``flash_attn_combine`` does the merge."""
 
-    def __init__(self, num_nodes: int, enable_skipping: bool = True, threshold: float = -10.0, max_batch_size: int = 4):
+    def __init__(self, num_nodes: int, enable_skipping: bool = True, threshold: float = -10.0, max_batch_size: int = 4,
+                 list_dtype: Optional[torch.dtype] = None):
         self.num_nodes = num_nodes
-        self.lite_attention = [LiteAttention(enable_skipping, threshold, max_batch_size) for _ in range(num_nodes)]
+        self.lite_attention = [LiteAttention(enable_skipping, threshold, max_batch_size, list_dtype) for _ in range(num_nodes)]
         self.set_threshold(threshold)
         # e4m3 inputs with return_softmax_lse=True: the caller merges partial results by that LSE (README.md:222-250), so the split
         # runs with the reference's form of P and its row sums (fp32 sums of the un-rounded P, softmax.h:275-296; fp32-exact LSE) even

@@ -1,6 +1,6 @@
 """Skip-list geometry and construction (host side, pure functions).
 
-A skip list is int32 ``[batch, heads, q_tiles, k_tiles + 1]``; each row is
+A skip list is int32 - or, as an option that halves the list state, int16 - ``[batch, heads, q_tiles, k_tiles + 1]``; each row is
 ``[L, start_0, end_0, start_1, end_1, ...]``: L valid entries, ranges in DESCENDING tile order, both
 ends inclusive for the kernel's reader (reference reader/writer at
 /root/reference/hopper/_internal/cpp/mainloop_fwd_sm90_tma_gmma_ws.hpp:47-192). The functions here
@@ -50,16 +50,39 @@ def must_skip_row(must_skip_list: Sequence[int], block_n: int, k_tiles: int) -> 
     return [len(ranges)] + ranges
 
 
-def new_skip_lists(batch: int, heads: int, q_tiles: int, k_tiles: int, device, row: Optional[Sequence[int]] = None
-                   ) -> torch.Tensor:
+def check_list_dtype(list_dtype: torch.dtype, k_tiles: int) -> torch.dtype:
+    """The element type of read / write lists: int32, or int16 when a row of ``k_tiles + 1`` entries fits it (every entry is a tile
+    index below ``k_tiles`` or a count of at most ``k_tiles``; ``la_fwd`` refuses longer rows with LA_FLAG_LIST_INT16)."""
+    if list_dtype not in (torch.int32, torch.int16):
+        raise ValueError(f"list_dtype must be torch.int32 or torch.int16, got {list_dtype}")
+    if list_dtype == torch.int16 and k_tiles + 1 > 32767:
+        raise ValueError(f"int16 skip lists hold rows of at most 32767 entries; this shape has k_tiles + 1 = {k_tiles + 1}")
+    return list_dtype
+
+
+def convert_lists(lists: torch.Tensor, list_dtype: torch.dtype) -> torch.Tensor:
+    """A list tensor in the other element type (checkpoints saved with one type, loaded into an object that keeps the other). Narrowing
+    checks the range first: a value outside int16 is not a list this build could have written, and must not wrap silently."""
+    check_list_dtype(list_dtype, 0)
+    if lists.dtype == list_dtype:
+        return lists
+    if list_dtype == torch.int16 and lists.numel() and (int(lists.max()) > 32767 or int(lists.min()) < -32768):
+        raise ValueError("skip list holds values outside int16 (max "
+                         f"{int(lists.max())}, min {int(lists.min())}): it cannot be narrowed to int16 lists")
+    return lists.to(list_dtype)
+
+
+def new_skip_lists(batch: int, heads: int, q_tiles: int, k_tiles: int, device, row: Optional[Sequence[int]] = None,
+                   list_dtype: torch.dtype = torch.int32) -> torch.Tensor:
     """Both ping-pong buffers ``[2, batch, heads, q_tiles, k_tiles + 1]``; default row ``[2, k_tiles-1, 0]``
-    = one range over every tile (lite_attention.py:124, 148-151)."""
-    lists = torch.zeros(2, batch, heads, q_tiles, k_tiles + 1, dtype=torch.int32, device=device)
+    = one range over every tile (lite_attention.py:124, 148-151). ``list_dtype``: int32, or int16 for half the bytes."""
+    check_list_dtype(list_dtype, k_tiles)
+    lists = torch.zeros(2, batch, heads, q_tiles, k_tiles + 1, dtype=list_dtype, device=device)
     if row is None:
         lists[..., 0] = 2
         lists[..., 1] = k_tiles - 1
     else:
-        lists[..., : len(row)] = torch.tensor(list(row), dtype=torch.int32, device=device)
+        lists[..., : len(row)] = torch.tensor(list(row), dtype=list_dtype, device=device)
     return lists
 
 
@@ -79,7 +102,7 @@ def must_do_row(must_do_list: Sequence[int], block_n: int, width: int, device) -
 def listed_fraction(lists: torch.Tensor) -> float:
     """Fraction of (q-tile, k-tile) pairs a list keeps: sum over rows and ranges of (start-end+1) over
     rows*k_tiles. The statistic lite_attention.py:61-85 meant to compute (Appendix B-3). Device lists are
-    reduced by the ``la_skip_list_stats`` kernel; host lists with a few tensor ops."""
+    reduced by the ``la_skip_list_stats_ex`` kernel; host lists with a few tensor ops. int32 and int16 lists alike."""
     rows = lists.shape[0] * lists.shape[1] * lists.shape[2]
     k_tiles = lists.shape[3] - 1
     if rows * k_tiles <= 0:
