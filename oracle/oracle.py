@@ -329,7 +329,10 @@ def simulate_writer(read_row: Sequence[int], flags: Sequence[bool],
         md = {"row": r, "len": r[0], "idx": 1, "start": r[1], "end": r[2]}
     L = int(read_row[0])
     idx = 1
-    start, end = int(read_row[1]), int(read_row[2])
+
+    def at(i):          # as walk_tiles: an entry behind the row reads as 0 (the one-tile row [len, start])
+        return int(read_row[i]) if i < len(read_row) else 0
+    start, end = at(1), at(2)
     n = start
     pos = 0
     skip = False
@@ -348,7 +351,7 @@ def simulate_writer(read_row: Sequence[int], flags: Sequence[bool],
         idx += 2
         if not idx <= L:
             break
-        start, end = int(read_row[idx]), int(read_row[idx + 1])
+        start, end = at(idx), at(idx + 1)
         n = start
     out[0] = len(out) - 1
     return out

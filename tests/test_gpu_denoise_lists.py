@@ -10,7 +10,10 @@ device (tools/selfcheck.py), each citing the reference lines it follows:
         tests/test_gpu_fragmented.py docstring; measured 0.0031 at max|ref| 0.52), |LSE - ref| <= 2e-4;
         fp8 <= 0.05 max|ref| + 1e-3, |LSE - ref| <= 2e-2 (row sums of the encoded P, helpers.fp8_lse_tol)
   * step-49 write list: for 24 sampled (head, q-tile) rows the skip vote of every walked tile (softmax.h:190-194) and the
-    writer state machine (mainloop...:142-192) restated in torch; rows equal except those with a tile within 1e-3 of thr
+    writer state machine (mainloop...:142-192) restated in torch; rows equal except those with a tile within 1e-3 of thr;
+    and for EVERY q-tile of one head: no row differs without a vote within 1e-3 of thr, and every row that does differ is reproduced
+    exactly by flipping some of its close votes (vote_writer_check's "unexplained" == 0; the checker itself is pinned to the oracle
+    by tests/test_selfcheck_cpu.py and tests/test_gpu_selfcheck.py)
   * walked(write) is a subset of walked(read) for ALL 11 840 rows (a skipped tile is never revisited), both start at Kt-1
   * dynamic work distribution == static map bit-exactly (O, LSE, write list) on these lists
   * the lists really are fragmented: some row holds more than 64 ranges
@@ -22,6 +25,7 @@ pytestmark = pytest.mark.gpu
 
 S, H, D = 75600, 40, 128
 F8 = torch.float8_e4m3fn
+EVERY_TILE_HEAD = 17        # the head whose q-tiles are ALL judged by vote_writer_check (296 items of 256 rows)
 
 
 @pytest.fixture(scope="module", params=[-4.22, -2.462], ids=["thr-4.22", "thr-2.46"])
@@ -79,6 +83,10 @@ def test_step49_bf16(run49):
     # vote + writer restated
     vw = sc.vote_writer_check(r["q"], r["k"], read, write, r["thr"], bm, bn, _items(qt))
     assert vw["ok"] and vw["items"] == 24 and vw["borderline"] <= 2, vw
+    # ... and EVERY q-tile of one head: no row may differ beyond what a flip of its own close votes reproduces
+    every = sc.vote_writer_check(r["q"], r["k"], read, write, r["thr"], bm, bn, [(EVERY_TILE_HEAD, m) for m in range(qt)])
+    print(f"step 49 bf16 thr {r['thr']}: sampled {vw}; every q-tile of head {EVERY_TILE_HEAD} {every}")
+    assert every["items"] == qt and every["bad"] == 0 and every["unexplained"] == 0, every
     # static map, NaN-prefilled output: bit-identical to the dynamic run
     out_s = torch.full_like(r["out"], float("nan"))
     wr_s = torch.full_like(read, -7)
@@ -114,6 +122,9 @@ def test_step49_fp8_on_the_same_lists(run49):
     assert res["ok"], res
     vw = sc.vote_writer_check(q, k, read, wr, r["thr"], bm, bn, _items(qt, seed=4))
     assert vw["ok"] and vw["borderline"] <= 2, vw
+    every = sc.vote_writer_check(q, k, read, wr, r["thr"], bm, bn, [(EVERY_TILE_HEAD, m) for m in range(qt)])
+    print(f"step 49 fp8 thr {r['thr']}: sampled {vw}; every q-tile of head {EVERY_TILE_HEAD} {every}")
+    assert every["items"] == qt and every["bad"] == 0 and every["unexplained"] == 0, every
     assert int((sc.lists_to_bitmap(wr) & ~sc.lists_to_bitmap(read)).sum()) == 0
     out_s = torch.full_like(out, float("nan"))
     wr_s = torch.full_like(read, -7)

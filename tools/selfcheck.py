@@ -70,15 +70,30 @@ def executed_flops(rows: torch.Tensor, heads: int, batch: int, S: int, Sk: int, 
 
 
 # ----------------------------------------------------------------------------------------- verification
+def _at(row: Sequence[int], i: int) -> int:
+    """Entry ``i`` of a list row; an entry behind the row reads as 0 (the one-tile row ``[L, start]`` has no room for its end, and a row of
+    an odd k_tiles may count a last end it could not store)."""
+    return int(row[i]) if i < len(row) else 0
+
+
+def _ranges_of_row(row: Sequence[int]):
+    """(start, end) of every range the reader loads: the first one whatever L says, then one per ``idx <= L`` (idx = 3, 5, ...), so an odd L
+    still loads the pair that begins at entry L (mainloop_fwd_sm90_tma_gmma_ws.hpp:93-115)."""
+    L, idx = int(row[0]), 1
+    while True:
+        yield _at(row, idx), _at(row, idx + 1)
+        idx += 2
+        if not idx <= L:
+            return
+
+
 def listed_key_mask(list_row: Sequence[int], block_n: int, seqlen_k: int, device) -> torch.Tensor:
     """bool[seqlen_k]: keys inside the tiles a skip-list row ``[L, start0, end0, ...]`` lists (ranges descending, both
     ends inclusive; the first range is walked even when L == 0, mainloop_fwd_sm90_tma_gmma_ws.hpp:93-101)."""
     mask = torch.zeros(seqlen_k, dtype=torch.bool, device=device)
-    n = max(int(list_row[0]), 2)
-    for i in range(1, n, 2):
-        s, e = int(list_row[i]), int(list_row[i + 1])
+    for s, e in _ranges_of_row(list_row):
         if s >= e:
-            mask[e * block_n: min((s + 1) * block_n, seqlen_k)] = True
+            mask[max(e, 0) * block_n: min((s + 1) * block_n, seqlen_k)] = True
     return mask
 
 
@@ -150,7 +165,7 @@ def lists_to_bitmap(lists: torch.Tensor) -> torch.Tensor:
     if kt % 2:
         body = torch.nn.functional.pad(body, (0, 1))
     pairs = body.unflatten(-1, (-1, 2))
-    live = (torch.arange(pairs.shape[1], device=lists.device)[None] < (flat[:, :1].clamp_min(2) // 2))
+    live = (torch.arange(pairs.shape[1], device=lists.device)[None] < ((flat[:, :1] + 1) // 2).clamp_min(1))   # idx = 1, 3, ... <= L
     starts, ends = pairs[..., 0].clamp(0, kt - 1), pairs[..., 1].clamp(0, kt - 1)
     live = live & (pairs[..., 0] >= pairs[..., 1])
     diff = torch.zeros(flat.shape[0], kt + 1, dtype=torch.int32, device=lists.device)
@@ -162,52 +177,93 @@ def lists_to_bitmap(lists: torch.Tensor) -> torch.Tensor:
 
 def walk_of_row(row: Sequence[int]) -> List[int]:
     """Tiles in the order the kernel's reader visits them for one list row (mainloop...:1804-1827)."""
-    n = max(int(row[0]), 2)
     seq: List[int] = []
-    for i in range(1, n, 2):
-        seq.extend(range(int(row[i]), int(row[i + 1]) - 1, -1))
+    for s, e in _ranges_of_row(row):
+        seq.extend(range(s, e - 1, -1))
     return seq
 
 
-def written_row(read_row: Sequence[int], flags: Sequence[bool]) -> List[int]:
-    """``SkipListWriter`` without a must-do list, restated (mainloop...:142-192): ``flags[i]`` is the skip vote of the i-th visited
-    tile (the first visited tile is recorded as not skipped whatever it voted, :1804-1805). Returns ``[L, entries...]``."""
+def written_row(read_row: Sequence[int], flags: Sequence[bool], must_do_row: Optional[Sequence[int]] = None) -> List[int]:
+    """``SkipListWriter`` restated (mainloop...:142-192): ``flags[i]`` is the skip vote of the i-th visited tile (the first visited tile is
+    recorded as not skipped whatever it voted, :1804-1805). The last vote is carried across ranges: a range that walks nothing closes with
+    the vote of the tile before it (:173-181). ``must_do_row`` (``[L, start0, end0, ...]``, descending, a tile n is must-do when
+    ``end < n <= start``): a tile voted out inside a must-do range is recorded as kept; the must-do reader moves on when the walk has passed
+    below its range (:154-162). Returns ``[L, entries...]``, unpadded and not cut to the row's width."""
     out = [0]
-    skipping = True
-    n_ranges = max(int(read_row[0]), 2) // 2
-    pos = 0
-    for r in range(n_ranges):
-        start, end = int(read_row[1 + 2 * r]), int(read_row[2 + 2 * r])
-        skip = False
-        for n in range(start, end - 1, -1):
-            skip = bool(flags[pos]) and pos > 0
+    state = {"skipping": True}
+    md = None
+    if must_do_row is not None:
+        md = {"row": [int(x) for x in must_do_row], "idx": 1}
+        md["len"], md["start"], md["end"] = _at(md["row"], 0), _at(md["row"], 1), _at(md["row"], 2)
+
+    def record(skip: bool, n: int, use_md: bool):
+        if use_md and md is not None and skip:
+            if md["end"] > n and md["idx"] <= md["len"]:
+                md["idx"] += 2
+                md["start"], md["end"] = _at(md["row"], md["idx"]), _at(md["row"], md["idx"] + 1)
+            skip = not (md["end"] < n <= md["start"])
+        if skip != state["skipping"]:                 # record_transition (:163-168)
+            out.append(n)
+            state["skipping"] = skip
+
+    ranges = _ranges_of_row(read_row)
+    start, end = next(ranges)
+    record(False, start, False)                       # the first visited tile, whatever the range says
+    n, pos, skip = start - 1, 1, False
+    while True:
+        while n >= end:
+            skip = bool(flags[pos])
             pos += 1
-            if skip != skipping:                      # record_transition (:163-168)
-                out.append(n)
-                skipping = skip
-        skipping = True                               # record_range_end (:173-181)
+            record(skip, n, True)
+            n -= 1
+        state["skipping"] = True                      # record_range_end (:173-181): judged on the RAW last vote
         if not skip:
             out.append(end)
+        nxt = next(ranges, None)
+        if nxt is None:
+            break
+        start, end = nxt
+        n = start
     out[0] = len(out) - 1
     return out
+
+
+def stored_row(row: Sequence[int], k_tiles: int) -> List[int]:
+    """What of a written row lands in a list row of ``k_tiles + 1`` entries: an entry behind the row is counted but not stored and the
+    stored length is capped at k_tiles (the memory-safety rule the kernels and the oracle share)."""
+    return [min(int(row[0]), k_tiles)] + [int(x) for x in row[1: k_tiles + 1]]
+
+
+EXPLAIN_MAX_CLOSE = 10     # close votes per row up to which every combination of flips is tried (2^10 writer runs)
 
 
 @torch.no_grad()
 def vote_writer_check(q: torch.Tensor, k: torch.Tensor, read_list: torch.Tensor, write_list: torch.Tensor, thr: float,
                       block_m: int, block_n: int, items: Iterable, batch: int = 0, softmax_scale: Optional[float] = None,
-                      margin_tol: float = 1e-3) -> Dict:
+                      margin_tol: float = 1e-3, must_do_row: Optional[Sequence[int]] = None, details: bool = False) -> Dict:
     """For every sampled ``(head, q-tile)`` of ``items``: fp32 scores of the whole q-tile (rows past seqlen_q are zero rows and
     vote, as the reference's TMA zero fill does) against all keys, the walk of the row's READ list, the skip vote of every
     walked tile — ``AND over the q-tile's rows of [(m_loc - m_prev) c <= thr]`` with the running max BEFORE the tile, c =
     softmax_scale log2 e (softmax.h:190-194) — and the write row the writer state machine produces from the votes, compared
     with the row the kernel wrote. A row that differs is "borderline" when one of its tiles has a decision margin within
     ``margin_tol`` of ``thr`` (fp32 summation order may flip it), otherwise "bad". q (B,S,H,D), k (B,Sk,Hk,D); lists
-    [B,H,Qt,Kt+1]. Returns {"items", "bad", "borderline", "max_ranges", "ok"}."""
+    [B,H,Qt,Kt+1]; ``must_do_row``: the 1-D must-do row the launch ran with (None: no must-do tile).
+
+    A borderline row is further *explained* when flipping some of its close votes (those within ``margin_tol`` of ``thr``) and running the
+    writer again reproduces the written row exactly; all combinations are tried when the row has at most ``EXPLAIN_MAX_CLOSE`` close
+    votes, otherwise the row counts in "unenumerated" (and in "borderline", as before). "unexplained": borderline rows that no
+    combination reproduces — a defect elsewhere in a row that happens to hold a close vote.
+    Returns {"items", "bad", "borderline", "unexplained", "unenumerated", "max_ranges", "ok"} with ok = (bad == 0); with ``details`` also
+    "details": {(head, q-tile): {"margin": fp32 [k_tiles] on the CPU, NaN on tiles not walked and on the first, "want": expected row as
+    stored, "status": "equal" | "bad" | "explained" | "unexplained" | "unenumerated"}}."""
     B, S, H, D = q.shape
     Sk, Hk = k.shape[1], k.shape[2]
     kt = -(-Sk // block_n)
     c = (D ** -0.5 if softmax_scale is None else softmax_scale) * 1.4426950408889634
-    res = {"items": 0, "bad": 0, "borderline": 0, "max_ranges": 0, "ok": True}
+    md = None if must_do_row is None else [int(x) for x in (must_do_row.tolist() if torch.is_tensor(must_do_row) else must_do_row)]
+    res = {"items": 0, "bad": 0, "borderline": 0, "unexplained": 0, "unenumerated": 0, "max_ranges": 0, "ok": True}
+    if details:
+        res["details"] = {}
     for h, m in items:
         rows = q[batch, m * block_m: (m + 1) * block_m, h].float()
         if rows.shape[0] < block_m:
@@ -221,15 +277,38 @@ def vote_writer_check(q: torch.Tensor, k: torch.Tensor, read_list: torch.Tensor,
         run = torch.cummax(wm, dim=1).values
         margin = ((wm[:, 1:] - run[:, :-1]) * c).amax(0)                                  # worst row of every visited tile but the first
         flags = [False] + (margin <= thr).tolist()
-        want = written_row(rd, flags)
-        got = write_list[batch, h, m, : want[0] + 1].tolist()
+        want = stored_row(written_row(rd, flags, md), kt)
+        wr_row = write_list[batch, h, m].tolist()
         res["items"] += 1
         res["max_ranges"] = max(res["max_ranges"], max(int(rd[0]), 2) // 2)
-        if got != want:
-            if bool(((margin - thr).abs() < margin_tol).any().item()):
-                res["borderline"] += 1
-            else:
+        status = "equal"
+        if wr_row[: want[0] + 1] != want:
+            close = (((margin - thr).abs() < margin_tol).nonzero().flatten() + 1).tolist()    # positions in the walk
+            if not close:
                 res["bad"] += 1
+                status = "bad"
+            else:
+                res["borderline"] += 1
+                if len(close) > EXPLAIN_MAX_CLOSE:
+                    res["unenumerated"] += 1
+                    status = "unenumerated"
+                else:
+                    status = "unexplained"
+                    for bits in range(1, 1 << len(close)):
+                        f2 = list(flags)
+                        for j, pos in enumerate(close):
+                            if bits >> j & 1:
+                                f2[pos] = not f2[pos]
+                        cand = stored_row(written_row(rd, f2, md), kt)
+                        if wr_row[: cand[0] + 1] == cand:
+                            status = "explained"
+                            break
+                    res["unexplained"] += status == "unexplained"
+        if details:
+            full = torch.full((kt,), float("nan"))
+            if len(walk) > 1:
+                full[torch.tensor(walk[1:])] = margin.float().cpu()
+            res["details"][(h, m)] = {"margin": full, "want": want, "status": status}
     res["ok"] = res["bad"] == 0
     return res
 
