@@ -107,8 +107,8 @@ def build_m16_variant(force: bool = False, verbose: bool = False) -> str:
     rec = _buildinfo.record_in_file(M16_VARIANT) if os.path.exists(M16_VARIANT) else None
     fresh = rec is not None and rec["src"] == _buildinfo.source_hash() and rec["variant"] == "1" and "m16" in rec["opts"] and rec["wrong_results"] == "0"
     # its own generator is hashed into no record (an edit to the A/B body must not invalidate the PRODUCT library): compare times (of the
-    # assembler core it shares too)
-    fresh = fresh and all(os.path.getmtime(os.path.join(CSRC, g)) <= os.path.getmtime(M16_VARIANT) for g in (X64_M16_GEN, "gen_asm.py"))
+    # assembler core and the blocks it shares too)
+    fresh = fresh and all(os.path.getmtime(os.path.join(CSRC, g)) <= os.path.getmtime(M16_VARIANT) for g in (X64_M16_GEN, "gen_asm.py", "gen_blocks.py"))
     if fresh and not force:
         return M16_VARIANT
     os.makedirs(os.path.dirname(M16_VARIANT), exist_ok=True)

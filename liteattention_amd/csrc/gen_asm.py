@@ -1,5 +1,5 @@
-"""Shared by the body generators (gen_fwd_x64.py, gen_fwd_x64_fp8.py, gen_fwd_x64_m16.py) and gen_epilogue.py: the assembler core,
-the SGPR map and the parameter block ABI. A generator runs as a script and takes all of it with ``from gen_asm import *``.
+"""Shared by the body generators (gen_fwd_x64.py, gen_fwd_x64_fp8.py, gen_fwd_x64_m16.py), gen_blocks.py and gen_epilogue.py: the assembler
+core, the SGPR map and the parameter block ABI (``from gen_asm import *``). What a body is made of sits on it: gen_blocks.py, gen_epilogue.py.
 
 The body is built in ``out`` as a list of items: a str (one line of assembly), ("LDS", text, tag) (an LDS operation whose completion
 a later wait may name), ("WAIT", tag) (a counted lgkmcnt wait for the youngest LDS operation of that tag) or ("DRAIN",). ``finalize``

@@ -1,5 +1,6 @@
 """Shared by gen_fwd_x64.py and gen_fwd_x64_fp8.py: the in-register epilogue of the 64-rows-per-wave kernels (gen_fwd_x64_m16.py
-reads its parameter words with ``read_epilogue_params``).
+reads its parameter words with ``read_epilogue_params``). It sits on gen_asm.py (assembler core, SGPR map) like gen_blocks.py (the
+other shared blocks of a body) and takes every register it touches as an argument of ``store_epilogue``.
 
 finalize (softmax.h:275-296) + store (epilogue_fwd.hpp:214-403) straight from the accumulators: every lane owns ONE query row
 (column lane & 31 of the 32x32 accumulator; lanes l and l ^ 32 split the head dim), so 1/l is lane-local after one half-wave
@@ -32,20 +33,18 @@ def read_epilogue_params(T):
     emit("s_nop 4")
 
 
-def store_epilogue(g, o_reg):
-    """g: the generator's globals (its register map); o_reg(qb, db) -> first AGPR."""
-    T, L0, L1, MREF, NEGINF, HH4, QROW = g["T"], g["L0"], g["L1"], g["MREF"], g["NEGINF"], g["HH4"], g["QROW"]
-    cvt = g.get("CVT_OP", "v_cvt_pk_bf16_f32")                 # the 16-bit output type follows the inputs (fp8 inputs: bf16)
-    n_qb, n_db = g.get("NQB", 2), g.get("DB", 4)               # q-blocks per wave, 32-wide d-blocks (head_dim 256: 1 and 8)
-    HH16 = g["MLOC"][0]                                        # dead after the loop: hh * 16 bytes
+def store_epilogue(o_reg, T, L0, L1, MREF, NEGINF, HH4, QROW, HH16, cvt, n_qb, n_db, lsum_agpr=None):
+    """o_reg(qb, db) -> first AGPR; T: temporaries; L0, L1, MREF, QROW: per q-block; HH16: a scratch register (hh * 16 bytes); cvt: the
+    fp32 -> 16-bit pack of the output type; n_qb q-blocks per wave, n_db 32-wide d-blocks (head_dim 256: 1 and 8); lsum_agpr: per
+    q-block the AGPR that holds the row sum, where the matrix pipe accumulated it (then L0 / L1 are not read)."""
     emit("; ---- finalize + store O (bf16) and LSE straight from the accumulators")
     read_epilogue_params(T)
     emit(f"v_lshlrev_b32 {v(HH16)}, 2, {v(HH4)}")
     for qb in range(n_qb):
         # l = sum over the two half-waves; inv = oscale / l (0 for l == 0 or NaN); lse = m_ref c ln2 + ln l + lse_add
-        if g.get("LSUM_AGPR"):
+        if lsum_agpr:
             # row sums accumulated by the matrix pipe (fp8: ones x P~^T): every lane already holds the complete sum of its row
-            emit(f"v_accvgpr_read_b32 {v(T[0])}, a{g['LSUM_AGPR'][qb]}")
+            emit(f"v_accvgpr_read_b32 {v(T[0])}, a{lsum_agpr[qb]}")
             emit("s_nop 1")
         else:
             emit(f"v_add_f32 {v(T[0])}, {v(L0[qb])}, {v(L1[qb])}")

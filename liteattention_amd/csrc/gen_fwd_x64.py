@@ -31,8 +31,10 @@ it has grown by more than `tau` (log2 units); P stays <= 2^tau. The skip vote us
 """
 import os
 import sys
+from types import SimpleNamespace
 
 from gen_asm import *
+from gen_blocks import *
 from gen_epilogue import store_epilogue
 
 set_label_prefix(".LX")
@@ -171,6 +173,7 @@ if W2:                                    # 90 VGPRs: S v[0:31] (one buffer), V^
     T = list(range(68, 84))               # (T[4], T[5]) an even-aligned pair
     ALPHA, MLOC2 = [84], [85]
     LANE, RIPROW, RAGK, RAGV = 86, 87, 88, 89
+R = SimpleNamespace(T=T, QBS=range(NQB), MLOC=MLOC, MTRUE=MTRUE, MREF=MREF, MTHR=MTHR, NMS=NMS, ALPHA=ALPHA, L0=L0, L1=L1, NEGINF=NEGINF)   # gen_blocks.py
 
 # ---------------------------------------------------------------- SGPR aliases of this generator (the map: gen_asm.py)
 S_STATE = S_FREE3         # HALF: the form of the NEXT step, computed in front of the drain: (a(i), a(i+1)) as bits 0, 1, or 4 = the walk is over
@@ -359,18 +362,7 @@ def row_max_ops(sset):
     """In-lane max of the 32 scores of each q-block into MLOC[qb] (two max3 chains each), interleaved over q-blocks."""
     if "norowmax" in OPT and W2:
         return []
-    per = []
-    for qb in range(NQB):
-        regs = [S_(sset, 0, qb) + r for r in range(16)] + [S_(sset, 1, qb) + r for r in range(16)]
-        ops = [f"    v_max_f32 {v(MLOC[qb])}, {v(regs[0])}, {v(regs[1])}", f"    v_max_f32 {v(MLOC2[qb])}, {v(regs[2])}, {v(regs[3])}"]
-        rest = regs[4:]
-        chains = [MLOC[qb], MLOC2[qb]]
-        for n_, i in enumerate(range(0, len(rest), 2)):
-            ch = chains[n_ & 1]
-            ops.append(f"    v_max3_f32 {v(ch)}, {v(ch)}, {v(rest[i])}, {v(rest[i + 1])}")
-        ops.append(f"    v_max_f32 {v(MLOC[qb])}, {v(MLOC[qb])}, {v(MLOC2[qb])}")
-        per.append(ops)
-    return [x for pair in zip(*per) for x in pair]
+    return row_max_chains([[S_(sset, kb, qb) + r for kb in (0, 1) for r in range(16)] for qb in range(NQB)], MLOC, MLOC2)
 
 
 def stats_bookkeeping(flush_label, flush_back):
@@ -435,75 +427,22 @@ def stats_ops(rare_label, back_label, flush_label, flush_back, inval_label, inva
     return o
 
 
-def rare_rescale_block(rare_label, back_label):
-    """Out of line: m_ref follows m_true; alpha = exp2((m_ref_old - m_true)*c); l *= alpha; O rescale flagged."""
-    label(rare_label)
-    for qb in range(NQB):
-        emit(f"v_sub_f32 {v(T[2 + qb])}, {v(MREF[qb])}, {v(MTRUE[qb])}")
-    for qb in range(NQB):
-        emit(f"v_mul_f32 {v(T[2 + qb])}, {s(S_C)}, {v(T[2 + qb])}")
-    for qb in range(NQB):
-        emit(f"v_exp_f32 {v(ALPHA[qb])}, {v(T[2 + qb])}")
-    for qb in range(NQB):
-        emit(f"v_mov_b32 {v(MREF[qb])}, {v(MTRUE[qb])}")
-    for qb in range(NQB):
-        emit(f"v_mul_f32 {v(NMS[qb])}, {s(S_NEGC)}, {v(MREF[qb])}")
-        emit(f"v_add_f32 {v(MTHR[qb])}, {s(S_TAU)}, {v(MREF[qb])}")
-    for qb in range(NQB):
-        emit(f"v_mul_f32 {v(L0[qb])}, {v(L0[qb])}, {v(ALPHA[qb])}")
-        emit(f"v_mul_f32 {v(L1[qb])}, {v(L1[qb])}, {v(ALPHA[qb])}")
-    emit(f"s_mov_b32 {s(S_RESC)}, 1")
-    emit(f"s_branch {back_label}")
+def flush_tail():
+    """HALF: the flush runs inside step i = 32 m + 30, before its end-of-step shift: the window holds a(i), a(i + 1) in bits 0..1 and the
+    NEXT activity word (positions 32 (m + 1) ...) goes to bits 2..33"""
+    emit(f"v_mov_b32 {v(T[4])}, {s(S_ACTPTR)}")
+    emit(f"ds_read_b32 {v(T[4])}, {v(T[4])}")
+    emit(f"s_add_u32 {s(S_ACTPTR)}, {s(S_ACTPTR)}, 4")
+    emit("s_waitcnt lgkmcnt(0)")
+    emit(f"v_readfirstlane_b32 {s(S_T0)}, {v(T[4])}")
+    emit(f"s_and_b32 {s(S_ACT)}, {s(S_ACT)}, 3")
+    emit(f"s_lshl_b32 {s(S_T1)}, {s(S_T0)}, 2")
+    emit(f"s_lshr_b32 {s(S_ACT + 1)}, {s(S_T0)}, 30")
+    emit(f"s_or_b32 {s(S_ACT)}, {s(S_ACT)}, {s(S_T1)}")
 
 
-def inval_block(lbl, back):
-    """Out of line (last step of a walk): -m_ref*c := -inf, so exp2(S*c - inf) = 0 for the tile that does not exist."""
-    label(lbl)
-    for qb in range(NQB):
-        emit(f"v_mov_b32 {v(MLOC[qb])}, {v(NEGINF)}")
-        emit(f"v_mov_b32 {v(NMS[qb])}, {v(NEGINF)}")
-    emit(f"s_branch {back}")
-
-
-def flush_block(flush_label, back_label):
-    """Out of line: doflags word |= domask by one lane; next word, domask = 0, bit = 1. Drains lgkmcnt (keeps counted waits valid)."""
-    label(flush_label)
-    flush_domask(T[4], T[5])
-    emit(f"s_add_u32 {s(S_DOWORD)}, {s(S_DOWORD)}, 4")
-    emit(f"s_mov_b32 {s(S_BIT)}, 1")
-    if HALF:
-        # the flush runs inside step i = 32 m + 30, before its end-of-step shift: the window holds a(i), a(i + 1) in bits 0..1 and the
-        # NEXT activity word (positions 32 (m + 1) ...) goes to bits 2..33
-        emit(f"v_mov_b32 {v(T[4])}, {s(S_ACTPTR)}")
-        emit(f"ds_read_b32 {v(T[4])}, {v(T[4])}")
-        emit(f"s_add_u32 {s(S_ACTPTR)}, {s(S_ACTPTR)}, 4")
-        emit("s_waitcnt lgkmcnt(0)")
-        emit(f"v_readfirstlane_b32 {s(S_T0)}, {v(T[4])}")
-        emit(f"s_and_b32 {s(S_ACT)}, {s(S_ACT)}, 3")
-        emit(f"s_lshl_b32 {s(S_T1)}, {s(S_T0)}, 2")
-        emit(f"s_lshr_b32 {s(S_ACT + 1)}, {s(S_T0)}, 30")
-        emit(f"s_or_b32 {s(S_ACT)}, {s(S_ACT)}, {s(S_T1)}")
-    else:
-        emit("s_waitcnt lgkmcnt(0)")
-    emit(f"s_branch {back_label}")
-
-
-def rescale_o_block(lbl, back):
-    """Out of line (rare): O^T *= alpha for both q-blocks (AGPR -> VGPR -> AGPR), after the PV MFMAs have drained."""
-    label(lbl)
-    emit("s_nop 15")
-    emit("s_nop 15")
-    for qb in range(NQB):
-        for base in range(0, 16 * DB, 8):
-            for k in range(8):
-                emit(f"v_accvgpr_read_b32 {v(T[k])}, a{O_(qb, 0) + base + k}")
-            for k in range(8):
-                emit(f"v_mul_f32 {v(T[k])}, {v(T[k])}, {v(ALPHA[qb])}")
-            for k in range(8):
-                emit(f"v_accvgpr_write_b32 a{O_(qb, 0) + base + k}, {v(T[k])}")
-    emit(f"s_mov_b32 {s(S_RESC)}, 0")
-    emit("s_nop 7")
-    emit(f"s_branch {back}")
+FLUSH_TAIL = flush_tail if HALF else None
+O_ACC = [(ALPHA[qb], range(O_(qb, 0), O_(qb, 0) + 16 * DB)) for qb in range(NQB)]       # rescale_o_block: what alpha scales
 
 
 def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
@@ -514,36 +453,27 @@ def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
     went negative = +4 GiB (found by the varlen tests: a 1-key sequence faulted)."""
     if "nodma" in OPT:
         return []
-    o = []
     # head_dim 256: 8 pieces per tensor in two groups of 4 (the instruction offset is a 13-bit signed field: 0..3072 only), M0 moved
     # by 4 KiB for the second group; the lane offsets of piece j carry +(3072 - 1024 (j & 3))
     per = min(4, PW)                       # pieces per M0 group (head_dim 64: 2 pieces per tensor in all)
-    for grp in range(PW // per):
-        if do_k:
-            o.append(f"    s_add_u32 m0, {s(S_DMAW)}, {kbuf_imm + 4096 * grp}")
-            o += [f"    global_load_lds_dwordx4 {v(LK[4 * grp + j])}, {sr(TBS[st])} offset:{1024 * j}{DMA_POLICY}" for j in range(per)]
-    for grp in range(PW // per):
-        if do_v:
-            o.append(f"    s_add_u32 m0, {s(S_DMAW)}, {V_REGION + vbuf_imm + 4096 * grp}")
-            o += [f"    global_load_lds_dwordx4 {v(LV[4 * grp + j])}, {sr(VBS[st])} offset:{1024 * j}{DMA_POLICY}" for j in range(per)]
+    grps = range(0, PW, per)
+    o = dma_issue([(S_DMAW, kbuf_imm + 1024 * g, LK[g:g + per], TBS[st]) for g in grps if do_k] +
+                  [(S_DMAW, V_REGION + vbuf_imm + 1024 * g, LV[g:g + per], VBS[st]) for g in grps if do_v], DMA_POLICY)
     if "dma2x" in OPT:                     # pricing only (HISTORY.md section 8, two 128-row workgroups per CU): every piece staged twice
         o = [x + "\n" + x if "global_load_lds" in x else x for x in o]
     return o
 
 
-def emit_gaps(pre, mf, post):
-    """One phase: per gap the pre items, the MFMA, the fillers. Pricing variant mfma16 (two 16x16x32 MFMAs per gap): with `spread` the
-    second MFMA of a gap sits behind the first half of the gap's fillers instead of right behind the first (a 16x16x32 MFMA holds the
-    matrix pipe ~17 cycles: back to back, the second one stalls at issue)."""
+def emit_phase(pre, mf, post):
+    """One phase (gen_blocks.emit_gaps). Pricing variant mfma16 (two 16x16x32 MFMAs per gap): with `spread` the second MFMA of a gap
+    sits behind the first half of the gap's fillers instead of right behind the first (a 16x16x32 MFMA holds the matrix pipe ~17
+    cycles: back to back, the second one stalls at issue)."""
     for t in range(NG):
         if MFMA16 and "spread" in OPT and "\n" in mf[t]:
-            a, b = mf[t].split("\n")
+            mf[t], b = mf[t].split("\n")
             h = (len(post[t]) + 1) // 2
-            for it in pre[t] + [a] + post[t][:h] + [b] + post[t][h:]:
-                out.append(it)
-        else:
-            for it in pre[t] + [mf[t]] + post[t]:
-                out.append(it)
+            post[t] = post[t][:h] + [b] + post[t][h:]
+    emit_gaps(pre, mf, post)
 
 
 def widen_last(n, since):
@@ -605,7 +535,7 @@ def step(variant, a_cur=True, a_nxt=True, drop=frozenset()):
     vq = softmax_stream(cur, list(range(XPAIRS, 16))) if a_cur and "nosoftmax" not in opt else []
     distribute(vq, post, 0, CAP1)
     mark = len(out)
-    emit_gaps(pre, mf, post)
+    emit_phase(pre, mf, post)
     if full:
         widen_last(int(opt_val(OPT, "wp2", "0")) if variant == 0 else int(opt_val(OPT, "wp2b", opt_val(OPT, "wp2", "0"))), mark)  # shift phase 2 (copy 0 / copy 1 of the step)
     if a_nxt and not a_cur:
@@ -664,16 +594,16 @@ def step(variant, a_cur=True, a_nxt=True, drop=frozenset()):
     vq += mixed
     if not a_nxt:
         vq += stats_bookkeeping(fl, flback)
-        deferred.append(lambda: flush_block(fl, flback))
+        deferred.append(lambda: flush_block(fl, flback, T, FLUSH_TAIL))
     elif "notail" not in opt:
         # (HALF: positions past the end of the walk have a = 0, so a form with statistics never runs at i == n - 1 and the test below never
         # fires there; it stays so that the hot loop is instruction for instruction - gap for gap - the tuned schedule of the form
         # without activity bits)
         inv, invback = new_label("inval"), new_label("inval_back")
         vq += stats_ops(rare, back, fl, flback, inv, invback)
-        deferred.append(lambda: inval_block(inv, invback))
-        deferred.append(lambda: rare_rescale_block(rare, back))
-        deferred.append(lambda: flush_block(fl, flback))
+        deferred.append(lambda: inval_block(inv, invback, R))
+        deferred.append(lambda: rare_rescale_block(rare, back, R))
+        deferred.append(lambda: flush_block(fl, flback, T, FLUSH_TAIL))
     if a_nxt and "nosoftmax" not in opt:
         vq += softmax_stream(nxt, list(range(XPAIRS)))
     # the first two gaps may only hold ops that do not read S_nxt (MFMA -> VALU read hazard): the SALU / seq part
@@ -689,7 +619,7 @@ def step(variant, a_cur=True, a_nxt=True, drop=frozenset()):
         for g_, grp in enumerate(groups):                           # one group per gap behind the statistics; what does not fit: the last gap
             post[min(t_stats + 1 + g_, NG - 1)] += grp
     mark = len(out)
-    emit_gaps(pre, mf, post)
+    emit_phase(pre, mf, post)
     if variant == 0 and full:
         # shift the second copy of the step against the first (code-placement experiments). HALF: a step is four scalar instructions (16
         # bytes: five in the PV gaps, one fewer behind the barrier) longer than the tuned form's; four widened encodings more put the second
@@ -710,7 +640,7 @@ def step(variant, a_cur=True, a_nxt=True, drop=frozenset()):
     emit(f"s_cmp_lg_u32 {s(S_RESC)}, 0")
     emit(f"s_cbranch_scc1 {resc}")
     label(resc_back)
-    deferred.append(lambda: rescale_o_block(resc, resc_back))
+    deferred.append(lambda: rescale_o_block(resc, resc_back, T, O_ACC))
     if HALF and not a_cur:
         # (the forms without PV: behind the conditional K-fragment block, which reads bit 2 of the window)
         for op in state_ops():
@@ -737,15 +667,8 @@ def next_state(shift=True):
     emit(f"s_cselect_b32 {s(S_STATE)}, {s(S_STATE)}, 4")
 
 
-def mask_first_tile_ops():
-    """seqlen-k mask of the first walked tile (mask.h:44-78; mainloop...:1626): columns >= tail_valid -> -inf."""
-    for kb in range(2):
-        for r in range(16):
-            key = 32 * kb + (r & 3) + 8 * (r >> 2)
-            emit(f"v_add_u32 {v(T[0])}, {key}, {v(HH4)}")
-            emit(f"v_cmp_gt_i32 vcc, {s(S_TAILVALID)}, {v(T[0])}")            # key < tail_valid -> keep
-            for qb in range(NQB):
-                emit(f"v_cndmask_b32 {v(S_(0, kb, qb) + r)}, {v(NEGINF)}, {v(S_(0, kb, qb) + r)}, vcc")
+# seqlen-k mask of the first walked tile: register r of key block kb holds key 32 kb + (r & 3) + 8 (r >> 2) + 4 hh, for every q-block
+MASK_KEYS = [(32 * kb + (r & 3) + 8 * (r >> 2), [S_(0, kb, qb) + r for qb in range(NQB)]) for kb in range(2) for r in range(16)]
 
 
 def w2_top_fillers(p):
@@ -807,7 +730,7 @@ def w2_stats(first_tile, can_be_first):
         emit(f"s_cbranch_scc0 {msk_back}")
         emit(f"s_cmp_lt_i32 {s(S_TAILVALID)}, 64")
         emit(f"s_cbranch_scc0 {msk_back}")
-        mask_first_tile_ops()
+        mask_ops(T, NEGINF, HH4, MASK_KEYS)
         emit(f"s_branch {msk_back}")
     if first_tile or can_be_first:
         msk, msk_back = new_label("w2mask"), new_label("w2mask_back")
@@ -896,7 +819,7 @@ def w2_stats(first_tile, can_be_first):
     emit(f"s_lshl_b32 {s(S_BIT)}, {s(S_BIT)}, 1")
     emit(f"s_cbranch_scc0 {fl}")
     label(flback)
-    deferred.append(lambda: flush_block(fl, flback))
+    deferred.append(lambda: flush_block(fl, flback, T, FLUSH_TAIL))
 
 
 def w2_pv(p):
@@ -1075,32 +998,15 @@ def prologue():
     emit(f"s_lshl_b32 {s(S_T0)}, {s(S_WAVE)}, {5 + NQB - 1}")     # 32 NQB rows per wave
     emit(f"s_add_u32 {s(S_T0)}, {s(S_T0)}, {s(S_QROW0)}")
     emit(f"s_sub_u32 {s(S_T1)}, {s(S_SEQLENQ)}, 1")
-    emit(f"v_lshlrev_b32 {v(T[6])}, 4, {v(T[0])}")            # hh * 16 bytes
-    for qb in range(NQB):
-        emit(f"v_add_u32 {v(QROW[qb])}, {s(S_T0)}, {v(T[1])}")
-        if qb:
-            emit(f"v_add_u32 {v(QROW[qb])}, 32, {v(QROW[qb])}")
-        emit(f"v_min_i32 {v(T[3])}, {v(QROW[qb])}, {s(S_T1)}")
-        emit(f"v_mad_u64_u32 {vr(T[4], 2)}, {sr(S_T64)}, {v(T[3])}, {s(S_QRS)}, 0")
-        emit(f"v_add_co_u32 {v(T[4])}, vcc, {v(T[4])}, {v(T[6])}")
-        emit(f"v_addc_co_u32 {v(T[5])}, vcc, 0, {v(T[5])}, vcc")
-        emit(f"v_add_co_u32 {v(T[4])}, vcc, {s(S_QBASE)}, {v(T[4])}")
-        emit(f"v_mov_b32 {v(T[7])}, {s(S_QBASE + 1)}")
-        emit(f"v_addc_co_u32 {v(T[5])}, vcc, {v(T[5])}, {v(T[7])}, vcc")
-        for ks in range(KS):
-            emit(f"global_load_dwordx4 {vr(4 * KS * qb + 4 * ks, 4)}, {vr(T[4], 2)}, off offset:{32 * ks}")
-    stamp(1)
-    emit("s_waitcnt vmcnt(0)")
-    stamp(2)
-    for qb in range(NQB):
-        emit(f"v_cmp_gt_i32 vcc, {s(S_SEQLENQ)}, {v(QROW[qb])}")
-        for r in range(4 * KS):
-            emit(f"v_cndmask_b32 {v(4 * KS * qb + r)}, 0, {v(4 * KS * qb + r)}, vcc")
-    for r in range(4 * KS * NQB):
-        emit(f"v_accvgpr_write_b32 a{Q_A0 + r}, {v(r)}")
-    emit("; ---- state")
-    for r in range(16 * DB * NQB):
-        emit(f"v_accvgpr_write_b32 a{r}, 0")
+
+    def q_row(qb, again):
+        if not again:
+            emit(f"v_add_u32 {v(QROW[qb])}, {s(S_T0)}, {v(T[1])}")
+            if qb:
+                emit(f"v_add_u32 {v(QROW[qb])}, 32, {v(QROW[qb])}")
+        return QROW[qb]
+    q_rows_to_agprs(T, NQB, KS, 32, Q_A0, q_row, loaded=lambda: (stamp(1), emit("s_waitcnt vmcnt(0)"), stamp(2)))     # (T[0] = hh)
+    zero_accumulators(range(16 * DB * NQB))
     for qb in range(NQB):
         emit(f"v_mov_b32 {v(MTRUE[qb])}, 0xff800000")
         emit(f"v_mov_b32 {v(L0[qb])}, 0")
@@ -1128,17 +1034,10 @@ def prologue():
         emit(("DRAIN",))
         emit("s_barrier")
         return
-    emit("; ---- tile addresses of positions 1..3 from the table; K(0) fragments -> AGPRs, S(0) = K(0) Q^T, then K(1) fragments")
-    emit(f"v_mov_b32 {v(T[6])}, {s(S_TAB)}")
-    emit(f"ds_read_b64 {vr(T[8], 2)}, {v(T[6])} offset:32")          # tab[2].k : K(2), staged below
-    emit(f"ds_read_b64 {vr(T[10], 2)}, {v(T[6])} offset:48")         # tab[3].k : K(3), staged by step 0
-    emit(f"ds_read_b64 {vr(T[12], 2)}, {v(T[6])} offset:24")         # tab[1].v : V(1), staged by step 0
-    emit(f"v_add_u32 {v(TABV)}, 32, {v(T[6])}")                      # step 0 reads tab[2].v and tab[4].k
+    read_tile_table(T, TABV)
     for j in range(NKF):
         emit(k_read(0, j))
-    emit(("DRAIN",))
-    emit(f"v_readfirstlane_b32 {s(TBS[0])}, {v(T[8])}")
-    emit(f"v_readfirstlane_b32 {s(TBS[0] + 1)}, {v(T[9])}")
+    k2_base(T)
     ord1 = [(f & 1) * KS + (f >> 1) for f in range(NKF)]
     if HALF:
         noqk0 = new_label("noqk0")
@@ -1152,33 +1051,14 @@ def prologue():
         emit(k_read(KV_TILE, j))
     emit(("DRAIN",))
     emit("s_barrier")                                          # every wave has read K(0) and K(1): both K buffers are free
-    # K(2) -> K buffer 0. V(1)/K(3) are staged by step 0.
-    for it in dma_ops(0, 0, do_k=True, do_v=False):
-        out.append(it)
-        if "m0" in it:
-            emit("s_nop 0")
-    for dst, src in ((TBS[0], T[10]), (TBS[0] + 1, T[11]), (VBS[0], T[12]), (VBS[0] + 1, T[13])):   # step 0 stages K(3), V(1)
-        emit(f"v_readfirstlane_b32 {s(dst)}, {v(src)}")
+    stage_k2(dma_ops(0, 0, do_k=True, do_v=False), T)            # K(2) -> K buffer 0; V(1) / K(3) are staged by step 0
     emit("s_nop 7")
     if HALF:
         nofirst = new_label("nofirst")
         emit(f"s_mov_b32 {s(S_DOMASK)}, 0")
         emit(f"s_bitcmp1_b32 {s(S_ACT)}, 0")
         emit(f"s_cbranch_scc0 {nofirst}")
-    # seqlen-k mask: only if n0 == k_tiles-1 and tail_valid < 64  (mask.h:44-78; first walked tile only, mainloop...:1626)
-    nomask = new_label("nomask")
-    emit(f"s_cmp_eq_u32 {s(S_FIRSTLAST)}, 1")                # the first walked tile is tile k_tiles - 1 (C++ shell)
-    emit(f"s_cbranch_scc0 {nomask}")
-    emit(f"s_cmp_lt_i32 {s(S_TAILVALID)}, 64")
-    emit(f"s_cbranch_scc0 {nomask}")
-    for kb in range(2):
-        for r in range(16):
-            key = 32 * kb + (r & 3) + 8 * (r >> 2)
-            emit(f"v_add_u32 {v(T[0])}, {key}, {v(HH4)}")
-            emit(f"v_cmp_gt_i32 vcc, {s(S_TAILVALID)}, {v(T[0])}")            # key < tail_valid -> keep
-            for qb in range(NQB):
-                emit(f"v_cndmask_b32 {v(S_(0, kb, qb) + r)}, {v(NEGINF)}, {v(S_(0, kb, qb) + r)}, vcc")
-    label(nomask)
+    first_tile_mask(T, NEGINF, HH4, MASK_KEYS)
     for op in row_max_ops(0):
         out.append(op)
     # first-tile stats: m_true = m_ref = row max; position 0 is never flagged (softmax.h:153)
@@ -1210,16 +1090,61 @@ def prologue():
 
 
 def epilogue():
-    emit("; ---- flush the last (partial) vote word")
-    nofl = new_label("nolastflush")
-    emit(f"s_cmp_eq_u32 {s(S_DOMASK)}, 0")
-    emit(f"s_cbranch_scc1 {nofl}")
-    flush_domask(T[4], T[5])
-    label(nofl)
-    emit("s_nop 15")                                           # the last PV MFMAs have written the accumulators
-    emit("s_nop 15")
-    store_epilogue(globals(), O_)                              # gen_epilogue.py: 1/l, bf16 O and LSE from the registers
+    flush_last_vote_word(T)
+    store_epilogue(O_, T, L0, L1, MREF, NEGINF, HH4, QROW, MLOC[0], CVT_OP, NQB, DB)     # gen_epilogue.py: 1/l, 16-bit O and LSE from the registers
     emit("s_waitcnt lgkmcnt(0)")
+
+
+def pad_second_copy(variant):
+    """pad4b (code-placement experiments): the second copy of the step against the first"""
+    for _ in range(variant * int(opt_val(OPT, "pad4b", "0"))):
+        emit("s_nop 0")
+
+
+def step_form(variant, done):
+    """The step copy `variant` of the loop: the plain step, or the dispatch of the half-vote / halfskip forms."""
+    if HALF:
+        # four forms of the step by (a(i), a(i+1)); S_STATE was computed in front of the previous drain (4 = the walk is over). The
+        # full form stays inline (the hot path: one compare and one branch in front of it, as in the form without activity bits),
+        # the others are out of line
+        notfull, after = new_label("notfull"), new_label("after_step")
+        emit(f"s_cmp_eq_u32 {s(S_STATE)}, 3")
+        emit(f"s_cbranch_scc0 {notfull}")
+        step(variant)
+        label(after)
+
+        def partial_forms():
+            l10, l01 = new_label("step10"), new_label("step01")
+            label(notfull)
+            emit(f"s_cmp_eq_u32 {s(S_STATE)}, 4")
+            emit(f"s_cbranch_scc1 {done}")
+            emit(f"s_cmp_eq_u32 {s(S_STATE)}, 1")
+            emit(f"s_cbranch_scc1 {l10}")
+            emit(f"s_cmp_eq_u32 {s(S_STATE)}, 2")
+            emit(f"s_cbranch_scc1 {l01}")
+            step(variant, a_cur=False, a_nxt=False)
+            emit(f"s_branch {after}")
+            label(l10)
+            step(variant, a_cur=True, a_nxt=False)
+            emit(f"s_branch {after}")
+            label(l01)
+            step(variant, a_cur=False, a_nxt=True)
+            emit(f"s_branch {after}")
+        deferred.append(partial_forms)
+    elif HALFSKIP:
+        # waves 0-1 sit out the steps with i % HALFSKIP == 0, waves 2-3 those with i % HALFSKIP == HALFSKIP / 2: what a workgroup
+        # walking the union of two per-128-row lists would do on the tiles only one half lists (HISTORY.md section 8.6 a)
+        lbl, after = new_label("light"), new_label("after_light")
+        emit(f"s_lshr_b32 {s(S_T0)}, {s(S_WAVE)}, 1")
+        emit(f"s_mul_i32 {s(S_T0)}, {s(S_T0)}, {HALFSKIP // 2}")
+        emit(f"s_and_b32 {s(S_T1)}, {s(S_I)}, {HALFSKIP - 1}")
+        emit(f"s_cmp_eq_u32 {s(S_T0)}, {s(S_T1)}")
+        emit(f"s_cbranch_scc1 {lbl}")
+        step(variant)
+        label(after)
+        deferred.append(lambda: (label(lbl), step(variant, drop=LIGHT), emit(f"s_branch {after}")))
+    else:                                # (the W2 body has its own loops: main())
+        step(variant)
 
 
 def main():
@@ -1249,78 +1174,13 @@ def main():
         epilogue()
         write_out()
         return
-    loop, done = new_label("loop"), new_label("done")
-    # Code placement (round 5). Where the loop head falls inside a 32-byte fetch window moves the body's throughput by up to 2-3 % with a
-    # period of 32 bytes (tools/debug/phase_sweep_bench.py, profiles/r05_code_placement.md: head_dim 128: 1311-1316 TFLOP/s at phase 0,
-    # 1329-1334 at phase 8; head_dim 64: 1011-1015 at 0, 1041 at 24) - and until round 5 that phase was whatever the C++ shell in front of
-    # the asm statement happened to leave: an edit to the list writer moved the headline kernel from phase 8 to phase 16 and cost 0.8 %.
-    # The head is now pinned: .p2align 5, then PHASE / 4 s_nop (executed once per item), per body the best measured phase.
-    # `align:N` / `pad4:N` override it for experiments.
-    if opt_val(OPT, "align", "") or opt_val(OPT, "pad4", ""):
-        if opt_val(OPT, "align", ""):
-            out.append(f".p2align {opt_val(OPT, 'align', '')}")
-        for _ in range(int(opt_val(OPT, "pad4", "0"))):
-            emit("s_nop 0")
-    else:
-        out.append(".p2align 5")
-        for _ in range(LOOP_PHASE // 4):
-            emit("s_nop 0")
+    # Code placement (round 5; gen_blocks.loop_head). Measured with tools/debug/phase_sweep_bench.py: head_dim 128: 1311-1316 TFLOP/s at
+    # phase 0, 1329-1334 at phase 8; head_dim 64: 1011-1015 at 0, 1041 at 24 - and until round 5 that phase was whatever the C++ shell
+    # in front of the asm statement happened to leave: an edit to the list writer moved the headline kernel from phase 8 to phase 16
+    # and cost 0.8 %.
+    loop_head(LOOP_PHASE, opt_val(OPT, "align", ""), opt_val(OPT, "pad4", ""))
     stamp(3)
-    label(loop)
-    for variant in (0, 1):
-        if variant == 1:
-            for _ in range(int(opt_val(OPT, "pad4b", "0"))):   # code-placement experiments: the second copy of the step against the first
-                emit("s_nop 0")
-        if not HALF:
-            emit(f"s_cmp_lt_u32 {s(S_I)}, {s(S_NTILES)}")
-            emit(f"s_cbranch_scc0 {done}")
-        if HALF:
-            # four forms of the step by (a(i), a(i+1)); S_STATE was computed in front of the previous drain (4 = the walk is over). The
-            # full form stays inline (the hot path: one compare and one branch in front of it, as in the form without activity bits),
-            # the others are out of line
-            notfull, after = new_label("notfull"), new_label("after_step")
-            emit(f"s_cmp_eq_u32 {s(S_STATE)}, 3")
-            emit(f"s_cbranch_scc0 {notfull}")
-            step(variant)
-            label(after)
-
-            def partial_forms(notfull=notfull, after=after, variant=variant):
-                l10, l01 = new_label("step10"), new_label("step01")
-                label(notfull)
-                emit(f"s_cmp_eq_u32 {s(S_STATE)}, 4")
-                emit(f"s_cbranch_scc1 {done}")
-                emit(f"s_cmp_eq_u32 {s(S_STATE)}, 1")
-                emit(f"s_cbranch_scc1 {l10}")
-                emit(f"s_cmp_eq_u32 {s(S_STATE)}, 2")
-                emit(f"s_cbranch_scc1 {l01}")
-                step(variant, a_cur=False, a_nxt=False)
-                emit(f"s_branch {after}")
-                label(l10)
-                step(variant, a_cur=True, a_nxt=False)
-                emit(f"s_branch {after}")
-                label(l01)
-                step(variant, a_cur=False, a_nxt=True)
-                emit(f"s_branch {after}")
-            deferred.append(partial_forms)
-        elif HALFSKIP:
-            # waves 0-1 sit out the steps with i % HALFSKIP == 0, waves 2-3 those with i % HALFSKIP == HALFSKIP / 2: what a workgroup
-            # walking the union of two per-128-row lists would do on the tiles only one half lists (HISTORY.md section 8.6 a)
-            assert not W2
-            lbl, after = new_label("light"), new_label("after_light")
-            emit(f"s_lshr_b32 {s(S_T0)}, {s(S_WAVE)}, 1")
-            emit(f"s_mul_i32 {s(S_T0)}, {s(S_T0)}, {HALFSKIP // 2}")
-            emit(f"s_and_b32 {s(S_T1)}, {s(S_I)}, {HALFSKIP - 1}")
-            emit(f"s_cmp_eq_u32 {s(S_T0)}, {s(S_T1)}")
-            emit(f"s_cbranch_scc1 {lbl}")
-            step(variant)
-            label(after)
-            deferred.append(lambda lbl=lbl, after=after, variant=variant: (label(lbl), step(variant, drop=LIGHT), emit(f"s_branch {after}")))
-        else:                            # (the W2 body has its own loops and returned above)
-            step(variant)
-    emit(f"s_branch {loop}")
-    for blk in deferred:
-        blk()
-    label(done)
+    unrolled_loop(step_form, end_test=not HALF, before_copy=pad_second_copy)
     stamp(4)
     epilogue()
     stamp(5)

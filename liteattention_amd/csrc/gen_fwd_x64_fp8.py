@@ -31,8 +31,10 @@ results equal the offset-8 ones except for P < 2^-12 (absolute 2.4e-4 of a weigh
 """
 import os
 import sys
+from types import SimpleNamespace
 
 from gen_asm import *
+from gen_blocks import *
 from gen_epilogue import store_epilogue
 
 set_label_prefix(".LF")
@@ -158,6 +160,7 @@ TABV = 222                                # LDS address of tab[i + 2], the tile-
 # mx: per row -m_ref c + 127; per row and tile the offset of the byte encoding; the tile's E8M0 scale byte per S set
 NMR, NMSB, SCB = [178, 179], [186, 187], [[188, 189], [215, 218]]      # (L0 / L1 are unused with the matrix-pipe row sums)
 MXT = [T[10], T[11]]
+R = SimpleNamespace(T=T, QBS=QBS, MLOC=MLOC, MTRUE=MTRUE, MREF=MREF, MTHR=MTHR, NMS=NMS, ALPHA=ALPHA, L0=L0, L1=L1, NEGINF=NEGINF)   # gen_blocks.py
 
 # ---------------------------------------------------------------- SGPR aliases of this generator (the map: gen_asm.py)
 S_C8, S_NEGC8, S_M8 = S_FREE0, S_FREE1, S_FREE2   # lin: 8 c and -8 c; mx: -8.0
@@ -289,18 +292,7 @@ def softmax_stream(sset, groups):
 
 
 def row_max_ops(sset):
-    per = []
-    for qb in QBS:
-        regs = [S_(sset, qb, 0) + r for r in range(32)]
-        ops = [f"    v_max_f32 {v(MLOC[qb])}, {v(regs[0])}, {v(regs[1])}", f"    v_max_f32 {v(MLOC2[qb])}, {v(regs[2])}, {v(regs[3])}"]
-        rest = regs[4:]
-        chains = [MLOC[qb], MLOC2[qb]]
-        for n_, i in enumerate(range(0, len(rest), 2)):
-            ch = chains[n_ & 1]
-            ops.append(f"    v_max3_f32 {v(ch)}, {v(ch)}, {v(rest[i])}, {v(rest[i + 1])}")
-        ops.append(f"    v_max_f32 {v(MLOC[qb])}, {v(MLOC[qb])}, {v(MLOC2[qb])}")
-        per.append(ops)
-    return [x for pair in zip(*per) for x in pair]
+    return row_max_chains([[S_(sset, qb, 0) + r for r in range(32)] for qb in QBS], MLOC, MLOC2)
 
 
 def stats_ops(rare_label, back_label, flush_label, flush_back, inval_label, inval_back, sset=0):
@@ -364,68 +356,17 @@ def float_bits(x):
     return struct.unpack("<I", struct.pack("<f", x))[0]
 
 
-def rare_rescale_block(rare_label, back_label):
-    label(rare_label)
+def rescale_lsum():
+    """LMFMA: the row sums live in accumulators and are rescaled with O: only register 0 of each block is ever read"""
     for qb in QBS:
-        emit(f"v_sub_f32 {v(T[2 + qb])}, {v(MREF[qb])}, {v(MTRUE[qb])}")
+        emit(f"v_accvgpr_read_b32 {v(T[qb])}, a{LSUM(qb)}")
     for qb in QBS:
-        emit(f"v_mul_f32 {v(T[2 + qb])}, {s(S_C)}, {v(T[2 + qb])}")
+        emit(f"v_mul_f32 {v(T[qb])}, {v(T[qb])}, {v(ALPHA[qb])}")
     for qb in QBS:
-        emit(f"v_exp_f32 {v(ALPHA[qb])}, {v(T[2 + qb])}")
-    for qb in QBS:
-        emit(f"v_mov_b32 {v(MREF[qb])}, {v(MTRUE[qb])}")
-    for qb in QBS:
-        set_nms(qb)
-        emit(f"v_add_f32 {v(MTHR[qb])}, {s(S_TAU)}, {v(MREF[qb])}")
-    for qb in QBS:
-        if not LMFMA:                        # (LMFMA: the row sums live in accumulators and are rescaled with O)
-            emit(f"v_mul_f32 {v(L0[qb])}, {v(L0[qb])}, {v(ALPHA[qb])}")
-            emit(f"v_mul_f32 {v(L1[qb])}, {v(L1[qb])}, {v(ALPHA[qb])}")
-    emit(f"s_mov_b32 {s(S_RESC)}, 1")
-    emit(f"s_branch {back_label}")
+        emit(f"v_accvgpr_write_b32 a{LSUM(qb)}, {v(T[qb])}")
 
 
-def inval_block(lbl, back):
-    label(lbl)
-    for qb in QBS:
-        emit(f"v_mov_b32 {v(MLOC[qb])}, {v(NEGINF)}")
-        emit(f"v_mov_b32 {v(NMS[qb])}, {v(NEGINF)}")
-    emit(f"s_branch {back}")
-
-
-def flush_block(flush_label, back_label):
-    label(flush_label)
-    flush_domask(T[4], T[5])
-    emit(f"s_add_u32 {s(S_DOWORD)}, {s(S_DOWORD)}, 4")
-    emit(f"s_mov_b32 {s(S_BIT)}, 1")
-    emit("s_waitcnt lgkmcnt(0)")
-    emit(f"s_branch {back_label}")
-
-
-def rescale_o_block(lbl, back):
-    label(lbl)
-    emit("s_nop 15")
-    emit("s_nop 15")
-    emit("s_nop 15")
-    emit("s_nop 15")
-    for qb in QBS:
-        for base in range(0, 16 * ND, 8):
-            for k in range(8):
-                emit(f"v_accvgpr_read_b32 {v(T[k])}, a{64 * qb + base + k}")
-            for k in range(8):
-                emit(f"v_mul_f32 {v(T[k])}, {v(T[k])}, {v(ALPHA[qb])}")
-            for k in range(8):
-                emit(f"v_accvgpr_write_b32 a{64 * qb + base + k}, {v(T[k])}")
-    if LMFMA:                                # the row sums: only register 0 of each block is ever read
-        for qb in QBS:
-            emit(f"v_accvgpr_read_b32 {v(T[qb])}, a{LSUM(qb)}")
-        for qb in QBS:
-            emit(f"v_mul_f32 {v(T[qb])}, {v(T[qb])}, {v(ALPHA[qb])}")
-        for qb in QBS:
-            emit(f"v_accvgpr_write_b32 a{LSUM(qb)}, {v(T[qb])}")
-    emit(f"s_mov_b32 {s(S_RESC)}, 0")
-    emit("s_nop 7")
-    emit(f"s_branch {back}")
+O_ACC = [(ALPHA[qb], range(64 * qb, 64 * qb + 16 * ND)) for qb in QBS]       # rescale_o_block: what alpha scales
 
 
 def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
@@ -433,14 +374,7 @@ def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
     and the LDS address alike). K: the per-lane offsets LK[j] carry +(1024 - 1024 j) and S_KBASE carries -1024, so they stay
     >= 0 when rows are clamped to a short sequence (the SADDR form's VGPR is an UNSIGNED 32-bit offset; see gen_fwd_x64.py
     dma_ops). V^T: LV is the same for both pieces (the prepared tile is copied linearly)."""
-    o = []
-    if do_k:
-        o.append(f"    s_add_u32 m0, {s(S_DMAW)}, {kbuf_imm}")
-        o += [f"    global_load_lds_dwordx4 {v(LK[j])}, {sr(TBS[st])} offset:{1024 * j}" for j in range(PIECES_K)]
-    if do_v:
-        o.append(f"    s_add_u32 m0, {s(S_DMAWV)}, {V_REGION + vbuf_imm}")
-        o += [f"    global_load_lds_dwordx4 {v(LV)}, {sr(VBS[st])} offset:{1024 * j}" for j in range(PIECES_V)]
-    return o
+    return dma_issue([(S_DMAW, kbuf_imm, LK[:PIECES_K], TBS[st])] * do_k + [(S_DMAWV, V_REGION + vbuf_imm, [LV] * PIECES_V, VBS[st])] * do_v)
 
 
 QK_ORDER = [(sx, kb, qb) for sx in range(NSX) for kb in (0, 1) for qb in QBS]      # dependent pairs are 4 MFMAs apart (one q-block: 2)
@@ -464,9 +398,7 @@ def step(variant):
         v0 = 0 if "vspread" in OPT else NG // 2          # vspread (A/B): the V^T fragment reads over the whole of phase 1 instead of its second half
         post[v0 + f * (NG - v0) // (2 * ND)].append(v_read(vbuf_cur, db, t))
     distribute(softmax_stream(cur, list(range(XPAIRS, 16))), post, int(opt_val(OPT, "smstart", "0")))
-    for t in range(NG):
-        out.append(mf[t])
-        out.extend(post[t])
+    emit_gaps([[]] * NG, mf, post)
 
     # ---- phase 2
     emit("s_nop 1")                          # the last e4m3 converts (VALU writes) -> first PV MFMA (reads them as B)
@@ -506,24 +438,21 @@ def step(variant):
     vq += mixed
     inv, invback = new_label("inval"), new_label("inval_back")
     vq += stats_ops(rare, back, fl, flback, inv, invback, sset=nxt)
-    deferred.append(lambda: inval_block(inv, invback))
-    deferred.append(lambda: rare_rescale_block(rare, back))
-    deferred.append(lambda: flush_block(fl, flback))
+    deferred.append(lambda: inval_block(inv, invback, R))
+    deferred.append(lambda: rare_rescale_block(rare, back, R, set_nms, l_in_vgprs=not LMFMA))
+    deferred.append(lambda: flush_block(fl, flback, T))
     vq += softmax_stream(nxt, list(range(XPAIRS)))
     # gap 0 holds only ops that do not read S_nxt (its last MFMA was issued just before this phase)
     post[0] += vq[:n_head]
     distribute(vq[n_head:], post, 1)
-    for t in range(NG2):
-        out.extend(pre[t])
-        out.append(mf[t])
-        out.extend(post[t])
+    emit_gaps(pre, mf, post)
 
     # ---- tail: rare O rescale, drain, barrier
     slow, slow_back = new_label("slow"), new_label("slow_back")
     emit(f"s_cmp_lg_u32 {s(S_RESC)}, 0")
     emit(f"s_cbranch_scc1 {slow}")
     label(slow_back)
-    deferred.append(lambda: rescale_o_block(slow, slow_back))
+    deferred.append(lambda: rescale_o_block(slow, slow_back, T, O_ACC, nops=4, tail=rescale_lsum if LMFMA else None))
     emit(("DRAIN",))
     if "nobarrier" not in OPT and not ("halfbarrier" in OPT and variant == 0):                 # pricing only
         emit("s_barrier")
@@ -641,13 +570,7 @@ def prologue():
         emit(f"v_add_u32 {v(QROW[qb])}, {s(S_T0)}, {v(T[1])}")
         if qb:
             emit(f"v_add_u32 {v(QROW[qb])}, 32, {v(QROW[qb])}")
-        emit(f"v_min_i32 {v(T[3])}, {v(QROW[qb])}, {s(S_T1)}")
-        emit(f"v_mad_u64_u32 {vr(T[4], 2)}, {sr(S_T64)}, {v(T[3])}, {s(S_QRS)}, 0")
-        emit(f"v_add_co_u32 {v(T[4])}, vcc, {v(T[4])}, {v(T[6])}")
-        emit(f"v_addc_co_u32 {v(T[5])}, vcc, 0, {v(T[5])}, vcc")
-        emit(f"v_add_co_u32 {v(T[4])}, vcc, {s(S_QBASE)}, {v(T[4])}")
-        emit(f"v_mov_b32 {v(T[7])}, {s(S_QBASE + 1)}")
-        emit(f"v_addc_co_u32 {v(T[5])}, vcc, {v(T[5])}, {v(T[7])}, vcc")
+        q_row_address(T, QROW[qb])
         for sx in range(NSX):
             for t in (0, 1):
                 if 64 * sx + 32 * t >= D:            # head_dim 96: d 96..127 does not exist - zero fragments (they meet the K tile's filler chunks)
@@ -663,9 +586,7 @@ def prologue():
     for qb in QBS:
         for r in range(8 * NSX):
             emit(f"v_accvgpr_write_b32 a{128 + 16 * qb + r}, {v(16 * qb + r)}")
-    emit("; ---- state")
-    for r in list(range(128)) + (list(range(LSUM(0), LSUM(NQB - 1) + 16)) if LMFMA else []):
-        emit(f"v_accvgpr_write_b32 a{r}, 0")
+    zero_accumulators(list(range(128)) + (list(range(LSUM(0), LSUM(NQB - 1) + 16)) if LMFMA else []))
     for qb in QBS:
         emit(f"v_mov_b32 {v(MTRUE[qb])}, 0xff800000")
         if not LMFMA:
@@ -673,17 +594,10 @@ def prologue():
             emit(f"v_mov_b32 {v(L1[qb])}, 0")
         emit(f"v_mov_b32 {v(ALPHA[qb])}, 1.0")
 
-    emit("; ---- tile addresses of positions 1..3 from the table; K(0) fragments -> AGPRs, S(0) = K(0) Q^T, then K(1) fragments")
-    emit(f"v_mov_b32 {v(T[6])}, {s(S_TAB)}")
-    emit(f"ds_read_b64 {vr(T[8], 2)}, {v(T[6])} offset:32")          # tab[2].k : K(2), staged below
-    emit(f"ds_read_b64 {vr(T[10], 2)}, {v(T[6])} offset:48")         # tab[3].k : K(3), staged by step 0
-    emit(f"ds_read_b64 {vr(T[12], 2)}, {v(T[6])} offset:24")         # tab[1].v : V^T(1), staged by step 0
-    emit(f"v_add_u32 {v(TABV)}, 32, {v(T[6])}")                      # step 0 reads tab[2].v and tab[4].k
+    read_tile_table(T, TABV)
     for (j, t) in K_FRAGS:
         emit(k_read(0, j, t))
-    emit(("DRAIN",))
-    emit(f"v_readfirstlane_b32 {s(TBS[0])}, {v(T[8])}")
-    emit(f"v_readfirstlane_b32 {s(TBS[0] + 1)}, {v(T[9])}")
+    k2_base(T)
     emit("s_nop 7")                                           # v_accvgpr_write (Q) / ds_read (K) -> MFMA operand reads
     for (sx, kb, qb) in QK_ORDER:
         out.append(mfma_qk(0, kb, sx, qb))
@@ -691,27 +605,10 @@ def prologue():
         emit(k_read(KV_TILE, j, t))
     emit(("DRAIN",))
     emit("s_barrier")                                          # every wave has read K(0) and K(1): both K buffers are free
-    for it in dma_ops(0, 0, do_k=True, do_v=False):            # K(2) -> K buffer 0. V^T(1) / K(3) are staged by step 0.
-        out.append(it)
-        if "m0" in it:
-            emit("s_nop 0")
-    for dst, src in ((TBS[0], T[10]), (TBS[0] + 1, T[11]), (VBS[0], T[12]), (VBS[0] + 1, T[13])):   # step 0 stages K(3), V^T(1)
-        emit(f"v_readfirstlane_b32 {s(dst)}, {v(src)}")
+    stage_k2(dma_ops(0, 0, do_k=True, do_v=False), T)          # K(2) -> K buffer 0. V^T(1) / K(3) are staged by step 0.
     emit("s_nop 15")                                           # S(0): the last MFMA's results before the VALU reads them
     emit("s_nop 15")
-    nomask = new_label("nomask")
-    emit(f"s_cmp_eq_u32 {s(S_FIRSTLAST)}, 1")                  # seqlen-k mask: first walked tile only (mask.h:44-78), if it is tile k_tiles-1
-    emit(f"s_cbranch_scc0 {nomask}")
-    emit(f"s_cmp_lt_i32 {s(S_TAILVALID)}, 64")
-    emit(f"s_cbranch_scc0 {nomask}")
-    for kb in range(2):
-        for r in range(16):
-            key = 32 * kb + (r & 3) + 8 * (r >> 2)
-            emit(f"v_add_u32 {v(T[0])}, {key}, {v(HH4)}")
-            emit(f"v_cmp_gt_i32 vcc, {s(S_TAILVALID)}, {v(T[0])}")
-            for qb in QBS:
-                emit(f"v_cndmask_b32 {v(S_(0, qb, kb) + r)}, {v(NEGINF)}, {v(S_(0, qb, kb) + r)}, vcc")
-    label(nomask)
+    first_tile_mask(T, NEGINF, HH4, [(32 * kb + (r & 3) + 8 * (r >> 2), [S_(0, qb, kb) + r for qb in QBS]) for kb in range(2) for r in range(16)])
     for op in row_max_ops(0):
         out.append(op)
     for qb in QBS:
@@ -738,47 +635,18 @@ def prologue():
 
 
 def epilogue():
-    emit("; ---- flush the last (partial) vote word")
-    nofl = new_label("nolastflush")
-    emit(f"s_cmp_eq_u32 {s(S_DOMASK)}, 0")
-    emit(f"s_cbranch_scc1 {nofl}")
-    flush_domask(T[4], T[5])
-    label(nofl)
-    emit("s_nop 15")                                           # the last PV MFMAs (16 passes each) have written the accumulators
-    emit("s_nop 15")
-    emit("s_nop 15")
-    emit("s_nop 15")
-    if LMFMA:
-        globals()["LSUM_AGPR"] = [LSUM(qb) for qb in QBS]      # l~ of the lane's row: register 0 of the row-sum accumulators
-    store_epilogue(globals(), O_)                              # gen_epilogue.py: v_descale / l, bf16 O and LSE from the registers
+    flush_last_vote_word(T, nops=4)                            # (the last PV MFMAs have 16 passes each)
+    store_epilogue(O_, T, L0, L1, MREF, NEGINF, HH4, QROW, MLOC[0], "v_cvt_pk_bf16_f32", NQB, DB,     # gen_epilogue.py: v_descale / l, bf16 O and LSE
+                   [LSUM(qb) for qb in QBS] if LMFMA else None)  # l~ of the lane's row: register 0 of the row-sum accumulators
     emit("s_waitcnt lgkmcnt(0)")
 
 
 def main():
     prologue()
-    loop, done = new_label("loop"), new_label("done")
-    # Code placement (round 5; see gen_fwd_x64.py main()): the loop head is pinned at the best measured phase inside a 32-byte window -
+    # Code placement (round 5; gen_blocks.loop_head): the loop head is pinned at the best measured phase inside a 32-byte window -
     # default form 0, exact-exp 24 (30.65 ms against 31.25 at phases 8 / 16: 2 %), exact-rowsum 8 (flat). `align:N` / `pad4:N` override.
-    if opt_val(OPT, "align", "") or opt_val(OPT, "pad4", ""):
-        if opt_val(OPT, "align", ""):
-            out.append(f".p2align {opt_val(OPT, 'align', '')}")
-        for _ in range(int(opt_val(OPT, "pad4", "0"))):
-            emit("s_nop 0")
-    else:
-        out.append(".p2align 5")
-        for _ in range((8 if not LMFMA else (0 if LIN else 24)) // 4):
-            emit("s_nop 0")
-    label(loop)
-    emit(f"s_cmp_lt_u32 {s(S_I)}, {s(S_NTILES)}")
-    emit(f"s_cbranch_scc0 {done}")
-    step(0)
-    emit(f"s_cmp_lt_u32 {s(S_I)}, {s(S_NTILES)}")
-    emit(f"s_cbranch_scc0 {done}")
-    step(1)
-    emit(f"s_branch {loop}")
-    for blk in deferred:
-        blk()
-    label(done)
+    loop_head(8 if not LMFMA else (0 if LIN else 24), opt_val(OPT, "align", ""), opt_val(OPT, "pad4", ""))
+    unrolled_loop(lambda variant, done: step(variant))
     epilogue()
     lines = finalize(OPT)
     path = sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_fp8_body.inc"

@@ -39,6 +39,7 @@ import os
 import sys
 
 from gen_asm import *
+from gen_blocks import *
 from gen_epilogue import S_CLN2, S_LSEADD, S_LSEB, S_OBASE, S_ORS, S_OSCALE, read_epilogue_params
 
 set_label_prefix(".LM")
@@ -271,51 +272,14 @@ def inval_block(lbl, back):
     emit(f"s_branch {back}")
 
 
-def flush_block(flush_label, back_label):
-    label(flush_label)
-    flush_domask(T[4], T[5])
-    emit(f"s_add_u32 {s(S_DOWORD)}, {s(S_DOWORD)}, 4")
-    emit(f"s_mov_b32 {s(S_BIT)}, 1")
-    emit("s_waitcnt lgkmcnt(0)")
-    emit(f"s_branch {back_label}")
-
-
-def rescale_o_block(lbl, back):
-    """Out of line (rare): O^T *= alpha of the lane's query per q-block (AGPR -> VGPR -> AGPR), after the PV MFMAs have drained."""
-    label(lbl)
-    emit("s_nop 15")
-    emit("s_nop 15")
-    for qb in range(NQB):
-        for base in range(0, 4 * DB, 8):
-            for k in range(8):
-                emit(f"v_accvgpr_read_b32 {v(T[k])}, a{O_(qb, 0) + base + k}")
-            for k in range(8):
-                emit(f"v_mul_f32 {v(T[k])}, {v(T[k])}, {v(ALPHA[qb])}")
-            for k in range(8):
-                emit(f"v_accvgpr_write_b32 a{O_(qb, 0) + base + k}, {v(T[k])}")
-    emit(f"s_mov_b32 {s(S_RESC)}, 0")
-    emit("s_nop 7")
-    emit(f"s_branch {back}")
+O_ACC = [(ALPHA[qb], range(O_(qb, 0), O_(qb, 0) + 4 * DB)) for qb in range(NQB)]       # rescale_o_block: alpha of the lane's query per q-block
 
 
 def dma_ops(kbuf_imm, vbuf_imm, do_k=True, do_v=True, st=0):
     """[m0K, K0..K3, m0V, V0..V3]: one M0 per tensor, the piece index on the instruction offset (see gen_fwd_x64.py dma_ops)."""
     if "nodma" in OPT:
         return []
-    o = []
-    if do_k:
-        o.append(f"    s_add_u32 m0, {s(S_DMAW)}, {kbuf_imm}")
-        o += [f"    global_load_lds_dwordx4 {v(LK[j])}, {sr(TBS[st])} offset:{1024 * j}{DMA_POLICY}" for j in range(4)]
-    if do_v:
-        o.append(f"    s_add_u32 m0, {s(S_DMAW)}, {V_REGION + vbuf_imm}")
-        o += [f"    global_load_lds_dwordx4 {v(LV[j])}, {sr(VBS[st])} offset:{1024 * j}{DMA_POLICY}" for j in range(4)]
-    return o
-
-
-def emit_gaps(pre, mf, post):
-    for t in range(NG):
-        for it in pre[t] + [mf[t]] + post[t]:
-            out.append(it)
+    return dma_issue([(S_DMAW, kbuf_imm, LK, TBS[st])] * do_k + [(S_DMAW, V_REGION + vbuf_imm, LV, VBS[st])] * do_v, DMA_POLICY)
 
 
 def step(variant):
@@ -373,7 +337,7 @@ def step(variant):
         vq += stats_ops(rare, back, fl, flback, inv, invback)
         deferred.append(lambda: inval_block(inv, invback))
         deferred.append(lambda: rare_rescale_block(rare, back))
-        deferred.append(lambda: flush_block(fl, flback))
+        deferred.append(lambda: flush_block(fl, flback, T))
     vq += softmax_stream(nxt, list(range(XQ)))
     # the first SAFE_GAPS gaps hold nothing that reads S_nxt (MFMA result -> VALU read hazard: the last QK MFMA has 8 passes)
     distribute(head, post, 0, 4, end=SAFE_GAPS)
@@ -385,7 +349,7 @@ def step(variant):
     emit(f"s_cmp_lg_u32 {s(S_RESC)}, 0")
     emit(f"s_cbranch_scc1 {resc}")
     label(resc_back)
-    deferred.append(lambda: rescale_o_block(resc, resc_back))
+    deferred.append(lambda: rescale_o_block(resc, resc_back, T, O_ACC))
     emit(("DRAIN",))
     if "nobarrier" not in OPT:
         emit("s_barrier")
@@ -453,49 +417,23 @@ def prologue():
     emit(f"s_add_u32 {s(S_T0)}, {s(S_T0)}, {s(S_QROW0)}")
     emit(f"s_sub_u32 {s(S_T1)}, {s(S_SEQLENQ)}, 1")
     emit(f"v_add_u32 {v(QROW_T)}, {s(S_T0)}, {v(LANE)}")                     # the lane's row in the transposed form
-    emit(f"v_lshlrev_b32 {v(T[6])}, 4, {v(T[0])}")                           # g * 16 bytes
-    for qb in range(NQB):                                                    # all 16 loads in flight together
+
+    def q_row(qb, again):                                                    # (both passes; all 16 loads in flight together)
         emit(f"v_add_u32 {v(T[8])}, {s(S_T0)}, {v(J16)}")
         if qb:
             emit(f"v_add_u32 {v(T[8])}, {16 * qb}, {v(T[8])}")
-        emit(f"v_min_i32 {v(T[3])}, {v(T[8])}, {s(S_T1)}")
-        emit(f"v_mad_u64_u32 {vr(T[4], 2)}, {sr(S_T64)}, {v(T[3])}, {s(S_QRS)}, 0")
-        emit(f"v_add_co_u32 {v(T[4])}, vcc, {v(T[4])}, {v(T[6])}")
-        emit(f"v_addc_co_u32 {v(T[5])}, vcc, 0, {v(T[5])}, vcc")
-        emit(f"v_add_co_u32 {v(T[4])}, vcc, {s(S_QBASE)}, {v(T[4])}")
-        emit(f"v_mov_b32 {v(T[7])}, {s(S_QBASE + 1)}")
-        emit(f"v_addc_co_u32 {v(T[5])}, vcc, {v(T[5])}, {v(T[7])}, vcc")
-        for ks in range(KS):
-            emit(f"global_load_dwordx4 {vr(16 * qb + 4 * ks, 4)}, {vr(T[4], 2)}, off offset:{64 * ks}")
-    emit("s_waitcnt vmcnt(0)")
-    for qb in range(NQB):
-        emit(f"v_add_u32 {v(T[8])}, {s(S_T0)}, {v(J16)}")
-        if qb:
-            emit(f"v_add_u32 {v(T[8])}, {16 * qb}, {v(T[8])}")
-        emit(f"v_cmp_gt_i32 vcc, {s(S_SEQLENQ)}, {v(T[8])}")
-        for r in range(16):
-            emit(f"v_cndmask_b32 {v(16 * qb + r)}, 0, {v(16 * qb + r)}, vcc")
-    for r in range(16 * NQB):
-        emit(f"v_accvgpr_write_b32 a{Q_A0 + r}, {v(r)}")
-    emit("; ---- state")
-    for r in range(4 * DB * NQB):
-        emit(f"v_accvgpr_write_b32 a{r}, 0")
+        return T[8]
+    q_rows_to_agprs(T, NQB, KS, 64, Q_A0, q_row)                             # (T[0] = g)
+    zero_accumulators(range(4 * DB * NQB))
     for qb in range(NQB):
         emit(f"v_mov_b32 {v(L[qb])}, 0")
         emit(f"v_mov_b32 {v(ALPHA[qb])}, 1.0")
 
-    emit("; ---- tile addresses of positions 1..3 from the table; K(0) fragments -> AGPRs, S(0) = K(0) Q^T, then K(1) fragments")
-    emit(f"v_mov_b32 {v(T[6])}, {s(S_TAB)}")
-    emit(f"ds_read_b64 {vr(T[8], 2)}, {v(T[6])} offset:32")          # tab[2].k : K(2), staged below
-    emit(f"ds_read_b64 {vr(T[10], 2)}, {v(T[6])} offset:48")         # tab[3].k : K(3), staged by step 0
-    emit(f"ds_read_b64 {vr(T[12], 2)}, {v(T[6])} offset:24")         # tab[1].v : V(1), staged by step 0
-    emit(f"v_add_u32 {v(TABV)}, 32, {v(T[6])}")                      # step 0 reads tab[2].v and tab[4].k
+    read_tile_table(T, TABV)
     for ks in range(KS):
         for kb in range(NKB):
             emit(k_read(0, kb, ks))
-    emit(("DRAIN",))
-    emit(f"v_readfirstlane_b32 {s(TBS[0])}, {v(T[8])}")
-    emit(f"v_readfirstlane_b32 {s(TBS[0] + 1)}, {v(T[9])}")
+    k2_base(T)
     for ks, kb, qb in QK_ORDER:
         out.append(mfma_qk(0, kb, ks, qb))
     for ks in range(KS):
@@ -503,26 +441,10 @@ def prologue():
             emit(k_read(KV_TILE, kb, ks))
     emit(("DRAIN",))
     emit("s_barrier")                                          # every wave has read K(0) and K(1): both K buffers are free
-    for it in dma_ops(0, 0, do_k=True, do_v=False):            # K(2) -> K buffer 0. V(1) / K(3) are staged by step 0.
-        out.append(it)
-        if "m0" in it:
-            emit("s_nop 0")
-    for dst, src in ((TBS[0], T[10]), (TBS[0] + 1, T[11]), (VBS[0], T[12]), (VBS[0] + 1, T[13])):
-        emit(f"v_readfirstlane_b32 {s(dst)}, {v(src)}")
+    stage_k2(dma_ops(0, 0, do_k=True, do_v=False), T)          # K(2) -> K buffer 0. V(1) / K(3) are staged by step 0.
     emit("s_nop 7")
-    # seqlen-k mask: only if the first walked tile is tile k_tiles - 1 and tail_valid < 64 (mask.h:44-78; mainloop...:1626)
-    nomask = new_label("nomask")
-    emit(f"s_cmp_eq_u32 {s(S_FIRSTLAST)}, 1")
-    emit(f"s_cbranch_scc0 {nomask}")
-    emit(f"s_cmp_lt_i32 {s(S_TAILVALID)}, 64")
-    emit(f"s_cbranch_scc0 {nomask}")
-    for kb in range(NKB):
-        for r in range(4):
-            emit(f"v_add_u32 {v(T[0])}, {16 * kb + r}, {v(G4)}")                  # key 16 kb + 4 g + r
-            emit(f"v_cmp_gt_i32 vcc, {s(S_TAILVALID)}, {v(T[0])}")               # key < tail_valid -> keep
-            for qb in range(NQB):
-                emit(f"v_cndmask_b32 {v(S_(0, qb, kb) + r)}, {v(NEGINF)}, {v(S_(0, qb, kb) + r)}, vcc")
-    label(nomask)
+    # register r of key block kb holds key 16 kb + 4 g + r, for every q-block
+    first_tile_mask(T, NEGINF, G4, [(16 * kb + r, [S_(0, qb, kb) + r for qb in range(NQB)]) for kb in range(NKB) for r in range(4)])
     for op in row_max_ops(0):
         out.append(op)
     emit("s_nop 1")
@@ -543,14 +465,7 @@ def prologue():
 def epilogue():
     """finalize (softmax.h:275-296) + store (epilogue_fwd.hpp:214-403) straight from the accumulators (parameter words 24-31:
     gen_epilogue.py)."""
-    emit("; ---- flush the last (partial) vote word")
-    nofl = new_label("nolastflush")
-    emit(f"s_cmp_eq_u32 {s(S_DOMASK)}, 0")
-    emit(f"s_cbranch_scc1 {nofl}")
-    flush_domask(T[4], T[5])
-    label(nofl)
-    emit("s_nop 15")                                           # the last PV MFMAs have written the accumulators
-    emit("s_nop 15")
+    flush_last_vote_word(T)
     emit("; ---- finalize + store O and LSE straight from the accumulators")
     read_epilogue_params(T)
     # l of every row, transposed: lane (j, g) = row 16 g + j of the wave = row `lane`
@@ -644,25 +559,8 @@ def epilogue():
 
 def main():
     prologue()
-    loop, done = new_label("loop"), new_label("done")
-    if opt_val(OPT, "align", "") or opt_val(OPT, "pad4", ""):  # code placement: see gen_fwd_x64.py main(); this body is pinned at phase 8 (not swept)
-        if opt_val(OPT, "align", ""):
-            out.append(f".p2align {opt_val(OPT, 'align', '')}")
-        for _ in range(int(opt_val(OPT, "pad4", "0"))):
-            emit("s_nop 0")
-    else:
-        out.append(".p2align 5")
-        emit("s_nop 0")
-        emit("s_nop 0")
-    label(loop)
-    for variant in (0, 1):
-        emit(f"s_cmp_lt_u32 {s(S_I)}, {s(S_NTILES)}")
-        emit(f"s_cbranch_scc0 {done}")
-        step(variant)
-    emit(f"s_branch {loop}")
-    for blk in deferred:
-        blk()
-    label(done)
+    loop_head(8, opt_val(OPT, "align", ""), opt_val(OPT, "pad4", ""))       # code placement (gen_blocks.py): pinned at phase 8 (not swept)
+    unrolled_loop(lambda variant, done: step(variant))
     epilogue()
     write_body(sys.argv[1] if len(sys.argv) > 1 else "la_fwd_x64_m16_body.inc",
                "// GENERATED by gen_fwd_x64_m16.py — do not edit. Inline-asm body of la_fwd_x64_kernel<.., 128> on v_mfma_f32_16x16x32.",

@@ -129,3 +129,39 @@ def test_m16_body_stays_inside_the_declared_clobbers_and_has_the_16x16x32_counts
         assert int(lo[0]) % 2 == 0, lo                                             # gfx950: VGPR tuples must be 64-bit aligned
     for lab in re.findall(r"^\s*([.\w%=]+):\s*$", body, flags=re.M):
         assert lab.endswith("%="), lab
+
+
+def _load(name, path):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("gen,own_tag", [("gen_fwd_x64.py", ()), ("gen_fwd_x64_fp8.py", ()), ("gen_fwd_x64_m16.py", ("m16",))])
+def test_every_schedule_only_word_is_an_option_the_generator_reads(gen, own_tag):
+    """SCHEDULE_ONLY decides whether a body's tag says wrong_results=0: a word in it that no code reads is a promise about nothing.
+    Read = `"word" in OPT` (or in a step's `opt = OPT | drop`) or `opt_val(OPT, "word", ...)`; `own_tag`: what the generator adds to
+    the tag itself."""
+    text = open(os.path.join(CSRC, gen)).read()
+    listed = set(re.findall(r'"(\w+)"', re.search(r"^SCHEDULE_ONLY = \{(.*?)\}", text, flags=re.M | re.S).group(1)))
+    read = set(re.findall(r'"(\w+)" (?:not )?in (?:OPT|opt)\b', text)) | set(re.findall(r'opt_val\(OPT, ["\'](\w+)["\']', text))
+    assert listed and listed - read - set(own_tag) == set()
+    assert set(own_tag) <= listed
+
+
+def test_body_digest_product_cases_are_what_the_build_generates(tmp_path):
+    """tools/body_digest.py (the byte-identity check of a generator refactor): its product cases are exactly the files
+    build.generate_bodies writes - a new body cannot escape the check."""
+    root = os.path.dirname(os.path.dirname(CSRC))
+    digest = _load("la_body_digest", os.path.join(root, "tools", "body_digest.py"))
+    (tmp_path / "a").mkdir()
+    (tmp_path / "b").mkdir()
+    cases = digest.product_cases(str(tmp_path / "a"))
+    generated, _ = digest.build.generate_bodies(str(tmp_path / "b"), variant=False)
+    consts = [p.replace("_body.inc", "_consts.h") for p in generated if os.path.exists(p.replace("_body.inc", "_consts.h"))]
+    assert sorted(cases) == sorted("product/" + os.path.basename(p) for p in generated + consts)
+    assert sorted(os.listdir(tmp_path / "b")) == sorted(os.path.basename(p) for p in cases.values()) and len(cases) == 34
+    for case, path in cases.items():
+        assert open(path, "rb").read() == open(tmp_path / "b" / os.path.basename(path), "rb").read(), case
