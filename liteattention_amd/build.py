@@ -16,12 +16,16 @@ import sys
 import tempfile
 
 try:
-    from . import _buildinfo
+    from . import _bodies, _buildinfo
 except ImportError:                       # loaded by path (__graft_entry__.build(), before the package can be imported)
     import importlib.util as _ilu
-    _spec = _ilu.spec_from_file_location("la_buildinfo", os.path.join(os.path.dirname(os.path.abspath(__file__)), "_buildinfo.py"))
-    _buildinfo = _ilu.module_from_spec(_spec)
-    _spec.loader.exec_module(_buildinfo)
+
+    def _sibling(name):
+        spec = _ilu.spec_from_file_location("la" + name, os.path.join(os.path.dirname(os.path.abspath(__file__)), name + ".py"))
+        mod = _ilu.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+    _bodies, _buildinfo = _sibling("_bodies"), _sibling("_buildinfo")
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
@@ -29,20 +33,6 @@ INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_NAME = "libliteattention_amd.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
 SOURCES, HEADERS = _buildinfo.SOURCES, _buildinfo.HEADERS
-X64_M16_GEN = "gen_fwd_x64_m16.py"                              # head_dim 128 on the 16x16x32 MFMA (A/B build -DLA_X64_M16=1)
-X64_GEN, X64_INC = "gen_fwd_x64.py", "la_fwd_x64_body.inc"      # the hand-scheduled main loop, included by la_fwd_kernel_x64.hip
-X64_F16_INC = "la_fwd_x64_f16_body.inc"                        # the same generator with LA_X64_DTYPE=f16 (fp16 MFMA / conversions)
-X64_BODIES = [(128, "bf16", X64_INC), (128, "f16", X64_F16_INC)] + [
-    (d, t, f"la_fwd_x64_d{d}_{'f16_' if t == 'f16' else ''}body.inc") for d in (64, 96, 192, 256) for t in ("bf16", "f16")]   # LA_X64_D / LA_X64_DTYPE
-X64_HALF_INC, X64_HALF_F16_INC = "la_fwd_x64_half_body.inc", "la_fwd_x64_half_f16_body.inc"      # LA_X64_FORM=half: the half-vote form of head_dim 128
-X64F8_GEN, X64F8_INC = "gen_fwd_x64_fp8.py", "la_fwd_x64_fp8_body.inc"     # fp8: the same structure on the block-scaled MFMA
-X64F8_EXP_INC = "la_fwd_x64_fp8_exp_body.inc"                               # LA_X64F8_OPT=exp: P = v_exp_f32 rounded by the hardware convert (LA_FLAG_FP8_MFMA_ROWSUM)
-X64F8_LVALU_INC = "la_fwd_x64_fp8_lvalu_body.inc"                           # LA_X64F8_OPT=lvalu: that, and fp32 row sums on the VALU (the DEFAULT fp8 form: the reference's arithmetic)
-
-
-def body_macro(head_dim: int, dtype: str) -> str:
-    """Name of the shell's include macro for a bf16 / fp16 body (la_fwd_kernel_x64.hip)."""
-    return "LA_X64_" + ("" if head_dim == 128 else f"D{head_dim}_") + ("F16_" if dtype == "f16" else "") + "BODY_INC"
 
 
 def _hipcc() -> str:
@@ -108,7 +98,7 @@ def build_m16_variant(force: bool = False, verbose: bool = False) -> str:
     fresh = rec is not None and rec["src"] == _buildinfo.source_hash() and rec["variant"] == "1" and "m16" in rec["opts"] and rec["wrong_results"] == "0"
     # its own generator is hashed into no record (an edit to the A/B body must not invalidate the PRODUCT library): compare times (of the
     # assembler core and the blocks it shares too)
-    fresh = fresh and all(os.path.getmtime(os.path.join(CSRC, g)) <= os.path.getmtime(M16_VARIANT) for g in (X64_M16_GEN, "gen_asm.py", "gen_blocks.py"))
+    fresh = fresh and all(os.path.getmtime(os.path.join(CSRC, g)) <= os.path.getmtime(M16_VARIANT) for g in (_bodies.X64_M16, "gen_asm.py", "gen_blocks.py"))
     if fresh and not force:
         return M16_VARIANT
     os.makedirs(os.path.dirname(M16_VARIANT), exist_ok=True)
@@ -120,58 +110,23 @@ def build_m16_variant(force: bool = False, verbose: bool = False) -> str:
         os.environ.update(saved)
 
 
-def _generator_env(variant: bool) -> dict:
-    """Environment of the body generators. Product build: no LA_X64* variable survives (LA_X64_OPT, LA_X64_D<D>_OPT, LA_X64F8_OPT,
-    LA_X64F8_<FORM>_OPT, LA_X64F8_DEFAULT_OPT, LA_X64_D, LA_X64_DTYPE - the last two are set per body below)."""
-    if variant:
-        return dict(os.environ)
-    return {k: v for k, v in os.environ.items() if not k.startswith("LA_X64")}
-
-
 def generate_bodies(gen_dir: str, variant: bool, defines=(), quiet=subprocess.DEVNULL):
-    """Run the body generators into ``gen_dir``. Returns (paths of the generated bodies, -D macros that point the shells at them).
-    Product build (``variant`` False): the generators see no LA_X64* option, whatever this process's environment holds."""
-    base_env = _generator_env(variant)
+    """Generate every body of the manifest (_bodies.BODIES) into ``gen_dir``. Returns (paths of the generated bodies, -D macros that
+    point the shells at them). Product build (``variant`` False): no option reaches a generator, whatever this process's environment
+    holds. Variant: each body takes the words of its own option variable (``Body.opt_var``), and two defines override records."""
+    defines = {d.replace(" ", "") for d in defines} if variant else set()
     generated, macros = [], []
-
-    def generate(gen, inc, env, macro, consts_macro=None):
-        path = os.path.join(gen_dir, inc)
-        subprocess.run([sys.executable, os.path.join(CSRC, gen), path], check=True, stdout=quiet, env=env)
+    for body in _bodies.BODIES:
+        if "LA_X64_M16=1" in defines:
+            body = _bodies.m16(body)
+        # -DLA_D64_W2=1 (A/B build): the head_dim-64 bodies default to the two-waves-per-SIMD schedule
+        default = "w2" if "LA_D64_W2=1" in defines and (body.gen, body.head_dim, body.form) == (_bodies.X64, 64, "") else ""
+        path = _bodies.generate(body, gen_dir, os.environ.get(body.opt_var, default) if variant else "", stdout=quiet)
         generated.append(path)
         if variant:
-            macros.append(f'-D{macro}="{path}"')
-            if consts_macro:
-                macros.append(f'-D{consts_macro}="{path.replace("_body.inc", "_consts.h")}"')
-
-    for head_dim, dtype, inc in X64_BODIES:       # one generated body per (head dim, 16-bit element type)
-        env = dict(base_env, LA_X64_D=str(head_dim), LA_X64_DTYPE=dtype)
-        if variant and head_dim != 128:            # LA_X64_OPT tunes the head_dim-128 body (tools/asm_variants.py); the others have their own knob
-            env["LA_X64_OPT"] = os.environ.get(f"LA_X64_D{head_dim}_OPT", "")
-            if head_dim == 64 and any(d.replace(" ", "") == "LA_D64_W2=1" for d in defines):
-                env["LA_X64_OPT"] = os.environ.get("LA_X64_D64_OPT", "w2")       # -DLA_D64_W2=1 (A/B build): the two-waves-per-SIMD body
-        gen = X64_GEN
-        if variant and head_dim == 128 and any(d.replace(" ", "") == "LA_X64_M16=1" for d in defines):
-            gen = X64_M16_GEN                       # -DLA_X64_M16=1 (A/B build): head_dim 128 on v_mfma_f32_16x16x32 (LA_X64_OPT tunes it)
-        generate(gen, inc, env, body_macro(head_dim, dtype))
-    for head_dim in (128, 64, 96):                         # skip lists per 128-row half (LA_FLAG_HALF_VOTE): the 256-row kernels
-        for dtype in ("bf16", "f16"):
-            stem = ("" if head_dim == 128 else f"d{head_dim}_") + "half_" + ("f16_" if dtype == "f16" else "")
-            env = dict(base_env, LA_X64_D=str(head_dim), LA_X64_DTYPE=dtype, LA_X64_FORM="half")
-            if variant:
-                env["LA_X64_OPT"] = os.environ.get("LA_X64_HALF_OPT" if head_dim == 128 else f"LA_X64_D{head_dim}_HALF_OPT", "")
-            generate(X64_GEN, f"la_fwd_x64_{stem}body.inc", env, "LA_X64_" + stem.upper() + "BODY_INC")
-    f8_default = os.environ.get("LA_X64F8_DEFAULT_OPT", "") if variant else ""      # a global LA_X64F8_OPT never reaches the default body
-    generate(X64F8_GEN, X64F8_INC, dict(base_env, LA_X64F8_OPT=f8_default), "LA_X64F8_BODY_INC", "LA_X64F8_CONSTS_INC")
-    for form, inc in (("exp", X64F8_EXP_INC), ("lvalu", X64F8_LVALU_INC)):       # LA_X64F8_<FORM>_OPT tunes that body alone (variants only)
-        extra = os.environ.get(f"LA_X64F8_{form.upper()}_OPT", "") if variant else ""
-        generate(X64F8_GEN, inc, dict(base_env, LA_X64F8_OPT=",".join(x for x in (extra, form) if x)),
-                 f"LA_X64F8_{form.upper()}_BODY_INC", f"LA_X64F8_{form.upper()}_CONSTS_INC")
-    for head_dim in (64, 96, 192, 256):           # the other head dims (round 6): the three forms of P again, LA_X64F8_D=<head dim>
-        for form in ("", "exp", "lvalu"):
-            stem = f"d{head_dim}_" + (form + "_" if form else "")
-            extra = os.environ.get(f"LA_X64F8_D{head_dim}_{form.upper() or 'DEFAULT'}_OPT", "") if variant else ""
-            generate(X64F8_GEN, f"la_fwd_x64_fp8_{stem}body.inc",
-                     dict(base_env, LA_X64F8_D=str(head_dim), LA_X64F8_OPT=",".join(x for x in (extra, form) if x)), f"LA_X64F8_{stem.upper()}BODY_INC")
+            macros.append(f'-D{body.macro}="{path}"')
+            if body.consts_macro:
+                macros.append(f'-D{body.consts_macro}="{path.replace("_body.inc", "_consts.h")}"')
     return generated, macros
 
 

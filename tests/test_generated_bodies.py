@@ -2,30 +2,33 @@
 whose inline-asm statement declares what they clobber (v0-v222, s35-s95, every AGPR, m0, vcc, scc): a register outside that set
 written by a body would silently corrupt compiler-owned state. Also pins the MFMA counts per step and that the head_dim-128 bodies of
 the two 16-bit types differ in nothing but the MFMA / convert opcodes."""
+import importlib.util
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "liteattention_amd", "csrc")
-CASES = [("gen_fwd_x64.py", {"LA_X64_D": str(d), "LA_X64_DTYPE": t}) for d in (96, 128, 192, 256) for t in ("bf16", "f16")] + \
-        [("gen_fwd_x64.py", {"LA_X64_D": str(d), "LA_X64_DTYPE": "bf16", "LA_X64_FORM": "half"}) for d in (64, 96, 128)] + \
-        [("gen_fwd_x64_fp8.py", dict({"LA_X64F8_D": str(d)}, **({"LA_X64F8_OPT": o} if o else {}))) for d in (64, 96, 128, 192, 256) for o in ("", "exp", "lvalu")]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "liteattention_amd", "csrc")
 
 
-def _generate(tmp_path, gen, env):
-    out = tmp_path / "body.inc"
-    e = dict(os.environ, **env)
-    e.pop("LA_X64_OPT", None)
-    if "LA_X64F8_OPT" not in env:
-        e.pop("LA_X64F8_OPT", None)
-    if gen == "gen_fwd_x64_fp8.py":         # the generator checks the body's NAME against its head dim and form of P
-        d, o = env.get("LA_X64F8_D", "128"), env.get("LA_X64F8_OPT", "")
-        out = tmp_path / ("la_fwd_x64_fp8_" + ("" if d == "128" else f"d{d}_") + (o + "_" if o else "") + "body.inc")
-    subprocess.run([sys.executable, os.path.join(CSRC, gen), str(out)], check=True, stdout=subprocess.DEVNULL, env=e)
-    return out.read_text()
+def _load(name, path):
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+bodies = _load("la_bodies_t", os.path.join(ROOT, "liteattention_amd", "_bodies.py"))      # the manifest, by path: importing the package needs the library
+CASES = bodies.BODIES
+
+
+def _case_id(b):
+    return "-".join(x for x in (b.gen[:-3], str(b.head_dim), "" if b.dtype == "fp8" else b.dtype, b.form) if x)
+
+
+def _generate(tmp_path, body, options=""):
+    return open(bodies.generate(body, str(tmp_path), options)).read()
 
 
 def _registers(text):
@@ -43,9 +46,9 @@ def _registers(text):
     return vmax, amax, sgprs
 
 
-@pytest.mark.parametrize("gen,env", CASES, ids=[f"{g[:-3]}-{'-'.join(e.values())}" for g, e in CASES])
-def test_body_stays_inside_the_declared_clobbers(tmp_path, gen, env):
-    text = _generate(tmp_path, gen, env)
+@pytest.mark.parametrize("case", CASES, ids=_case_id)
+def test_body_stays_inside_the_declared_clobbers(tmp_path, case):
+    text = _generate(tmp_path, case)
     body = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith((";", "//")))
     vmax, amax, sgprs = _registers(body)
     assert 0 <= vmax <= 222, vmax                      # LA_X64_CLOBBERS: v0 .. v222
@@ -61,7 +64,7 @@ def test_body_stays_inside_the_declared_clobbers(tmp_path, gen, env):
 @pytest.mark.parametrize("D,per_phase", [(96, 24), (128, 32), (192, 24), (256, 32)])
 def test_mfma_count_per_step(tmp_path, D, per_phase):
     """prologue QK of tile 0 (one phase) + two unrolled steps of (QK + PV): 5 phases of MFMAs."""
-    text = _generate(tmp_path, "gen_fwd_x64.py", {"LA_X64_D": str(D)})
+    text = _generate(tmp_path, bodies.find(D, "bf16"))
     assert text.count("v_mfma_f32_32x32x16_bf16") == 5 * per_phase
     assert "v_mfma_f32_32x32x16_f16" not in text
 
@@ -72,7 +75,7 @@ def test_fp8_mfma_count_per_step(tmp_path, D, qk, pv, form):
     """fp8 bodies (gen_fwd_x64_fp8.py, LA_X64F8_D): prologue QK of tile 0 + two unrolled steps of (QK + PV [+ one row-sum MFMA per q-block in the
     matrix-pipe row-sum forms]); 64-row bodies (64 / 128) hold two q-blocks per wave, the 192 / 256 bodies one. The head_dim-192 body clamps the
     K tile's DMA source chunks to the 12 that exist."""
-    text = _generate(tmp_path, "gen_fwd_x64_fp8.py", dict({"LA_X64F8_D": str(D)}, **({"LA_X64F8_OPT": form} if form else {})))
+    text = _generate(tmp_path, bodies.find(D, "fp8", form))
     rowsum = 0 if form == "lvalu" else (2 if D <= 128 else 1)
     assert text.count("v_mfma_scale_f32_32x32x64_f8f6f4") == qk + 2 * (qk + pv + rowsum)
     assert ("v_min_u32" in text) == (D in (96, 192))
@@ -80,8 +83,8 @@ def test_fp8_mfma_count_per_step(tmp_path, D, qk, pv, form):
 
 
 def test_fp16_body_differs_only_in_the_type_dependent_opcodes(tmp_path):
-    a = _generate(tmp_path, "gen_fwd_x64.py", {"LA_X64_D": "128", "LA_X64_DTYPE": "bf16"})
-    b = _generate(tmp_path, "gen_fwd_x64.py", {"LA_X64_D": "128", "LA_X64_DTYPE": "f16"})
+    a = _generate(tmp_path, bodies.find(128, "bf16"))
+    b = _generate(tmp_path, bodies.find(128, "f16"))
     norm = lambda t: t.replace("v_mfma_f32_32x32x16_bf16", "MFMA").replace("v_mfma_f32_32x32x16_f16", "MFMA") \
                       .replace("v_cvt_pk_bf16_f32", "CVT").replace("v_cvt_pk_f16_f32", "CVT")                      # noqa: E731
     la, lb = norm(a).splitlines(), norm(b).splitlines()
@@ -93,10 +96,7 @@ def test_two_waves_per_simd_body_of_head_dim_64_fits_two_waves(tmp_path):
     """The A/B body of round 4 (gen_fwd_x64.py LA_X64_OPT=w2, -DLA_D64_W2=1; profiles/r04_head_dim_64.md): an 8-wave workgroup with two
     waves per SIMD needs <= 256 registers per wave INCLUDING what the C++ shell keeps across the body: the body stays inside v0-v89 +
     a0-a79 (LA_X64W2_CLOBBERS), has 8 + 8 MFMAs per step and two loops (waves 0-3 / waves 4-7, the latter one QK ahead)."""
-    out = tmp_path / "w2.inc"
-    e = dict(os.environ, LA_X64_D="64", LA_X64_OPT="w2")
-    subprocess.run([sys.executable, os.path.join(CSRC, "gen_fwd_x64.py"), str(out)], check=True, stdout=subprocess.DEVNULL, env=e)
-    text = out.read_text()
+    text = _generate(tmp_path, bodies.find(64, "bf16"), "w2")
     body = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith((";", "//")))
     vmax, amax, sgprs = _registers(body)
     assert 0 <= vmax <= 89 and 0 <= amax <= 79, (vmax, amax)
@@ -113,11 +113,7 @@ def test_two_waves_per_simd_body_of_head_dim_64_fits_two_waves(tmp_path):
 def test_m16_body_stays_inside_the_declared_clobbers_and_has_the_16x16x32_counts(tmp_path, dtype):
     """The head_dim-128 body on v_mfma_f32_16x16x32 (gen_fwd_x64_m16.py, round 5; A/B build -DLA_X64_M16=1): same shell, same clobber
     set; 64 + 64 MFMAs per step (prologue QK + two unrolled steps = 5 phases of 64), no 32x32x16 MFMA, 64-bit VGPR tuples even-aligned."""
-    out = tmp_path / "m16.inc"
-    e = dict(os.environ, LA_X64_DTYPE=dtype)
-    e.pop("LA_X64_OPT", None)
-    subprocess.run([sys.executable, os.path.join(CSRC, "gen_fwd_x64_m16.py"), str(out)], check=True, stdout=subprocess.DEVNULL, env=e)
-    text = out.read_text()
+    text = _generate(tmp_path, bodies.m16(bodies.find(128, dtype)))
     assert "la_body_options: m16; wrong_results=0" in text.splitlines()[1]
     body = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith((";", "//")))
     vmax, amax, sgprs = _registers(body)
@@ -129,14 +125,6 @@ def test_m16_body_stays_inside_the_declared_clobbers_and_has_the_16x16x32_counts
         assert int(lo[0]) % 2 == 0, lo                                             # gfx950: VGPR tuples must be 64-bit aligned
     for lab in re.findall(r"^\s*([.\w%=]+):\s*$", body, flags=re.M):
         assert lab.endswith("%="), lab
-
-
-def _load(name, path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location(name, path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.mark.parametrize("gen,own_tag", [("gen_fwd_x64.py", ()), ("gen_fwd_x64_fp8.py", ()), ("gen_fwd_x64_m16.py", ("m16",))])
@@ -154,8 +142,7 @@ def test_every_schedule_only_word_is_an_option_the_generator_reads(gen, own_tag)
 def test_body_digest_product_cases_are_what_the_build_generates(tmp_path):
     """tools/body_digest.py (the byte-identity check of a generator refactor): its product cases are exactly the files
     build.generate_bodies writes - a new body cannot escape the check."""
-    root = os.path.dirname(os.path.dirname(CSRC))
-    digest = _load("la_body_digest", os.path.join(root, "tools", "body_digest.py"))
+    digest = _load("la_body_digest", os.path.join(ROOT, "tools", "body_digest.py"))
     (tmp_path / "a").mkdir()
     (tmp_path / "b").mkdir()
     cases = digest.product_cases(str(tmp_path / "a"))
@@ -165,3 +152,45 @@ def test_body_digest_product_cases_are_what_the_build_generates(tmp_path):
     assert sorted(os.listdir(tmp_path / "b")) == sorted(os.path.basename(p) for p in cases.values()) and len(cases) == 34
     for case, path in cases.items():
         assert open(path, "rb").read() == open(tmp_path / "b" / os.path.basename(path), "rb").read(), case
+
+
+def _shell_macros(shell):
+    """({macro: default file} of the `#ifndef NAME` / `#define NAME "file"` pairs of body / consts includes, [macros the shell #includes])."""
+    text = open(os.path.join(CSRC, shell)).read()
+    pairs = re.findall(r'^#ifndef (\w+_(?:BODY|CONSTS)_INC)\b.*\n#define (\w+) "([^"]+)"', text, flags=re.M)
+    assert all(a == b for a, b, _ in pairs) and len({a for a, _, _ in pairs}) == len(pairs), pairs
+    return {a: f for a, _, f in pairs}, re.findall(r"^#include (\w+_(?:BODY|CONSTS)_INC)\b", text, flags=re.M)
+
+
+def _shell_wants():
+    """{shell: {macro: default file}} by the manifest."""
+    want = {bodies.SHELL: {}, bodies.SHELL_F8: {}}
+    for b in bodies.BODIES:
+        macros = want[bodies.SHELL_F8 if b.dtype == "fp8" else bodies.SHELL]
+        macros[b.macro] = b.inc
+        if b.consts_macro:
+            macros[b.consts_macro] = b.inc.replace("_body.inc", "_consts.h")
+    return want
+
+
+def test_the_manifest_and_the_shells_name_the_same_bodies():
+    """A variant build points a shell at its own bodies with -D<MACRO>="<path>": a macro the shell does not know would compile, include
+    the tree's default body and measure the product against itself. So: (a) each shell's (macro, default file) pairs are the
+    manifest's records of that shell, no more and no fewer; (b) the shell includes every macro it defines."""
+    for shell, macros in _shell_wants().items():
+        defined, included = _shell_macros(shell)
+        assert defined == macros, shell                                              # (a)
+        assert set(defined) <= set(included), set(defined) - set(included)          # (b)
+
+
+def test_a_variant_build_passes_one_define_per_manifest_macro(tmp_path, monkeypatch):
+    """(c) with every option variable unset, a variant generation passes exactly one -D per manifest macro, each naming a file that
+    exists (a test of its own: it runs the 31 generators, the two static checks above do not)."""
+    for k in [k for k in os.environ if k.startswith("LA_X64")]:
+        monkeypatch.delenv(k)
+    build = _load("la_build_t3", os.path.join(ROOT, "liteattention_amd", "build.py"))
+    generated, macros = build.generate_bodies(str(tmp_path), variant=True)
+    passed = dict(re.fullmatch(r'-D(\w+)="(.+)"', m).groups() for m in macros)
+    assert len(passed) == len(macros) == 34 and all(os.path.isfile(p) for p in passed.values())
+    assert {m: os.path.relpath(p, str(tmp_path)) for m, p in passed.items()} == {m: f for ms in _shell_wants().values() for m, f in ms.items()}
+    assert [os.path.basename(p) for p in generated] == [b.inc for b in bodies.BODIES]

@@ -23,27 +23,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("la_build", os.path.join(ROOT, "liteattention_amd", "build.py"))   # by path: the package
 build = importlib.util.module_from_spec(_spec)                                                                   # import needs the .so
 _spec.loader.exec_module(build)
+bodies = build._bodies                   # the manifest: every case below is one of its records, with option words
 VALUES = dict(x=3, cap1=2, cap2=2, align=6, pad4=2, pad4b=1, halfskip=4, mfma16="both", dmapol="nt", tau=4, safe=2)
-X64_FORMS = {"d64": {"LA_X64_D": "64"}, "d128": {"LA_X64_D": "128"}, "d256": {"LA_X64_D": "256"}, "half": {"LA_X64_D": "128", "LA_X64_FORM": "half"}}
+X64_FORMS = {"d64": bodies.find(64, "bf16"), "d128": bodies.find(128, "bf16"), "d256": bodies.find(256, "bf16"), "half": bodies.find(128, "bf16", "half")}
 
 
 def option_words(gen):
-    text = open(os.path.join(build.CSRC, gen)).read()
+    text = open(os.path.join(bodies.CSRC, gen)).read()
     return sorted(set(re.findall(r'"(\w+)" (?:not )?in OPT\b', text)) | set(re.findall(r'opt_val\(OPT, ["\'](\w+)["\']', text)))
 
 
 def generator_cases():
-    """(case, generator, environment, output file name)"""
-    cases = [(f"ab/m16-{t}", build.X64_M16_GEN, {"LA_X64_DTYPE": t}, "body.inc") for t in ("bf16", "f16")]
-    cases.append(("ab/d64-w2", build.X64_GEN, {"LA_X64_D": "64", "LA_X64_OPT": "w2"}, "body.inc"))
+    """(case, manifest record, option words)"""
+    m16 = bodies.m16(bodies.find(128, "bf16"))
+    cases = [(f"ab/m16-{t}", bodies.m16(bodies.find(128, t)), "") for t in ("bf16", "f16")] + [("ab/d64-w2", bodies.find(64, "bf16"), "w2")]
     word = lambda w: f"{w}:{VALUES[w]}" if w in VALUES else w                                                   # noqa: E731
-    for w in option_words(build.X64_GEN):
-        cases += [(f"opt/gen_fwd_x64/{form}/{w}", build.X64_GEN, dict(env, LA_X64_OPT=word(w)), "body.inc") for form, env in X64_FORMS.items()]
-    for w in option_words(build.X64F8_GEN):
-        for d in ("64", "128", "192"):       # the generator checks the body's name against its head dim and form of P
-            name = "la_fwd_x64_fp8_" + ("" if d == "128" else f"d{d}_") + word(w) + "_body.inc"
-            cases.append((f"opt/gen_fwd_x64_fp8/d{d}/{w}", build.X64F8_GEN, {"LA_X64F8_D": d, "LA_X64F8_OPT": word(w)}, name))
-    cases += [(f"opt/gen_fwd_x64_m16/d128/{w}", build.X64_M16_GEN, {"LA_X64_OPT": word(w)}, "body.inc") for w in option_words(build.X64_M16_GEN)]
+    for w in option_words(bodies.X64):
+        cases += [(f"opt/gen_fwd_x64/{form}/{w}", body, word(w)) for form, body in X64_FORMS.items()]
+    for w in option_words(bodies.X64F8):
+        form = w if w in ("exp", "lvalu") else ""       # a form word selects that form's record: the generator checks the body's name against its form of P
+        cases += [(f"opt/gen_fwd_x64_fp8/d{d}/{w}", bodies.find(d, "fp8", form), "" if form else word(w)) for d in (64, 128, 192)]
+    cases += [(f"opt/gen_fwd_x64_m16/d128/{w}", m16, word(w)) for w in option_words(m16.gen)]
     return cases
 
 
@@ -61,15 +61,15 @@ def run_all(keep):
     for case in sorted(files):
         h.update(os.path.basename(files[case]).encode() + b"\0" + open(files[case], "rb").read())
     print(f"product: {len(files)} files, sha256 {h.hexdigest()[:16]}", file=sys.stderr)
-    base = {k: v for k, v in os.environ.items() if not k.startswith("LA_X64")}
 
     def one(c):
-        case, gen, env, name = c
+        case, body, words = c
         d = os.path.join(keep, case)
         os.makedirs(d)
-        r = subprocess.run([sys.executable, os.path.join(build.CSRC, gen), os.path.join(d, name)], env=dict(base, **env),
-                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        return case, (os.path.join(d, name) if r.returncode == 0 else None)
+        try:
+            return case, bodies.generate(body, d, words, stderr=subprocess.DEVNULL)
+        except subprocess.CalledProcessError:
+            return case, None
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
         files.update(ex.map(one, generator_cases()))
     return files
