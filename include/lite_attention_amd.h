@@ -20,6 +20,8 @@
  *   la_combine            <- mha_combine / flash_fwd_combine (LSE-weighted merge of partial outputs,
  *                            hopper/_internal/cpp/flash_api.cpp fwd_combine; oracle
  *                            hopper/tests/test_flash_attn.py:1178-1187)
+ *   la_output_error       <- nothing: the reference names "error calibration" (README.md:14) and measures no error anywhere;
+ *                            one-pass fp64 error statistics of an output against a reference output, per (batch, head, row bin)
  *
  * Rules of the boundary:
  *   - plain C: pointers, sizes, scalars. No torch types, no C++ types, no exceptions.
@@ -39,7 +41,8 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
+#define LA_ABI_VERSION 9   /* la_output_error was ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+                            * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
 
@@ -277,6 +280,33 @@ int la_blockmask_to_lists(const uint8_t* blockmask, int64_t mask_batch_stride, i
 int la_blockmask_to_lists_ex(const uint8_t* blockmask, int64_t mask_batch_stride, int64_t mask_head_stride, int32_t batch,
                              int32_t num_heads, int32_t q_tiles, int32_t k_tiles, const int32_t* q_tiles_valid,
                              const int32_t* k_tiles_valid, void* lists, int32_t list_elem_size, int32_t* empty_rows, void* stream);
+
+/* Error statistics of `out` against `ref`, both (B, S, H, D) with ELEMENT strides and a contiguous last dimension, each of its own
+ * element type (LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32: a bf16 kernel output against the dense bf16 output, or against an fp32
+ * reference). head_dim: any positive multiple of 8 (not tied to the instantiated head dims). A bin is rows_per_bin consecutive rows of
+ * one (batch, head), the last one may be shorter: nbins = ceil(seqlen / rows_per_bin); rows_per_bin = seqlen gives one row of numbers
+ * per head, rows_per_bin = block_m the error per q-tile.
+ *   stats   device double [batch, num_heads, nbins, LA_STAT_COUNT] contiguous; EVERY element is written, the caller zeroes nothing.
+ *           Per bin over all head_dim columns: the sums and the maximum below, and the number of elements at which out or ref is not
+ *           finite - those elements are left out of the five other numbers (one NaN does not erase a head's statistic).
+ * One pass: every element is loaded once (16-byte loads), converted to fp64 and reduced in an order the shape alone fixes - no atomics,
+ * no workspace: two launches on the same data give bit-identical stats. Asynchronous on `stream`.
+ * Errors (all before any HIP call): NULL out / ref / stats LA_ERR_NULL_ARG; another dtype LA_ERR_DTYPE; a non-positive size or more than
+ * 2^31 - 1 bins in all LA_ERR_SHAPE; head_dim % 8 LA_ERR_HEAD_DIM; a negative stride, or a pointer / row / head (/ batch, when batch > 1)
+ * stride that takes a row start off a 16-byte boundary for its dtype, LA_ERR_STRIDE. */
+typedef enum la_error_stat {
+    LA_STAT_ABS_DIFF = 0,        /* sum |out - ref|      */
+    LA_STAT_ABS_REF = 1,         /* sum |ref|            */
+    LA_STAT_SQ_DIFF = 2,         /* sum (out - ref)^2    */
+    LA_STAT_SQ_REF = 3,          /* sum ref^2            */
+    LA_STAT_MAX_ABS_DIFF = 4,    /* max |out - ref|      */
+    LA_STAT_NONFINITE = 5        /* elements where out or ref is NaN or +-inf */
+} la_error_stat;
+#define LA_STAT_COUNT 6
+int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride, int64_t out_row_stride, int64_t out_head_stride,
+                    const void* ref, int32_t ref_dtype, int64_t ref_batch_stride, int64_t ref_row_stride, int64_t ref_head_stride,
+                    int32_t batch, int32_t seqlen, int32_t num_heads, int32_t head_dim, int32_t rows_per_bin,
+                    double* stats, void* stream);
 
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)

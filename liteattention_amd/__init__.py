@@ -21,11 +21,12 @@ if not _BUILDING:
     from .lite_attention import LiteAttention, SeqParallelLiteAttention  # noqa: E402
     from .compat import (blockmask_to_skip_lists, fa2_flash_attn_func, flash_attn_varlen_func,  # noqa: E402
                          flash_blocksparse_attn_func, flash_blocksparse_attn_qkvpacked_func)
-    from .calibration import calibrate_threshold  # noqa: E402
+    from .calibration import ErrorStats, calibrate_error_schedule, calibrate_threshold, output_error  # noqa: E402
     from .parallel import (HeadShardedLiteAttention, RingSeqParallelLiteAttention,  # noqa: E402
                            UlyssesLiteAttention)
 
 __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flash_attn_combine", "combine_partials",
            "get_tile_sizes", "skip_list_stats", "fa2_flash_attn_func", "flash_attn_varlen_func",
            "flash_blocksparse_attn_func", "flash_blocksparse_attn_qkvpacked_func", "blockmask_to_skip_lists", "calibrate_threshold",
+           "calibrate_error_schedule", "output_error", "ErrorStats",
            "HeadShardedLiteAttention", "UlyssesLiteAttention", "RingSeqParallelLiteAttention", "__version__"]

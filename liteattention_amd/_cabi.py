@@ -26,8 +26,10 @@ LA_ERR_Q_WINDOW = -13
 EXPORTED_SYMBOLS = (
     "la_abi_version", "la_get_tile_sizes", "la_get_tile_sizes_ex", "la_fwd", "la_fwd_workspace_bytes", "la_skip_list_stats", "la_combine",
     "la_status_string", "la_last_hip_error", "la_blockmask_to_lists", "la_device_slots", "la_build_info", "la_combine_list",
-    "la_skip_list_stats_ex", "la_blockmask_to_lists_ex",
+    "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error",
 )
+(LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
+LA_STAT_COUNT = 6
 
 
 class LaFwdArgs(ctypes.Structure):
@@ -167,6 +169,10 @@ def load() -> ctypes.CDLL:
                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                              ctypes.c_void_p]
     lib.la_blockmask_to_lists_ex.restype = ctypes.c_int
+    lib.la_output_error.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.la_output_error.restype = ctypes.c_int
     lib.la_device_slots.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.la_device_slots.restype = ctypes.c_int
     lib.la_status_string.argtypes = [ctypes.c_int]

@@ -457,4 +457,28 @@ int la_combine_list(const void* const* o_partials, int32_t partial_is_16bit, con
     return LA_OK;
 }
 
+int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride, int64_t out_row_stride, int64_t out_head_stride,
+                    const void* ref, int32_t ref_dtype, int64_t ref_batch_stride, int64_t ref_row_stride, int64_t ref_head_stride,
+                    int32_t batch, int32_t seqlen, int32_t num_heads, int32_t head_dim, int32_t rows_per_bin, double* stats, void* stream_) {
+    if (!out || !ref || !stats) return LA_ERR_NULL_ARG;
+    const auto dtype_ok = [](int32_t d) { return d == LA_DTYPE_BF16 || d == LA_DTYPE_FP16 || d == LA_DTYPE_FP32; };
+    if (!dtype_ok(out_dtype) || !dtype_ok(ref_dtype)) return LA_ERR_DTYPE;
+    if (batch <= 0 || seqlen <= 0 || num_heads <= 0 || head_dim <= 0 || rows_per_bin <= 0) return LA_ERR_SHAPE;
+    if (head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
+    // every row start is a 16-byte boundary: the pointer, and every stride that is used, in units of 16 / element size
+    const auto strides_ok = [&](const void* p, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
+        const int64_t unit = d == LA_DTYPE_FP32 ? 4 : 8;
+        return bs >= 0 && rs >= 0 && hs >= 0 && aligned16(p) && rs % unit == 0 && hs % unit == 0 && (batch == 1 || bs % unit == 0);
+    };
+    if (!strides_ok(out, out_dtype, out_batch_stride, out_row_stride, out_head_stride) ||
+        !strides_ok(ref, ref_dtype, ref_batch_stride, ref_row_stride, ref_head_stride)) return LA_ERR_STRIDE;
+    const int64_t nbins = (static_cast<int64_t>(seqlen) + rows_per_bin - 1) / rows_per_bin;
+    if (static_cast<int64_t>(batch) * num_heads * nbins > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per stats row
+    const hipError_t err = la::launch_output_error(out, out_dtype, out_batch_stride, out_row_stride, out_head_stride, ref, ref_dtype,
+                                                   ref_batch_stride, ref_row_stride, ref_head_stride, batch, seqlen, num_heads, head_dim,
+                                                   rows_per_bin, stats, static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
 }  // extern "C"

@@ -11,6 +11,8 @@
 //    attention_combine_ref (/root/reference/hopper/tests/test_flash_attn.py:1178-1187) and of the
 //    reference's (compiled-out) FlashAttnFwdCombine kernel
 //    (/root/reference/hopper/_internal/cpp/flash_fwd_combine_kernel.h).
+//  * output_error: one-pass error statistics of an output against a reference output (la_output_error), per (batch, head, bin of
+//    rows), in fp64. No counterpart: the reference names "error calibration" (README.md:14) and ships nothing that measures an error.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -326,6 +328,147 @@ hipError_t launch_combine_list(const void* const* o_partials, bool partial_is_16
     else if (f16) LA_COMBINE_LIST(false, true, false);
     else LA_COMBINE_LIST(false, false, false);
 #undef LA_COMBINE_LIST
+    return hipGetLastError();
+}
+
+// ---- output_error: Sum|out - ref|, Sum|ref|, Sum(out - ref)^2, Sum ref^2, max|out - ref| and the number of non-finite elements of one bin
+// (rows_per_bin consecutive rows x head_dim columns of one (batch, head)). One workgroup per (b, h, bin); a thread takes the bin's
+// 8-element chunks tid, tid + 256, ... in ascending order (each element loaded once, 16-byte loads: one for 16-bit elements, two for
+// fp32), converts to fp64 and reduces a chunk by a fixed pairwise tree before adding it to its running sums. Then a shuffle tree inside
+// the wave and a fixed-order sum of the four wave results through LDS: the order of every addition depends on the shape alone - no
+// atomics, no workspace, bit-identical results for every launch on the same data. HBM-bound: about 10 fp64 operations per element pair.
+template <int DT> struct ErrLoad;          // DT: la_dtype of the operand; load8 -> 8 consecutive elements as fp64
+template <> struct ErrLoad<0> {            // bf16
+    static constexpr int kBytes = 2;
+    static __device__ __forceinline__ void load8(const void* base, int64_t off, bool ok, double (&x)[8]) {
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 w = {0u, 0u, 0u, 0u};
+        if (ok) w = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(base) + off);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = static_cast<double>(__uint_as_float(w[i] << 16));
+            x[2 * i + 1] = static_cast<double>(__uint_as_float(w[i] & 0xffff0000u));
+        }
+    }
+};
+template <> struct ErrLoad<1> {            // fp16
+    static constexpr int kBytes = 2;
+    static __device__ __forceinline__ void load8(const void* base, int64_t off, bool ok, double (&x)[8]) {
+        f16x8 w = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (ok) w = *reinterpret_cast<const f16x8*>(static_cast<const uint16_t*>(base) + off);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = static_cast<double>(static_cast<float>(w[i]));
+    }
+};
+template <> struct ErrLoad<3> {            // fp32
+    static constexpr int kBytes = 4;
+    static __device__ __forceinline__ void load8(const void* base, int64_t off, bool ok, double (&x)[8]) {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
+        if (ok) {
+            a = *reinterpret_cast<const f32x4*>(static_cast<const float*>(base) + off);
+            c = *reinterpret_cast<const f32x4*>(static_cast<const float*>(base) + off + 4);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { x[i] = static_cast<double>(a[i]); x[4 + i] = static_cast<double>(c[i]); }
+    }
+};
+
+constexpr int kErrStats = 6;               // LA_STAT_COUNT
+constexpr int kErrUnroll = 4;              // chunks of one thread whose loads are issued together
+
+template <int DT_OUT, int DT_REF>
+__global__ void __launch_bounds__(256) output_error_kernel(const void* __restrict__ out, int64_t o_bs, int64_t o_rs, int64_t o_hs,
+                                                            const void* __restrict__ ref, int64_t r_bs, int64_t r_rs, int64_t r_hs,
+                                                            int seqlen, int num_heads, int head_dim, int rows_per_bin, int nbins,
+                                                            double* __restrict__ stats) {
+    __shared__ double part[4][kErrStats];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t item = blockIdx.x;                           // (b * H + h) * nbins + bin: the index of the stats row as well
+    const int bin = static_cast<int>(item % nbins);
+    const int64_t bh = item / nbins;
+    const int h = static_cast<int>(bh % num_heads), b = static_cast<int>(bh / num_heads);
+    const int row0 = bin * rows_per_bin;
+    const int rows = min(rows_per_bin, seqlen - row0);
+    const int cpr = head_dim / 8;                              // chunks per row
+    const int64_t nchunks = static_cast<int64_t>(rows) * cpr;
+    const int64_t o_base = b * o_bs + row0 * o_rs + h * o_hs, r_base = b * r_bs + row0 * r_rs + h * r_hs;
+
+    double s_ad = 0.0, s_ar = 0.0, s_dd = 0.0, s_rr = 0.0, mx = 0.0;
+    unsigned bad = 0;                                          // a thread sees at most 2^31 / 256 rows of 8 elements
+    // chunk c = tid + 256 j sits at (row, ch) = (c / cpr, c % cpr): kept by stepping 256 chunks at a time, no division in the loop
+    const int row_step = 256 / cpr, ch_step = 256 % cpr;
+    int row = tid / cpr, ch = tid % cpr;
+    for (int64_t c0 = tid; c0 < nchunks; c0 += 256 * kErrUnroll) {
+        double xo[kErrUnroll][8], xr[kErrUnroll][8];
+#pragma unroll
+        for (int u = 0; u < kErrUnroll; ++u) {                 // a chunk behind the bin reads as zeros: it adds +0 to every statistic
+            const bool ok = c0 + 256 * u < nchunks;
+            ErrLoad<DT_OUT>::load8(out, o_base + row * o_rs + ch * 8, ok, xo[u]);
+            ErrLoad<DT_REF>::load8(ref, r_base + row * r_rs + ch * 8, ok, xr[u]);
+            row += row_step; ch += ch_step;
+            if (ch >= cpr) { ch -= cpr; ++row; }
+        }
+#pragma unroll
+        for (int u = 0; u < kErrUnroll; ++u) {
+            double ad[8], ar[8], dd[8], rr[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const double d = xo[u][i] - xr[u][i];          // finite operands give a finite difference; anything else does not
+                const bool fin = __builtin_isfinite(d);
+                bad += fin ? 0u : 1u;
+                const double dz = fin ? d : 0.0, rz = fin ? xr[u][i] : 0.0;
+                ad[i] = fabs(dz); ar[i] = fabs(rz); dd[i] = dz * dz; rr[i] = rz * rz;
+                mx = fmax(mx, ad[i]);
+            }
+            s_ad += ((ad[0] + ad[1]) + (ad[2] + ad[3])) + ((ad[4] + ad[5]) + (ad[6] + ad[7]));
+            s_ar += ((ar[0] + ar[1]) + (ar[2] + ar[3])) + ((ar[4] + ar[5]) + (ar[6] + ar[7]));
+            s_dd += ((dd[0] + dd[1]) + (dd[2] + dd[3])) + ((dd[4] + dd[5]) + (dd[6] + dd[7]));
+            s_rr += ((rr[0] + rr[1]) + (rr[2] + rr[3])) + ((rr[4] + rr[5]) + (rr[6] + rr[7]));
+        }
+    }
+    double s_bad = static_cast<double>(bad);
+    for (int off = 32; off > 0; off >>= 1) {
+        s_ad += __shfl_down(s_ad, off); s_ar += __shfl_down(s_ar, off);
+        s_dd += __shfl_down(s_dd, off); s_rr += __shfl_down(s_rr, off);
+        mx = fmax(mx, __shfl_down(mx, off)); s_bad += __shfl_down(s_bad, off);
+    }
+    if (lane == 0) {
+        part[wave][0] = s_ad; part[wave][1] = s_ar; part[wave][2] = s_dd; part[wave][3] = s_rr; part[wave][4] = mx; part[wave][5] = s_bad;
+    }
+    __syncthreads();
+    if (tid < kErrStats) {                                     // one thread per statistic: waves 0, 1, 2, 3 in this order
+        const double a0 = part[0][tid], a1 = part[1][tid], a2 = part[2][tid], a3 = part[3][tid];
+        stats[item * kErrStats + tid] = tid == 4 ? fmax(fmax(a0, a1), fmax(a2, a3)) : (a0 + a1) + (a2 + a3);
+    }
+}
+
+template <int DT_OUT>
+static void launch_output_error_t(int ref_dtype, dim3 grid, hipStream_t stream, const void* out, int64_t o_bs, int64_t o_rs, int64_t o_hs,
+                                  const void* ref, int64_t r_bs, int64_t r_rs, int64_t r_hs, int seqlen, int num_heads, int head_dim,
+                                  int rows_per_bin, int nbins, double* stats) {
+#define LA_OUTPUT_ERROR(DT_REF) \
+    hipLaunchKernelGGL((output_error_kernel<DT_OUT, DT_REF>), grid, dim3(256), 0, stream, out, o_bs, o_rs, o_hs, ref, r_bs, r_rs, r_hs, seqlen, \
+                       num_heads, head_dim, rows_per_bin, nbins, stats)
+    if (ref_dtype == 0) LA_OUTPUT_ERROR(0);
+    else if (ref_dtype == 1) LA_OUTPUT_ERROR(1);
+    else LA_OUTPUT_ERROR(3);
+#undef LA_OUTPUT_ERROR
+}
+
+// out_dtype / ref_dtype: 0 bf16, 1 fp16, 3 fp32 (la_dtype; checked by the caller). grid = batch * num_heads * nbins workgroups (< 2^31, checked by the caller).
+hipError_t launch_output_error(const void* out, int out_dtype, int64_t o_bs, int64_t o_rs, int64_t o_hs, const void* ref, int ref_dtype,
+                               int64_t r_bs, int64_t r_rs, int64_t r_hs, int batch, int seqlen, int num_heads, int head_dim, int rows_per_bin,
+                               double* stats, hipStream_t stream) {
+    const int nbins = (seqlen + rows_per_bin - 1) / rows_per_bin;
+    const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(batch) * num_heads * nbins));
+    (void)hipGetLastError();
+    if (out_dtype == 0)
+        launch_output_error_t<0>(ref_dtype, grid, stream, out, o_bs, o_rs, o_hs, ref, r_bs, r_rs, r_hs, seqlen, num_heads, head_dim, rows_per_bin, nbins, stats);
+    else if (out_dtype == 1)
+        launch_output_error_t<1>(ref_dtype, grid, stream, out, o_bs, o_rs, o_hs, ref, r_bs, r_rs, r_hs, seqlen, num_heads, head_dim, rows_per_bin, nbins, stats);
+    else
+        launch_output_error_t<3>(ref_dtype, grid, stream, out, o_bs, o_rs, o_hs, ref, r_bs, r_rs, r_hs, seqlen, num_heads, head_dim, rows_per_bin, nbins, stats);
     return hipGetLastError();
 }
 

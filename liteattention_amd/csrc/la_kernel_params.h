@@ -110,5 +110,8 @@ hipError_t launch_combine(const void* o_partial, bool partial_is_16bit, bool f16
 hipError_t launch_combine_list(const void* const* o_partials, bool partial_is_16bit, bool f16, const float* const* lse_partials, uint16_t* o,
                                float* lse, int num_splits, int batch, int seqlen_q, int num_heads, int head_dim_v, hipStream_t stream,
                                bool out_f32 = false);
+hipError_t launch_output_error(const void* out, int out_dtype, int64_t o_bs, int64_t o_rs, int64_t o_hs, const void* ref, int ref_dtype,
+                               int64_t r_bs, int64_t r_rs, int64_t r_hs, int batch, int seqlen, int num_heads, int head_dim, int rows_per_bin,
+                               double* stats, hipStream_t stream);   // la_output_error: fp64 [batch, heads, bins, 6], every element written
 
 }  // namespace la

@@ -16,7 +16,7 @@ Behavioural differences, all fixes of reference defects:
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple, Union
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -49,6 +49,8 @@ class LiteAttention:
         self._shape_key = None                     # what the lists were built for
         self._must_do_rows = {}                    # (tokens, block_n, row width, device) -> device row (LRU, _MUST_DO_ROWS_MAX)
         self._last_percentage = 0.0
+        self._threshold_schedule: Optional[Tuple[float, ...]] = None   # per-step thresholds (set_threshold_schedule); None = the constant
+        self._step = 0                             # calls that used the lists since they were last (re)initialised
         self.enable_skipping = enable_skipping
         self.max_batch_size = max_batch_size
         self.set_threshold(threshold)
@@ -118,6 +120,7 @@ class LiteAttention:
             self._skip_list = self._init_skip_list(query, value, must_skip_list)
             self._shape_key = key
             self._phase = 0
+            self._step = 0
             if _verbose():
                 print("[Warning]: reinitialized skip list during the forward pass")
         elif query.shape[0] > self._skip_list.shape[1]:
@@ -133,6 +136,14 @@ class LiteAttention:
         self._phase = 1 - rd
         return self._skip_list[rd], self._skip_list[1 - rd]
 
+    def _take_threshold(self, sparse: bool) -> float:
+        """The threshold of the call whose lists were just handed out; a call that uses the lists advances the step counter (a dense
+        call leaves it alone, as it leaves the lists alone). Without a schedule: ``self.threshold``, as ever."""
+        thr = self.current_threshold() if sparse else self.threshold
+        if sparse:
+            self._step += 1
+        return thr
+
     def preallocate(self, query: Tensor, value: Tensor, batch: Optional[int] = None, must_skip_list: list = None):
         """Size the lists for ``batch`` sequences (default ``max_batch_size``) of this shape NOW, so that no later call has to grow them:
         what a caller does before capturing calls into a HIP graph (a graph keeps the list pointers of its capture; growth replaces the
@@ -143,7 +154,7 @@ class LiteAttention:
                get_tile_sizes(query.shape[3], query.dtype.itemsize), self.list_dtype)
         if self._skip_list is None or key != self._shape_key:
             self._skip_list = self._init_skip_list(query, value, must_skip_list, batch=batch)
-            self._shape_key, self._phase = key, 0
+            self._shape_key, self._phase, self._step = key, 0, 0
         elif batch > self._skip_list.shape[1]:
             grown = self._init_skip_list(query, value, must_skip_list, batch=batch)
             grown[:, : self._skip_list.shape[1]] = self._skip_list
@@ -192,7 +203,7 @@ class LiteAttention:
             # build has no split kernel, hopper/setup.py:48)
             extra["num_splits"] = -1
         output = flash_attn_func(q=query, k=key, v=value, softmax_scale=scale, attn_read_list=read_list,
-                                 attn_must_do_list=must_do, attn_write_list=write_list, thr=self.threshold,
+                                 attn_must_do_list=must_do, attn_write_list=write_list, thr=self._take_threshold(read_list is not None),
                                  return_softmax_lse=return_softmax_lse, **extra)
         if read_list is not None and _verbose():
             self._last_percentage = self.calc_percentage(read_list[: query.shape[0]])
@@ -216,7 +227,7 @@ class LiteAttention:
         q, k, v = [x if x.stride(-1) == 1 else x.contiguous() for x in (query, key, value)]
         out, lse, *_ = mha_fwd(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
                                softmax_scale=scale, attn_read_list=read_list, attn_must_do_list=must_do,
-                               attn_write_list=write_list, thr=self.threshold, _must_do_is_1d=True,
+                               attn_write_list=write_list, thr=self._take_threshold(read_list is not None), _must_do_is_1d=True,
                                _q_windows=q_windows, _window_hook=window_hook, _static_sched=static_sched)
         return (out, lse) if return_softmax_lse else out
 
@@ -227,12 +238,36 @@ class LiteAttention:
         self._phase = 0
         self._shape_key = None
         self._last_percentage = 0.0
+        self._step = 0
 
     def set_threshold(self, threshold: float):
-        """Threshold must be negative unless env LITE_ATTENTION_DEBUG != "FALSE" (:306-313)."""
+        """Threshold must be negative unless env LITE_ATTENTION_DEBUG != "FALSE" (:306-313). Removes a threshold schedule: a constant
+        is a constant."""
         if threshold >= 0 and os.getenv("LITE_ATTENTION_DEBUG", "FALSE") == "FALSE":
             raise ValueError("threshold must be negative when debug mode is not enabled")
         self.threshold = threshold
+        self._threshold_schedule = None
+
+    def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
+        """Per-step thresholds (extension; the reference's "error calibration" contribution, README.md:14, has no API there): the
+        i-th call that uses the skip lists since the last ``reset_skip_state()`` - or since the lists were last re-initialised by a
+        shape change - runs at ``thresholds[min(i, len - 1)]``. The threshold of call i shapes the list call i + 1 reads. Dense calls
+        (``enable_skip_optimization(False)``) do not count. Every entry is checked like ``set_threshold``'s; ``None`` removes the
+        schedule and the constant ``threshold`` applies again. ``calibration.calibrate_error_schedule`` finds such a schedule."""
+        if thresholds is None:
+            self._threshold_schedule = None
+            return
+        sched = tuple(float(t) for t in thresholds)
+        if not sched:
+            raise ValueError("an empty threshold schedule: pass None to remove the schedule")
+        if any(t >= 0 for t in sched) and os.getenv("LITE_ATTENTION_DEBUG", "FALSE") == "FALSE":
+            raise ValueError("threshold must be negative when debug mode is not enabled")
+        self._threshold_schedule = sched
+
+    def current_threshold(self) -> float:
+        """The threshold the next call that uses the skip lists will pass."""
+        sched = self._threshold_schedule
+        return self.threshold if sched is None else sched[min(self._step, len(sched) - 1)]
 
     def enable_skip_optimization(self, enable: bool = True):
         self.enable_skipping = enable
@@ -249,6 +284,25 @@ class LiteAttention:
             return 0.0
         return 1.0 - self.calc_percentage(rl[: (rl.shape[0] if batch is None else batch)])
 
+    def snapshot(self) -> dict:
+        """Both ping-pong lists, the phase and the step counter, copied ON THE DEVICE (no host round trip, no sync: ``state_dict()``
+        takes 112 MB per layer through the host at S = 75 600, H = 40). For ``restore``; thresholds are not part of it."""
+        return {"skip_list": None if self._skip_list is None else self._skip_list.clone(), "phase": self._phase, "step": self._step,
+                "shape_key": self._shape_key}
+
+    def restore(self, snap: dict):
+        """Back to ``snapshot()``: the calls that follow are bit-identical (O, LSE, lists) to those that followed the snapshot. Lists
+        of the snapshot's shape are overwritten in place (their addresses stay valid); the snapshot itself is left untouched."""
+        if snap["skip_list"] is None:
+            self.reset_skip_state()
+            return
+        if self._skip_list is not None and self._skip_list.shape == snap["skip_list"].shape \
+                and self._skip_list.dtype == snap["skip_list"].dtype and self._skip_list.device == snap["skip_list"].device:
+            self._skip_list.copy_(snap["skip_list"])
+        else:
+            self._skip_list = snap["skip_list"].clone()
+        self._phase, self._step, self._shape_key = snap["phase"], snap["step"], snap["shape_key"]
+
     def state_dict(self) -> dict:
         """Everything a run needs to continue bit-identically: both ping-pong lists, the phase, the threshold and what the
         lists were built for (shape key incl. the DEVICE they live on). Tensors are returned on the CPU."""
@@ -261,6 +315,8 @@ class LiteAttention:
             "device": None if key is None else str(key[5]),
             "tile_sizes": None if key is None else tuple(key[6]),
             "list_dtype": str(self.list_dtype).replace("torch.", ""),      # of the saved lists (absent before int16 lists existed: int32)
+            "threshold_schedule": None if self._threshold_schedule is None else list(self._threshold_schedule),
+            "step": self._step,                                            # both absent before threshold schedules existed: None, 0
         }
 
     def load_state_dict(self, state: dict, device=None):
@@ -272,6 +328,8 @@ class LiteAttention:
         self.enable_skipping = state["enable_skipping"]
         self.max_batch_size = state["max_batch_size"]
         self.reset_skip_state()
+        sched = state.get("threshold_schedule")
+        self._threshold_schedule = None if sched is None else tuple(float(t) for t in sched)
         if state["skip_list"] is None:
             return
         if device is None:
@@ -292,6 +350,7 @@ class LiteAttention:
             raise ValueError("the saved lists do not match the tile geometry of the kernel selected now")
         self._skip_list = _sl.convert_lists(state["skip_list"], self.list_dtype).to(dev).contiguous()
         self._phase = state["phase"]
+        self._step = int(state.get("step", 0))
         self._shape_key = (sq, sk, h, d, dtype, dev, tuple(tiles), self.list_dtype)
 
 
@@ -332,6 +391,10 @@ class SeqParallelLiteAttention:
     def set_threshold(self, threshold: float):
         for la in self.lite_attention:
             la.set_threshold(threshold)
+
+    def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
+        for la in self.lite_attention:
+            la.set_threshold_schedule(thresholds)
 
     def enable_skip_optimization(self, enable: bool = True):
         for la in self.lite_attention:

@@ -188,6 +188,9 @@ class HeadShardedLiteAttention:
     def set_threshold(self, threshold: float):
         self.local.set_threshold(threshold)
 
+    def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
+        self.local.set_threshold_schedule(thresholds)
+
 
 class UlyssesLiteAttention:
     """Sequence-sharded in, sequence-sharded out; heads sharded inside (the DeepSpeed-Ulysses scheme, which is what
@@ -247,6 +250,9 @@ class UlyssesLiteAttention:
 
     def set_threshold(self, threshold: float):
         self.inner.set_threshold(threshold)
+
+    def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
+        self.inner.set_threshold_schedule(thresholds)
 
 
 class RingSeqParallelLiteAttention:
@@ -323,3 +329,6 @@ class RingSeqParallelLiteAttention:
 
     def set_threshold(self, threshold: float):
         self.states.set_threshold(threshold)
+
+    def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
+        self.states.set_threshold_schedule(thresholds)
