@@ -69,6 +69,7 @@ _FWD_SCHEMA = (
     "Tensor? attn_write_list = None,"
     "float thr = -3.0) -> (Tensor(out!), Tensor, Tensor, Tensor)"
 )
+_COMBINE_SCHEMA = "fwd_combine(Tensor out_partial, Tensor lse_partial, Tensor(out!)? out = None, ScalarType? out_dtype = None) -> (Tensor(out!), Tensor)"
 
 
 _KERNEL_HEAD_DIM = {}      # (head_dim, element_size, kernel-selection flags) -> instantiated head_dim (the library's table never changes)
@@ -148,15 +149,14 @@ def _check_list(t: Optional[torch.Tensor], name: str, q: torch.Tensor, dtypes=(t
     return t.data_ptr()
 
 
-_tls = threading.local()
+class _Scope(threading.local):
+    """What the ``fwd_flags`` blocks this thread is inside of add to, and take out of, the flags of a forward call."""
+    flags = 0
+    clear = 0
 
 
-def _scoped_flags() -> int:
-    return getattr(_tls, "flags", 0)
-
-
-def _scoped_clear() -> int:
-    return getattr(_tls, "clear", 0)
+_tls = _Scope()
+_EXTRA_FLAGS = _cabi.LA_FLAG_EXACT_RESCALE | _cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P      # what fwd_flags / _flags accept
 
 
 @contextlib.contextmanager
@@ -166,16 +166,157 @@ def fwd_flags(flags: int, clear: int = 0):
     registered op, the varlen adapters): the reference's signatures have no argument for them. ``clear``: flags taken OUT of whatever the
     host default (``LA_FP8_P``) or an outer block set: ``SeqParallelLiteAttention`` clears the two fp8 flags to get the reference's
     fp32-exact LSE for e4m3 inputs whose partial results are merged by LSE, whatever form of P the process runs with otherwise."""
-    ok = _cabi.LA_FLAG_EXACT_RESCALE | _cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P
-    if (flags | clear) & ~ok:
+    if (flags | clear) & ~_EXTRA_FLAGS:
         raise ValueError("fwd_flags accepts LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM and LA_FLAG_FP8_ENCODED_P only")
-    prev, prev_clear = _scoped_flags(), _scoped_clear()
+    prev, prev_clear = _tls.flags, _tls.clear
     _tls.flags = (prev | flags) & ~clear
     _tls.clear = (prev_clear | clear) & ~flags
     try:
         yield
     finally:
         _tls.flags, _tls.clear = prev, prev_clear
+
+
+# ---- what the three routes to la_fwd share: mha_fwd (fixed-length), _split_kv_one_sequence (a split key range at batch 1) and
+# _mha_fwd_varlen (packed batches). tests/test_host_calls_cpu.py pins every field each of them hands to the library.
+_FIXED, _SPLIT, _PACKED = 0, 1, 2
+_LABEL = ("", " (split-KV)", " (varlen)")                   # the route, as the error messages name it
+_FP8 = torch.float8_e4m3fn
+_DTYPE_CODE = {torch.float16: _cabi.LA_DTYPE_FP16, _FP8: _cabi.LA_DTYPE_FP8_E4M3, torch.float32: _cabi.LA_DTYPE_FP32}
+_ARGS_SIZE = ctypes.sizeof(_cabi.LaFwdArgs)
+_DESCALE_FIELDS = tuple((f"{n}_descale", f"{n}_descale_batch_stride", f"{n}_descale_head_stride") for n in "qkv")
+_OUT_MSG = ("For FP16/BF16 input, output must have the same dtype as inputs (BF16 for FP8 input), shape "
+            "(batch, seqlen_q, nheads, headdim_v) and a contiguous last dimension")
+_OUT_MSG_PACKED = "out must have the input dtype (bf16 for fp8 inputs), shape (total_q, nheads, headdim) and a contiguous last dimension"
+
+
+def _dtype_code(dtype: torch.dtype) -> int:
+    """``LA_DTYPE_*`` of a tensor type (the callers have checked the type: bf16 is what remains)."""
+    return _DTYPE_CODE.get(dtype, _cabi.LA_DTYPE_BF16)
+
+
+def _check_inputs(q, k, v, descales, batch, kv_msg, packed):
+    """What the fixed-length and the packed route both ask of q / k / v (4-D, or packed 3-D) and of the descales, after their own rank
+    check (the supported dtypes are checked once, at the top of ``mha_fwd``, the only way in). ``kv_msg``: the route's wording."""
+    if q.stride(-1) != 1 or k.stride(-1) != 1 or v.stride(-1) != 1:
+        raise RuntimeError("Input tensor must have contiguous last dimension")                   # :726-728
+    qs, ks, vs = q.shape, k.shape, v.shape
+    D, Hk = qs[-1], ks[-2]
+    if ks[-1] != D or vs[:-1] != ks[:-1] or (vs[-1] != D if packed else ks[0] != qs[0]):
+        raise RuntimeError(kv_msg)                     # (fixed-length: another head_dim_v is the caller's NotImplementedError)
+    if qs[-2] % Hk != 0:
+        raise RuntimeError("Number of heads in key/value must divide number of heads in query")  # :777
+    is_fp8 = q.dtype == _FP8
+    if D % (16 if is_fp8 else 8) != 0:
+        raise RuntimeError("head_size should be a multiple of " + ("16" if is_fp8 else "8"))     # :854-856
+    if descales[0] is None and descales[1] is None and descales[2] is None:
+        return
+    for name, t in zip(("q_descale", "k_descale", "v_descale"), descales):
+        if t is None:
+            continue
+        if not is_fp8:
+            raise RuntimeError(f"{name} is only supported for fp8 inputs")
+        if t.dtype != torch.float32 or tuple(t.shape) != (batch, Hk) or t.device != q.device:      # :1003-1022
+            raise RuntimeError(f"{name} must be a float32 tensor of shape (batch_size, nheads_k) on the input device")
+
+
+def _check_out(out, shape, dtype, msg):
+    if out is not None and (out.dtype != dtype or tuple(out.shape) != shape or out.stride(-1) != 1):   # :863
+        raise RuntimeError(msg)
+
+
+def _pad_head_dim(t, D_kernel):
+    """Zero-pad the last dim to the instantiated head_dim (exact, see ``kernel_head_dim``); fp8: pad the bytes (0x00 is +0.0 in e4m3)."""
+    if t.dtype == _FP8:
+        return torch.nn.functional.pad(t.view(torch.uint8), (0, D_kernel - t.shape[-1])).view(t.dtype)
+    return torch.nn.functional.pad(t, (0, D_kernel - t.shape[-1]))
+
+
+def _unpadded(res, out, shape, dtype, device):
+    """The result of the padded retry, sliced into the caller's ``out`` (or a contiguous new one, as the reference returns it)."""
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    out.copy_(res[0][..., :shape[-1]])
+    return (out, *res[1:])
+
+
+def _outputs(out, softmax_lse):
+    """``(out, softmax_lse, out_accum, softmax_lse_accum)``: the accumulators are the reference's split scratch, empty here."""
+    empty = torch.empty(0, dtype=torch.float32, device=out.device)
+    return out, softmax_lse, empty, empty
+
+
+def _fwd_args(q, k, v, out, lse, descales, batch, seqlen_q, seqlen_k, softmax_scale, block_m, block_n,
+              read_ptr=None, write_ptr=None, must_ptr=None, must_do_is_1d=False, thr=0.0):
+    """The ``la_fwd_args`` of one launch over 4-D (batch, seqlen, heads, head_dim) or packed 3-D (tokens, heads, head_dim) tensors
+    (packed: batch strides 0; the caller adds cu_seqlens / total_q). ``flags``, the workspace and the q-tile window are the caller's."""
+    a = _cabi.LaFwdArgs()
+    a.struct_size = _ARGS_SIZE
+    a.dtype = _dtype_code(q.dtype)
+    for t, (ptr, batch_stride, head_stride) in zip(descales, _DESCALE_FIELDS):
+        if t is not None:
+            setattr(a, ptr, t.data_ptr())
+            setattr(a, batch_stride, t.stride(0))
+            setattr(a, head_stride, t.stride(1))
+    a.q, a.k, a.v, a.o, a.lse = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr()
+    sq, sk, sv, so = q.stride(), k.stride(), v.stride(), out.stride()
+    if len(sq) == 4:
+        a.q_batch_stride, a.k_batch_stride, a.v_batch_stride, a.o_batch_stride = sq[0], sk[0], sv[0], so[0]
+    a.q_row_stride, a.q_head_stride = sq[-3], sq[-2]
+    a.k_row_stride, a.k_head_stride = sk[-3], sk[-2]
+    a.v_row_stride, a.v_head_stride = sv[-3], sv[-2]
+    a.o_row_stride, a.o_head_stride = so[-3], so[-2]
+    a.batch, a.seqlen_q, a.seqlen_k = batch, seqlen_q, seqlen_k
+    a.num_heads, a.head_dim = q.shape[-2:]
+    a.num_heads_k, a.head_dim_v = k.shape[-2], a.head_dim
+    a.softmax_scale = float(softmax_scale)
+    a.read_list, a.write_list, a.must_do_list = read_ptr, write_ptr, must_ptr
+    a.must_do_is_1d = 1 if must_do_is_1d else 0
+    a.thr = float(thr)
+    a.block_m, a.block_n = block_m, block_n
+    return a
+
+
+def _route_flags(route, host_flags, explicit, list_flags, is_fp8):
+    """``la_fwd_args.flags`` of a route from the host defaults (the environment), the caller's ``_flags``, the ``fwd_flags`` scope and
+    the dtype of the lists. The routes differ, and tests/golden/host_calls.json pins how:"""
+    scoped, clear = _tls.flags, _tls.clear
+    if route == _FIXED:      # every host default (e4m3 has no 128-row kernel); the clear also takes out the caller's explicit _flags (ADVICE.md, fwd_flags)
+        return (((host_flags & ~(_cabi.LA_FLAG_KERNEL_128ROW if is_fp8 else 0)) | explicit | scoped) & ~clear) | list_flags
+    if route == _SPLIT:      # no explicit _flags; always the static map, the caller's _static_sched is not looked at (ADVICE.md, fwd_flags); keeps EXACT_RESCALE for e4m3
+        keep = _EXTRA_FLAGS if is_fp8 else (_cabi.GEOMETRY_FLAGS | _cabi.LA_FLAG_EXACT_RESCALE)
+        return ((host_flags | scoped) & keep & ~clear) | _cabi.LA_FLAG_STATIC_SCHED
+    # packed: no explicit _flags; LA_SCHED=static passes; e4m3 drops EXACT_RESCALE, which the split route keeps
+    keep = (_cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P) if is_fp8 else (_cabi.GEOMETRY_FLAGS | _cabi.LA_FLAG_EXACT_RESCALE)
+    return ((host_flags | scoped) & ~clear & (keep | _cabi.LA_FLAG_STATIC_SCHED)) | list_flags
+
+
+def _add_workspace(a, device, route):
+    """Caller-owned scratch (the C side allocates nothing): fp8 = the pre-transposed V tiles; the ticket counter of the dynamic work
+    distribution; the partials of a dense key range cut into runs. The library is asked with ``a.flags`` as they are now. Returns the
+    tensor: it must live until the launches are enqueued (then the caching allocator's stream-ordered reuse frees it). WHETHER a route
+    asks is the route's: always (fixed), e4m3 only (split: ADVICE.md, _split_kv_one_sequence), lists or e4m3 (packed)."""
+    need = _cabi.load().la_fwd_workspace_bytes(ctypes.byref(a))
+    if need < 0:
+        raise RuntimeError(f"lite_attention::fwd{_LABEL[route]}: {_cabi.status_string(int(need))}")
+    if need == 0:
+        return None
+    workspace = torch.empty(int(need), dtype=torch.uint8, device=device)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), int(need)
+    return workspace
+
+
+def _launch(lib, a, stream, route):
+    """``la_fwd`` on ``stream``; a return code becomes the route's exception."""
+    rc = lib.la_fwd(ctypes.byref(a), stream)
+    if rc == _cabi.LA_OK:
+        return
+    msg = _cabi.status_string(rc)
+    if rc == _cabi.LA_ERR_UNSUPPORTED and route != _SPLIT:      # the split route reports it as a RuntimeError like every other code
+        raise NotImplementedError(msg)
+    if rc == _cabi.LA_ERR_LAUNCH and route == _FIXED:           # only the fixed-length route adds the HIP error
+        msg += f" (hipError {lib.la_last_hip_error()})"
+    raise RuntimeError(f"lite_attention::fwd{_LABEL[route]}: {msg}")
 
 
 def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=None, cu_seqlens_k=None,
@@ -197,24 +338,25 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     collective running beside the launch gets CUs as items retire); "after_first" sets it on every window but the first
     (no collective is in flight beside window 0). ``_flags``: extra ``LA_FLAG_*`` bits ORed into ``la_fwd_args.flags`` (tests / A/B:
     LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM, LA_FLAG_FP8_ENCODED_P); kernel-selection bits that change the tile geometry are not accepted here."""
-    _flags |= _scoped_flags()
-    if _flags & ~(_cabi.LA_FLAG_EXACT_RESCALE | _cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P):
+    if _flags & ~_EXTRA_FLAGS:
         raise ValueError("_flags accepts LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM and LA_FLAG_FP8_ENCODED_P only")
     if not q.is_cuda:
         raise RuntimeError("lite_attention::fwd has no CPU implementation (HIP device tensors required)")
-    if q.dtype not in (torch.bfloat16, torch.float16, torch.float8_e4m3fn):
+    if q.dtype not in (torch.bfloat16, torch.float16, _FP8):
         raise RuntimeError("FlashAttention only supports fp16, bf16, and fp8_e4m3 type")          # :715
-    is_fp8 = q.dtype == torch.float8_e4m3fn
+    is_fp8 = q.dtype == _FP8
     if k.dtype != q.dtype or v.dtype != q.dtype:
         raise RuntimeError("query and key must have the same dtype")                              # :718-719
-    for name, val in (("k_new", k_new), ("v_new", v_new), ("q_v", q_v), ("cu_seqlens_k_new", cu_seqlens_k_new),
-                      ("seqused_q", seqused_q), ("seqused_k", seqused_k), ("page_table", page_table),
-                      ("kv_batch_idx", kv_batch_idx), ("leftpad_k", leftpad_k), ("rotary_cos", rotary_cos),
-                      ("rotary_sin", rotary_sin), ("seqlens_rotary", seqlens_rotary),
-                      ("scheduler_metadata", scheduler_metadata)):
-        if val is not None:
-            raise NotImplementedError(f"{name} is outside the QK-Skip hot path (compiled out of the reference's "
-                                      "default LiteAttention build, hopper/setup.py:47-63)")
+    # the reference's arguments this build has no path for. The chain and the tuple of names below are ONE list written twice (the chain
+    # keeps 13 tuples per call out of the hot path): a name goes into both, and gets a refuse_arg_<name> case in tests/host_calls.py
+    if not (k_new is None and v_new is None and q_v is None and cu_seqlens_k_new is None and seqused_q is None and seqused_k is None
+            and page_table is None and kv_batch_idx is None and leftpad_k is None and rotary_cos is None and rotary_sin is None
+            and seqlens_rotary is None and scheduler_metadata is None):
+        given = locals()
+        name = next(n for n in ("k_new", "v_new", "q_v", "cu_seqlens_k_new", "seqused_q", "seqused_k", "page_table", "kv_batch_idx",
+                                "leftpad_k", "rotary_cos", "rotary_sin", "seqlens_rotary", "scheduler_metadata") if given[n] is not None)
+        raise NotImplementedError(f"{name} is outside the QK-Skip hot path (compiled out of the reference's "
+                                  "default LiteAttention build, hopper/setup.py:47-63)")
     if is_causal or window_size_left >= 0 or window_size_right >= 0 or attention_chunk != 0:
         raise NotImplementedError("causal / local / chunked attention is outside the QK-Skip hot path "
                                   "(the reference's skip walk is non-causal only, mainloop:1757-1827)")
@@ -226,36 +368,21 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
         raise NotImplementedError("split-KV (num_splits > 1) serves dense fixed-length launches only: a skip list walks ITS tiles of the whole key range")
     if pack_gqa:
         raise NotImplementedError("pack_gqa is compiled out (hopper/setup.py:53)")
+    descales = (q_descale, k_descale, v_descale)
     if cu_seqlens_q is not None or cu_seqlens_k is not None:
-        return _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, q_descale, k_descale,
-                               v_descale, softmax_scale, attn_read_list, attn_write_list, attn_must_do_list, thr, _must_do_is_1d)
+        return _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales,
+                               softmax_scale, attn_read_list, attn_write_list, attn_must_do_list, thr, _must_do_is_1d)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise RuntimeError("q, k, v must be 4D tensors (batch, seqlen, nheads, headdim)")
-    if q.stride(-1) != 1 or k.stride(-1) != 1 or v.stride(-1) != 1:
-        raise RuntimeError("Input tensor must have contiguous last dimension")                   # :726-728
     B, Sq, H, D = q.shape
-    Bk, Sk, Hk, Dk = k.shape
-    Dv = v.shape[-1]
-    if (Bk, Dk) != (B, D) or tuple(v.shape[:3]) != (B, Sk, Hk):
-        raise RuntimeError("k/v shape mismatch: expected k (batch, seqlen_k, nheads_k, headdim), v (batch, seqlen_k, nheads_k, headdim_v)")
-    if H % Hk != 0:
-        raise RuntimeError("Number of heads in key/value must divide number of heads in query")  # :777
-    if D % (16 if is_fp8 else 8) != 0:
-        raise RuntimeError("head_size should be a multiple of " + ("16" if is_fp8 else "8"))     # :854-856
-    descales = []
-    for name, t in (("q_descale", q_descale), ("k_descale", k_descale), ("v_descale", v_descale)):
-        if t is None:
-            descales.append(None)
-            continue
-        if not is_fp8:
-            raise RuntimeError(f"{name} is only supported for fp8 inputs")
-        if t.dtype != torch.float32 or tuple(t.shape) != (B, Hk) or t.device != q.device:          # :1003-1022
-            raise RuntimeError(f"{name} must be a float32 tensor of shape (batch_size, nheads_k) on the input device")
-        descales.append(t)
-    if Dv != D:
+    _check_inputs(q, k, v, descales, B, "k/v shape mismatch: expected k (batch, seqlen_k, nheads_k, headdim), "
+                  "v (batch, seqlen_k, nheads_k, headdim_v)", False)
+    Sk = k.shape[1]
+    if v.shape[-1] != D:
         raise NotImplementedError("head_dim_v != head_dim is outside the QK-Skip hot path in this build")
     if softmax_scale is None:
         softmax_scale = D ** -0.5
+    host_flags = _cabi.default_flags()                       # the environment is read once per route
     if (num_splits > 1 or num_splits == -1) and attn_read_list is None and _q_windows is None:
         # split-KV on the host (round 6; the reference: get_num_splits / num_splits_heuristic, flash_api.cpp:437-465, heuristics.h:25-58,
         # compiled out of its default build, hopper/setup.py:48 - where num_splits = 0 therefore means 1, as it does here): a dense launch
@@ -264,46 +391,30 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
         # over the splits (batch 1: the splits are the batch of a fixed-length launch; else a packed batch), then la_combine.
         n = _num_splits(B, H, Sq, Sk, D, q.element_size(), max(num_splits, 0))
         if n > 1:
-            res = _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales)
+            res = _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales, host_flags)
             if res is not None:
                 return res
 
-    host_flags = _cabi.default_flags()                       # the environment is read ONCE per call
+    out_dtype = torch.bfloat16 if is_fp8 else q.dtype                                            # :859
     # (e4m3: native bodies at head dims 64 / 96 / 128 / 192 / 256 since round 6 - rounds 3-5 up-converted 192 / 256 here with torch elementwise passes
     # and ran the bf16 kernels; the sizes between run zero-padded on the next one, like the 2-byte types)
     D_kernel = kernel_head_dim(D, q.element_size(), host_flags)
+    _check_out(out, (B, Sq, H, D), out_dtype, _OUT_MSG)
     if D_kernel != D:
         # head_dim between the instantiated sizes: zero-pad the last dim (one extra pass over q, k, v; exact, see
         # kernel_head_dim), run the D_kernel kernel with the ORIGINAL softmax scale, slice the output
-        def pad_last(t):                                     # fp8: pad the bytes (0x00 is +0.0 in e4m3)
-            if is_fp8:
-                return torch.nn.functional.pad(t.view(torch.uint8), (0, D_kernel - D)).view(t.dtype)
-            return torch.nn.functional.pad(t, (0, D_kernel - D))
-        out_dtype = torch.bfloat16 if is_fp8 else q.dtype
-        if out is not None and (out.dtype != out_dtype or tuple(out.shape) != (B, Sq, H, D) or out.stride(-1) != 1):
-            raise RuntimeError("For FP16/BF16 input, output must have the same dtype as inputs (BF16 for FP8 input), shape "
-                               "(batch, seqlen_q, nheads, headdim_v) and a contiguous last dimension")
-        qp, kp, vp = pad_last(q), pad_last(k), pad_last(v)
-        res = mha_fwd(qp, kp, vp, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
+        res = mha_fwd(_pad_head_dim(q, D_kernel), _pad_head_dim(k, D_kernel), _pad_head_dim(v, D_kernel),
+                      q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
                       softmax_scale=softmax_scale, attn_read_list=attn_read_list, attn_must_do_list=attn_must_do_list,
                       attn_write_list=attn_write_list, thr=thr, _must_do_is_1d=_must_do_is_1d, _q_windows=_q_windows,
                       _static_sched=_static_sched, _flags=_flags,
                       _window_hook=None if _window_hook is None else
                       (lambda i, o, r0, r1: _window_hook(i, o[..., :D], r0, r1)))
-        if out is None:
-            out = torch.empty((B, Sq, H, D), dtype=out_dtype, device=q.device)      # contiguous, as the reference returns it
-        out.copy_(res[0][..., :D])
-        return (out, *res[1:])
-
-    out_dtype = torch.bfloat16 if is_fp8 else q.dtype                                            # :859
+        return _unpadded(res, out, (B, Sq, H, D), out_dtype, q.device)
     if out is None:
-        out = torch.empty((B, Sq, H, Dv), dtype=out_dtype, device=q.device)                      # :872-886
-    else:
-        if out.dtype != out_dtype or tuple(out.shape) != (B, Sq, H, Dv) or out.stride(-1) != 1:  # :863
-            raise RuntimeError("For FP16/BF16 input, output must have the same dtype as inputs (BF16 for FP8 input), shape "
-                               "(batch, seqlen_q, nheads, headdim_v) and a contiguous last dimension")
+        out = torch.empty((B, Sq, H, D), dtype=out_dtype, device=q.device)                       # :872-886
     softmax_lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)                  # :887-892
-    empty = torch.empty(0, dtype=torch.float32, device=q.device)
+    res = _outputs(out, softmax_lse)
 
     list_flags = _list_flags(attn_read_list, attn_write_list)
     read_ptr = _check_list(attn_read_list, "attn_read_list", q, LIST_DTYPES)
@@ -326,37 +437,11 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     if _must_do_is_1d and attn_must_do_list is not None and attn_must_do_list.numel() < 3:
         raise RuntimeError("1-D attn_must_do_list needs at least [len, start, end]")
 
-    a = _cabi.LaFwdArgs()
-    a.struct_size = ctypes.sizeof(_cabi.LaFwdArgs)
-    a.dtype = _cabi.LA_DTYPE_FP8_E4M3 if is_fp8 else (_cabi.LA_DTYPE_FP16 if q.dtype == torch.float16 else _cabi.LA_DTYPE_BF16)
-    for name, t in zip(("q", "k", "v"), descales):
-        if t is not None:
-            setattr(a, f"{name}_descale", t.data_ptr())
-            setattr(a, f"{name}_descale_batch_stride", t.stride(0))
-            setattr(a, f"{name}_descale_head_stride", t.stride(1))
-    a.q, a.k, a.v, a.o, a.lse = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), softmax_lse.data_ptr()
-    a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
-    a.k_batch_stride, a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1), k.stride(2)
-    a.v_batch_stride, a.v_row_stride, a.v_head_stride = v.stride(0), v.stride(1), v.stride(2)
-    a.o_batch_stride, a.o_row_stride, a.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
-    a.batch, a.seqlen_q, a.seqlen_k = B, Sq, Sk
-    a.num_heads, a.num_heads_k, a.head_dim, a.head_dim_v = H, Hk, D, Dv
-    a.softmax_scale = float(softmax_scale)
-    a.read_list, a.write_list, a.must_do_list = read_ptr, write_ptr, must_ptr
-    a.must_do_is_1d = 1 if _must_do_is_1d else 0
-    a.thr = float(thr)
-    a.block_m, a.block_n = block_m, block_n
-    # caller-owned scratch (the C side allocates nothing): fp8 = the pre-transposed V tiles; bf16 with lists = the ticket
-    # counter of the dynamic work distribution. Freed after the launch by the caching allocator's stream-ordered reuse.
-    workspace = None
-    base_flags = (((host_flags & ~(_cabi.LA_FLAG_KERNEL_128ROW if is_fp8 else 0)) | _flags) & ~_scoped_clear()) | list_flags
+    a = _fwd_args(q, k, v, out, softmax_lse, descales, B, Sq, Sk, softmax_scale, block_m, block_n,
+                  read_ptr, write_ptr, must_ptr, _must_do_is_1d, thr)
+    base_flags = _route_flags(_FIXED, host_flags, _flags, list_flags, is_fp8)
     a.flags = base_flags | (_cabi.LA_FLAG_STATIC_SCHED if _static_sched is True else 0)
-    need = _cabi.load().la_fwd_workspace_bytes(ctypes.byref(a))
-    if need < 0:
-        raise RuntimeError(f"lite_attention::fwd: {_cabi.status_string(int(need))}")
-    if need > 0:
-        workspace = torch.empty(int(need), dtype=torch.uint8, device=q.device)
-        a.workspace, a.workspace_bytes = workspace.data_ptr(), int(need)
+    workspace = _add_workspace(a, q.device, _FIXED)           # noqa: F841 - alive until the launches are enqueued
     windows = [(0, 0)] if _q_windows is None else [(int(b0), int(c0)) for b0, c0 in _q_windows]
     if _q_windows is not None and any(c0 <= 0 or b0 < 0 or b0 + c0 > q_tiles for b0, c0 in windows):
         raise RuntimeError(f"q-tile windows must lie inside [0, {q_tiles}) with positive counts; got {windows}")
@@ -367,18 +452,10 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
             a.flags = base_flags | (_cabi.LA_FLAG_V_PREPARED if (is_fp8 and i > 0) else 0) | \
                       (_cabi.LA_FLAG_STATIC_SCHED if (_static_sched is True or (_static_sched == "after_first" and i > 0))
                        else 0)                                                   # V^T tiles prepared by window 0
-            stream = torch.cuda.current_stream(q.device).cuda_stream                              # :1219
-            rc = lib.la_fwd(ctypes.byref(a), ctypes.c_void_p(stream))
-            if rc != _cabi.LA_OK:
-                msg = _cabi.status_string(rc)
-                if rc == _cabi.LA_ERR_UNSUPPORTED:
-                    raise NotImplementedError(msg)
-                if rc == _cabi.LA_ERR_LAUNCH:
-                    msg += f" (hipError {lib.la_last_hip_error()})"
-                raise RuntimeError(f"lite_attention::fwd: {msg}")
+            _launch(lib, a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _FIXED)   # :1219
             if _window_hook is not None:
                 _window_hook(i, out, w_begin * block_m, min(Sq, (w_begin + w_count) * block_m) if w_count else Sq)
-    return out, softmax_lse, empty, empty
+    return res
 
 
 def num_splits_heuristic(total_mblocks: int, slots: int, num_n_blocks: int, max_splits: int = 128, keys: Optional[int] = None) -> int:
@@ -416,18 +493,17 @@ def _num_splits(B, H, Sq, Sk, D, element_size, requested):
     return num_splits_heuristic(B * H * -(-Sq // block_m), cus * per, k_tiles, keys=Sk)
 
 
-def _split_kv_one_sequence(q, k, v, n, chunk, out, softmax_scale, descales=(None, None, None)):
+def _split_kv_one_sequence(q, k, v, n, chunk, out, softmax_scale, descales, flags):
     """batch == 1 (the diffusion-inference case): the splits ARE the batch of a fixed-length launch - q with batch stride 0 (every split
     reads the same query rows: no replication), K / V with batch stride = one chunk of rows, partial O (n, Sq, H, D) and partial LSE
     (n, H, Sq) written in exactly the layout la_combine reads; a ragged last chunk is a second launch of batch 1. Two or three library
     calls and three allocations in all (the packed-batch form above costs a dozen tensor ops, which is what a 0.3 ms kernel notices).
     e4m3: the descales (1, Hk) ride with batch stride 0 like q; partial and merged O are bf16; one workspace for the prepared V^T tiles."""
     _, Sq, H, D = q.shape
-    Sk, Hk = k.shape[1], k.shape[2]
+    Sk = k.shape[1]
     es = q.element_size()
-    flags = _cabi.default_flags()
     block_m, block_n = _cabi.get_tile_sizes(D, es, flags)
-    is_fp8 = q.dtype == torch.float8_e4m3fn
+    is_fp8 = q.dtype == _FP8
     o_dtype = torch.bfloat16 if is_fp8 else q.dtype
     if out is None:
         out = torch.empty((1, Sq, H, D), dtype=o_dtype, device=q.device)
@@ -436,34 +512,18 @@ def _split_kv_one_sequence(q, k, v, n, chunk, out, softmax_scale, descales=(None
     o_part = torch.empty((n, Sq, H, D), dtype=o_dtype, device=q.device)
     lse_part = torch.empty((n, H, Sq), dtype=torch.float32, device=q.device)
     lse = torch.empty((1, H, Sq), dtype=torch.float32, device=q.device)
-    a = _cabi.LaFwdArgs()
-    a.struct_size = ctypes.sizeof(_cabi.LaFwdArgs)
-    a.dtype = _cabi.LA_DTYPE_FP8_E4M3 if is_fp8 else (_cabi.LA_DTYPE_FP16 if q.dtype == torch.float16 else _cabi.LA_DTYPE_BF16)
-    o_cabi_dtype = _cabi.LA_DTYPE_BF16 if is_fp8 else a.dtype
-    for name, t in zip(("q", "k", "v"), descales):                # (1, Hk) fp32: every split reads the same row
-        if t is not None:
-            setattr(a, f"{name}_descale", t.data_ptr())
-            setattr(a, f"{name}_descale_batch_stride", 0)
-            setattr(a, f"{name}_descale_head_stride", t.stride(1))
-    a.q, a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.data_ptr(), 0, q.stride(1), q.stride(2)
-    a.k_row_stride, a.k_head_stride, a.k_batch_stride = k.stride(1), k.stride(2), chunk * k.stride(1)
-    a.v_row_stride, a.v_head_stride, a.v_batch_stride = v.stride(1), v.stride(2), chunk * v.stride(1)
-    a.o_batch_stride, a.o_row_stride, a.o_head_stride = Sq * H * D, H * D, D
-    a.seqlen_q, a.num_heads, a.num_heads_k, a.head_dim, a.head_dim_v = Sq, H, Hk, D, D
-    a.softmax_scale = float(softmax_scale)
-    a.block_m, a.block_n = block_m, block_n
-    keep = (_cabi.LA_FLAG_EXACT_RESCALE | _cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P) if is_fp8 else (_cabi.GEOMETRY_FLAGS | _cabi.LA_FLAG_EXACT_RESCALE)
-    a.flags = ((flags | _scoped_flags()) & keep & ~_scoped_clear()) | _cabi.LA_FLAG_STATIC_SCHED
     full = n if Sk == n * chunk else n - 1                      # equal chunks; then the ragged one
-    lib = _cabi.load()
-    workspace = None
+    a = _fwd_args(q, k, v, o_part, lse_part, descales, max(full, 1), Sq, chunk, softmax_scale, block_m, block_n)
+    # what makes it a split: q and the descales (1, Hk) are read by every split, a K / V batch is one chunk of rows; K / V / O / LSE
+    # pointers, batch and seqlen_k are set per launch - and cleared here, so that the workspace query below sees the block it has
+    # always seen, without them (tests/golden/host_calls.json pins the query's block as well as the launches')
+    a.q_batch_stride = a.q_descale_batch_stride = a.k_descale_batch_stride = a.v_descale_batch_stride = 0
+    a.k_batch_stride, a.v_batch_stride = chunk * k.stride(1), chunk * v.stride(1)
+    a.k = a.v = a.o = a.lse = None
+    a.flags = _route_flags(_SPLIT, flags, 0, 0, is_fp8)
     if is_fp8:                                                  # the prepared V^T tiles of the larger of the two launches
-        a.batch, a.seqlen_k = max(full, 1), chunk
-        need = lib.la_fwd_workspace_bytes(ctypes.byref(a))
-        if need < 0:
-            raise RuntimeError(f"lite_attention::fwd (split-KV): {_cabi.status_string(int(need))}")
-        workspace = torch.empty(int(need), dtype=torch.uint8, device=q.device)
-        a.workspace, a.workspace_bytes = workspace.data_ptr(), int(need)
+        workspace = _add_workspace(a, q.device, _SPLIT)         # noqa: F841 - alive until the launches are enqueued
+    lib = _cabi.load()
     with torch.cuda.device(q.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
         for first, count, keys in ((0, full, chunk), (full, n - full, Sk - full * chunk)):
@@ -472,20 +532,17 @@ def _split_kv_one_sequence(q, k, v, n, chunk, out, softmax_scale, descales=(None
             a.batch, a.seqlen_k = count, keys
             a.k, a.v = k.data_ptr() + first * chunk * k.stride(1) * es, v.data_ptr() + first * chunk * v.stride(1) * es
             a.o, a.lse = o_part.data_ptr() + first * Sq * H * D * 2, lse_part.data_ptr() + first * H * Sq * 4
-            rc = lib.la_fwd(ctypes.byref(a), stream)
-            if rc != _cabi.LA_OK:
-                raise RuntimeError(f"lite_attention::fwd (split-KV): {_cabi.status_string(rc)}")
-        rc = lib.la_combine(o_part.data_ptr(), 1, lse_part.data_ptr(), out.data_ptr(), o_cabi_dtype, lse.data_ptr(), n, 1, Sq, H, D, stream)
+            _launch(lib, a, stream, _SPLIT)
+        rc = lib.la_combine(o_part.data_ptr(), 1, lse_part.data_ptr(), out.data_ptr(), _dtype_code(o_dtype), lse.data_ptr(), n, 1, Sq, H, D, stream)
     if rc != _cabi.LA_OK:
         raise RuntimeError(f"la_combine (split-KV): {_cabi.status_string(rc)}")
-    empty = torch.empty(0, dtype=torch.float32, device=q.device)
-    return out, lse, empty, empty
+    return _outputs(out, lse)
 
 
 _SPLIT_CU = {}      # (B, n, Sq, Sk, chunk, device) -> (cu_seqlens_q, cu_seqlens_k): tiny device tensors, built once per shape
 
 
-def _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales):
+def _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales, flags):
     """Dense attention with the key range cut into ``n`` tile-aligned chunks: sequence (b, s) of a packed batch = the queries of batch b
     against chunk s of its keys - q is replicated per split (it is the small operand whenever splitting pays), K / V are the caller's
     tensors seen as packed rows (no copy) - one launch of the packed-batch kernel, then the LSE merge (la_combine). Returns None when K / V
@@ -495,13 +552,14 @@ def _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales):
     for t in (k, v):
         if B > 1 and t.stride(0) != Sk * t.stride(1):
             return None
-    _, block_n = get_tile_sizes(D, q.element_size())
+    D_kernel = kernel_head_dim(D, q.element_size(), flags)
+    _, block_n = _cabi.get_tile_sizes(D_kernel, q.element_size(), flags)
     chunk = -(-(-(-Sk // block_n)) // n) * block_n            # keys per split: whole tiles
     n = -(-Sk // chunk)                                         # (no empty trailing split)
     if n <= 1:
         return None
-    if B == 1 and kernel_head_dim(D, q.element_size()) == D and (q.dtype == torch.float8_e4m3fn or all(t is None for t in descales)):
-        return _split_kv_one_sequence(q, k, v, n, chunk, out, softmax_scale, descales)
+    if B == 1 and D_kernel == D and (q.dtype == _FP8 or all(t is None for t in descales)):
+        return _split_kv_one_sequence(q, k, v, n, chunk, out, softmax_scale, descales, flags)
     key = (B, n, Sq, Sk, chunk, str(q.device))
     cu = _SPLIT_CU.get(key)
     if cu is None:
@@ -514,19 +572,19 @@ def _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales):
     k_p = k.as_strided((B * Sk, Hk, D), (k.stride(1), k.stride(2), 1))
     v_p = v.as_strided((B * Sk, Hk, D), (v.stride(1), v.stride(2), 1))
     ds = [None if t is None else t.repeat_interleave(n, dim=0) for t in descales]
-    o_p, lse_p, *_ = _mha_fwd_varlen(q_rep, k_p, v_p, None, cu[0], cu[1], Sq, chunk, ds[0], ds[1], ds[2], softmax_scale, None, None)
+    o_p, lse_p, *_ = _mha_fwd_varlen(q_rep, k_p, v_p, None, cu[0], cu[1], Sq, chunk, ds, softmax_scale, None, None)
     o_part = o_p.view(B, n, Sq, H, D).transpose(0, 1)          # (n, B, Sq, H, D) view; mha_combine makes it contiguous (q-sized copies)
     lse_part = lse_p.view(H, B, n, Sq).permute(2, 1, 3, 0)     # logical (n, B, Sq, H), seqlen contiguous: the layout fwd_combine takes
     res, lse = mha_combine(o_part, lse_part, out=out)
-    empty = torch.empty(0, dtype=torch.float32, device=q.device)
-    return res, lse.transpose(1, 2).contiguous(), empty, empty
+    return _outputs(res, lse.transpose(1, 2).contiguous())
 
 
-def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, q_descale, k_descale, v_descale,
+def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales,
                     softmax_scale, attn_read_list, attn_write_list, attn_must_do_list=None, thr=-3.0, _must_do_is_1d=False):
     """Packed variable-length batches (flash_api.cpp:672-674, 736-760): q (total_q, H, D), k/v (total_k, Hk, D), cu_seqlens_*
     int32 [B+1] on the device, max_seqlen_* size the grid. ONE launch, no host sync (fp8: plus the V^T prepare pass, which reads
-    cu_seqlens_k itself). bf16 / fp16 / e4m3 at every head dim, e4m3 with descales (B, Hk). lse is (H, total_q).
+    cu_seqlens_k itself). bf16 / fp16 / e4m3 at every head dim, e4m3 with ``descales`` = (q, k, v), each (B, Hk) or None. lse is
+    (H, total_q). The dtypes have been checked by ``mha_fwd``.
     Skip lists (extension; the reference's varlen entry point has none, hopper/_internal/flash_attn_interface.py:638-682):
     ``[>= B, H, ceil(max_seqlen_q / kBlockM), ceil(max_seqlen_k / kBlockN) + 1]``, row (b, h, m) describing q-tile m of sequence b
     over THAT sequence's k-tiles - what the static block-sparse adapter needs to run a packed batch in one launch."""
@@ -534,11 +592,6 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
         raise RuntimeError("cu_seqlens_q and cu_seqlens_k must be given together")
     if (attn_read_list is None) != (attn_write_list is None):
         raise RuntimeError("attn_read_list and attn_write_list must be given together")
-    if q.dtype not in (torch.bfloat16, torch.float16, torch.float8_e4m3fn):
-        raise RuntimeError("FlashAttention only supports fp16, bf16, and fp8_e4m3 type")          # :715
-    is_fp8 = q.dtype == torch.float8_e4m3fn
-    if k.dtype != q.dtype or v.dtype != q.dtype:
-        raise RuntimeError("query and key must have the same dtype")
     if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
         raise RuntimeError("varlen: q, k, v must be 3D tensors (total_tokens, nheads, headdim)")
     for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
@@ -548,63 +601,30 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
         raise RuntimeError("cu_seqlens_q and cu_seqlens_k must both have batch + 1 entries")
     if max_seqlen_q is None or max_seqlen_k is None:
         raise RuntimeError("max_seqlen_q and max_seqlen_k must be provided if cu_seqlens are provided")           # :744-746
-    if q.stride(-1) != 1 or k.stride(-1) != 1 or v.stride(-1) != 1:
-        raise RuntimeError("Input tensor must have contiguous last dimension")
     Tq, H, D = q.shape
-    Tk, Hk, Dk = k.shape
-    if Dk != D or tuple(v.shape) != (Tk, Hk, D):
-        raise RuntimeError("k/v shape mismatch: expected k, v (total_k, nheads_k, headdim)")
-    if H % Hk != 0:
-        raise RuntimeError("Number of heads in key/value must divide number of heads in query")
-    if D % (16 if is_fp8 else 8) != 0:
-        raise RuntimeError("head_size should be a multiple of " + ("16" if is_fp8 else "8"))
+    B = cu_seqlens_q.numel() - 1
+    _check_inputs(q, k, v, descales, B, "k/v shape mismatch: expected k, v (total_k, nheads_k, headdim)", True)
     if softmax_scale is None:
         softmax_scale = D ** -0.5
-    B = cu_seqlens_q.numel() - 1
-    descales = []
-    for name, t in (("q_descale", q_descale), ("k_descale", k_descale), ("v_descale", v_descale)):
-        if t is not None:
-            if not is_fp8:
-                raise RuntimeError(f"{name} is only supported for fp8 inputs")
-            if t.dtype != torch.float32 or tuple(t.shape) != (B, Hk) or t.device != q.device:      # :1003-1022
-                raise RuntimeError(f"{name} must be a float32 tensor of shape (batch_size, nheads_k) on the input device")
-        descales.append(t)
+    is_fp8 = q.dtype == _FP8
     out_dtype = torch.bfloat16 if is_fp8 else q.dtype                                              # :859-863
     D_kernel = kernel_head_dim(D, q.element_size())
+    _check_out(out, (Tq, H, D), out_dtype, _OUT_MSG_PACKED)
     if D_kernel != D:
-        if out is not None and (out.dtype != out_dtype or tuple(out.shape) != (Tq, H, D) or out.stride(-1) != 1):
-            raise RuntimeError("out must have the input dtype (bf16 for fp8 inputs), shape (total_q, nheads, headdim) and a contiguous last dimension")
-
-        def pad(t):                                              # fp8: pad the bytes (0x00 is +0.0 in e4m3), as mha_fwd does
-            if is_fp8:
-                return torch.nn.functional.pad(t.view(torch.uint8), (0, D_kernel - D)).view(t.dtype)
-            return torch.nn.functional.pad(t, (0, D_kernel - D))
-        res = _mha_fwd_varlen(pad(q), pad(k), pad(v), None, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales[0],
-                              descales[1], descales[2], softmax_scale, attn_read_list, attn_write_list, attn_must_do_list, thr, _must_do_is_1d)
-        if out is None:
-            out = torch.empty((Tq, H, D), dtype=out_dtype, device=q.device)        # contiguous (total_q, H, D), as the reference's
-        out.copy_(res[0][..., :D])
-        return (out, *res[1:])
+        res = _mha_fwd_varlen(_pad_head_dim(q, D_kernel), _pad_head_dim(k, D_kernel), _pad_head_dim(v, D_kernel), None, cu_seqlens_q,
+                              cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales, softmax_scale, attn_read_list, attn_write_list,
+                              attn_must_do_list, thr, _must_do_is_1d)
+        return _unpadded(res, out, (Tq, H, D), out_dtype, q.device)
     if out is None:
         out = torch.empty((Tq, H, D), dtype=out_dtype, device=q.device)
-    elif out.dtype != out_dtype or tuple(out.shape) != (Tq, H, D) or out.stride(-1) != 1:
-        raise RuntimeError("out must have the input dtype (bf16 for fp8 inputs), shape (total_q, nheads, headdim) and a contiguous last dimension")
     softmax_lse = torch.empty((H, Tq), dtype=torch.float32, device=q.device)
-    empty = torch.empty(0, dtype=torch.float32, device=q.device)
+    res = _outputs(out, softmax_lse)
     if Tq == 0 or max_seqlen_q <= 0:
-        return out, softmax_lse, empty, empty
+        return res
     flags = _cabi.default_flags()
     block_m, block_n = _cabi.get_tile_sizes(D, q.element_size(), flags)
-    a = _cabi.LaFwdArgs()
-    a.struct_size = ctypes.sizeof(_cabi.LaFwdArgs)
-    a.dtype = _cabi.LA_DTYPE_FP8_E4M3 if is_fp8 else (_cabi.LA_DTYPE_FP16 if q.dtype == torch.float16 else _cabi.LA_DTYPE_BF16)
-    for name, t in zip(("q", "k", "v"), descales):
-        if t is not None:
-            setattr(a, f"{name}_descale", t.data_ptr())
-            setattr(a, f"{name}_descale_batch_stride", t.stride(0))
-            setattr(a, f"{name}_descale_head_stride", t.stride(1))
-    workspace = None
     list_flags = _list_flags(attn_read_list, attn_write_list)
+    lists = ()
     if attn_read_list is not None:
         q_tiles, k_tiles = -(-int(max_seqlen_q) // block_m), -(-max(int(max_seqlen_k), 0) // block_n)
         for name, t in (("attn_read_list", attn_read_list), ("attn_write_list", attn_write_list),
@@ -619,39 +639,16 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
         if _must_do_is_1d and attn_must_do_list is not None and (
                 attn_must_do_list.dtype != torch.int32 or attn_must_do_list.dim() != 1 or attn_must_do_list.numel() < 3):
             raise RuntimeError("1-D attn_must_do_list must be a contiguous int32 vector [len, start, end, ...]")
-        a.read_list, a.write_list = attn_read_list.data_ptr(), attn_write_list.data_ptr()
-        a.must_do_list = None if attn_must_do_list is None else attn_must_do_list.data_ptr()
-        a.must_do_is_1d = 1 if _must_do_is_1d else 0
-        a.thr = float(thr)
-    a.q, a.k, a.v, a.o, a.lse = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), softmax_lse.data_ptr()
-    a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1)
-    a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1)
-    a.v_row_stride, a.v_head_stride = v.stride(0), v.stride(1)
-    a.o_row_stride, a.o_head_stride = out.stride(0), out.stride(1)
-    a.batch, a.seqlen_q, a.seqlen_k = B, int(max_seqlen_q), max(int(max_seqlen_k), 0)
-    a.num_heads, a.num_heads_k, a.head_dim, a.head_dim_v = H, Hk, D, D
-    a.softmax_scale = float(softmax_scale)
-    a.block_m, a.block_n = block_m, block_n
-    flags = (flags | _scoped_flags()) & ~_scoped_clear()
-    a.flags = flags & ((_cabi.LA_FLAG_FP8_MFMA_ROWSUM | _cabi.LA_FLAG_FP8_ENCODED_P | _cabi.LA_FLAG_STATIC_SCHED) if is_fp8 else
-                       (_cabi.GEOMETRY_FLAGS | _cabi.LA_FLAG_EXACT_RESCALE | _cabi.LA_FLAG_STATIC_SCHED))
-    a.flags |= list_flags
+        lists = (attn_read_list.data_ptr(), attn_write_list.data_ptr(),
+                 None if attn_must_do_list is None else attn_must_do_list.data_ptr(), _must_do_is_1d, thr)
+    a = _fwd_args(q, k, v, out, softmax_lse, descales, B, int(max_seqlen_q), max(int(max_seqlen_k), 0), softmax_scale, block_m, block_n, *lists)
     a.cu_seqlens_q, a.cu_seqlens_k, a.total_q = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr(), Tq
+    a.flags = _route_flags(_PACKED, flags, 0, list_flags, is_fp8)
     if attn_read_list is not None or is_fp8:      # ticket counters of the dynamic work distribution (as in the fixed-length path); fp8: + the V^T tiles
-        need = _cabi.load().la_fwd_workspace_bytes(ctypes.byref(a))
-        if need < 0:
-            raise RuntimeError(f"lite_attention::fwd (varlen): {_cabi.status_string(int(need))}")
-        if need > 0:
-            workspace = torch.empty(int(need), dtype=torch.uint8, device=q.device)
-            a.workspace, a.workspace_bytes = workspace.data_ptr(), int(need)
+        workspace = _add_workspace(a, q.device, _PACKED)      # noqa: F841 - alive until the launch is enqueued
     with torch.cuda.device(q.device):
-        rc = _cabi.load().la_fwd(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
-    if rc != _cabi.LA_OK:
-        msg = _cabi.status_string(rc)
-        if rc == _cabi.LA_ERR_UNSUPPORTED:
-            raise NotImplementedError(msg)
-        raise RuntimeError(f"lite_attention::fwd (varlen): {msg}")
-    return out, softmax_lse, empty, empty
+        _launch(_cabi.load(), a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _PACKED)
+    return res
 
 
 # ---- op registration: torch.ops.lite_attention.fwd (flash_api.cpp:1722-1763, 1819-1824) ----------
@@ -678,12 +675,18 @@ def _register_op():
             lse = torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=q.device)
         else:
             lse = torch.empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32, device=q.device)
-        empty = torch.empty(0, dtype=torch.float32, device=q.device)
-        return out, lse, empty, torch.empty(0, dtype=torch.float32, device=q.device)
+        return _outputs(out, lse)
 
     lib.impl("fwd", _fwd_impl, "CUDA")
     lib.impl("fwd", _fwd_meta, "Meta")
     _op_lib = lib
+
+
+def _register_combine_op():
+    """``lite_attention::fwd_combine`` beside ``fwd`` (flash_api.cpp:1787-1791, 1822); called below ``mha_combine``."""
+    _op_lib.define(_COMBINE_SCHEMA)
+    _op_lib.impl("fwd_combine", mha_combine, "CUDA")
+    _op_lib.impl("fwd_combine", _combine_meta, "Meta")
 
 
 _register_op()
@@ -804,8 +807,7 @@ def mha_combine(out_partial: torch.Tensor, lse_partial: torch.Tensor, out: Optio
     with torch.cuda.device(out_partial.device):
         stream = torch.cuda.current_stream(out_partial.device).cuda_stream
         rc = _cabi.load().la_combine(op.data_ptr(), int(op.dtype != torch.float32), lp.data_ptr(), res.data_ptr(),
-                                     {torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}.get(out_dtype, _cabi.LA_DTYPE_BF16),
-                                     lse.data_ptr(), ns, B, S, H, Dp, ctypes.c_void_p(stream))
+                                     _dtype_code(out_dtype), lse.data_ptr(), ns, B, S, H, Dp, ctypes.c_void_p(stream))
     if rc != _cabi.LA_OK:
         raise RuntimeError(f"la_combine: {_cabi.status_string(rc)}")
     if not direct:
@@ -824,14 +826,6 @@ def _combine_meta(out_partial, lse_partial, out=None, out_dtype=None):
     return out, torch.empty((B, H, S), dtype=torch.float32, device=out_partial.device).transpose(1, 2)
 
 
-def _register_combine_op():
-    """``lite_attention::fwd_combine`` beside ``fwd`` (flash_api.cpp:1787-1791, 1822)."""
-    _op_lib.define(_COMBINE_SCHEMA)
-    _op_lib.impl("fwd_combine", mha_combine, "CUDA")
-    _op_lib.impl("fwd_combine", _combine_meta, "Meta")
-
-
-_COMBINE_SCHEMA = "fwd_combine(Tensor out_partial, Tensor lse_partial, Tensor(out!)? out = None, ScalarType? out_dtype = None) -> (Tensor(out!), Tensor)"
 _register_combine_op()
 
 
@@ -861,6 +855,8 @@ def combine_partials(outs, lses, out: Optional[torch.Tensor] = None, out_dtype: 
             raise RuntimeError("every lse must be fp32 (batch, nheads, seqlen) on the device of the partials")
     if out_dtype is None:
         out_dtype = out.dtype if out is not None else o0.dtype
+    if out_dtype not in (torch.bfloat16, torch.float16, torch.float32):
+        raise RuntimeError("Output type must be FP32, FP16 or BF16")
     if o0.dtype != torch.float32 and o0.dtype != out_dtype:
         raise RuntimeError("16-bit partial results must have the output dtype")
     if out is None:
@@ -874,8 +870,7 @@ def combine_partials(outs, lses, out: Optional[torch.Tensor] = None, out_dtype: 
     with torch.cuda.device(o0.device):
         stream = torch.cuda.current_stream(o0.device).cuda_stream
         rc = _cabi.load().la_combine_list(o_ptrs, int(o0.dtype != torch.float32), l_ptrs, out.data_ptr(),
-                                          {torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}.get(out_dtype, _cabi.LA_DTYPE_BF16),
-                                          None if lse is None else lse.data_ptr(), n, B, S, H, Dv, ctypes.c_void_p(stream))
+                                          _dtype_code(out_dtype), None if lse is None else lse.data_ptr(), n, B, S, H, Dv, ctypes.c_void_p(stream))
     if rc != _cabi.LA_OK:
         raise RuntimeError(f"la_combine_list: {_cabi.status_string(rc)}")
     return (out, lse) if return_lse else out
