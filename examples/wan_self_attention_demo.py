@@ -6,7 +6,10 @@ q/k/v cast to bf16, ONE `self.lite_attention(q, k, v)` call, result back to fp32
 checkpoints here); what it demonstrates is the drop-in at the module boundary: shapes, dtypes, one LiteAttention instance
 per layer, the skip state carried across denoising steps.
 
-    python examples/wan_self_attention_demo.py [--frames 5 --height 16 --width 16 --heads 4 --steps 6 --threshold -6]
+    python examples/wan_self_attention_demo.py [--frames 5 --height 16 --width 16 --heads 4 --steps 6 --threshold -6] [--fused-prep]
+
+`--fused-prep` (`fused_prep=True` on the modules): RMSNorm, RoPE and the bf16 cast of q and k run as ONE pass each (`qk_prep`) instead of
+the eager lines below.
 
 Prints, per denoising step, the fraction of tiles skipped and the error against the same block with skipping disabled.
 """
@@ -19,6 +22,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lite_attention import LiteAttention  # noqa: E402  (same import line as the reference recipe)
+from lite_attention import qk_prep, rope_tables  # noqa: E402  (the fused q / k prologue: fused_prep=True)
 
 
 class RMSNorm(nn.Module):
@@ -54,10 +58,10 @@ def rope_3d(x, grid, theta=10000.0):
 
 
 class WanLikeSelfAttention(nn.Module):
-    def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1):
+    def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1, fused_prep=False):
         super().__init__()
         assert dim % num_heads == 0
-        self.num_heads, self.head_dim = num_heads, dim // num_heads
+        self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
         # the recipe: ONE LiteAttention per attention layer (its skip lists are that layer's state)
@@ -65,6 +69,11 @@ class WanLikeSelfAttention(nn.Module):
 
     def forward(self, x, grid):
         b, s, n, d = *x.shape[:2], self.num_heads, self.head_dim
+        if self.fused_prep:                                         # norm + rope + cast of q and of k: one pass each
+            tables = rope_tables(grid, d, device=x.device)
+            q = qk_prep(self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables, out_dtype=torch.bfloat16)
+            k = qk_prep(self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables, out_dtype=torch.bfloat16)
+            return self.o(self.lite_attention(q, k, self.v(x).view(b, s, n, d).bfloat16()).float().flatten(2))
         q = self.norm_q(self.q(x)).view(b, s, n, d)
         k = self.norm_k(self.k(x)).view(b, s, n, d)
         v = self.v(x).view(b, s, n, d)
@@ -79,18 +88,23 @@ class WanLikeCrossAttention(nn.Module):
     because the prompts of a batch have different lengths. With `compat_shims/` on the path those imports resolve to the gfx950
     kernel: one dense launch for the whole ragged batch, no host sync."""
 
-    def __init__(self, dim, num_heads):
+    def __init__(self, dim, num_heads, fused_prep=False):
         super().__init__()
-        self.num_heads, self.head_dim = num_heads, dim // num_heads
+        self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
 
     def forward(self, x, context, context_lens):
         import flash_attn_interface                                 # FA3 name, served by compat_shims/flash_attn_interface.py
         b, s, n, d = *x.shape[:2], self.num_heads, self.head_dim
-        q = self.norm_q(self.q(x)).view(b * s, n, d).bfloat16()
         lens = [int(l) for l in context_lens]
-        k = torch.cat([self.norm_k(self.k(context[i, :l])) for i, l in enumerate(lens)]).view(-1, n, d).bfloat16()
+        if self.fused_prep:                                         # no rope on the text side: norm + cast, one pass each
+            q = qk_prep(self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, out_dtype=torch.bfloat16).view(b * s, n, d)
+            k_all = torch.cat([self.k(context[i, :l]) for i, l in enumerate(lens)]).view(1, -1, n, d)
+            k = qk_prep(k_all, self.norm_k.weight, self.norm_k.eps, out_dtype=torch.bfloat16).view(-1, n, d)
+        else:
+            q = self.norm_q(self.q(x)).view(b * s, n, d).bfloat16()
+            k = torch.cat([self.norm_k(self.k(context[i, :l])) for i, l in enumerate(lens)]).view(-1, n, d).bfloat16()
         v = torch.cat([self.v(context[i, :l]) for i, l in enumerate(lens)]).view(-1, n, d).bfloat16()
         cu_q = torch.arange(0, (b + 1) * s, s, dtype=torch.int32, device=x.device)
         cu_k = torch.tensor([0] + lens, device=x.device).cumsum(0).to(torch.int32)
@@ -109,15 +123,15 @@ class WanLikeCrossAttention(nn.Module):
         return self.o(torch.stack(outs))
 
 
-def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True):
+def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False):
     torch.manual_seed(seed)
     dim, grid = heads * 128, (frames, height, width)
     S = frames * height * width
-    sparse = WanLikeSelfAttention(dim, heads, threshold=threshold).to(device)
+    sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
     # under which tokens of the same frame attend to each other
     sparse.k.load_state_dict(sparse.q.state_dict())
-    dense = WanLikeSelfAttention(dim, heads, enable_skipping=False).to(device)
+    dense = WanLikeSelfAttention(dim, heads, enable_skipping=False, fused_prep=fused_prep).to(device)
     dense.load_state_dict(sparse.state_dict())
     # a latent with frame-to-frame structure, denoised over `steps` steps (noise level 0.5 -> 0.05)
     base = torch.randn(1, frames, 1, dim, device=device).expand(1, frames, height * width, dim).reshape(1, S, dim) * 2.0
@@ -141,5 +155,6 @@ if __name__ == "__main__":
     for name, default in (("frames", 5), ("height", 16), ("width", 16), ("heads", 4), ("steps", 6)):
         ap.add_argument(f"--{name}", type=int, default=default)
     ap.add_argument("--threshold", type=float, default=-6.0)
+    ap.add_argument("--fused-prep", action="store_true", help="norm + rope + cast of q and k in one pass each (qk_prep)")
     a = ap.parse_args()
-    run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold)
+    run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep)

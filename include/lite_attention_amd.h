@@ -22,6 +22,8 @@
  *                            hopper/tests/test_flash_attn.py:1178-1187)
  *   la_output_error       <- nothing: the reference names "error calibration" (README.md:14) and measures no error anywhere;
  *                            one-pass fp64 error statistics of an output against a reference output, per (batch, head, row bin)
+ *   la_qk_prep            <- nothing: the reference starts at the attention call; what a Wan2.x block runs on q and k just before it
+ *                            (RMSNorm, 3-axis RoPE, the cast to bf16: README.md:268-323 leaves them to eager torch) in one pass
  *
  * Rules of the boundary:
  *   - plain C: pointers, sizes, scalars. No torch types, no C++ types, no exceptions.
@@ -41,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error was ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error and la_qk_prep were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -307,6 +309,56 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
                     const void* ref, int32_t ref_dtype, int64_t ref_batch_stride, int64_t ref_row_stride, int64_t ref_head_stride,
                     int32_t batch, int32_t seqlen, int32_t num_heads, int32_t head_dim, int32_t rows_per_bin,
                     double* stats, void* stream);
+
+/* The q / k prologue of a Wan2.x-style attention block in one pass: RMSNorm, 3-axis RoPE on INTERLEAVED pairs, the cast to bf16 / fp16.
+ * Per token (b, s) of x (B, S, H, D), in fp32 with ONE rounding at the store:
+ *   r       = rsqrt(mean(x^2 over the norm group) + eps)     LA_NORM_TOKEN: the H*D elements of the token (Wan's RMSNorm(dim));
+ *                                                            LA_NORM_HEAD: the D elements of one head; LA_NORM_NONE: r = 1, weight ignored
+ *   y[h][c] = x[h][c] * r * w[c']                            w fp32 [H*D] (TOKEN) or [D] (HEAD); weight == NULL reads as ones
+ *   p = pos_offset + s;  (c0, c1, c2) = (p / (e1*e2), (p / e2) % e1, p % e2)     for axis_extent = (e0, e1, e2)
+ *   pair j of a head = elements (2j, 2j+1); axis a owns pairs [P_a, P_a + n_a), P_a = n_0 + ... + n_(a-1), n = axis_pairs
+ *   (cos, sin) = rope_table[a][c_a][j - P_a]                 fp32 [e_a, n_a, 2] contiguous, built on the host: no transcendental on the device
+ *   out(2j) = y(2j) cos - y(2j+1) sin;  out(2j+1) = y(2j) sin + y(2j+1) cos;  pairs j >= n_0 + n_1 + n_2 pass through (partial rotary)
+ *   all three tables NULL: no rotation (norm and cast only, e.g. the q / k of a cross-attention)
+ * Arithmetic: the sum of squares is fp32, like the torch expression it replaces - a token whose squares overflow fp32 gives what torch
+ * gives (r = 0). Against Wan's `.type_as(x) * weight` followed by a rope that rounds again this has one fewer intermediate rounding.
+ * The order of the reduction depends on the shape alone: two launches give bit-identical output. Asynchronous on `stream`; no workspace,
+ * no atomics. x is read once and out written once, 16 bytes at a time.
+ * In-place (out == x) is allowed when the two dtypes have equal size and all strides are equal: a token's elements are all read before
+ * any of them is stored (LA_NORM_HEAD / LA_NORM_NONE: a head's elements). ANY OTHER overlap of x and out is the caller's error and is
+ * not detected.
+ * Errors (all before any HIP call): NULL args / x / out LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; in_dtype other than bf16 / fp16 /
+ * fp32 or out_dtype other than bf16 / fp16 LA_ERR_DTYPE; an unknown norm_mode LA_ERR_UNSUPPORTED; a non-positive size LA_ERR_SHAPE;
+ * head_dim % 8 != 0 or head_dim > 256 LA_ERR_HEAD_DIM; LA_NORM_TOKEN with H*D > 16384 LA_ERR_UNSUPPORTED (the token stays in
+ * registers between the reduction and the store: those of one wave up to H*D = 5120, of the four waves of a workgroup up to 16384 = 256
+ * lanes x 64 elements); a negative stride, a pointer or a used stride (batch / row / head, one whose dimension is larger than 1) that takes
+ * a row start off a 16-byte boundary for its dtype, a head stride of 2^31 / H elements or more, a weight off 16 bytes or a table off 8
+ * bytes LA_ERR_STRIDE; a negative axis_pairs entry or their sum above head_dim / 2 LA_ERR_SHAPE; a NULL table with axis_pairs > 0
+ * unless all three are NULL LA_ERR_NULL_ARG; pos_offset < 0, or, when rotating, a non-positive extent or pos_offset + seqlen > e0*e1*e2
+ * LA_ERR_SHAPE. */
+typedef enum la_norm_mode {
+    LA_NORM_NONE = 0,
+    LA_NORM_TOKEN = 1,
+    LA_NORM_HEAD = 2
+} la_norm_mode;
+typedef struct la_qk_prep_args {
+    uint32_t struct_size;        /* = sizeof(la_qk_prep_args)                                     */
+    int32_t  in_dtype;           /* la_dtype of x: LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32  */
+    int32_t  out_dtype;          /* la_dtype of out: LA_DTYPE_BF16 or LA_DTYPE_FP16               */
+    int32_t  norm_mode;          /* la_norm_mode                                                  */
+    const void* x;               /* (B, S, H, D), last dimension contiguous                       */
+    void*       out;             /* (B, S, H, D), last dimension contiguous                       */
+    int64_t x_batch_stride, x_row_stride, x_head_stride;          /* in elements                  */
+    int64_t out_batch_stride, out_row_stride, out_head_stride;
+    int32_t batch, seqlen, num_heads, head_dim;
+    const float* weight;         /* fp32 [H*D] (LA_NORM_TOKEN) or [D] (LA_NORM_HEAD); NULL = ones  */
+    float   eps;
+    int32_t pos_offset;          /* position of row 0 on the (e0, e1, e2) grid, row-major         */
+    const float* rope_table[3];  /* fp32 [axis_extent[a], axis_pairs[a], 2] = (cos, sin)           */
+    int32_t axis_extent[3];
+    int32_t axis_pairs[3];
+} la_qk_prep_args;
+int la_qk_prep(const la_qk_prep_args* args, void* stream);
 
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)

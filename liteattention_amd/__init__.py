@@ -22,6 +22,7 @@ if not _BUILDING:
     from .compat import (blockmask_to_skip_lists, fa2_flash_attn_func, flash_attn_varlen_func,  # noqa: E402
                          flash_blocksparse_attn_func, flash_blocksparse_attn_qkvpacked_func)
     from .calibration import ErrorStats, calibrate_error_schedule, calibrate_threshold, output_error  # noqa: E402
+    from .qk_prep import RopeTables, qk_prep, qk_prep_reference, rope_tables, wan_rope_parts  # noqa: E402
     from .parallel import (HeadShardedLiteAttention, RingSeqParallelLiteAttention,  # noqa: E402
                            UlyssesLiteAttention)
 
@@ -29,4 +30,5 @@ __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flas
            "get_tile_sizes", "skip_list_stats", "fa2_flash_attn_func", "flash_attn_varlen_func",
            "flash_blocksparse_attn_func", "flash_blocksparse_attn_qkvpacked_func", "blockmask_to_skip_lists", "calibrate_threshold",
            "calibrate_error_schedule", "output_error", "ErrorStats",
+           "qk_prep", "qk_prep_reference", "rope_tables", "wan_rope_parts", "RopeTables",
            "HeadShardedLiteAttention", "UlyssesLiteAttention", "RingSeqParallelLiteAttention", "__version__"]

@@ -481,4 +481,62 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
     return LA_OK;
 }
 
+int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || !a->out) return LA_ERR_NULL_ARG;
+    const bool in_ok = a->in_dtype == LA_DTYPE_BF16 || a->in_dtype == LA_DTYPE_FP16 || a->in_dtype == LA_DTYPE_FP32;
+    if (!in_ok || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
+    if (a->norm_mode != LA_NORM_NONE && a->norm_mode != LA_NORM_TOKEN && a->norm_mode != LA_NORM_HEAD) return LA_ERR_UNSUPPORTED;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
+    // LA_NORM_TOKEN: the token stays in registers from the load to the store - of one wave up to 5120 elements, of the four waves of a
+    // workgroup up to 8 chunks of 8 elements per lane
+    if (a->norm_mode == LA_NORM_TOKEN && static_cast<int64_t>(a->num_heads) * a->head_dim > 16384) return LA_ERR_UNSUPPORTED;
+    // every row start is a 16-byte boundary: the pointer, and every stride that is used, in units of 16 / element size; the kernels
+    // keep a chunk's offset from its token's start in 32 bits
+    const auto strides_ok = [&](const void* p, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
+        const int64_t unit = d == LA_DTYPE_FP32 ? 4 : 8;
+        return bs >= 0 && rs >= 0 && hs >= 0 && aligned16(p) && (a->seqlen == 1 || rs % unit == 0) && (a->num_heads == 1 || hs % unit == 0) &&
+               (a->batch == 1 || bs % unit == 0) && hs <= (0x7fffffffLL - a->head_dim) / a->num_heads;
+    };
+    if (!strides_ok(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride) ||
+        !strides_ok(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride)) return LA_ERR_STRIDE;
+    if (a->weight && !aligned16(a->weight)) return LA_ERR_STRIDE;                 // read 16 bytes at a time
+    for (int i = 0; i < 3; ++i)
+        if (reinterpret_cast<uintptr_t>(a->rope_table[i]) & 7u) return LA_ERR_STRIDE;      // (cos, sin) is one 8-byte load
+    int64_t pairs = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (a->axis_pairs[i] < 0) return LA_ERR_SHAPE;
+        pairs += a->axis_pairs[i];
+    }
+    if (pairs > a->head_dim / 2) return LA_ERR_SHAPE;
+    const bool rotate = a->rope_table[0] || a->rope_table[1] || a->rope_table[2];      // all three NULL: norm and cast only
+    if (a->pos_offset < 0) return LA_ERR_SHAPE;
+    if (rotate) {
+        for (int i = 0; i < 3; ++i)
+            if (!a->rope_table[i] && a->axis_pairs[i] > 0) return LA_ERR_NULL_ARG;
+        int64_t positions = 1;
+        for (int i = 0; i < 3; ++i) {
+            if (a->axis_extent[i] <= 0) return LA_ERR_SHAPE;
+            positions *= a->axis_extent[i];                       // three factors below 2^31: the product of the first two fits, the third is checked
+            if (i == 1 && positions > 0x7fffffffLL) return LA_ERR_SHAPE;
+        }
+        if (positions > 0x7fffffffLL || static_cast<int64_t>(a->pos_offset) + a->seqlen > positions) return LA_ERR_SHAPE;
+    }
+    la::QkPrepParams p = {};
+    p.x = a->x; p.out = a->out; p.weight = a->norm_mode == LA_NORM_NONE ? nullptr : a->weight;
+    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
+    p.o_bs = a->out_batch_stride; p.o_rs = a->out_row_stride; p.o_hs = a->out_head_stride;
+    p.tokens = static_cast<int64_t>(a->batch) * a->seqlen;
+    p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    p.norm_mode = a->norm_mode; p.rotate = rotate && pairs > 0 ? 1 : 0;
+    p.ext1 = rotate ? a->axis_extent[1] : 1; p.ext2 = rotate ? a->axis_extent[2] : 1;
+    for (int i = 0; i < 3; ++i) { p.table[i] = a->rope_table[i]; p.pairs[i] = rotate ? a->axis_pairs[i] : 0; }
+    p.pos_offset = a->pos_offset; p.eps = a->eps;
+    const hipError_t err = la::launch_qk_prep(p, a->in_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
 }  // extern "C"

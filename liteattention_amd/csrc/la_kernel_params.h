@@ -114,4 +114,22 @@ hipError_t launch_output_error(const void* out, int out_dtype, int64_t o_bs, int
                                int64_t r_bs, int64_t r_rs, int64_t r_hs, int batch, int seqlen, int num_heads, int head_dim, int rows_per_bin,
                                double* stats, hipStream_t stream);   // la_output_error: fp64 [batch, heads, bins, 6], every element written
 
+// la_qk_prep (la_prep_qk.hip): what the kernels read, checked and filled by la_api.hip. Strides in elements.
+struct QkPrepParams {
+    const void* x;
+    void* out;
+    const float* weight;         // NULL = ones
+    const float* table[3];       // fp32 [extent_a, pairs_a, 2] (cos, sin); only read when rotate != 0 and pairs_a > 0
+    int64_t x_bs, x_rs, x_hs, o_bs, o_rs, o_hs;
+    int64_t tokens;              // batch * seqlen
+    int seqlen, num_heads, head_dim;
+    int norm_mode;               // 0 none, 1 token, 2 head (la_norm_mode)
+    int rotate;                  // 0: no table is read
+    int ext1, ext2;              // extents of axes 1 and 2: position p -> (p / (ext1 * ext2), (p / ext2) % ext1, p % ext2)
+    int pairs[3];
+    int pos_offset;
+    float eps;
+};
+hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream);   // dtypes: 0 bf16, 1 fp16, 3 fp32 (in only)
+
 }  // namespace la

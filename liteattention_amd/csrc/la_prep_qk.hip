@@ -1,0 +1,353 @@
+// la_prep_qk.hip — the q / k prologue of a Wan2.x-style attention block in ONE pass (la_qk_prep): RMSNorm over the token (or over each
+// head, or none), 3-axis RoPE on interleaved pairs from host-built (cos, sin) tables, the cast to bf16 / fp16. x is read once and out is
+// written once; between the two everything is fp32 and the only rounding is the one at the store.
+//
+// Mapping: one WAVE per token (b, s), four tokens per 256-thread workgroup (tokens above 5120 elements under LA_NORM_TOKEN: one
+// workgroup per token), grid-stride over tokens with at most kMaxGrid workgroups.
+// The token is cut into chunks of 8 consecutive elements (one 16-byte load of 16-bit elements, two of fp32; one 16-byte store); a chunk
+// never straddles a head (head_dim % 8 == 0). What a lane needs that does not depend on the token - the column and the offsets of its
+// chunks, the axis and table column of the rotation pairs it stages - is resolved before the token loop; its slice of the weight is the
+// same for every token and is reread from L1 / L2 (keeping it in registers too costs the occupancy the stream needs).
+//
+//  * la_qk_prep_token_kernel<IN, OUT, NCH, WG> (LA_NORM_TOKEN): lane l owns chunks l, l + 64, ... (NCH <= 10 of them, NCH * 512 >=
+//    H * D), keeps all of them in registers from the load to the store, sums its squares chunk by chunk (a fixed pairwise tree inside
+//    a chunk), and the wave finishes the sum with a 6-step xor butterfly: the order of every addition depends on the shape alone,
+//    every lane holds the same bits, two launches agree bitwise. No atomics, no workspace. Above H * D = 5120 (WG) the four waves of
+//    the workgroup share ONE token (chunks tid, tid + 256, ..., at most 8 per lane: H * D <= 16384, the limit la_qk_prep states) and
+//    their four sums are added in a fixed order through LDS: 32 chunks per lane of one wave do not fit the register file.
+//  * la_qk_prep_head_kernel<IN, OUT> (LA_NORM_HEAD, LA_NORM_NONE): a head's D / 8 chunks sit on G = 2^ceil(log2(D / 8)) <= 32
+//    neighbouring lanes (lanes past D / 8 idle), 64 / G heads per pass, kHeadUnroll passes loaded together; the sum of a head is the
+//    xor butterfly over its G lanes.
+//
+// The rotation of a token is one row of at most head_dim / 2 (cos, sin) pairs - row c_a of table a for the pairs axis a owns, (1, 0)
+// behind them - the same for every head. The wave gathers it into its own 1 KiB of LDS once per token (two pairs per lane, 8-byte
+// loads that hit L2: the three tables together are (e0 + e1 + e2) * D / 2 * 8 bytes) and every chunk reads its four pairs from there
+// with two 16-byte LDS loads: the axis of a pair is looked up per PAIR while staging, never per chunk (at head_dim 128 the axis
+// boundaries fall at elements 44 and 86, inside a chunk). Only the wave that wrote a row reads it: LDS instructions of one wave execute
+// in order, a wavefront-scope fence keeps the compiler from reordering them, no workgroup barrier is needed and waves of a workgroup
+// may run different numbers of tokens.
+//
+// In-place (out == x with equal strides and element sizes): a chunk is stored by the lane that loaded it, after every load of its
+// token (token kernel) or of its batch of passes (head kernel); x and out carry no __restrict__.
+//
+// Arithmetic: r = rsqrt(sum(x^2) / n + eps) with the sum in fp32 as in the torch expression it replaces (a token whose squares
+// overflow fp32 gives r = 0 there and here); y = (x * r) * w; out = (y0 cos - y1 sin, y0 sin + y1 cos). One fewer rounding than Wan's
+// `.type_as(x) * weight` followed by a rope that rounds again: DESIGN.md §7.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "la_kernel_params.h"
+
+namespace la {
+namespace {
+
+typedef unsigned int pq_u32x4 __attribute__((ext_vector_type(4)));
+typedef float pq_f32x4 __attribute__((ext_vector_type(4)));
+typedef float pq_f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 pq_f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 pq_bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kMaxGrid = 2048;             // workgroups: 8 per compute unit; the rest of the tokens by grid stride
+constexpr int kRotRow = 128;               // pairs of one token's rotation row (head_dim <= 256)
+constexpr int kHeadUnroll = 4;             // passes of the head kernel whose loads are issued together
+
+template <int DT> struct PrepLoad;         // DT: la_dtype; raw = 8 consecutive elements as loaded (what a lane keeps of a chunk), to_float -> fp32
+template <> struct PrepLoad<0> {           // bf16
+    typedef pq_u32x4 raw;
+    static __device__ __forceinline__ raw zero() { return raw{0u, 0u, 0u, 0u}; }
+    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
+        return *reinterpret_cast<const pq_u32x4*>(static_cast<const uint16_t*>(base) + off);
+    }
+    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = __uint_as_float(w[i] << 16);
+            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    }
+};
+template <> struct PrepLoad<1> {           // fp16
+    typedef pq_f16x8 raw;
+    static __device__ __forceinline__ raw zero() { return raw{0, 0, 0, 0, 0, 0, 0, 0}; }
+    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
+        return *reinterpret_cast<const pq_f16x8*>(static_cast<const uint16_t*>(base) + off);
+    }
+    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = static_cast<float>(w[i]);
+    }
+};
+template <> struct PrepLoad<3> {           // fp32
+    struct raw { pq_f32x4 a, c; };
+    static __device__ __forceinline__ raw zero() { return raw{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}; }
+    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
+        const float* q = static_cast<const float*>(base) + off;
+        return raw{*reinterpret_cast<const pq_f32x4*>(q), *reinterpret_cast<const pq_f32x4*>(q + 4)};
+    }
+    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { x[i] = w.a[i]; x[4 + i] = w.c[i]; }
+    }
+};
+
+template <int DT> struct PrepStore;        // fp32 -> 8 elements, round to nearest even, one 16-byte store
+template <> struct PrepStore<0> {
+    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
+        pq_bf16x8 w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = static_cast<__bf16>(y[i]);
+        *reinterpret_cast<pq_bf16x8*>(static_cast<uint16_t*>(base) + off) = w;
+    }
+};
+template <> struct PrepStore<1> {
+    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
+        pq_f16x8 w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = static_cast<_Float16>(y[i]);
+        *reinterpret_cast<pq_f16x8*>(static_cast<uint16_t*>(base) + off) = w;
+    }
+};
+
+__device__ __forceinline__ float sum_squares8(const float (&v)[8]) {
+    return ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) + ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
+}
+
+__device__ __forceinline__ void load_weight8(const float* __restrict__ weight, int idx, float (&w)[8]) {
+    const pq_f32x4 a = *reinterpret_cast<const pq_f32x4*>(weight + idx), c = *reinterpret_cast<const pq_f32x4*>(weight + idx + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { w[i] = a[i]; w[4 + i] = c[i]; }
+}
+
+// LDS accesses of ONE wave before / after this point stay on their side of it (the hardware runs them in order)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The two rotation pairs a lane stages per token (pairs lane and lane + 64 of the row): axis (-1: behind the rotated pairs) and column
+// inside the axis' table row. Token independent.
+struct RotStage {
+    int axis[2], col[2];
+    __device__ __forceinline__ void init(const QkPrepParams& p, int lane) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int j = lane + 64 * k, p1 = p.pairs[0], p2 = p.pairs[0] + p.pairs[1], p3 = p2 + p.pairs[2];
+            axis[k] = j >= p3 ? -1 : (j >= p1) + (j >= p2);
+            col[k] = j - (j >= p2 ? p2 : (j >= p1 ? p1 : 0));
+        }
+    }
+    // gather the row of position `pos` (wave-uniform) into `row` (this wave's kRotRow pairs of LDS)
+    __device__ __forceinline__ void stage(const QkPrepParams& p, int pos, int lane, float* row) const {
+        const int plane = p.ext1 * p.ext2;
+        const int c0 = pos / plane, rem = pos - c0 * plane, c1 = rem / p.ext2, c2 = rem - c1 * p.ext2;
+        const float* __restrict__ r0 = p.table[0] + static_cast<int64_t>(c0) * p.pairs[0] * 2;
+        const float* __restrict__ r1 = p.table[1] + static_cast<int64_t>(c1) * p.pairs[1] * 2;
+        const float* __restrict__ r2 = p.table[2] + static_cast<int64_t>(c2) * p.pairs[2] * 2;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            pq_f32x2 cs = {1.f, 0.f};
+            if (axis[k] >= 0) cs = *reinterpret_cast<const pq_f32x2*>((axis[k] == 0 ? r0 : (axis[k] == 1 ? r1 : r2)) + 2 * col[k]);
+            *reinterpret_cast<pq_f32x2*>(row + 2 * (lane + 64 * k)) = cs;
+        }
+    }
+};
+
+// y (8 elements starting at element e of a head) *= scale * w, then the pairs below `rot_pairs` are rotated by the staged row
+template <bool ROT>
+__device__ __forceinline__ void scale_rotate8(float (&y)[8], float r, const float (&w)[8], int e, int rot_pairs, const float* row) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = (y[i] * r) * w[i];
+    if (ROT) {
+        const pq_f32x4 t0 = *reinterpret_cast<const pq_f32x4*>(row + e), t1 = *reinterpret_cast<const pq_f32x4*>(row + e + 4);
+        const float cs[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a = y[2 * k], b = y[2 * k + 1], c = cs[2 * k], s = cs[2 * k + 1];
+            const bool on = (e >> 1) + k < rot_pairs;              // a pair behind the rotated ones passes through untouched (inf stays inf)
+            y[2 * k] = on ? a * c - b * s : a;
+            y[2 * k + 1] = on ? a * s + b * c : b;
+        }
+    }
+}
+
+// WG false: one wave per token. WG true (H * D > 5120): the four waves of the workgroup share one token, so that a lane still keeps
+// at most 10 chunks; the four partial sums meet in LDS and are added in a fixed order.
+template <int DT_IN, int DT_OUT, int NCH, bool WG>
+__global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParams p) {
+    __shared__ __attribute__((aligned(16))) float rot_lds[4][2 * kRotRow];
+    __shared__ float part[4];
+    typedef typename PrepLoad<DT_IN>::raw raw_t;
+    constexpr int kLanes = WG ? 256 : 64;                          // lanes that share a token
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int D = p.head_dim, n = p.num_heads * D, nchunks = n >> 3;
+    const int rot_pairs = p.pairs[0] + p.pairs[1] + p.pairs[2];
+    const bool rotate = p.rotate != 0;
+    const float* __restrict__ weight = p.weight;
+    float* row = rot_lds[wave];                                    // WG: every wave stages its own copy of the token's row
+    const int first = WG ? static_cast<int>(threadIdx.x) : lane;
+
+    // chunk i of this lane = chunk first + kLanes i of the token: its first element inside its head (-1: no such chunk) and its
+    // element offsets from the token's start in x and out (below 2^31, checked by la_qk_prep)
+    int col[NCH], x_off[NCH], o_off[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = first + kLanes * i;
+        const int head = (c * 8) / D;
+        col[i] = c < nchunks ? c * 8 - head * D : -1;
+        x_off[i] = static_cast<int>(head * p.x_hs) + col[i];
+        o_off[i] = static_cast<int>(head * p.o_hs) + col[i];
+    }
+    RotStage rs;
+    rs.init(p, lane);
+
+    const int64_t t0 = WG ? static_cast<int64_t>(blockIdx.x) : static_cast<int64_t>(blockIdx.x) * 4 + wave;
+    const int64_t t_step = WG ? static_cast<int64_t>(gridDim.x) : static_cast<int64_t>(gridDim.x) * 4;
+    for (int64_t t = t0; t < p.tokens; t += t_step) {              // WG: the same trips for every thread of the workgroup
+        const int64_t b = t / p.seqlen;
+        const int s = static_cast<int>(t - b * p.seqlen);
+        const int64_t x_tok = b * p.x_bs + s * p.x_rs, o_tok = b * p.o_bs + s * p.o_rs;
+        raw_t v[NCH];                                              // the token: it stays in registers until it is stored
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) v[i] = col[i] >= 0 ? PrepLoad<DT_IN>::load(p.x, x_tok + x_off[i]) : PrepLoad<DT_IN>::zero();
+        if (rotate) rs.stage(p, p.pos_offset + s, lane, row);
+        float ss = 0.f;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            float y[8];
+            PrepLoad<DT_IN>::to_float(v[i], y);
+            ss += sum_squares8(y);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+        if (WG) {
+            if (lane == 0) part[wave] = ss;
+            __syncthreads();
+            ss = (part[0] + part[1]) + (part[2] + part[3]);
+            __syncthreads();                                       // part is rewritten for the next token
+        }
+        const float r = rsqrtf(ss / static_cast<float>(n) + p.eps);
+        if (rotate) wave_lds_fence();
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            if (col[i] >= 0) {
+                float y[8], w[8];
+                PrepLoad<DT_IN>::to_float(v[i], y);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = 1.f;
+                if (weight) load_weight8(weight, (first + kLanes * i) * 8, w);      // 4 H D bytes every token rereads: they stay in L1 / L2
+                if (rotate) scale_rotate8<true>(y, r, w, col[i], rot_pairs, row);
+                else scale_rotate8<false>(y, r, w, col[i], rot_pairs, row);
+                PrepStore<DT_OUT>::store8(p.out, o_tok + o_off[i], y);
+            }
+        }
+        if (rotate) wave_lds_fence();                              // the next token's row is staged behind this token's reads
+    }
+}
+
+template <int DT_IN, int DT_OUT>
+__global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams p, int group_log2) {
+    __shared__ __attribute__((aligned(16))) float rot_lds[4][2 * kRotRow];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int D = p.head_dim, H = p.num_heads;
+    const int G = 1 << group_log2, heads_per_pass = 64 >> group_log2;
+    const int sub = lane >> group_log2, e = (lane & (G - 1)) * 8;  // this lane: head `sub` of a pass, elements [e, e + 8) of it
+    const bool col_ok = e < D;
+    const bool norm = p.norm_mode == 2;
+    const int rot_pairs = p.pairs[0] + p.pairs[1] + p.pairs[2];
+    const bool rotate = p.rotate != 0;
+    float* row = rot_lds[wave];
+    float w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = 1.f;
+    if (norm && p.weight && col_ok) load_weight8(p.weight, e, w);
+    RotStage rs;
+    rs.init(p, lane);
+
+    for (int64_t t = static_cast<int64_t>(blockIdx.x) * 4 + wave; t < p.tokens; t += static_cast<int64_t>(gridDim.x) * 4) {
+        const int64_t b = t / p.seqlen;
+        const int s = static_cast<int>(t - b * p.seqlen);
+        const int64_t x_tok = b * p.x_bs + s * p.x_rs + e, o_tok = b * p.o_bs + s * p.o_rs + e;
+        if (rotate) {
+            rs.stage(p, p.pos_offset + s, lane, row);
+            wave_lds_fence();
+        }
+        for (int h0 = 0; h0 < H; h0 += heads_per_pass * kHeadUnroll) {
+            typename PrepLoad<DT_IN>::raw raw[kHeadUnroll];
+#pragma unroll
+            for (int u = 0; u < kHeadUnroll; ++u) {
+                const int h = h0 + u * heads_per_pass + sub;
+                raw[u] = col_ok && h < H ? PrepLoad<DT_IN>::load(p.x, x_tok + h * p.x_hs) : PrepLoad<DT_IN>::zero();
+            }
+#pragma unroll
+            for (int u = 0; u < kHeadUnroll; ++u) {
+                const int h = h0 + u * heads_per_pass + sub;
+                float y[8], r = 1.f;
+                PrepLoad<DT_IN>::to_float(raw[u], y);
+                if (norm) {                                        // uniform: every lane of the wave takes part in the butterfly
+                    float ss = sum_squares8(y);
+                    for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+                    r = rsqrtf(ss / static_cast<float>(D) + p.eps);
+                }
+                if (col_ok && h < H) {
+                    if (rotate) scale_rotate8<true>(y, r, w, e, rot_pairs, row);
+                    else scale_rotate8<false>(y, r, w, e, rot_pairs, row);
+                    PrepStore<DT_OUT>::store8(p.out, o_tok + h * p.o_hs, y);
+                }
+            }
+        }
+        if (rotate) wave_lds_fence();
+    }
+}
+
+dim3 grid_for(int64_t tokens, int tokens_per_block) {
+    const int64_t blocks = (tokens + tokens_per_block - 1) / tokens_per_block;
+    return dim3(static_cast<unsigned>(blocks < kMaxGrid ? blocks : kMaxGrid));
+}
+
+template <int DT_IN, int DT_OUT>
+void launch_token(const QkPrepParams& p, hipStream_t stream) {
+    const int nchunks = p.num_heads * p.head_dim / 8;              // <= 2048, checked by la_qk_prep
+    const int need = (nchunks + 63) / 64;                          // chunks per lane with one wave per token
+#define LA_QK_PREP_TOKEN(NCH, WG) \
+    hipLaunchKernelGGL((la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG>), grid_for(p.tokens, WG ? 1 : 4), dim3(256), 0, stream, p)
+    if (need <= 1) LA_QK_PREP_TOKEN(1, false);
+    else if (need <= 2) LA_QK_PREP_TOKEN(2, false);
+    else if (need <= 4) LA_QK_PREP_TOKEN(4, false);
+    else if (need <= 8) LA_QK_PREP_TOKEN(8, false);
+    else if (need <= 10) LA_QK_PREP_TOKEN(10, false);
+    else if (nchunks <= 4 * 256) LA_QK_PREP_TOKEN(4, true);        // one workgroup per token
+    else LA_QK_PREP_TOKEN(8, true);
+#undef LA_QK_PREP_TOKEN
+}
+
+template <int DT_IN, int DT_OUT>
+void launch_typed(const QkPrepParams& p, hipStream_t stream) {
+    if (p.norm_mode == 1) {
+        launch_token<DT_IN, DT_OUT>(p, stream);
+    } else {
+        int group_log2 = 0;
+        while ((8 << group_log2) < p.head_dim) ++group_log2;       // head_dim <= 256: at most 5
+        hipLaunchKernelGGL((la_qk_prep_head_kernel<DT_IN, DT_OUT>), grid_for(p.tokens, 4), dim3(256), 0, stream, p, group_log2);
+    }
+}
+
+template <int DT_IN>
+void launch_in(const QkPrepParams& p, int out_dtype, hipStream_t stream) {
+    if (out_dtype == 0) launch_typed<DT_IN, 0>(p, stream);
+    else launch_typed<DT_IN, 1>(p, stream);
+}
+
+}  // namespace
+
+hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (in_dtype == 0) launch_in<0>(p, out_dtype, stream);
+    else if (in_dtype == 1) launch_in<1>(p, out_dtype, stream);
+    else launch_in<3>(p, out_dtype, stream);
+    return hipGetLastError();
+}
+
+}  // namespace la

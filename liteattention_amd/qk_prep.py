@@ -1,0 +1,227 @@
+"""The q / k prologue of a Wan2.x-style attention block in one pass over each tensor: RMSNorm, 3-axis RoPE on interleaved pairs and the
+cast to bf16 / fp16 (``la_qk_prep``), in place of the ten-odd eager passes with fp32 temporaries that precede the attention call.
+
+    tables = rope_tables((frames, height, width), head_dim, device=x.device)     # once per grid; cached
+    q = qk_prep(q_proj.view(b, s, n, d), norm_q.weight, norm_q.eps, tables)      # bf16, ready for LiteAttention
+    k = qk_prep(k_proj.view(b, s, n, d), norm_k.weight, norm_k.eps, tables)
+
+``qk_prep_reference`` is the same formula in torch fp64, for tests and for users who want to check."""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from . import _cabi
+
+_IN_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}
+_OUT_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16}
+_NORM_MODES = {None: _cabi.LA_NORM_NONE, "none": _cabi.LA_NORM_NONE, "token": _cabi.LA_NORM_TOKEN, "head": _cabi.LA_NORM_HEAD}
+
+
+class RopeTables(NamedTuple):
+    """``tables[a]`` is fp32 ``[grid[a], axis_pairs[a], 2]`` = (cos, sin) of axis a's angles; its first dimension is the axis extent."""
+    tables: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]
+    axis_pairs: Tuple[int, int, int]
+
+
+def wan_rope_parts(head_dim: int) -> Tuple[int, int, int]:
+    """Elements of a head that each of the (frames, height, width) axes rotates, as Wan splits them: (d - 2 (d // 3), d // 3, d // 3)
+    with the last two made even and the first taking the rest."""
+    third = head_dim // 3
+    third -= third % 2
+    return head_dim - 2 * third, third, third
+
+
+_TABLES = {}      # (grid, head_dim, theta, parts, device) -> RopeTables
+
+
+def rope_tables(grid: Sequence[int], head_dim: int, theta: float = 10000.0, parts: Optional[Sequence[int]] = None,
+                device=None) -> RopeTables:
+    """The three (cos, sin) tables ``la_qk_prep`` rotates with, and the pairs per axis. ``grid`` = (e0, e1, e2): token s of a sequence
+    sits at (s // (e1 e2), (s // e2) % e1, s % e2). ``parts``: elements of a head per axis (even, their sum at most ``head_dim``; what is
+    left passes through unrotated); default ``wan_rope_parts(head_dim)``. 1-D RoPE is ``grid=(S, 1, 1), parts=(head_dim, 0, 0)``.
+    Axis a with d elements uses the frequencies 1 / theta^(2 i / d), i < d / 2, in fp32 as the eager rope computes them; the angle
+    position x frequency is evaluated in fp64 and rounded to fp32 (which makes it the eager rope's own fp32 product), its cosine and
+    sine are evaluated in fp64 and rounded to fp32. Built on the host, cached per (grid, head_dim, theta, parts, device)."""
+    grid = tuple(int(g) for g in grid)
+    parts = wan_rope_parts(head_dim) if parts is None else tuple(int(p) for p in parts)
+    if len(grid) != 3 or any(g <= 0 for g in grid):
+        raise ValueError(f"grid must be three positive extents, got {grid}")
+    if len(parts) != 3 or any(p < 0 or p % 2 for p in parts) or sum(parts) > head_dim:
+        raise ValueError(f"parts must be three even, non-negative element counts summing to at most head_dim = {head_dim}, got {parts}")
+    device = torch.device("cpu" if device is None else device)
+    key = (grid, int(head_dim), float(theta), parts, str(device))
+    hit = _TABLES.get(key)
+    if hit is not None:
+        return hit
+    tables = []
+    for extent, d in zip(grid, parts):
+        if d == 0:
+            tables.append(torch.zeros(extent, 0, 2, dtype=torch.float32, device=device))
+            continue
+        freqs = 1.0 / theta ** (torch.arange(0, d, 2).float() / d)
+        ang = (torch.arange(extent).double()[:, None] * freqs.double()[None]).float().double()
+        tables.append(torch.stack((ang.cos(), ang.sin()), dim=-1).float().contiguous().to(device))
+    while len(_TABLES) >= 16:                                    # a handful of grids per process; never grow without bound
+        _TABLES.pop(next(iter(_TABLES)))
+    res = _TABLES[key] = RopeTables(tuple(tables), tuple(p // 2 for p in parts))
+    return res
+
+
+def _unpack_tables(tables, head_dim):
+    if tables is None:
+        return None, (0, 0, 0)
+    tabs, pairs = tables
+    pairs = tuple(int(n) for n in pairs)
+    if len(tabs) != 3 or len(pairs) != 3:
+        raise ValueError("tables: (three tensors, three pair counts), as rope_tables returns them")
+    for t, n in zip(tabs, pairs):
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[1] != n or t.shape[2] != 2 or not t.is_contiguous():
+            raise ValueError(f"a rope table must be contiguous fp32 [extent, {n}, 2], got {t.dtype} {tuple(t.shape)}")
+    if sum(pairs) > head_dim // 2:
+        raise ValueError(f"the axes rotate {sum(pairs)} pairs, a head has {head_dim // 2}")
+    return tuple(tabs), pairs
+
+
+def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None):
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise ValueError("x must live on a GPU (there is no CPU path; qk_prep_reference is the formula in torch)")
+    if x.dtype not in _IN_DTYPES:
+        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
+    if norm not in _NORM_MODES:
+        raise ValueError('norm: "token", "head" or None')
+    mode = _NORM_MODES[norm]
+    B, S, H, D = x.shape
+    if out is None:
+        if out_dtype is None:
+            out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.bfloat16
+        out = torch.empty((B, S, H, D), dtype=out_dtype, device=x.device)
+    elif out_dtype is not None and out.dtype != out_dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype says {out_dtype}")
+    if out.dtype not in _OUT_DTYPES:
+        raise TypeError(f"out: bf16 or fp16, got {out.dtype}")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    if x.stride(-1) != 1 or out.stride(-1) != 1:
+        raise ValueError("the last dimension of x and out must be contiguous")
+    if B * S == 0:
+        return out
+    if weight is not None and mode != _cabi.LA_NORM_NONE:
+        want = H * D if mode == _cabi.LA_NORM_TOKEN else D
+        if weight.dtype != torch.float32 or weight.numel() != want or not weight.is_contiguous() or weight.device != x.device:
+            raise ValueError(f"weight must be contiguous fp32 with {want} elements on {x.device} "
+                             f"(got {weight.dtype}, {tuple(weight.shape)}, {weight.device})")
+    a = _cabi.LaQkPrepArgs()
+    a.struct_size = ctypes.sizeof(_cabi.LaQkPrepArgs)
+    a.in_dtype, a.out_dtype, a.norm_mode = _IN_DTYPES[x.dtype], _OUT_DTYPES[out.dtype], mode
+    a.x, a.out = x.data_ptr(), out.data_ptr()
+    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
+    a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
+    a.eps, a.pos_offset = float(eps), int(pos_offset)
+    if tables is not None:
+        for i, (t, n) in enumerate(zip(tables, axis_pairs)):
+            if t.device != x.device:
+                raise ValueError(f"rope table {i} lives on {t.device}, x on {x.device}: build the tables with device=x.device")
+            a.rope_table[i] = t.data_ptr() if n > 0 else None
+            a.axis_extent[i], a.axis_pairs[i] = t.shape[0], n
+    with torch.cuda.device(x.device):
+        rc = _cabi.load().la_qk_prep(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_qk_prep: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()}, out strides {out.stride()}, "
+                           f"norm {norm!r}, pos_offset {pos_offset}, {S} rows on a grid of "
+                           f"{[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]})")
+    return out
+
+
+def qk_prep(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+            norm: Optional[str] = "token", pos_offset: int = 0, out: Optional[torch.Tensor] = None,
+            out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``out = cast(rope(rmsnorm(x) * weight))`` for ``x`` (B, S, H, D) bf16 / fp16 / fp32 on the GPU, in one pass (``la_qk_prep``):
+    fp32 arithmetic, one rounding at the store. ``x`` may be any view whose last dimension is contiguous and whose rows start on
+    16-byte boundaries - e.g. the q or k slice of a fused (B, S, 3, H, D) projection.
+
+    norm      "token": RMSNorm over the H * D elements of a token (Wan's ``RMSNorm(dim)``; ``weight`` fp32 [H * D]; H * D <= 16384),
+              "head": over the D elements of a head (``weight`` fp32 [D]), None: no norm, ``weight`` ignored. ``weight=None``: ones.
+    tables    what ``rope_tables`` returns, on ``x.device``; None: no rotation. Row s is rotated as position ``pos_offset + s`` of the
+              tables' grid (a chunk of a longer sequence passes its first position).
+    out       bf16 or fp16, same shape; default: a new contiguous tensor of ``out_dtype`` (default: ``x.dtype``, bf16 for fp32 input).
+              ``out`` may BE ``x`` (same dtype, same strides: in place); any other overlap of the two is an error nobody detects.
+    No host sync, no allocation besides ``out``; asynchronous on the current stream. It captures into a HIP graph when the tables
+    were built before the capture (building them copies from the host)."""
+    tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
+    return _qk_prep_impl(x, weight, eps, tabs, pairs, norm, pos_offset, out, out_dtype)
+
+
+def qk_prep_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+                      norm: Optional[str] = "token", pos_offset: int = 0, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The formula of ``qk_prep`` in torch fp64 on whatever device ``x`` lives on, from the same fp32 weight and tables. Returns fp64
+    (the unrounded value), or ``out_dtype`` when given."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    if norm not in _NORM_MODES:
+        raise ValueError('norm: "token", "head" or None')
+    mode = _NORM_MODES[norm]
+    B, S, H, D = x.shape
+    y = x.double()
+    if mode != _cabi.LA_NORM_NONE:
+        eps64 = float(torch.tensor(eps, dtype=torch.float32))                 # the kernel is handed eps as fp32
+        dims = (2, 3) if mode == _cabi.LA_NORM_TOKEN else (3,)
+        y = y * torch.rsqrt(y.pow(2).mean(dims, keepdim=True) + eps64)
+        if weight is not None:
+            y = y * (weight.double().view(H, D) if mode == _cabi.LA_NORM_TOKEN else weight.double().view(D))
+    tabs, pairs = _unpack_tables(tables, D)
+    if tabs is not None and sum(pairs) > 0:
+        e1, e2 = tabs[1].shape[0], tabs[2].shape[0]
+        pos = pos_offset + torch.arange(S, device=x.device)
+        if pos_offset < 0 or pos_offset + S > tabs[0].shape[0] * e1 * e2:
+            raise ValueError("pos_offset + S exceeds the grid of the tables")
+        coords = (pos // (e1 * e2), (pos // e2) % e1, pos % e2)
+        cs = torch.cat([t.to(x.device)[c].double() for t, c in zip(tabs, coords)], dim=1)      # (S, rotated pairs, 2)
+        n = cs.shape[1]
+        cos, sin = cs[None, :, None, :, 0], cs[None, :, None, :, 1]
+        pair = y[..., :2 * n].reshape(B, S, H, n, 2)
+        a, b = pair[..., 0], pair[..., 1]
+        rot = torch.stack((a * cos - b * sin, a * sin + b * cos), dim=-1).reshape(B, S, H, 2 * n)
+        y = torch.cat((rot, y[..., 2 * n:]), dim=-1)
+    return y if out_dtype is None else y.to(out_dtype)
+
+
+# ---- op registration: torch.ops.lite_attention.qk_prep, beside fwd / fwd_combine ---------------------------------------------------------
+_QK_PREP_SCHEMA = ("qk_prep(Tensor x, Tensor? weight = None, float eps = 1e-6, Tensor[]? tables = None, int[]? axis_pairs = None, "
+                   "str? norm = \"token\", int pos_offset = 0, Tensor(out!)? out = None, ScalarType? out_dtype = None) -> Tensor(out!)")
+_op_lib = None
+
+
+def _qk_prep_op(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None):
+    tabs, pairs = _unpack_tables(None if tables is None else (tables, axis_pairs or ()), x.shape[-1])
+    return _qk_prep_impl(x, weight, eps, tabs, pairs, norm, pos_offset, out, out_dtype)
+
+
+def _qk_prep_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None):
+    """Shapes and dtypes only (fake-tensor tracing treats the op as opaque)."""
+    if out is not None:
+        return out
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.bfloat16
+    return torch.empty(x.shape, dtype=out_dtype, device=x.device)
+
+
+def _register_op():
+    global _op_lib
+    if _op_lib is not None:
+        return
+    from . import flash_attn_interface  # noqa: F401  (defines the library this is a fragment of)
+    lib = torch.library.Library("lite_attention", "FRAGMENT")
+    lib.define(_QK_PREP_SCHEMA)
+    lib.impl("qk_prep", _qk_prep_op, "CUDA")
+    lib.impl("qk_prep", _qk_prep_meta, "Meta")
+    _op_lib = lib
+
+
+_register_op()
