@@ -163,7 +163,8 @@ typedef struct la_fwd_args {
     int32_t num_heads, num_heads_k;
     int32_t head_dim, head_dim_v;
 
-    float   softmax_scale;       /* scores = q.k * softmax_scale (flash_api.cpp:125)              */
+    float   softmax_scale;       /* scores = q.k * softmax_scale (flash_api.cpp:125). 0 = uniform attention over the walked keys:
+                                    O = mean of V, LSE = ln of their number (run at 2^-100 / log2 e, where every exp2 is exactly 1) */
 
     /* fp8 only: per-(batch, kv-head) descales, fp32; NULL = 1.0 (flash_api.cpp:1003-1022) */
     const float* q_descale; const float* k_descale; const float* v_descale;

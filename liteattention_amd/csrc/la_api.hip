@@ -262,6 +262,9 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
         p.q_tile_begin = p.q_tile_begin / 2;
     }
     p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);  // flash_api.cpp:125-126
+    // softmax_scale = 0 (uniform attention: O = mean of V, LSE = ln seqlen_k) runs at c = 2^-100: every |score * c| stays far below 2^-24, so
+    // each exp2 is exactly 1, while c = 0 makes NaN of the -inf of a masked key and of an empty running maximum (-inf * 0) and inf of tau / c
+    if (p.scale_log2 == 0.0f) p.scale_log2 = 0x1p-100f;
     p.thr = a->thr;                                                                      // flash_api.cpp:930
     p.rescale_tau = (a->flags & LA_FLAG_EXACT_RESCALE) ? 0.0f : kRescaleTauBf16;
     p.cu_seqlens_q = a->cu_seqlens_q; p.cu_seqlens_k = a->cu_seqlens_k; p.total_q = a->total_q;

@@ -46,6 +46,14 @@ def test_lists_fp16_and_fragmented_lists_on_the_16x16x32_body():
     assert " passed" in r.stdout and "failed" not in r.stdout
 
 
+def test_score_staircases_on_the_16x16x32_body():
+    """The lazy O-rescale of this body works on a TRANSPOSED running state (gen_fwd_x64_m16.py): the staircases of
+    tests/test_gpu_score_range.py at head_dim 128, bf16 and fp16, lazily and exactly rescaled, and the zero-scale case."""
+    r = _run(["tests/test_gpu_score_range.py", "-k", "d128 and not e4m3 and not v2 and not half"])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert " passed" in r.stdout and "failed" not in r.stdout
+
+
 def test_the_process_really_ran_the_16x16x32_kernel():
     """The kernel symbol is the same (la_fwd_x64_kernel<.., 128>): what tells the bodies apart is the instruction stream. The library on
     disk must hold 16x16x32 MFMAs in its gfx950 code object, and the product library none (it is all 32x32x16 / fp8 scaled)."""
