@@ -56,7 +56,8 @@ typedef enum la_status {
     LA_ERR_HEAD_DIM = -4,        /* head_dim not instantiated / not a multiple of 8 (flash_api.cpp:854) */
     LA_ERR_SHAPE = -5,           /* non-positive sizes, num_heads % num_heads_k != 0 (flash_api.cpp:777). seqlen_k == 0 is NOT
                                   * an error: la_fwd stores o = 0, lse = +inf like the reference (flash_api.cpp:1241-1245) */
-    LA_ERR_STRIDE = -6,          /* last dim must be contiguous (flash_api.cpp:726-728) / 16-byte rows  */
+    LA_ERR_STRIDE = -6,          /* last dim must be contiguous (flash_api.cpp:726-728) / 16-byte rows; la_fwd: a K or V row stride above
+                                  * LA_MAX_KV_ROW_STRIDE_BYTES, a Q or O row stride of 2^30 elements or more */
     LA_ERR_TILE_MISMATCH = -7,   /* block_m/block_n echo != la_get_tile_sizes (list indexing would be wrong) */
     LA_ERR_LISTS = -8,           /* read list without write list, or vice versa                   */
     LA_ERR_UNSUPPORTED = -9,     /* feature outside the hot path (causal, dv != d, ...)           */
@@ -65,6 +66,12 @@ typedef enum la_status {
     LA_ERR_WORKSPACE = -12,      /* fp8: workspace missing or smaller than la_fwd_workspace_bytes() */
     LA_ERR_Q_WINDOW = -13        /* q_tile_begin/q_tile_count outside [0, ceil(seqlen_q/block_m)]  */
 } la_status;
+
+/* The largest K / V row stride la_fwd accepts, in BYTES. The kernels stage a 64-row key tile with one 64-bit tile address plus a per-lane
+ * offset row_in_tile * row_stride_bytes + chunk + bias held in 32 bits: unsigned in the hand-scheduled bodies (rows 0 .. 63,
+ * chunk + bias <= 3584: 63 * 2^26 + 3584 < 2^32), signed in the 128-row template (at most 14 rows of a wave's 16: 14 * 2^26 < 2^31).
+ * 2^26 is the largest power of two inside both bounds. */
+#define LA_MAX_KV_ROW_STRIDE_BYTES 67108864
 
 /* la_fwd_args.flags */
 #define LA_FLAG_KERNEL_128ROW 4u /* A/B: run the hipcc-scheduled 128-row template (32 rows per wave) where the default is the
@@ -154,6 +161,9 @@ typedef struct la_fwd_args {
     void*       o;               /* bf16 (also for fp8 inputs, flash_api.cpp:859)                 */
     float*      lse;             /* may be NULL: LSE not stored                                   */
 
+    /* Elements; non-negative multiples of 16 bytes. Batch and head strides, and with them every operand's extent, are 64-bit throughout
+     * (an operand may lie many GiB from its base pointer). Row strides: q / o below 2^30 elements; k / v at most
+     * LA_MAX_KV_ROW_STRIDE_BYTES BYTES (2^25 bf16 / fp16 elements, 2^26 e4m3 elements) - LA_ERR_STRIDE above, before any launch. */
     int64_t q_batch_stride, q_row_stride, q_head_stride;
     int64_t k_batch_stride, k_row_stride, k_head_stride;
     int64_t v_batch_stride, v_row_stride, v_head_stride;

@@ -90,7 +90,7 @@ const char* la_status_string(int status) {
         case LA_ERR_DTYPE: return "FlashAttention only supports fp16, bf16, and fp8_e4m3 type; this build instantiates all three";
         case LA_ERR_HEAD_DIM: return "head_size not instantiated in this build (bf16 / fp16: 64, 96, 128, 192, 256 - under LA_FLAG_KERNEL_128ROW only 64, 128, 256; fp8: 64, 96, 128, 192, 256)";
         case LA_ERR_SHAPE: return "invalid shape (batch, seqlen_q, heads and head_dim must be positive; number of heads in key/value must divide number of heads in query)";
-        case LA_ERR_STRIDE: return "Input tensor must have contiguous last dimension and 16-byte aligned rows";
+        case LA_ERR_STRIDE: return "Input tensor must have contiguous last dimension and 16-byte aligned rows (la_fwd: K / V row stride at most 2^26 bytes, Q / O row stride below 2^30 elements)";
         case LA_ERR_TILE_MISMATCH: return "block_m/block_n do not match la_get_tile_sizes(): skip lists would be mis-indexed";
         case LA_ERR_LISTS: return "attn_read_list and attn_write_list must be given together";
         case LA_ERR_UNSUPPORTED: return "feature outside the QK-Skip hot path (head_dim_v != head_dim, unknown flags, skip lists with cu_seqlens on the 128-row kernels or, for bf16 / fp16, above head_dim 128)";
@@ -186,8 +186,13 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
         const int gran = (fp8 && i < 9) ? 16 : 8;                                        // 16-byte rows: 16 fp8 / 8 bf16 elements
         if (s % gran != 0 || s < 0) return LA_ERR_STRIDE;
     }
-    if (a->k_row_stride > 0x3fffffff || a->v_row_stride > 0x3fffffff || a->o_row_stride > 0x3fffffff || a->q_row_stride > 0x3fffffff)
-        return LA_ERR_STRIDE;                                                             // byte strides kept in 32 bits
+    if (a->o_row_stride > 0x3fffffff || a->q_row_stride > 0x3fffffff)
+        return LA_ERR_STRIDE;                                                             // byte strides kept in 32 bits (the row offset itself is 64-bit)
+    // K / V: a lane's DMA offset inside a key tile, row_in_tile * row_stride_bytes + chunk + bias, is an UNSIGNED 32-bit register of the
+    // load (hand-scheduled bodies: rows 0 .. 63, chunk < 512, bias <= 3072) or an int (128-row template: rows 0 .. 14 and 0 .. 7 of a wave's
+    // slice): 63 * 2^26 + 3584 < 2^32 and 14 * 2^26 < 2^31. LA_MAX_KV_ROW_STRIDE_BYTES is the largest power of two inside both.
+    if (a->k_row_stride > LA_MAX_KV_ROW_STRIDE_BYTES / esize || a->v_row_stride > LA_MAX_KV_ROW_STRIDE_BYTES / esize)
+        return LA_ERR_STRIDE;
     if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || !aligned16(a->o)) return LA_ERR_STRIDE;
 
     const bool varlen = a->cu_seqlens_q != nullptr || a->cu_seqlens_k != nullptr;

@@ -202,6 +202,49 @@ def test_varlen_argument_validation():
     assert lib.la_fwd(ctypes.byref(a), None) == _cabi.LA_ERR_SHAPE
 
 
+@pytest.mark.parametrize("dtype,esize,flags,block_m", [
+    (_cabi.LA_DTYPE_BF16, 2, 0, None), (_cabi.LA_DTYPE_FP16, 2, 0, None), (_cabi.LA_DTYPE_FP8_E4M3, 1, 0, None),
+    (_cabi.LA_DTYPE_BF16, 2, _cabi.LA_FLAG_KERNEL_128ROW, 128), (_cabi.LA_DTYPE_FP16, 2, _cabi.LA_FLAG_KERNEL_128ROW, 128),
+], ids=["bf16", "fp16", "e4m3", "bf16-128row", "fp16-128row"])           # (there is no 128-row e4m3 kernel)
+def test_kv_row_stride_above_the_bound_is_refused(dtype, esize, flags, block_m):
+    """The kernels hold a lane's offset inside a key tile, row_in_tile * row_stride_bytes + chunk + bias, in 32 bits, so la_fwd refuses a
+    K or V row stride above LA_MAX_KV_ROW_STRIDE_BYTES = 2^26 bytes (2^25 16-bit elements, 2^26 e4m3 elements) with LA_ERR_STRIDE before
+    anything is launched: here the bound plus one 16-byte granule, for K and V each, everything else valid (tile echo included). Refusals
+    only - the accepting side, a launch AT the bound, is the `rows` axis of tests/test_gpu_far_addresses.py. Q and O keep 2^30 elements."""
+    header = open(HEADER).read()
+    bound = int(re.search(r"#define\s+LA_MAX_KV_ROW_STRIDE_BYTES\s+(\d+)", header).group(1))
+    assert bound == 1 << 26 and 63 * bound + 3584 < 1 << 32 and 15 * bound < 1 << 31
+    lib = _cabi.load()
+    H, D = 2, 128
+    bm, bn = _cabi.get_tile_sizes(D, esize, flags)
+    assert block_m is None or bm == block_m
+
+    def args(**over):
+        a = _cabi.LaFwdArgs()
+        a.struct_size = ctypes.sizeof(_cabi.LaFwdArgs)
+        a.dtype, a.flags = dtype, flags
+        a.q = a.k = a.v = a.o = a.lse = 0x10000
+        a.batch, a.seqlen_q, a.seqlen_k, a.num_heads, a.num_heads_k, a.head_dim, a.head_dim_v = 1, 150, 150, H, H, D, D
+        a.softmax_scale = D ** -0.5
+        a.block_m, a.block_n = bm, bn
+        for n in "qkvo":
+            setattr(a, f"{n}_batch_stride", 150 * H * D)
+            setattr(a, f"{n}_row_stride", H * D)
+            setattr(a, f"{n}_head_stride", D)
+        for name, val in over.items():
+            setattr(a, name, val)
+        return a
+
+    granule = 16 // esize
+    for name in ("k_row_stride", "v_row_stride"):
+        assert lib.la_fwd(ctypes.byref(args(**{name: bound // esize + granule})), None) == _cabi.LA_ERR_STRIDE, name
+        assert lib.la_fwd(ctypes.byref(args(**{name: 0x3fffffff - 0x3fffffff % granule})), None) == _cabi.LA_ERR_STRIDE, name   # accepted before
+        assert lib.la_fwd(ctypes.byref(args(**{name: 1 << 62})), None) == _cabi.LA_ERR_STRIDE, name       # (no overflow in the check itself)
+    for name in ("q_row_stride", "o_row_stride"):
+        assert lib.la_fwd(ctypes.byref(args(**{name: 1 << 30})), None) == _cabi.LA_ERR_STRIDE, name
+    assert "2^26" in _cabi.status_string(_cabi.LA_ERR_STRIDE)
+
+
 def test_missing_library_fails_loudly(tmp_path):
     """The product must not fall back to anything when the HIP extension is absent: import raises."""
     code = "import sys; sys.path.insert(0, %r)\nimport liteattention_amd\n" % ROOT
