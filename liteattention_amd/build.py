@@ -224,7 +224,7 @@ def _check_no_scratch(remarks: str, defines) -> None:
         raise RuntimeError("no kernel-resource-usage remark of an x64 kernel was parsed: the no-scratch check cannot run "
                            "(-Rpass-analysis=kernel-resource-usage output changed?)")
     if bad and not any(d.split("=")[0] == "LA_PROFILE_PHASES" for d in defines):
-        raise RuntimeError("x64 kernels must not spill to scratch (see liteattention_amd/csrc/la_fwd_kernel_x64.hip, "
+        raise RuntimeError("x64 kernels must not spill to scratch (see liteattention_amd/csrc/la_fwd_shell.h, "
                            f"COMPILER HAZARD): {bad}")
 
 

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/lite_attention_amd.h"
+#include "la_fwd_shell.h"      // fwd_lds_size_x64, X_LDS_LIMIT: the LDS a launch of the hand-scheduled kernels needs
 #include "la_kernel_params.h"
 #include "la_tiles.h"
 
@@ -42,14 +43,11 @@ bool uses_half_vote(int head_dim, int element_size, uint32_t flags) {
 // bound (LA_ERR_SEQLEN); a dense launch does not need it: with the workspace la_fwd_workspace_bytes() asks for, la_fwd cuts the keys into
 // the fewest equal runs of tiles that fit, runs them as launches on partial O / LSE buffers in the workspace and merges them by LSE
 // (la_combine's kernel) - the reference has no such bound (its producer reads the list from global memory, mainloop...:47-115).
-size_t walk_lds_bytes(int k_tiles, int head_dim, int element_size) {
-    return element_size == 1 ? la::fwd_lds_bytes_x64_fp8(k_tiles, nullptr, nullptr, head_dim) : la::fwd_lds_bytes_x64(k_tiles, nullptr, head_dim);
-}
 int dense_tiles_per_launch(int head_dim, int element_size) {
     int lo = 1, hi = 1 << 20;                         // largest k_tiles whose walk fits (the LDS bytes grow with k_tiles)
     while (lo < hi) {
         const int mid = lo + (hi - lo + 1) / 2;
-        if (walk_lds_bytes(mid, head_dim, element_size) <= 160 * 1024) lo = mid; else hi = mid - 1;
+        if (la::fwd_lds_size_x64(element_size, head_dim, mid).bytes <= la::X_LDS_LIMIT) lo = mid; else hi = mid - 1;
     }
     return lo;
 }
@@ -130,7 +128,7 @@ int64_t la_fwd_workspace_bytes(const la_fwd_args* a) {
         if (a->read_list == nullptr && !(a->flags & LA_FLAG_KERNEL_128ROW) && a->cu_seqlens_q == nullptr && a->seqlen_k > 0 && a->batch > 0 &&
             a->seqlen_q > 0 && a->num_heads > 0 && la::tile_shape(a->head_dim, 2).block_m != 0) {
             const int k_tiles = (a->seqlen_k + 63) / 64;
-            if (la::fwd_lds_bytes_x64(k_tiles, nullptr, a->head_dim) > 160 * 1024) {
+            if (la::fwd_lds_size_x64(2, a->head_dim, k_tiles).bytes > la::X_LDS_LIMIT) {
                 const DenseSplit d = dense_split(k_tiles, a->head_dim, a->batch, a->seqlen_q, a->num_heads, a->head_dim_v);
                 need = static_cast<int64_t>(kSchedWorkspaceBytes + d.n * (d.o_bytes + d.lse_bytes));
             }
@@ -143,7 +141,7 @@ int64_t la_fwd_workspace_bytes(const la_fwd_args* a) {
     if (trc != LA_OK) return trc;
     if (a->batch <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->seqlen_k < 0) return LA_ERR_SHAPE;
     const int k_tiles = (a->seqlen_k + bn - 1) / bn;
-    if (a->read_list == nullptr && a->cu_seqlens_q == nullptr && a->seqlen_q > 0 && walk_lds_bytes(k_tiles, a->head_dim, 1) > 160 * 1024) {
+    if (a->read_list == nullptr && a->cu_seqlens_q == nullptr && a->seqlen_q > 0 && la::fwd_lds_size_x64(1, a->head_dim, k_tiles).bytes > la::X_LDS_LIMIT) {
         // a dense key range longer than one launch's walk (see dense_split): the V^T tiles of ONE run (the runs follow each other on the
         // stream), the ticket counters, the partial O / LSE of the runs
         const DenseSplit d = dense_split(k_tiles, a->head_dim, a->batch, a->seqlen_q, a->num_heads, a->head_dim_v, 1);
@@ -223,7 +221,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     DenseSplit f8d{};
     if (fp8) {
         const int kt = (a->seqlen_k + bn - 1) / bn;
-        f8_split = a->read_list == nullptr && !varlen && walk_lds_bytes(kt, a->head_dim, 1) > 160 * 1024;
+        f8_split = a->read_list == nullptr && !varlen && la::fwd_lds_size_x64(1, a->head_dim, kt).bytes > la::X_LDS_LIMIT;
         if (f8_split) f8d = dense_split(kt, a->head_dim, a->batch, a->seqlen_q, a->num_heads, a->head_dim_v, 1);
         f8_tiles = la::fp8_workspace_bytes(a->batch, a->num_heads_k, f8_split ? f8d.chunk_tiles : kt, a->head_dim);   // split: the tiles of ONE run
         const uint64_t need = f8_tiles + kSchedWorkspaceBytes + (f8_split ? f8d.n * (f8d.o_bytes + f8d.lse_bytes) : 0);
@@ -283,12 +281,12 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     p.v_descale_batch_stride = a->v_descale_batch_stride; p.v_descale_head_stride = a->v_descale_head_stride;
 
     if (!fp8 && (a->flags & LA_FLAG_KERNEL_128ROW) &&
-        la::fwd_lds_bytes_v2(a->head_dim <= 128 ? a->head_dim : 256, p.k_tiles, nullptr) > 160 * 1024) return LA_ERR_SEQLEN;
+        la::fwd_lds_bytes_v2(a->head_dim <= 128 ? a->head_dim : 256, p.k_tiles, nullptr) > la::X_LDS_LIMIT) return LA_ERR_SEQLEN;
     if (static_cast<int64_t>(p.batch) * p.num_heads * p.q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
 
     if (fp8) {
         const int p_mode = (a->flags & LA_FLAG_FP8_ENCODED_P) ? 0 : (a->flags & LA_FLAG_FP8_MFMA_ROWSUM) ? 1 : 2;   // default: the reference's arithmetic
-        if (walk_lds_bytes(p.k_tiles, a->head_dim, 1) > 160 * 1024) {
+        if (la::fwd_lds_size_x64(1, a->head_dim, p.k_tiles).bytes > la::X_LDS_LIMIT) {
             // lists keep the bound; a dense launch is cut into runs of tiles that fit, as for bf16 / fp16 below: per run the V^T prepare pass of
             // ITS keys into the one tile region (the runs follow each other on the stream), the forward on bf16 partial O / LSE, then the merge
             if (!f8_split || p.q_tile_count != p.q_tiles || (a->flags & LA_FLAG_V_PREPARED)) return LA_ERR_SEQLEN;
@@ -339,7 +337,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     if ((skipable || x64) && a->workspace != nullptr && a->workspace_bytes >= kSchedWorkspaceBytes && aligned16(a->workspace) &&
         !(a->flags & LA_FLAG_STATIC_SCHED))
         p.work_counter = static_cast<unsigned*>(a->workspace);
-    if (x64 && la::fwd_lds_bytes_x64(p.k_tiles, nullptr, a->head_dim, nullptr, half_vote && skipable) > 160 * 1024) {
+    if (x64 && la::fwd_lds_size_x64(2, a->head_dim, p.k_tiles, half_vote && skipable).bytes > la::X_LDS_LIMIT) {
         // lists keep the bound; a dense launch is cut into runs of tiles that fit (dense_split) when the caller gave the workspace for it
         if (skipable || varlen || p.q_tile_count != p.q_tiles) return LA_ERR_SEQLEN;
         const DenseSplit d = dense_split(p.k_tiles, a->head_dim, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v);

@@ -154,6 +154,22 @@ def test_body_digest_product_cases_are_what_the_build_generates(tmp_path):
         assert open(path, "rb").read() == open(tmp_path / "b" / os.path.basename(path), "rb").read(), case
 
 
+def test_shell_digest_covers_the_shells_of_the_manifest(tmp_path):
+    """tools/shell_digest.py (the gate for moving a piece of a shell into la_fwd_shell.h) compiles the shells the manifest names, and
+    its reader takes a function's resource counts and mnemonic counts from device assembly."""
+    digest = _load("la_shell_digest", os.path.join(ROOT, "tools", "shell_digest.py"))
+    assert digest.SHELLS == [bodies.SHELL, bodies.SHELL_F8]
+    asm = tmp_path / "k.s"
+    asm.write_text("\t.text\n\t.type\tf,@function\nf: ; @f\n; %bb.0:\n\ts_nop 0\n.LBB0_1:\n\ts_nop 1\n\ts_endpgm\n\t.p2align 2\n.Lfunc_end0:\n"
+                   "; Kernel info:\n; TotalNumSgprs: 8\n; NumVgprs: 3\n; NumAgprs: 0\n; ScratchSize: 0\n"
+                   "\t.amdgpu_metadata\n---\namdhsa.kernels:\n  - .agpr_count:     0\n    .args:\n      - .offset:         0\n"
+                   "    .group_segment_fixed_size: 0\n    .name:           f\n    .private_segment_fixed_size: 0\n    .sgpr_count:     8\n"
+                   "    .sgpr_spill_count: 5\n    .vgpr_count:     3\n    .vgpr_spill_count: 0\namdhsa.target:   amdgcn-amd-amdhsa--gfx950\n")
+    rec = digest.digest(str(asm))["f"]
+    assert rec["mnemonics"] == {"s_nop": 2, "s_endpgm": 1} and rec["total"] == 3
+    assert (rec["vgpr_count"], rec["sgpr_count"], rec["sgpr_spill_count"], rec["private_segment_fixed_size"]) == (3, 8, 5, 0)
+
+
 def _shell_macros(shell):
     """({macro: default file} of the `#ifndef NAME` / `#define NAME "file"` pairs of body / consts includes, [macros the shell #includes])."""
     text = open(os.path.join(CSRC, shell)).read()
