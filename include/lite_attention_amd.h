@@ -24,6 +24,8 @@
  *                            one-pass fp64 error statistics of an output against a reference output, per (batch, head, row bin)
  *   la_qk_prep            <- nothing: the reference starts at the attention call; what a Wan2.x block runs on q and k just before it
  *                            (RMSNorm, 3-axis RoPE, the cast to bf16: README.md:268-323 leaves them to eager torch) in one pass
+ *   la_qk_prep_fp8        <- nothing: the same pass with an e4m3 result, per-head descales and the running per-head amax a scale
+ *                            is made from - the producer of the fp8 forward's operands (q, k, and v with LA_NORM_NONE)
  *
  * Rules of the boundary:
  *   - plain C: pointers, sizes, scalars. No torch types, no C++ types, no exceptions.
@@ -43,7 +45,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error and la_qk_prep were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep and la_qk_prep_fp8 were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -370,6 +372,49 @@ typedef struct la_qk_prep_args {
     int32_t axis_pairs[3];
 } la_qk_prep_args;
 int la_qk_prep(const la_qk_prep_args* args, void* stream);
+
+/* la_qk_prep with an e4m3 (OCP e4m3fn, LA_DTYPE_FP8_E4M3) result and the per-head scales the fp8 la_fwd takes: the producer of its
+ * operands. Nothing is quantized inside la_fwd; the caller owns the scales and hands la_fwd the SAME descale tensors it gave here.
+ * With y the fp32 value la_qk_prep would round (same norm, weight and rope, in the same order) and g = h / heads_per_scale:
+ *   amax[b][g]  = max(amax[b][g], |y|)   over the unscaled y. A RUNNING maximum into the caller's fp32 buffer (zero it for a fresh one),
+ *                 taken as the unsigned maximum of the bit pattern of |y|: independent of the order (two launches agree bitwise), and
+ *                 a NaN anywhere in the group makes amax[b][g] NaN. One global atomic per (group, batch) and workgroup.
+ *   out         = e4m3_rne(clamp(y * (1 / descale[b][g]), -448, +448))   round to nearest even; the clamp is explicit (no mode bit
+ *                 matters) and keeps a NaN a NaN; descale == NULL reads as 1.0; the reciprocal is one IEEE division per group. The
+ *                 cast is torch's float8_e4m3fn cast.
+ *   out == NULL   the amax pass alone: x is read once, nothing but amax is written. Amax pass + quantizing pass = exact "current
+ *                 scaling" in two reads and one 1-byte write; with the previous step's amax ("delayed scaling") one read, one write.
+ * heads_per_scale: 1 for k and v, H_q / H_kv for q - la_fwd's q / k / v descales are per (batch, kv-head). LA_NORM_NONE without tables
+ * is the V form (scale, clamp, cast, amax). descale and amax are fp32 [batch, num_heads / heads_per_scale] addressed by their strides
+ * (in elements). A descale that is zero, negative or not finite is the caller's error and is NOT detected.
+ * out must not overlap x (the element sizes differ: there is no in-place form); an overlap is the caller's error and is not detected.
+ * Errors (all before any HIP call), in the codes of la_qk_prep: NULL args / x, or out and amax both NULL, LA_ERR_NULL_ARG; in_dtype
+ * LA_ERR_DTYPE; heads_per_scale < 1 or not a divisor of num_heads LA_ERR_SHAPE; a negative descale / amax stride, or one of the two
+ * pointers off a 4-byte boundary, LA_ERR_STRIDE; more than 1024 heads LA_ERR_UNSUPPORTED (a workgroup keeps the scale and the running
+ * maximum of every head in LDS); an out pointer or used out stride that takes a row, head or batch start off an 8-byte boundary
+ * LA_ERR_STRIDE; everything else (norm_mode, sizes, head_dim, the x alignment rules, weight, tables, positions) as la_qk_prep. */
+typedef struct la_qk_prep_fp8_args {
+    uint32_t struct_size;        /* = sizeof(la_qk_prep_fp8_args)                                 */
+    int32_t  in_dtype;           /* la_dtype of x: LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32  */
+    int32_t  norm_mode;          /* la_norm_mode                                                  */
+    int32_t  heads_per_scale;    /* heads that share one descale / amax element; divides num_heads */
+    const void* x;               /* (B, S, H, D), last dimension contiguous                       */
+    void*       out;             /* e4m3 (B, S, H, D), last dimension contiguous; NULL: amax only */
+    int64_t x_batch_stride, x_row_stride, x_head_stride;          /* in elements                  */
+    int64_t out_batch_stride, out_row_stride, out_head_stride;
+    int32_t batch, seqlen, num_heads, head_dim;
+    const float* weight;         /* fp32 [H*D] (LA_NORM_TOKEN) or [D] (LA_NORM_HEAD); NULL = ones  */
+    float   eps;
+    int32_t pos_offset;          /* position of row 0 on the (e0, e1, e2) grid, row-major         */
+    const float* rope_table[3];  /* fp32 [axis_extent[a], axis_pairs[a], 2] = (cos, sin)           */
+    int32_t axis_extent[3];
+    int32_t axis_pairs[3];
+    const float* descale;        /* fp32 [B, H / heads_per_scale] by the strides below; NULL = 1.0 */
+    int64_t descale_batch_stride, descale_head_stride;
+    float*  amax;                /* fp32 [B, H / heads_per_scale]; NULL = not wanted (then out must be given) */
+    int64_t amax_batch_stride, amax_head_stride;
+} la_qk_prep_fp8_args;
+int la_qk_prep_fp8(const la_qk_prep_fp8_args* args, void* stream);
 
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)

@@ -23,6 +23,7 @@ if not _BUILDING:
                          flash_blocksparse_attn_func, flash_blocksparse_attn_qkvpacked_func)
     from .calibration import ErrorStats, calibrate_error_schedule, calibrate_threshold, output_error  # noqa: E402
     from .qk_prep import RopeTables, qk_prep, qk_prep_reference, rope_tables, wan_rope_parts  # noqa: E402
+    from .qk_prep import E4m3Scales, descale_from_amax, qk_prep_amax, qk_prep_fp8, qk_prep_fp8_reference  # noqa: E402
     from .parallel import (HeadShardedLiteAttention, RingSeqParallelLiteAttention,  # noqa: E402
                            UlyssesLiteAttention)
 
@@ -31,4 +32,5 @@ __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flas
            "flash_blocksparse_attn_func", "flash_blocksparse_attn_qkvpacked_func", "blockmask_to_skip_lists", "calibrate_threshold",
            "calibrate_error_schedule", "output_error", "ErrorStats",
            "qk_prep", "qk_prep_reference", "rope_tables", "wan_rope_parts", "RopeTables",
+           "qk_prep_fp8", "qk_prep_amax", "descale_from_amax", "qk_prep_fp8_reference", "E4m3Scales",
            "HeadShardedLiteAttention", "UlyssesLiteAttention", "RingSeqParallelLiteAttention", "__version__"]

@@ -26,7 +26,7 @@ LA_ERR_Q_WINDOW = -13
 EXPORTED_SYMBOLS = (
     "la_abi_version", "la_get_tile_sizes", "la_get_tile_sizes_ex", "la_fwd", "la_fwd_workspace_bytes", "la_skip_list_stats", "la_combine",
     "la_status_string", "la_last_hip_error", "la_blockmask_to_lists", "la_device_slots", "la_build_info", "la_combine_list",
-    "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error", "la_qk_prep",
+    "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error", "la_qk_prep", "la_qk_prep_fp8",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -71,6 +71,21 @@ class LaQkPrepArgs(ctypes.Structure):
         ("batch", ctypes.c_int32), ("seqlen", ctypes.c_int32), ("num_heads", ctypes.c_int32), ("head_dim", ctypes.c_int32),
         ("weight", ctypes.c_void_p), ("eps", ctypes.c_float), ("pos_offset", ctypes.c_int32),
         ("rope_table", ctypes.c_void_p * 3), ("axis_extent", ctypes.c_int32 * 3), ("axis_pairs", ctypes.c_int32 * 3),
+    ]
+
+
+class LaQkPrepFp8Args(ctypes.Structure):
+    """Mirror of ``la_qk_prep_fp8_args`` (field order and types must match the header)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("in_dtype", ctypes.c_int32), ("norm_mode", ctypes.c_int32), ("heads_per_scale", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("x_batch_stride", ctypes.c_int64), ("x_row_stride", ctypes.c_int64), ("x_head_stride", ctypes.c_int64),
+        ("out_batch_stride", ctypes.c_int64), ("out_row_stride", ctypes.c_int64), ("out_head_stride", ctypes.c_int64),
+        ("batch", ctypes.c_int32), ("seqlen", ctypes.c_int32), ("num_heads", ctypes.c_int32), ("head_dim", ctypes.c_int32),
+        ("weight", ctypes.c_void_p), ("eps", ctypes.c_float), ("pos_offset", ctypes.c_int32),
+        ("rope_table", ctypes.c_void_p * 3), ("axis_extent", ctypes.c_int32 * 3), ("axis_pairs", ctypes.c_int32 * 3),
+        ("descale", ctypes.c_void_p), ("descale_batch_stride", ctypes.c_int64), ("descale_head_stride", ctypes.c_int64),
+        ("amax", ctypes.c_void_p), ("amax_batch_stride", ctypes.c_int64), ("amax_head_stride", ctypes.c_int64),
     ]
 
 
@@ -189,6 +204,8 @@ def load() -> ctypes.CDLL:
     lib.la_output_error.restype = ctypes.c_int
     lib.la_qk_prep.argtypes = [ctypes.POINTER(LaQkPrepArgs), ctypes.c_void_p]
     lib.la_qk_prep.restype = ctypes.c_int
+    lib.la_qk_prep_fp8.argtypes = [ctypes.POINTER(LaQkPrepFp8Args), ctypes.c_void_p]
+    lib.la_qk_prep_fp8.restype = ctypes.c_int
     lib.la_device_slots.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.la_device_slots.restype = ctypes.c_int
     lib.la_status_string.argtypes = [ctypes.c_int]

@@ -487,12 +487,12 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
     return LA_OK;
 }
 
-int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_args)) return LA_ERR_STRUCT_SIZE;
-    if (!a->x || !a->out) return LA_ERR_NULL_ARG;
-    const bool in_ok = a->in_dtype == LA_DTYPE_BF16 || a->in_dtype == LA_DTYPE_FP16 || a->in_dtype == LA_DTYPE_FP32;
-    if (!in_ok || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
+}  // extern "C"
+
+// What la_qk_prep and la_qk_prep_fp8 check alike, from the norm mode on, and the kernel parameters they share. A: either argument
+// struct (the same field names). out_dtype: la_dtype of out (LA_DTYPE_FP8_E4M3: 8 elements = 8 bytes, row starts on 8-byte boundaries).
+template <class A>
+static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParams& p) {
     if (a->norm_mode != LA_NORM_NONE && a->norm_mode != LA_NORM_TOKEN && a->norm_mode != LA_NORM_HEAD) return LA_ERR_UNSUPPORTED;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
@@ -501,13 +501,15 @@ int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
     if (a->norm_mode == LA_NORM_TOKEN && static_cast<int64_t>(a->num_heads) * a->head_dim > 16384) return LA_ERR_UNSUPPORTED;
     // every row start is a 16-byte boundary: the pointer, and every stride that is used, in units of 16 / element size; the kernels
     // keep a chunk's offset from its token's start in 32 bits
-    const auto strides_ok = [&](const void* p, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
+    // (e4m3: 8 elements are 8 bytes, stored at once - an 8-byte boundary)
+    const auto strides_ok = [&](const void* ptr, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
         const int64_t unit = d == LA_DTYPE_FP32 ? 4 : 8;
-        return bs >= 0 && rs >= 0 && hs >= 0 && aligned16(p) && (a->seqlen == 1 || rs % unit == 0) && (a->num_heads == 1 || hs % unit == 0) &&
+        const bool ptr_ok = d == LA_DTYPE_FP8_E4M3 ? (reinterpret_cast<uintptr_t>(ptr) & 7u) == 0 : aligned16(ptr);
+        return bs >= 0 && rs >= 0 && hs >= 0 && ptr_ok && (a->seqlen == 1 || rs % unit == 0) && (a->num_heads == 1 || hs % unit == 0) &&
                (a->batch == 1 || bs % unit == 0) && hs <= (0x7fffffffLL - a->head_dim) / a->num_heads;
     };
     if (!strides_ok(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride) ||
-        !strides_ok(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride)) return LA_ERR_STRIDE;
+        (a->out && !strides_ok(a->out, out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride))) return LA_ERR_STRIDE;
     if (a->weight && !aligned16(a->weight)) return LA_ERR_STRIDE;                 // read 16 bytes at a time
     for (int i = 0; i < 3; ++i)
         if (reinterpret_cast<uintptr_t>(a->rope_table[i]) & 7u) return LA_ERR_STRIDE;      // (cos, sin) is one 8-byte load
@@ -530,7 +532,7 @@ int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
         }
         if (positions > 0x7fffffffLL || static_cast<int64_t>(a->pos_offset) + a->seqlen > positions) return LA_ERR_SHAPE;
     }
-    la::QkPrepParams p = {};
+    p = {};
     p.x = a->x; p.out = a->out; p.weight = a->norm_mode == LA_NORM_NONE ? nullptr : a->weight;
     p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
     p.o_bs = a->out_batch_stride; p.o_rs = a->out_row_stride; p.o_hs = a->out_head_stride;
@@ -540,7 +542,42 @@ int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
     p.ext1 = rotate ? a->axis_extent[1] : 1; p.ext2 = rotate ? a->axis_extent[2] : 1;
     for (int i = 0; i < 3; ++i) { p.table[i] = a->rope_table[i]; p.pairs[i] = rotate ? a->axis_pairs[i] : 0; }
     p.pos_offset = a->pos_offset; p.eps = a->eps;
+    return LA_OK;
+}
+
+extern "C" {
+
+int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || !a->out) return LA_ERR_NULL_ARG;
+    const bool in_ok = a->in_dtype == LA_DTYPE_BF16 || a->in_dtype == LA_DTYPE_FP16 || a->in_dtype == LA_DTYPE_FP32;
+    if (!in_ok || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
+    la::QkPrepParams p;
+    const int rc = qk_prep_check_and_fill(a, a->out_dtype, p);
+    if (rc != LA_OK) return rc;
     const hipError_t err = la::launch_qk_prep(p, a->in_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
+int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_fp8_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || (!a->out && !a->amax)) return LA_ERR_NULL_ARG;
+    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (a->num_heads <= 0 || a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
+    if (a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 || a->amax_head_stride < 0 ||
+        ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u)) return LA_ERR_STRIDE;
+    la::QkPrepParams p;
+    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, p);
+    if (rc != LA_OK) return rc;
+    if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;      // a workgroup keeps every head's scale and maximum in LDS
+    p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
+    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
+    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
+    p.heads_per_scale = a->heads_per_scale;
+    const hipError_t err = la::launch_qk_prep_fp8(p, a->in_dtype, static_cast<hipStream_t>(stream_));
     if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
     return LA_OK;
 }

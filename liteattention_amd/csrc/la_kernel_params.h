@@ -127,7 +127,14 @@ struct QkPrepParams {
     int pairs[3];
     int pos_offset;
     float eps;
+    // la_qk_prep_fp8 only (la_qk_prep leaves them zero): the e4m3 output form. Scale group of head h = h / heads_per_scale.
+    const float* descale;        // [batch, groups] by the strides below; NULL = 1.0. out = e4m3(clamp(y * (1 / descale), +-448))
+    float* amax;                 // [batch, groups] running maximum of |y| (as the unsigned maximum of its bit pattern); NULL = not wanted
+    int64_t ds_bs, ds_hs, am_bs, am_hs;
+    int heads_per_scale;         // >= 1, divides num_heads; num_heads <= kQkPrepScaleSlots
 };
+constexpr int kQkPrepScaleSlots = 1024;      // heads whose scale and running amax a workgroup keeps in LDS (la_qk_prep_fp8)
 hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream);   // dtypes: 0 bf16, 1 fp16, 3 fp32 (in only)
+hipError_t launch_qk_prep_fp8(const QkPrepParams& p, int in_dtype, hipStream_t stream);      // out e4m3; p.out == NULL: the amax pass alone
 
 }  // namespace la

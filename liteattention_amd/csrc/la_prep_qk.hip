@@ -33,6 +33,17 @@
 // Arithmetic: r = rsqrt(sum(x^2) / n + eps) with the sum in fp32 as in the torch expression it replaces (a token whose squares
 // overflow fp32 gives r = 0 there and here); y = (x * r) * w; out = (y0 cos - y1 sin, y0 sin + y1 cos). One fewer rounding than Wan's
 // `.type_as(x) * weight` followed by a rope that rounds again: DESIGN.md §7.
+//
+// The e4m3 output form (la_qk_prep_fp8; PrepPolicy<1>: quantize, PrepPolicy<2>: the amax pass alone, nothing stored). y above is
+// computed by the same instructions in the same order; two steps follow it:
+//  * amax: the unsigned maximum over the bit patterns of |y| (order-free; any NaN wins), per lane in registers (token kernel) or per
+//    head over its G lanes (head kernel), then per head in LDS with ds atomics, and ONE global atomicMax per (scale group, batch) when
+//    the workgroup leaves a batch. For that the workgroup must leave a batch as a whole: the loop of these forms runs over ROUNDS of
+//    4 consecutive tokens of ONE batch (one token when the workgroup shares it), the same trips for every thread, batches in rising
+//    order; a round past the end of its batch keeps its spare waves idle (they load, stage and store nothing).
+//  * quantize: z = y * inv, inv = 1 / descale one IEEE division per group when the workgroup enters a batch (kept per head in LDS);
+//    z is clamped to +-448 by two compares that a NaN fails, so a NaN stays a NaN; then the hardware's round-to-nearest-even e4m3
+//    conversion (OCP e4m3fn on gfx950) of values that cannot overflow: no mode bit matters. 8 elements = 8 bytes, one 8-byte store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,6 +55,7 @@ namespace {
 typedef unsigned int pq_u32x4 __attribute__((ext_vector_type(4)));
 typedef float pq_f32x4 __attribute__((ext_vector_type(4)));
 typedef float pq_f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int pq_u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 pq_f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 pq_bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -107,6 +119,62 @@ template <> struct PrepStore<1> {
         *reinterpret_cast<pq_f16x8*>(static_cast<uint16_t*>(base) + off) = w;
     }
 };
+
+template <> struct PrepStore<2> {           // e4m3: y is inside +-448 or NaN (scale_clamp8); 8 bytes, one 8-byte store
+    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+        *reinterpret_cast<pq_u32x2*>(static_cast<uint8_t*>(base) + off) = pq_u32x2{static_cast<unsigned>(lo), static_cast<unsigned>(hi)};
+    }
+};
+
+// What follows y: 0 the 16-bit store of la_qk_prep; 1 amax + scale + clamp + e4m3 store; 2 amax alone (x is read, nothing is written)
+template <int MODE> struct PrepPolicy {
+    static constexpr bool kScaled = MODE != 0;                     // per-head LDS tables, the loop over rounds
+    static constexpr bool kStore = MODE != 2;
+};
+
+__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+
+__device__ __forceinline__ unsigned absmax8(const float (&y)[8]) {
+    unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m = umax(m, __float_as_uint(y[i]) & 0x7fffffffu);
+    return m;
+}
+
+__device__ __forceinline__ void scale_clamp8(float (&y)[8], float inv) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        float z = y[i] * inv;
+        z = z > 448.f ? 448.f : z;                                 // a NaN fails both compares and stays
+        y[i] = z < -448.f ? -448.f : z;
+    }
+}
+
+// The workgroup leaves batch old_b (-1: none) and enters new_b (-1: none): the maxima its waves collected per head in am_tab go out,
+// one atomic per scale group, and the reciprocal scales of new_b come in. Every thread of the workgroup calls it at the same trip.
+template <bool STORE>
+__device__ __forceinline__ void scale_turn(const QkPrepParams& p, unsigned* am_tab, float* inv_tab, int64_t old_b, int64_t new_b) {
+    __syncthreads();                                               // am_tab is complete, inv_tab no longer read
+    const int hps = p.heads_per_scale, groups = p.num_heads / hps;
+    for (int g = threadIdx.x; g < groups; g += 256) {
+        unsigned m = 0;
+        for (int j = 0; j < hps; ++j) {
+            m = umax(m, am_tab[g * hps + j]);
+            am_tab[g * hps + j] = 0;
+        }
+        if (old_b >= 0 && p.amax && m) atomicMax(reinterpret_cast<unsigned*>(p.amax + old_b * p.am_bs + g * p.am_hs), m);
+        if (STORE && new_b >= 0) {
+            const float inv = p.descale ? __fdiv_rn(1.f, p.descale[new_b * p.ds_bs + g * p.ds_hs]) : 1.f;
+            for (int j = 0; j < hps; ++j) inv_tab[g * hps + j] = inv;
+        }
+    }
+    __syncthreads();
+}
 
 __device__ __forceinline__ float sum_squares8(const float (&v)[8]) {
     return ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) + ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
@@ -173,10 +241,13 @@ __device__ __forceinline__ void scale_rotate8(float (&y)[8], float r, const floa
 
 // WG false: one wave per token. WG true (H * D > 5120): the four waves of the workgroup share one token, so that a lane still keeps
 // at most 10 chunks; the four partial sums meet in LDS and are added in a fixed order.
-template <int DT_IN, int DT_OUT, int NCH, bool WG>
+template <int DT_IN, int DT_OUT, int NCH, bool WG, int MODE>
 __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParams p) {
+    typedef PrepPolicy<MODE> POL;
     __shared__ __attribute__((aligned(16))) float rot_lds[4][2 * kRotRow];
     __shared__ float part[4];
+    __shared__ unsigned am_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
+    __shared__ float inv_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
     typedef typename PrepLoad<DT_IN>::raw raw_t;
     constexpr int kLanes = WG ? 256 : 64;                          // lanes that share a token
     const int lane = threadIdx.x & 63;
@@ -191,10 +262,16 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
     // chunk i of this lane = chunk first + kLanes i of the token: its first element inside its head (-1: no such chunk) and its
     // element offsets from the token's start in x and out (below 2^31, checked by la_qk_prep)
     int col[NCH], x_off[NCH], o_off[NCH];
+    unsigned am[NCH];                                              // e4m3 forms: this lane's running maxima of the current batch, per chunk
+    // ... and the head of chunk i, recomputed where it is needed (a register per chunk costs the e4m3 forms a wave of occupancy):
+    // floor((c8 + 0.5) / D) in fp32 is exact for c8 < 16384, D <= 256 (the quotient stays 0.5 / 256 away from an integer)
+    const float rcp_d = 1.f / static_cast<float>(D);
+    const auto head_of = [&](int i) { return static_cast<int>((static_cast<float>((first + kLanes * i) * 8) + 0.5f) * rcp_d); };
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c = first + kLanes * i;
         const int head = (c * 8) / D;
+        am[i] = 0;
         col[i] = c < nchunks ? c * 8 - head * D : -1;
         x_off[i] = static_cast<int>(head * p.x_hs) + col[i];
         o_off[i] = static_cast<int>(head * p.o_hs) + col[i];
@@ -204,14 +281,39 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
 
     const int64_t t0 = WG ? static_cast<int64_t>(blockIdx.x) : static_cast<int64_t>(blockIdx.x) * 4 + wave;
     const int64_t t_step = WG ? static_cast<int64_t>(gridDim.x) : static_cast<int64_t>(gridDim.x) * 4;
-    for (int64_t t = t0; t < p.tokens; t += t_step) {              // WG: the same trips for every thread of the workgroup
-        const int64_t b = t / p.seqlen;
-        const int s = static_cast<int>(t - b * p.seqlen);
+    // e4m3 forms: t counts rounds (kPerRound consecutive tokens of one batch), the same trips for every thread
+    constexpr int kPerRound = WG ? 1 : 4;
+    const int64_t rpb = (p.seqlen + kPerRound - 1) / kPerRound;
+    const int64_t t_end = POL::kScaled ? p.tokens / p.seqlen * rpb : p.tokens;
+    int64_t cur_b = -1;
+    if (POL::kScaled)
+        for (int h = threadIdx.x; h < p.num_heads; h += 256) am_tab[h] = 0;      // (the first scale_turn starts with a barrier)
+    for (int64_t t = POL::kScaled ? static_cast<int64_t>(blockIdx.x) : t0; t < t_end; t += POL::kScaled ? static_cast<int64_t>(gridDim.x) : t_step) {
+        int64_t b;                                                 // WG: the same trips for every thread of the workgroup
+        int s;
+        bool live = true;                                          // false: a spare wave of a batch's last round
+        if constexpr (POL::kScaled) {
+            b = t / rpb;
+            s = static_cast<int>(t - b * rpb) * kPerRound + (WG ? 0 : wave);
+            live = s < p.seqlen;
+            if (b != cur_b) {
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    if (col[i] >= 0 && am[i]) atomicMax(&am_tab[head_of(i)], am[i]);
+                    am[i] = 0;
+                }
+                scale_turn<POL::kStore>(p, am_tab, inv_tab, cur_b, b);
+                cur_b = b;
+            }
+        } else {
+            b = t / p.seqlen;
+            s = static_cast<int>(t - b * p.seqlen);
+        }
         const int64_t x_tok = b * p.x_bs + s * p.x_rs, o_tok = b * p.o_bs + s * p.o_rs;
         raw_t v[NCH];                                              // the token: it stays in registers until it is stored
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) v[i] = col[i] >= 0 ? PrepLoad<DT_IN>::load(p.x, x_tok + x_off[i]) : PrepLoad<DT_IN>::zero();
-        if (rotate) rs.stage(p, p.pos_offset + s, lane, row);
+        for (int i = 0; i < NCH; ++i) v[i] = col[i] >= 0 && live ? PrepLoad<DT_IN>::load(p.x, x_tok + x_off[i]) : PrepLoad<DT_IN>::zero();
+        if (rotate && live) rs.stage(p, p.pos_offset + s, lane, row);
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -231,7 +333,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
         if (rotate) wave_lds_fence();
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
-            if (col[i] >= 0) {
+            if (col[i] >= 0 && live) {
                 float y[8], w[8];
                 PrepLoad<DT_IN>::to_float(v[i], y);
 #pragma unroll
@@ -239,16 +341,29 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
                 if (weight) load_weight8(weight, (first + kLanes * i) * 8, w);      // 4 H D bytes every token rereads: they stay in L1 / L2
                 if (rotate) scale_rotate8<true>(y, r, w, col[i], rot_pairs, row);
                 else scale_rotate8<false>(y, r, w, col[i], rot_pairs, row);
-                PrepStore<DT_OUT>::store8(p.out, o_tok + o_off[i], y);
+                if constexpr (POL::kScaled) {
+                    am[i] = umax(am[i], absmax8(y));
+                    if constexpr (POL::kStore) scale_clamp8(y, inv_tab[head_of(i)]);
+                }
+                if constexpr (POL::kStore) PrepStore<DT_OUT>::store8(p.out, o_tok + o_off[i], y);
             }
         }
         if (rotate) wave_lds_fence();                              // the next token's row is staged behind this token's reads
     }
+    if constexpr (POL::kScaled) {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i)
+            if (col[i] >= 0 && am[i]) atomicMax(&am_tab[head_of(i)], am[i]);
+        scale_turn<false>(p, am_tab, inv_tab, cur_b, -1);
+    }
 }
 
-template <int DT_IN, int DT_OUT>
+template <int DT_IN, int DT_OUT, int MODE>
 __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams p, int group_log2) {
+    typedef PrepPolicy<MODE> POL;
     __shared__ __attribute__((aligned(16))) float rot_lds[4][2 * kRotRow];
+    __shared__ unsigned am_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
+    __shared__ float inv_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int D = p.head_dim, H = p.num_heads;
@@ -266,12 +381,32 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
     RotStage rs;
     rs.init(p, lane);
 
-    for (int64_t t = static_cast<int64_t>(blockIdx.x) * 4 + wave; t < p.tokens; t += static_cast<int64_t>(gridDim.x) * 4) {
-        const int64_t b = t / p.seqlen;
-        const int s = static_cast<int>(t - b * p.seqlen);
+    // e4m3 forms: t counts rounds (4 consecutive tokens of one batch), the same trips for every thread
+    const int64_t rpb = (p.seqlen + 3) / 4;
+    const int64_t t_end = POL::kScaled ? p.tokens / p.seqlen * rpb : p.tokens;
+    int64_t cur_b = -1;
+    if (POL::kScaled)
+        for (int h = threadIdx.x; h < H; h += 256) am_tab[h] = 0;                // (the first scale_turn starts with a barrier)
+    for (int64_t t = POL::kScaled ? static_cast<int64_t>(blockIdx.x) : static_cast<int64_t>(blockIdx.x) * 4 + wave; t < t_end;
+         t += POL::kScaled ? static_cast<int64_t>(gridDim.x) : static_cast<int64_t>(gridDim.x) * 4) {
+        int64_t b;
+        int s;
+        bool live = true;                                          // false: a spare wave of a batch's last round
+        if constexpr (POL::kScaled) {
+            b = t / rpb;
+            s = static_cast<int>(t - b * rpb) * 4 + wave;
+            live = s < p.seqlen;
+            if (b != cur_b) {
+                scale_turn<POL::kStore>(p, am_tab, inv_tab, cur_b, b);
+                cur_b = b;
+            }
+        } else {
+            b = t / p.seqlen;
+            s = static_cast<int>(t - b * p.seqlen);
+        }
         const int64_t x_tok = b * p.x_bs + s * p.x_rs + e, o_tok = b * p.o_bs + s * p.o_rs + e;
         if (rotate) {
-            rs.stage(p, p.pos_offset + s, lane, row);
+            if (live) rs.stage(p, p.pos_offset + s, lane, row);
             wave_lds_fence();
         }
         for (int h0 = 0; h0 < H; h0 += heads_per_pass * kHeadUnroll) {
@@ -279,7 +414,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
 #pragma unroll
             for (int u = 0; u < kHeadUnroll; ++u) {
                 const int h = h0 + u * heads_per_pass + sub;
-                raw[u] = col_ok && h < H ? PrepLoad<DT_IN>::load(p.x, x_tok + h * p.x_hs) : PrepLoad<DT_IN>::zero();
+                raw[u] = col_ok && h < H && live ? PrepLoad<DT_IN>::load(p.x, x_tok + h * p.x_hs) : PrepLoad<DT_IN>::zero();
             }
 #pragma unroll
             for (int u = 0; u < kHeadUnroll; ++u) {
@@ -291,15 +426,25 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
                     for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
                     r = rsqrtf(ss / static_cast<float>(D) + p.eps);
                 }
-                if (col_ok && h < H) {
+                unsigned m = 0;
+                if (col_ok && h < H && live) {
                     if (rotate) scale_rotate8<true>(y, r, w, e, rot_pairs, row);
                     else scale_rotate8<false>(y, r, w, e, rot_pairs, row);
-                    PrepStore<DT_OUT>::store8(p.out, o_tok + h * p.o_hs, y);
+                    if constexpr (POL::kScaled) {
+                        m = absmax8(y);
+                        if constexpr (POL::kStore) scale_clamp8(y, inv_tab[h]);
+                    }
+                    if constexpr (POL::kStore) PrepStore<DT_OUT>::store8(p.out, o_tok + h * p.o_hs, y);
+                }
+                if constexpr (POL::kScaled) {                      // uniform: the head's maximum over its G lanes, one ds atomic per head
+                    for (int off = G >> 1; off > 0; off >>= 1) m = umax(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), off)));
+                    if ((lane & (G - 1)) == 0 && m) atomicMax(&am_tab[h], m);
                 }
             }
         }
         if (rotate) wave_lds_fence();
     }
+    if constexpr (POL::kScaled) scale_turn<false>(p, am_tab, inv_tab, cur_b, -1);
 }
 
 dim3 grid_for(int64_t tokens, int tokens_per_block) {
@@ -307,12 +452,18 @@ dim3 grid_for(int64_t tokens, int tokens_per_block) {
     return dim3(static_cast<unsigned>(blocks < kMaxGrid ? blocks : kMaxGrid));
 }
 
-template <int DT_IN, int DT_OUT>
+// workgroups of an e4m3 form: one per round of `per_round` tokens of one batch
+dim3 grid_for_rounds(const QkPrepParams& p, int per_round) {
+    return grid_for(p.tokens / p.seqlen * ((p.seqlen + per_round - 1) / per_round), 1);
+}
+
+template <int DT_IN, int DT_OUT, int MODE>
 void launch_token(const QkPrepParams& p, hipStream_t stream) {
     const int nchunks = p.num_heads * p.head_dim / 8;              // <= 2048, checked by la_qk_prep
     const int need = (nchunks + 63) / 64;                          // chunks per lane with one wave per token
 #define LA_QK_PREP_TOKEN(NCH, WG) \
-    hipLaunchKernelGGL((la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG>), grid_for(p.tokens, WG ? 1 : 4), dim3(256), 0, stream, p)
+    hipLaunchKernelGGL((la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>), \
+                       MODE ? grid_for_rounds(p, WG ? 1 : 4) : grid_for(p.tokens, WG ? 1 : 4), dim3(256), 0, stream, p)
     if (need <= 1) LA_QK_PREP_TOKEN(1, false);
     else if (need <= 2) LA_QK_PREP_TOKEN(2, false);
     else if (need <= 4) LA_QK_PREP_TOKEN(4, false);
@@ -323,21 +474,28 @@ void launch_token(const QkPrepParams& p, hipStream_t stream) {
 #undef LA_QK_PREP_TOKEN
 }
 
-template <int DT_IN, int DT_OUT>
+template <int DT_IN, int DT_OUT, int MODE>
 void launch_typed(const QkPrepParams& p, hipStream_t stream) {
     if (p.norm_mode == 1) {
-        launch_token<DT_IN, DT_OUT>(p, stream);
+        launch_token<DT_IN, DT_OUT, MODE>(p, stream);
     } else {
         int group_log2 = 0;
         while ((8 << group_log2) < p.head_dim) ++group_log2;       // head_dim <= 256: at most 5
-        hipLaunchKernelGGL((la_qk_prep_head_kernel<DT_IN, DT_OUT>), grid_for(p.tokens, 4), dim3(256), 0, stream, p, group_log2);
+        hipLaunchKernelGGL((la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>), MODE ? grid_for_rounds(p, 4) : grid_for(p.tokens, 4), dim3(256), 0,
+                           stream, p, group_log2);
     }
 }
 
 template <int DT_IN>
 void launch_in(const QkPrepParams& p, int out_dtype, hipStream_t stream) {
-    if (out_dtype == 0) launch_typed<DT_IN, 0>(p, stream);
-    else launch_typed<DT_IN, 1>(p, stream);
+    if (out_dtype == 0) launch_typed<DT_IN, 0, 0>(p, stream);
+    else launch_typed<DT_IN, 1, 0>(p, stream);
+}
+
+template <int DT_IN>
+void launch_in_fp8(const QkPrepParams& p, hipStream_t stream) {
+    if (p.out) launch_typed<DT_IN, 2, 1>(p, stream);
+    else launch_typed<DT_IN, 2, 2>(p, stream);
 }
 
 }  // namespace
@@ -347,6 +505,14 @@ hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hi
     if (in_dtype == 0) launch_in<0>(p, out_dtype, stream);
     else if (in_dtype == 1) launch_in<1>(p, out_dtype, stream);
     else launch_in<3>(p, out_dtype, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_qk_prep_fp8(const QkPrepParams& p, int in_dtype, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (in_dtype == 0) launch_in_fp8<0>(p, stream);
+    else if (in_dtype == 1) launch_in_fp8<1>(p, stream);
+    else launch_in_fp8<3>(p, stream);
     return hipGetLastError();
 }
 

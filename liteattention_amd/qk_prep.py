@@ -5,7 +5,11 @@ cast to bf16 / fp16 (``la_qk_prep``), in place of the ten-odd eager passes with 
     q = qk_prep(q_proj.view(b, s, n, d), norm_q.weight, norm_q.eps, tables)      # bf16, ready for LiteAttention
     k = qk_prep(k_proj.view(b, s, n, d), norm_k.weight, norm_k.eps, tables)
 
-``qk_prep_reference`` is the same formula in torch fp64, for tests and for users who want to check."""
+``qk_prep_reference`` is the same formula in torch fp64, for tests and for users who want to check.
+
+The e4m3 form (``la_qk_prep_fp8``) is the producer of the fp8 forward's operands: ``qk_prep_fp8`` (scale, clamp, cast to
+``float8_e4m3fn`` at the store), ``qk_prep_amax`` (the per-head amax pass alone), ``descale_from_amax`` and ``E4m3Scales``, which keeps
+the buffers of one tensor and returns ``(x8, descale)``; the descales then go into the attention call as ``q/k/v_descale``."""
 from __future__ import annotations
 
 import ctypes
@@ -192,6 +196,175 @@ def qk_prep_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, ep
     return y if out_dtype is None else y.to(out_dtype)
 
 
+# ---- the e4m3 form: la_qk_prep_fp8 -----------------------------------------------------------------------------------------------------------
+E4M3_MAX = 448.0
+_TINY = 2.0 ** -100        # the smallest amax a descale is made from: its reciprocal, 448 / tiny / margin, stays finite in fp32 (0 * it = 0)
+
+
+def _qk_prep_fp8_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, descale, amax, heads_per_scale, out, store):
+    """One ``la_qk_prep_fp8`` call. ``store``: quantize into ``out`` (allocated when None); otherwise the amax pass alone."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise ValueError("x must live on a GPU (there is no CPU path; qk_prep_fp8_reference is the formula in torch)")
+    if x.dtype not in _IN_DTYPES:
+        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
+    if norm not in _NORM_MODES:
+        raise ValueError('norm: "token", "head" or None')
+    mode = _NORM_MODES[norm]
+    B, S, H, D = x.shape
+    hps = int(heads_per_scale)
+    if hps < 1 or H % hps:
+        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
+    for name, t in (("descale", descale), ("amax_out", amax)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, H // hps) or t.device != x.device):
+            raise ValueError(f"{name} must be fp32 {(B, H // hps)} on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if store:
+        if out is None:
+            out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
+        if out.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    elif amax is None:
+        raise ValueError("the amax pass needs amax_out")
+    if x.stride(-1) != 1 or (store and out.stride(-1) != 1):
+        raise ValueError("the last dimension of x and out must be contiguous")
+    if B * S == 0:
+        return out
+    if weight is not None and mode != _cabi.LA_NORM_NONE:
+        want = H * D if mode == _cabi.LA_NORM_TOKEN else D
+        if weight.dtype != torch.float32 or weight.numel() != want or not weight.is_contiguous() or weight.device != x.device:
+            raise ValueError(f"weight must be contiguous fp32 with {want} elements on {x.device} "
+                             f"(got {weight.dtype}, {tuple(weight.shape)}, {weight.device})")
+    a = _cabi.LaQkPrepFp8Args()
+    a.struct_size = ctypes.sizeof(_cabi.LaQkPrepFp8Args)
+    a.in_dtype, a.norm_mode, a.heads_per_scale = _IN_DTYPES[x.dtype], mode, hps
+    a.x = x.data_ptr()
+    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
+    if store:
+        a.out = out.data_ptr()
+        a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
+        if descale is not None:
+            a.descale, a.descale_batch_stride, a.descale_head_stride = descale.data_ptr(), descale.stride(0), descale.stride(1)
+    if amax is not None:
+        a.amax, a.amax_batch_stride, a.amax_head_stride = amax.data_ptr(), amax.stride(0), amax.stride(1)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
+    a.eps, a.pos_offset = float(eps), int(pos_offset)
+    if tables is not None:
+        for i, (t, n) in enumerate(zip(tables, axis_pairs)):
+            if t.device != x.device:
+                raise ValueError(f"rope table {i} lives on {t.device}, x on {x.device}: build the tables with device=x.device")
+            a.rope_table[i] = t.data_ptr() if n > 0 else None
+            a.axis_extent[i], a.axis_pairs[i] = t.shape[0], n
+    with torch.cuda.device(x.device):
+        rc = _cabi.load().la_qk_prep_fp8(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_qk_prep_fp8: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()}, out strides "
+                           f"{out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, pos_offset {pos_offset}, {S} rows "
+                           f"on a grid of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]})")
+    return out
+
+
+def qk_prep_fp8(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+                norm: Optional[str] = "token", pos_offset: int = 0, *, descale: Optional[torch.Tensor] = None,
+                amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``qk_prep`` with a ``float8_e4m3fn`` result (``la_qk_prep_fp8``): with y the fp32 value ``qk_prep`` would round,
+    ``out = e4m3(clamp(y / descale[b, h // heads_per_scale], -448, 448))``, round to nearest even, a NaN stays a NaN.
+
+    descale          fp32 (B, H // heads_per_scale), the tensor the attention call then takes as ``q_descale`` / ``k_descale`` /
+                     ``v_descale`` (``heads_per_scale`` = 1 for k and v, H_q // H_kv for q); None: 1.0. A descale that is zero, negative
+                     or not finite is the caller's error.
+    amax_out         fp32 (B, H // heads_per_scale): raised to the largest ``|y|`` of its group (a RUNNING maximum: zero it for a fresh
+                     one; a NaN in the group makes it NaN). None: not computed.
+    norm / tables    as ``qk_prep``; ``norm=None`` without tables is the V form (scale, clamp, cast, amax).
+    out              float8_e4m3fn, same shape, rows / heads / batches on 8-byte boundaries; it must not overlap ``x``.
+    No host sync, no allocation besides ``out``; asynchronous on the current stream; captures into a HIP graph like ``qk_prep``."""
+    tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
+    return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True)
+
+
+def qk_prep_amax(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+                 norm: Optional[str] = "token", pos_offset: int = 0, *, amax_out: Optional[torch.Tensor] = None,
+                 heads_per_scale: int = 1) -> torch.Tensor:
+    """The amax pass of ``qk_prep_fp8`` alone: x is read once, nothing else is written. Returns ``amax_out`` (B, H // heads_per_scale)
+    fp32 raised to the largest ``|y|`` of each group - the bits the quantizing call reports; None: a new zeroed tensor."""
+    tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
+    if amax_out is None and x.dim() == 4:
+        amax_out = torch.zeros((x.shape[0], x.shape[2] // max(1, int(heads_per_scale))), dtype=torch.float32, device=x.device)
+    _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, None, amax_out, heads_per_scale, None, False)
+    return amax_out
+
+
+def descale_from_amax(amax: torch.Tensor, margin: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``clamp_min(amax, tiny) * margin / 448``: the descale under which the largest ``|y|`` seen lands on ``448 / margin``. On the
+    device of ``amax``, no host sync, graph-capturable; a NaN amax gives a NaN descale (and NaN outputs: the signal survives)."""
+    out = torch.clamp_min(amax, _TINY, out=out)
+    return out.mul_(float(margin)).div_(E4M3_MAX)
+
+
+def qk_prep_fp8_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+                          norm: Optional[str] = "token", pos_offset: int = 0, *, descale: Optional[torch.Tensor] = None,
+                          heads_per_scale: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The formula of ``qk_prep_fp8`` in torch fp64: ``(clamp(y / descale, -448, 448)`` UNROUNDED, ``amax`` (B, H // heads_per_scale)
+    of the unscaled ``|y|)``, both fp64, with ``y = qk_prep_reference(...)``."""
+    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset)
+    B, S, H, D = y.shape
+    hps = int(heads_per_scale)
+    if hps < 1 or H % hps:
+        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
+    amax = y.abs().reshape(B, S, H // hps, hps * D).amax(dim=(1, 3))          # (amax propagates a NaN, as the kernel's does)
+    if descale is not None:
+        y = y / descale.double().to(y.device).repeat_interleave(hps, dim=1)[:, None, :, None]
+    return y.clamp(-E4M3_MAX, E4M3_MAX), amax
+
+
+class E4m3Scales:
+    """The amax and descale buffers of ONE tensor (q, k or v of one layer) across calls: ``x8, descale = scales(x, ...)`` quantizes
+    with ``qk_prep_fp8`` and returns the descale to hand to the attention call.
+
+    mode "current"   every call runs the amax pass, makes the descale from it and quantizes with it: exact, two reads of x.
+    mode "delayed"   step t quantizes with the descale made from step t - 1's amax and collects its own amax in the same pass: one
+                     read of x. The first call has no history and runs the amax pass. ``margin`` > 1 leaves headroom for the growth
+                     of amax from one step to the next (what exceeds it saturates at +-448).
+    The buffers (amax, descale, the e4m3 result) are allocated by the first call and reused: no host sync, no allocation after
+    it - the result of a call is overwritten by the next one."""
+
+    _amax_pass = staticmethod(qk_prep_amax)
+    _quant_pass = staticmethod(qk_prep_fp8)
+
+    def __init__(self, mode: str = "current", margin: float = 1.0, heads_per_scale: int = 1):
+        if mode not in ("current", "delayed"):
+            raise ValueError('mode: "current" or "delayed"')
+        if not margin > 0:
+            raise ValueError("margin must be positive")
+        self.mode, self.margin, self.heads_per_scale = mode, float(margin), int(heads_per_scale)
+        self.amax = self.descale = self.out = None
+        self.calls = 0
+
+    def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0):
+        B, S, H, D = x.shape
+        hps = self.heads_per_scale
+        first = self.amax is None or self.out.shape != x.shape or self.out.device != x.device
+        if first:
+            self.amax = torch.zeros((B, H // hps), dtype=torch.float32, device=x.device)
+            self.descale = torch.empty_like(self.amax)
+            self.out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
+        if first or self.mode == "current":
+            self.amax.zero_()
+            self._amax_pass(x, weight, eps, tables, norm, pos_offset, amax_out=self.amax, heads_per_scale=hps)
+        descale_from_amax(self.amax, self.margin, out=self.descale)
+        collect = None
+        if self.mode == "delayed":                               # this step's amax, for the next step's descale
+            self.amax.zero_()
+            collect = self.amax
+        self._quant_pass(x, weight, eps, tables, norm, pos_offset, descale=self.descale, amax_out=collect, heads_per_scale=hps,
+                         out=self.out)
+        self.calls += 1
+        return self.out, self.descale
+
+
 # ---- op registration: torch.ops.lite_attention.qk_prep, beside fwd / fwd_combine ---------------------------------------------------------
 _QK_PREP_SCHEMA = ("qk_prep(Tensor x, Tensor? weight = None, float eps = 1e-6, Tensor[]? tables = None, int[]? axis_pairs = None, "
                    "str? norm = \"token\", int pos_offset = 0, Tensor(out!)? out = None, ScalarType? out_dtype = None) -> Tensor(out!)")
@@ -212,6 +385,23 @@ def _qk_prep_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="
     return torch.empty(x.shape, dtype=out_dtype, device=x.device)
 
 
+_QK_PREP_FP8_SCHEMA = ("qk_prep_fp8(Tensor x, Tensor? weight = None, float eps = 1e-6, Tensor[]? tables = None, int[]? axis_pairs = None, "
+                       "str? norm = \"token\", int pos_offset = 0, Tensor? descale = None, Tensor(amax!)? amax_out = None, "
+                       "int heads_per_scale = 1, Tensor(out!)? out = None) -> Tensor(out!)")
+
+
+def _qk_prep_fp8_op(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, descale=None, amax_out=None,
+                    heads_per_scale=1, out=None):
+    tabs, pairs = _unpack_tables(None if tables is None else (tables, axis_pairs or ()), x.shape[-1])
+    return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True)
+
+
+def _qk_prep_fp8_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, descale=None, amax_out=None,
+                      heads_per_scale=1, out=None):
+    """Shape and dtype only."""
+    return out if out is not None else torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+
+
 def _register_op():
     global _op_lib
     if _op_lib is not None:
@@ -221,6 +411,9 @@ def _register_op():
     lib.define(_QK_PREP_SCHEMA)
     lib.impl("qk_prep", _qk_prep_op, "CUDA")
     lib.impl("qk_prep", _qk_prep_meta, "Meta")
+    lib.define(_QK_PREP_FP8_SCHEMA)
+    lib.impl("qk_prep_fp8", _qk_prep_fp8_op, "CUDA")
+    lib.impl("qk_prep_fp8", _qk_prep_fp8_meta, "Meta")
     _op_lib = lib
 
 
