@@ -9,7 +9,8 @@ per layer, the skip state carried across denoising steps.
     python examples/wan_self_attention_demo.py [--frames 5 --height 16 --width 16 --heads 4 --steps 6 --threshold -6] [--fused-prep]
 
 `--fused-prep` (`fused_prep=True` on the modules): RMSNorm, RoPE and the bf16 cast of q and k run as ONE pass each (`qk_prep`) instead of
-the eager lines below.
+the eager lines below. `--fp8 --smooth-k`: each key head's mean over the tokens is subtracted before the e4m3 cast (`SmoothedQK`); the
+output needs no correction.
 
 Prints, per denoising step, the fraction of tiles skipped and the error against the same block with skipping disabled.
 """
@@ -24,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lite_attention import LiteAttention  # noqa: E402  (same import line as the reference recipe)
 from lite_attention import qk_prep, rope_tables  # noqa: E402  (the fused q / k prologue: fused_prep=True)
 from lite_attention import E4m3Scales  # noqa: E402  (its e4m3 form with per-head scales: fp8=True)
+from lite_attention import SmoothedQK  # noqa: E402  (... with the keys mean-shifted before they are quantized: smooth_k=True)
 
 
 class RMSNorm(nn.Module):
@@ -60,13 +62,16 @@ def rope_3d(x, grid, theta=10000.0):
 
 class WanLikeSelfAttention(nn.Module):
     def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1, fused_prep=False, *, fp8=False,
-                 fp8_mode="current", fp8_margin=1.0):
+                 fp8_mode="current", fp8_margin=1.0, smooth_k=False):
         super().__init__()
         assert dim % num_heads == 0
         self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
         # fp8: q, k and v are produced in e4m3 by qk_prep_fp8, each with the per-head scales of its own E4m3Scales
         self.fp8 = fp8
         self.scales = [E4m3Scales(mode=fp8_mode, margin=fp8_margin) for _ in range(3)] if fp8 else None
+        # smooth_k: q and k go through one SmoothedQK instead (k first, q with the dots that would restore the LSE); v as before
+        assert fp8 or not smooth_k, "smooth_k is a form of the fp8 path"
+        self.smoothed = SmoothedQK(mode=fp8_mode, margin=fp8_margin) if smooth_k else None
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
         # the recipe: ONE LiteAttention per attention layer (its skip lists are that layer's state)
@@ -76,8 +81,12 @@ class WanLikeSelfAttention(nn.Module):
         b, s, n, d = *x.shape[:2], self.num_heads, self.head_dim
         if self.fp8:                                                # norm + rope + scale + e4m3 cast of q and k, scale + cast of v
             tables = rope_tables(grid, d, device=x.device)
-            q, dq = self.scales[0](self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables)
-            k, dk = self.scales[1](self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables)
+            if self.smoothed is not None:
+                q, k, dq, dk, _ = self.smoothed.pair(self.q(x).view(b, s, n, d), self.k(x).view(b, s, n, d), self.norm_q.weight,
+                                                     self.norm_k.weight, self.norm_q.eps, tables)
+            else:
+                q, dq = self.scales[0](self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables)
+                k, dk = self.scales[1](self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables)
             v, dv = self.scales[2](self.v(x).view(b, s, n, d), norm=None)
             return self.o(self.lite_attention(q, k, v, q_descale=dq, k_descale=dk, v_descale=dv).float().flatten(2))
         if self.fused_prep:                                         # norm + rope + cast of q and of k: one pass each
@@ -135,11 +144,11 @@ class WanLikeCrossAttention(nn.Module):
 
 
 def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False, *,
-        fp8=False, fp8_mode="current", fp8_margin=1.0):
+        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False):
     torch.manual_seed(seed)
     dim, grid = heads * 128, (frames, height, width)
     S = frames * height * width
-    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin)
+    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k)
     sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep, **kw).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
     # under which tokens of the same frame attend to each other
@@ -172,6 +181,7 @@ if __name__ == "__main__":
     ap.add_argument("--fp8", action="store_true", help="q, k and v in e4m3 with per-head scales (qk_prep_fp8 through E4m3Scales)")
     ap.add_argument("--fp8-mode", choices=("current", "delayed"), default="current")
     ap.add_argument("--fp8-margin", type=float, default=1.0)
+    ap.add_argument("--smooth-k", action="store_true", help="with --fp8: subtract each key head's mean before the e4m3 cast (SmoothedQK)")
     a = ap.parse_args()
     run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep, fp8=a.fp8, fp8_mode=a.fp8_mode,
-        fp8_margin=a.fp8_margin)
+        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k)

@@ -26,6 +26,9 @@
  *                            (RMSNorm, 3-axis RoPE, the cast to bf16: README.md:268-323 leaves them to eager torch) in one pass
  *   la_qk_prep_fp8        <- nothing: the same pass with an e4m3 result, per-head descales and the running per-head amax a scale
  *                            is made from - the producer of the fp8 forward's operands (q, k, and v with LA_NORM_NONE)
+ *   la_qk_prep_smooth     <- nothing: la_qk_prep_fp8 that can subtract a per-head vector from k before quantizing ("smooth K"), with
+ *                            the deterministic column sums that vector is made from (la_colsum_finish) and the q . c row dots that
+ *                            undo its shift of the LSE
  *
  * Rules of the boundary:
  *   - plain C: pointers, sizes, scalars. No torch types, no C++ types, no exceptions.
@@ -45,7 +48,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep and la_qk_prep_fp8 were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows) and la_colsum_finish were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -415,6 +418,70 @@ typedef struct la_qk_prep_fp8_args {
     int64_t amax_batch_stride, amax_head_stride;
 } la_qk_prep_fp8_args;
 int la_qk_prep_fp8(const la_qk_prep_fp8_args* args, void* stream);
+
+/* la_qk_prep_fp8 with K smoothing: the same pass can subtract a per-head vector before it quantizes, and collect what a caller needs
+ * to choose that vector and to undo its effect on the LSE. Subtracting c[b][h][:] from every key of a head lowers every score of a
+ * query row by the same softmax_scale * (q . c): P, O and the skip vote are unchanged, LSE' = LSE - softmax_scale * (q . c) (natural
+ * log). With y the fp32 value la_qk_prep would round (same norm, weight and rope, in the same order); every addition is optional:
+ *   shift        fp32 [B, H, D] by its strides (elements). y' = y - shift[b][h][:], ONE fp32 subtraction behind the rope and before
+ *                scale and clamp; amax becomes the running maximum of |y'| and out = e4m3_rne(clamp(y' * (1 / descale))). NULL: y' = y.
+ *   colsum_part  fp32 [n_parts, B, H, D] contiguous, n_parts = la_qk_prep_smooth_parts(S, H, D): part[p][b][h][d] = the sum of the
+ *                UNSHIFTED y over rows [p R, (p + 1) R) of the batch, R = la_qk_prep_smooth_part_rows(S, H, D), added in row order from
+ *                0.0f (a part without rows is written as zeros; every element is written). The row -> part map and the order of the
+ *                additions depend on (S, H, D) alone - not on the device, the grid or the timing; no float atomics: two launches
+ *                agree bitwise, and a launch that also quantizes reports the same sums as one that does not.
+ *   dot_vec / dot_out   dot_vec fp32 [B, H / heads_per_dot, D] by its strides, dot_out fp32 [B, H, S] contiguous (the layout of lse):
+ *                dot_out[b][h][s] = sum_d y[b][s][h][d] * dot_vec[b][h / heads_per_dot][d], of the UNSHIFTED, unquantized y, in a fixed
+ *                order (bit-reproducible). For q: heads_per_dot = H_q / H_kv and dot_vec = the shift given for k. Both or neither.
+ *   out == NULL  nothing is quantized (a sums-only, dots-only or amax-only pass); allowed when amax, colsum_part or dot_out is given.
+ * la_colsum_finish: mean_out[b][h][d] = (part[0][b][h][d] + part[1][b][h][d] + ...) / S, added in index order; mean_out by its strides.
+ * With shift, colsum_part and dot_vec all NULL the call IS la_qk_prep_fp8 (the same kernels, the same bits).
+ * Errors (all before any HIP call), in this order: NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; NULL x, or out, amax,
+ * colsum_part and dot_out all NULL, or exactly one of dot_vec / dot_out, LA_ERR_NULL_ARG; in_dtype LA_ERR_DTYPE; heads_per_scale, or
+ * (with dot_vec) heads_per_dot, below 1 or not a divisor of num_heads LA_ERR_SHAPE; a negative descale / amax stride, or descale, amax
+ * or dot_out off a 4-byte boundary, LA_ERR_STRIDE; a negative shift / dot_vec stride, shift, dot_vec or colsum_part off a 16-byte
+ * boundary, or a used shift / dot_vec stride (batch > 1; more than one head / group) that is no multiple of 4 elements LA_ERR_STRIDE;
+ * then every check of la_qk_prep_fp8 from norm_mode on, in its order and codes; more than 1024 heads LA_ERR_UNSUPPORTED; colsum_part
+ * with more column sums than a thread keeps in LDS LA_ERR_UNSUPPORTED: LA_NORM_TOKEN serves every H*D it accepts, LA_NORM_HEAD /
+ * LA_NORM_NONE serve H <= 16 * (64 / G) heads, G = D / 8 rounded up to a power of two (64 heads of 128, 32 of 256).
+ * NOT detected: a colsum_part shorter than n_parts * B * H * D, a dot_out shorter than B * H * S, buffers that overlap each other, x or
+ * out, a descale that is zero, negative or not finite. */
+typedef struct la_qk_prep_smooth_args {
+    uint32_t struct_size;        /* = sizeof(la_qk_prep_smooth_args)                              */
+    int32_t  in_dtype;           /* la_dtype of x: LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32  */
+    int32_t  norm_mode;          /* la_norm_mode                                                  */
+    int32_t  heads_per_scale;    /* heads that share one descale / amax element; divides num_heads */
+    const void* x;               /* (B, S, H, D), last dimension contiguous                       */
+    void*       out;             /* e4m3 (B, S, H, D), last dimension contiguous; NULL: not stored */
+    int64_t x_batch_stride, x_row_stride, x_head_stride;          /* in elements                  */
+    int64_t out_batch_stride, out_row_stride, out_head_stride;
+    int32_t batch, seqlen, num_heads, head_dim;
+    const float* weight;         /* fp32 [H*D] (LA_NORM_TOKEN) or [D] (LA_NORM_HEAD); NULL = ones  */
+    float   eps;
+    int32_t pos_offset;          /* position of row 0 on the (e0, e1, e2) grid, row-major         */
+    const float* rope_table[3];  /* fp32 [axis_extent[a], axis_pairs[a], 2] = (cos, sin)           */
+    int32_t axis_extent[3];
+    int32_t axis_pairs[3];
+    const float* descale;        /* fp32 [B, H / heads_per_scale] by the strides below; NULL = 1.0 */
+    int64_t descale_batch_stride, descale_head_stride;
+    float*  amax;                /* fp32 [B, H / heads_per_scale]; NULL = not wanted               */
+    int64_t amax_batch_stride, amax_head_stride;
+    const float* shift;          /* fp32 [B, H, D] by the strides below; NULL = no shift           */
+    int64_t shift_batch_stride, shift_head_stride;
+    float*  colsum_part;         /* fp32 [n_parts, B, H, D] contiguous; NULL = not wanted          */
+    const float* dot_vec;        /* fp32 [B, H / heads_per_dot, D] by the strides below; NULL = no dots */
+    int64_t dot_vec_batch_stride, dot_vec_head_stride;
+    float*  dot_out;             /* fp32 [B, H, S] contiguous; given exactly when dot_vec is       */
+    int32_t heads_per_dot;       /* heads that share one dot_vec row; divides num_heads            */
+    int32_t reserved0;           /* 0                                                              */
+} la_qk_prep_smooth_args;
+int la_qk_prep_smooth(const la_qk_prep_smooth_args* args, void* stream);
+/* Parts and rows per part of colsum_part for a shape: pure functions of their arguments (LA_ERR_SHAPE for a non-positive one). */
+int la_qk_prep_smooth_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim);
+int la_qk_prep_smooth_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim);
+/* Errors: NULL part / mean_out LA_ERR_NULL_ARG; a non-positive size LA_ERR_SHAPE; a negative stride or a pointer off 4 bytes LA_ERR_STRIDE. */
+int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
+                     float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride, void* stream);
 
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)

@@ -24,6 +24,8 @@ if not _BUILDING:
     from .calibration import ErrorStats, calibrate_error_schedule, calibrate_threshold, output_error  # noqa: E402
     from .qk_prep import RopeTables, qk_prep, qk_prep_reference, rope_tables, wan_rope_parts  # noqa: E402
     from .qk_prep import E4m3Scales, descale_from_amax, qk_prep_amax, qk_prep_fp8, qk_prep_fp8_reference  # noqa: E402
+    from .qk_prep import (SmoothedQK, colsum_finish, lse_unshift, qk_prep_colmean, qk_prep_smooth, qk_prep_smooth_parts,  # noqa: E402
+                          qk_prep_smooth_reference)
     from .parallel import (HeadShardedLiteAttention, RingSeqParallelLiteAttention,  # noqa: E402
                            UlyssesLiteAttention)
 
@@ -33,4 +35,5 @@ __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flas
            "calibrate_error_schedule", "output_error", "ErrorStats",
            "qk_prep", "qk_prep_reference", "rope_tables", "wan_rope_parts", "RopeTables",
            "qk_prep_fp8", "qk_prep_amax", "descale_from_amax", "qk_prep_fp8_reference", "E4m3Scales",
+           "qk_prep_smooth", "qk_prep_colmean", "colsum_finish", "qk_prep_smooth_parts", "qk_prep_smooth_reference", "lse_unshift", "SmoothedQK",
            "HeadShardedLiteAttention", "UlyssesLiteAttention", "RingSeqParallelLiteAttention", "__version__"]

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "la_abi_version", "la_get_tile_sizes", "la_get_tile_sizes_ex", "la_fwd", "la_fwd_workspace_bytes", "la_skip_list_stats", "la_combine",
     "la_status_string", "la_last_hip_error", "la_blockmask_to_lists", "la_device_slots", "la_build_info", "la_combine_list",
     "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error", "la_qk_prep", "la_qk_prep_fp8",
+    "la_qk_prep_smooth", "la_qk_prep_smooth_parts", "la_qk_prep_smooth_part_rows", "la_colsum_finish",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -86,6 +87,16 @@ class LaQkPrepFp8Args(ctypes.Structure):
         ("rope_table", ctypes.c_void_p * 3), ("axis_extent", ctypes.c_int32 * 3), ("axis_pairs", ctypes.c_int32 * 3),
         ("descale", ctypes.c_void_p), ("descale_batch_stride", ctypes.c_int64), ("descale_head_stride", ctypes.c_int64),
         ("amax", ctypes.c_void_p), ("amax_batch_stride", ctypes.c_int64), ("amax_head_stride", ctypes.c_int64),
+    ]
+
+
+class LaQkPrepSmoothArgs(ctypes.Structure):
+    """Mirror of ``la_qk_prep_smooth_args``: the fields of ``la_qk_prep_fp8_args``, then the shift, the part sums and the row dots."""
+    _fields_ = LaQkPrepFp8Args._fields_ + [
+        ("shift", ctypes.c_void_p), ("shift_batch_stride", ctypes.c_int64), ("shift_head_stride", ctypes.c_int64),
+        ("colsum_part", ctypes.c_void_p),
+        ("dot_vec", ctypes.c_void_p), ("dot_vec_batch_stride", ctypes.c_int64), ("dot_vec_head_stride", ctypes.c_int64),
+        ("dot_out", ctypes.c_void_p), ("heads_per_dot", ctypes.c_int32), ("reserved0", ctypes.c_int32),
     ]
 
 
@@ -206,6 +217,14 @@ def load() -> ctypes.CDLL:
     lib.la_qk_prep.restype = ctypes.c_int
     lib.la_qk_prep_fp8.argtypes = [ctypes.POINTER(LaQkPrepFp8Args), ctypes.c_void_p]
     lib.la_qk_prep_fp8.restype = ctypes.c_int
+    lib.la_qk_prep_smooth.argtypes = [ctypes.POINTER(LaQkPrepSmoothArgs), ctypes.c_void_p]
+    lib.la_qk_prep_smooth.restype = ctypes.c_int
+    for fn in (lib.la_qk_prep_smooth_parts, lib.la_qk_prep_smooth_part_rows):
+        fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        fn.restype = ctypes.c_int
+    lib.la_colsum_finish.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+    lib.la_colsum_finish.restype = ctypes.c_int
     lib.la_device_slots.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.la_device_slots.restype = ctypes.c_int
     lib.la_status_string.argtypes = [ctypes.c_int]

@@ -206,6 +206,12 @@ def _build_record(generated, defines, variant: bool) -> str:
     return f"src={_buildinfo.source_hash()};variant={1 if variant else 0};wrong_results={1 if wrong else 0};opts={text}"
 
 
+def _is_smooth_prep_kernel(name: str) -> bool:
+    """The PrepPolicy<3> / <4> forms of the prologue kernels (la_qk_prep_smooth; the policy is the last template argument): their column
+    sums live in LDS so that the accumulators cost no registers, and a spill would undo that."""
+    return "la_qk_prep_" in name and "_kernelI" in name and ("Li3EEEv" in name or "Li4EEEv" in name)
+
+
 def _check_no_scratch(remarks: str, defines) -> None:
     """The x64 kernels (a C++ shell around an asm body that clobbers nearly the whole register file) must not use scratch:
     hipcc (ROCm 7.2) has been seen to place the spill store of a value that is live across the body inside a finished
@@ -215,7 +221,7 @@ def _check_no_scratch(remarks: str, defines) -> None:
     for line in remarks.splitlines():
         if "Function Name:" in line:
             name = line.split("Function Name:")[1].split()[0]
-        elif "ScratchSize [bytes/lane]:" in line and name and "la_fwd_x64_" in name:
+        elif "ScratchSize [bytes/lane]:" in line and name and ("la_fwd_x64_" in name or _is_smooth_prep_kernel(name)):
             size = int(line.split("ScratchSize [bytes/lane]:")[1].split()[0])
             seen += 1
             if size != 0:
@@ -224,7 +230,7 @@ def _check_no_scratch(remarks: str, defines) -> None:
         raise RuntimeError("no kernel-resource-usage remark of an x64 kernel was parsed: the no-scratch check cannot run "
                            "(-Rpass-analysis=kernel-resource-usage output changed?)")
     if bad and not any(d.split("=")[0] == "LA_PROFILE_PHASES" for d in defines):
-        raise RuntimeError("x64 kernels must not spill to scratch (see liteattention_amd/csrc/la_fwd_shell.h, "
+        raise RuntimeError("x64 and la_qk_prep_smooth kernels must not spill to scratch (see liteattention_amd/csrc/la_fwd_shell.h, "
                            f"COMPILER HAZARD): {bad}")
 
 

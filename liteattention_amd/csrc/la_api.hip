@@ -582,4 +582,72 @@ int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream_) {
     return LA_OK;
 }
 
+int la_qk_prep_smooth_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
+    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
+    return 4 * la::qk_prep_part_blocks(seqlen);                   // today a function of seqlen alone
+}
+
+int la_qk_prep_smooth_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
+    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
+    return la::qk_prep_part_rows(seqlen);
+}
+
+int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_smooth_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || (!a->out && !a->amax && !a->colsum_part && !a->dot_out)) return LA_ERR_NULL_ARG;
+    if ((a->dot_out != nullptr) != (a->dot_vec != nullptr)) return LA_ERR_NULL_ARG;
+    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (a->num_heads <= 0 || a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
+    if (a->dot_vec && (a->heads_per_dot < 1 || a->num_heads % a->heads_per_dot != 0)) return LA_ERR_SHAPE;
+    if (a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 || a->amax_head_stride < 0 ||
+        ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax) | reinterpret_cast<uintptr_t>(a->dot_out)) & 3u))
+        return LA_ERR_STRIDE;
+    // shift and dot_vec rows are read 16 bytes at a time, the part sums are written so
+    const auto rows16 = [&](const float* ptr, int64_t bs, int64_t hs, int heads) {
+        return bs >= 0 && hs >= 0 && aligned16(ptr) && (a->batch <= 1 || bs % 4 == 0) && (heads <= 1 || hs % 4 == 0);
+    };
+    if ((a->shift && !rows16(a->shift, a->shift_batch_stride, a->shift_head_stride, a->num_heads)) ||
+        (a->dot_vec && !rows16(a->dot_vec, a->dot_vec_batch_stride, a->dot_vec_head_stride, a->num_heads / a->heads_per_dot)) ||
+        !aligned16(a->colsum_part)) return LA_ERR_STRIDE;
+    la::QkPrepParams p;
+    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, p);
+    if (rc != LA_OK) return rc;
+    if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;
+    // a thread keeps the running sums of its columns in LDS: at most 16 chunks of 8
+    if (a->colsum_part && la::qk_prep_sum_slots(p) > la::kQkPrepSumSlots) return LA_ERR_UNSUPPORTED;
+    p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
+    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
+    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
+    p.heads_per_scale = a->heads_per_scale;
+    p.batch = a->batch;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipError_t err;
+    if (!a->shift && !a->colsum_part && !a->dot_vec) {              // nothing added: la_qk_prep_fp8's own kernels
+        err = la::launch_qk_prep_fp8(p, a->in_dtype, stream);
+    } else {
+        p.shift = a->shift; p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
+        p.colsum_part = a->colsum_part;
+        p.dot_vec = a->dot_vec; p.dv_bs = a->dot_vec_batch_stride; p.dv_hs = a->dot_vec_head_stride;
+        p.heads_per_dot = a->dot_vec ? a->heads_per_dot : 1; p.dot_out = a->dot_out;
+        p.part_rows = la::qk_prep_part_rows(a->seqlen); p.part_blocks = la::qk_prep_part_blocks(a->seqlen);
+        err = la::launch_qk_prep_smooth(p, a->in_dtype, stream);
+    }
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
+int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
+                     float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride, void* stream_) {
+    if (!part || !mean_out) return LA_ERR_NULL_ARG;
+    if (n_parts <= 0 || batch <= 0 || num_heads <= 0 || head_dim <= 0 || seqlen <= 0) return LA_ERR_SHAPE;
+    if (mean_batch_stride < 0 || mean_head_stride < 0 || ((reinterpret_cast<uintptr_t>(part) | reinterpret_cast<uintptr_t>(mean_out)) & 3u))
+        return LA_ERR_STRIDE;
+    if (static_cast<int64_t>(batch) * num_heads * head_dim > 0x7fffffffLL * 256) return LA_ERR_SHAPE;      // one thread per column
+    const hipError_t err = la::launch_colsum_finish(part, n_parts, batch, num_heads, head_dim, seqlen, mean_out, mean_batch_stride,
+                                                    mean_head_stride, static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
 }  // extern "C"

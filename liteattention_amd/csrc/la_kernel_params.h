@@ -132,9 +132,29 @@ struct QkPrepParams {
     float* amax;                 // [batch, groups] running maximum of |y| (as the unsigned maximum of its bit pattern); NULL = not wanted
     int64_t ds_bs, ds_hs, am_bs, am_hs;
     int heads_per_scale;         // >= 1, divides num_heads; num_heads <= kQkPrepScaleSlots
+    // la_qk_prep_smooth only (the others leave them zero): every pointer NULL = that step off
+    const float* shift;          // [batch, heads, head_dim] by sh_bs / sh_hs: out and amax are taken from y - shift
+    float* colsum_part;          // [4 part_blocks, batch, heads, head_dim] contiguous: sums of the unshifted y over the rows of each part
+    const float* dot_vec;        // [batch, heads / heads_per_dot, head_dim] by dv_bs / dv_hs
+    float* dot_out;              // [batch, heads, seqlen] contiguous: sum_d y * dot_vec, of the unshifted y
+    int64_t sh_bs, sh_hs, dv_bs, dv_hs;
+    int heads_per_dot;
+    int batch;
+    int part_rows, part_blocks;  // rows of a part; part p = rows [p part_rows, (p + 1) part_rows) of a batch; 4 parts per block
 };
 constexpr int kQkPrepScaleSlots = 1024;      // heads whose scale and running amax a workgroup keeps in LDS (la_qk_prep_fp8)
+constexpr int kQkPrepSumSlots = 16;          // chunks of 8 columns a thread keeps running column sums for in LDS (la_qk_prep_smooth): 128 KiB
 hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream);   // dtypes: 0 bf16, 1 fp16, 3 fp32 (in only)
 hipError_t launch_qk_prep_fp8(const QkPrepParams& p, int in_dtype, hipStream_t stream);      // out e4m3; p.out == NULL: the amax pass alone
+// la_qk_prep_smooth: rows of a part and blocks of 4 parts for a sequence length - the one place the row -> part map is decided
+inline int qk_prep_part_rows(int seqlen) { const int r = static_cast<int>((static_cast<int64_t>(seqlen) + 1023) / 1024); return r < 16 ? 16 : r; }
+inline int qk_prep_part_blocks(int seqlen) {
+    const int r = qk_prep_part_rows(seqlen);
+    return static_cast<int>(((static_cast<int64_t>(seqlen) + r - 1) / r + 3) / 4);
+}
+int qk_prep_sum_slots(const QkPrepParams& p);      // chunks per thread the column sums of this shape need (<= kQkPrepSumSlots or unsupported)
+hipError_t launch_qk_prep_smooth(const QkPrepParams& p, int in_dtype, hipStream_t stream);   // out e4m3 or NULL, plus shift / column sums / row dots
+hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean,
+                                int64_t m_bs, int64_t m_hs, hipStream_t stream);
 
 }  // namespace la

@@ -44,6 +44,19 @@
 //  * quantize: z = y * inv, inv = 1 / descale one IEEE division per group when the workgroup enters a batch (kept per head in LDS);
 //    z is clamped to +-448 by two compares that a NaN fails, so a NaN stays a NaN; then the hardware's round-to-nearest-even e4m3
 //    conversion (OCP e4m3fn on gfx950) of values that cannot overflow: no mode bit matters. 8 elements = 8 bytes, one 8-byte store.
+//
+// K smoothing (la_qk_prep_smooth; PrepPolicy<3>, and PrepPolicy<4> when nothing is stored; the same two templates). y is computed as
+// above; then, each step on when its pointer is given: the column sums and the row dots take y, y' = y - shift[b][h][:] (one fp32
+// subtraction), and amax / quantize take y'.
+//  * rows -> workgroups: a batch's rows are cut into PARTS of part_rows consecutive rows (qk_prep_part_rows: a function of the sequence
+//    length alone), a workgroup takes a BLOCK of 4 parts of one batch, one part per wave (when the workgroup shares a token: the 4
+//    parts one after the other), blocks by grid stride. Every thread runs the same trips, so the barriers of scale_turn still meet.
+//  * column sums: a thread's running sums of ITS columns live in LDS (colsum_lds, dynamic: 8 KiB per chunk slot, only when asked for)
+//    - no register is spent on them and no other thread touches them, so there is no atomic and no barrier. They start at 0 with a
+//    part's first row, take the rows in order and go to part[p][b][h][d] behind its last row with two 16-byte vector stores per chunk:
+//    the bits depend on (S, H, D) alone. la_colsum_finish_kernel adds the parts in index order and divides by S.
+//  * row dots: a chunk's share (a fixed tree of its 8 products) goes to LDS by chunk index; one thread per head adds the D / 8 shares
+//    in column order (token kernel), or the head's G lanes run the xor butterfly (head kernel). One 4-byte vector store per (head, row).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -131,11 +144,40 @@ template <> struct PrepStore<2> {           // e4m3: y is inside +-448 or NaN (s
     }
 };
 
-// What follows y: 0 the 16-bit store of la_qk_prep; 1 amax + scale + clamp + e4m3 store; 2 amax alone (x is read, nothing is written)
+// What follows y: 0 the 16-bit store of la_qk_prep; 1 amax + scale + clamp + e4m3 store; 2 amax alone (x is read, nothing is written);
+// 3 / 4 la_qk_prep_smooth: 1 / 2 of y - shift, plus the column sums and row dots of y (each on when its pointer is given)
 template <int MODE> struct PrepPolicy {
     static constexpr bool kScaled = MODE != 0;                     // per-head LDS tables, the loop over rounds
-    static constexpr bool kStore = MODE != 2;
+    static constexpr bool kStore = MODE == 0 || MODE == 1 || MODE == 3;
+    static constexpr bool kSmooth = MODE >= 3;                     // the loop over blocks of 4 parts, each part's rows in order
 };
+
+// The running column sums of la_qk_prep_smooth: element j of chunk slot q of thread t at ((q * 8 + j) * 256 + t). A thread reads and
+// writes its own words only: no barrier, no atomic, and the order of the additions is the order of the rows.
+extern __shared__ float colsum_lds[];
+
+__device__ __forceinline__ void colsum_zero(int slots) {
+    for (int q = 0; q < slots * 8; ++q) colsum_lds[q * 256 + threadIdx.x] = 0.f;
+}
+__device__ __forceinline__ void colsum_add8(int slot, const float (&y)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) colsum_lds[(slot * 8 + j) * 256 + threadIdx.x] += y[j];
+}
+__device__ __forceinline__ void colsum_flush8(int slot, float* dst) {
+    float* t = colsum_lds + slot * 8 * 256 + threadIdx.x;
+    *reinterpret_cast<pq_f32x4*>(dst) = pq_f32x4{t[0], t[256], t[512], t[768]};
+    *reinterpret_cast<pq_f32x4*>(dst + 4) = pq_f32x4{t[1024], t[1280], t[1536], t[1792]};
+}
+
+__device__ __forceinline__ void load_f32x8(const float* __restrict__ src, float (&w)[8]) {
+    const pq_f32x4 a = *reinterpret_cast<const pq_f32x4*>(src), c = *reinterpret_cast<const pq_f32x4*>(src + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { w[i] = a[i]; w[4 + i] = c[i]; }
+}
+
+__device__ __forceinline__ float dot8(const float (&y)[8], const float (&c)[8]) {
+    return ((y[0] * c[0] + y[1] * c[1]) + (y[2] * c[2] + y[3] * c[3])) + ((y[4] * c[4] + y[5] * c[5]) + (y[6] * c[6] + y[7] * c[7]));
+}
 
 __device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
 
@@ -248,6 +290,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
     __shared__ float part[4];
     __shared__ unsigned am_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
     __shared__ float inv_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
+    __shared__ float dot_lds[POL::kSmooth ? NCH * 256 : 1];        // smooth: a chunk's share of its head's row dot, by chunk (and wave)
     typedef typename PrepLoad<DT_IN>::raw raw_t;
     constexpr int kLanes = WG ? 256 : 64;                          // lanes that share a token
     const int lane = threadIdx.x & 63;
@@ -258,6 +301,8 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
     const float* __restrict__ weight = p.weight;
     float* row = rot_lds[wave];                                    // WG: every wave stages its own copy of the token's row
     const int first = WG ? static_cast<int>(threadIdx.x) : lane;
+    constexpr bool store = POL::kStore;
+    float* dots = dot_lds + (WG ? 0 : wave * NCH * 64);
 
     // chunk i of this lane = chunk first + kLanes i of the token: its first element inside its head (-1: no such chunk) and its
     // element offsets from the token's start in x and out (below 2^31, checked by la_qk_prep)
@@ -284,18 +329,35 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
     // e4m3 forms: t counts rounds (kPerRound consecutive tokens of one batch), the same trips for every thread
     constexpr int kPerRound = WG ? 1 : 4;
     const int64_t rpb = (p.seqlen + kPerRound - 1) / kPerRound;
-    const int64_t t_end = POL::kScaled ? p.tokens / p.seqlen * rpb : p.tokens;
+    // smooth: t counts blocks of 4 parts of one batch; a wave walks the rows of its part in order (WG: the workgroup walks the 4 parts
+    // one after the other), `trips` rounds, the same for every thread
+    const int part_rows = POL::kSmooth ? p.part_rows : 1, trips = POL::kSmooth ? (WG ? 4 * part_rows : part_rows) : 1;
+    const int64_t t_end = POL::kSmooth ? static_cast<int64_t>(p.batch) * p.part_blocks : (POL::kScaled ? p.tokens / p.seqlen * rpb : p.tokens);
     int64_t cur_b = -1;
     if (POL::kScaled)
         for (int h = threadIdx.x; h < p.num_heads; h += 256) am_tab[h] = 0;      // (the first scale_turn starts with a barrier)
-    for (int64_t t = POL::kScaled ? static_cast<int64_t>(blockIdx.x) : t0; t < t_end; t += POL::kScaled ? static_cast<int64_t>(gridDim.x) : t_step) {
+    for (int64_t t = POL::kScaled ? static_cast<int64_t>(blockIdx.x) : t0; t < t_end; t += POL::kScaled ? static_cast<int64_t>(gridDim.x) : t_step)
+    for (int trip = 0; trip < trips; ++trip) {
         int64_t b;                                                 // WG: the same trips for every thread of the workgroup
         int s;
         bool live = true;                                          // false: a spare wave of a batch's last round
+        int part_row = 0;                                          // smooth: the row inside its part, and the part
+        int64_t part_id = 0;
         if constexpr (POL::kScaled) {
-            b = t / rpb;
-            s = static_cast<int>(t - b * rpb) * kPerRound + (WG ? 0 : wave);
-            live = s < p.seqlen;
+            if constexpr (POL::kSmooth) {
+                b = t / p.part_blocks;
+                const int sub = WG ? trip / part_rows : wave;
+                part_row = WG ? trip - sub * part_rows : trip;
+                part_id = (t - b * p.part_blocks) * 4 + sub;
+                const int64_t s64 = part_id * part_rows + part_row;
+                live = s64 < p.seqlen;
+                s = static_cast<int>(live ? s64 : 0);
+                if (p.colsum_part && part_row == 0) colsum_zero(NCH);
+            } else {
+                b = t / rpb;
+                s = static_cast<int>(t - b * rpb) * kPerRound + (WG ? 0 : wave);
+                live = s < p.seqlen;
+            }
             if (b != cur_b) {
 #pragma unroll
                 for (int i = 0; i < NCH; ++i) {
@@ -341,11 +403,44 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
                 if (weight) load_weight8(weight, (first + kLanes * i) * 8, w);      // 4 H D bytes every token rereads: they stay in L1 / L2
                 if (rotate) scale_rotate8<true>(y, r, w, col[i], rot_pairs, row);
                 else scale_rotate8<false>(y, r, w, col[i], rot_pairs, row);
+                if constexpr (POL::kSmooth) {                      // sums and dots see y, the maximum and the store y - shift
+                    if (p.colsum_part) colsum_add8(i, y);
+                    if (p.dot_vec) {
+                        float c[8];
+                        load_f32x8(p.dot_vec + b * p.dv_bs + (head_of(i) / p.heads_per_dot) * p.dv_hs + col[i], c);
+                        dots[first + kLanes * i] = dot8(y, c);
+                    }
+                    if (p.shift) {
+                        float c[8];
+                        load_f32x8(p.shift + b * p.sh_bs + head_of(i) * p.sh_hs + col[i], c);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) y[j] -= c[j];
+                    }
+                }
                 if constexpr (POL::kScaled) {
                     am[i] = umax(am[i], absmax8(y));
-                    if constexpr (POL::kStore) scale_clamp8(y, inv_tab[head_of(i)]);
+                    if (store) scale_clamp8(y, inv_tab[head_of(i)]);
                 }
-                if constexpr (POL::kStore) PrepStore<DT_OUT>::store8(p.out, o_tok + o_off[i], y);
+                if (store) PrepStore<DT_OUT>::store8(p.out, o_tok + o_off[i], y);
+            }
+        }
+        if constexpr (POL::kSmooth) {
+            if (p.dot_vec) {                                       // a head's D / 8 shares, added in column order by one thread
+                if (WG) __syncthreads();                           // (the next token writes `dots` behind its own barriers)
+                else wave_lds_fence();
+                const int cph = D >> 3;
+                for (int h = first; h < p.num_heads && live; h += kLanes) {
+                    float acc = 0.f;
+                    for (int k = 0; k < cph; ++k) acc += dots[h * cph + k];
+                    p.dot_out[(b * p.num_heads + h) * p.seqlen + s] = acc;
+                }
+                if (!WG) wave_lds_fence();
+            }
+            if (p.colsum_part && part_row == part_rows - 1) {
+                float* dst = p.colsum_part + (part_id * p.batch + b) * n;
+#pragma unroll
+                for (int i = 0; i < NCH; ++i)
+                    if (col[i] >= 0) colsum_flush8(i, dst + (first + kLanes * i) * 8);
             }
         }
         if (rotate) wave_lds_fence();                              // the next token's row is staged behind this token's reads
@@ -383,19 +478,35 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
 
     // e4m3 forms: t counts rounds (4 consecutive tokens of one batch), the same trips for every thread
     const int64_t rpb = (p.seqlen + 3) / 4;
-    const int64_t t_end = POL::kScaled ? p.tokens / p.seqlen * rpb : p.tokens;
+    // smooth: t counts blocks of 4 parts of one batch, a wave walks the rows of its part in order; a thread's column sums: slot
+    // (pass * kHeadUnroll + u) of colsum_lds
+    const int trips = POL::kSmooth ? p.part_rows : 1;
+    const int sum_slots = (H + heads_per_pass * kHeadUnroll - 1) / (heads_per_pass * kHeadUnroll) * kHeadUnroll;
+    constexpr bool store = POL::kStore;
+    const int64_t t_end = POL::kSmooth ? static_cast<int64_t>(p.batch) * p.part_blocks : (POL::kScaled ? p.tokens / p.seqlen * rpb : p.tokens);
     int64_t cur_b = -1;
     if (POL::kScaled)
         for (int h = threadIdx.x; h < H; h += 256) am_tab[h] = 0;                // (the first scale_turn starts with a barrier)
     for (int64_t t = POL::kScaled ? static_cast<int64_t>(blockIdx.x) : static_cast<int64_t>(blockIdx.x) * 4 + wave; t < t_end;
-         t += POL::kScaled ? static_cast<int64_t>(gridDim.x) : static_cast<int64_t>(gridDim.x) * 4) {
+         t += POL::kScaled ? static_cast<int64_t>(gridDim.x) : static_cast<int64_t>(gridDim.x) * 4)
+    for (int trip = 0; trip < trips; ++trip) {
         int64_t b;
         int s;
         bool live = true;                                          // false: a spare wave of a batch's last round
+        int64_t part = 0;
         if constexpr (POL::kScaled) {
-            b = t / rpb;
-            s = static_cast<int>(t - b * rpb) * 4 + wave;
-            live = s < p.seqlen;
+            if constexpr (POL::kSmooth) {
+                b = t / p.part_blocks;
+                part = (t - b * p.part_blocks) * 4 + wave;
+                const int64_t s64 = part * trips + trip;
+                live = s64 < p.seqlen;
+                s = static_cast<int>(live ? s64 : 0);
+                if (p.colsum_part && trip == 0) colsum_zero(sum_slots);
+            } else {
+                b = t / rpb;
+                s = static_cast<int>(t - b * rpb) * 4 + wave;
+                live = s < p.seqlen;
+            }
             if (b != cur_b) {
                 scale_turn<POL::kStore>(p, am_tab, inv_tab, cur_b, b);
                 cur_b = b;
@@ -427,18 +538,48 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
                     r = rsqrtf(ss / static_cast<float>(D) + p.eps);
                 }
                 unsigned m = 0;
+                float dot = 0.f;
                 if (col_ok && h < H && live) {
                     if (rotate) scale_rotate8<true>(y, r, w, e, rot_pairs, row);
                     else scale_rotate8<false>(y, r, w, e, rot_pairs, row);
+                    if constexpr (POL::kSmooth) {                  // sums and dots see y, the maximum and the store y - shift
+                        if (p.colsum_part) colsum_add8(h0 / heads_per_pass + u, y);
+                        if (p.dot_vec) {
+                            float c[8];
+                            load_f32x8(p.dot_vec + b * p.dv_bs + (h / p.heads_per_dot) * p.dv_hs + e, c);
+                            dot = dot8(y, c);
+                        }
+                        if (p.shift) {
+                            float c[8];
+                            load_f32x8(p.shift + b * p.sh_bs + h * p.sh_hs + e, c);
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) y[j] -= c[j];
+                        }
+                    }
                     if constexpr (POL::kScaled) {
                         m = absmax8(y);
-                        if constexpr (POL::kStore) scale_clamp8(y, inv_tab[h]);
+                        if (store) scale_clamp8(y, inv_tab[h]);
                     }
-                    if constexpr (POL::kStore) PrepStore<DT_OUT>::store8(p.out, o_tok + h * p.o_hs, y);
+                    if (store) PrepStore<DT_OUT>::store8(p.out, o_tok + h * p.o_hs, y);
+                }
+                if constexpr (POL::kSmooth) {
+                    if (p.dot_vec) {                               // uniform: the head's dot over its G lanes, a fixed butterfly
+                        for (int off = G >> 1; off > 0; off >>= 1) dot += __shfl_xor(dot, off);
+                        if ((lane & (G - 1)) == 0 && h < H && live) p.dot_out[(b * H + h) * p.seqlen + s] = dot;
+                    }
                 }
                 if constexpr (POL::kScaled) {                      // uniform: the head's maximum over its G lanes, one ds atomic per head
                     for (int off = G >> 1; off > 0; off >>= 1) m = umax(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), off)));
                     if ((lane & (G - 1)) == 0 && m) atomicMax(&am_tab[h], m);
+                }
+            }
+        }
+        if constexpr (POL::kSmooth) {
+            if (p.colsum_part && trip == trips - 1) {
+                float* dst = p.colsum_part + (part * p.batch + b) * H * D + e;
+                for (int q = 0; q < sum_slots; ++q) {
+                    const int h = (q / kHeadUnroll) * heads_per_pass * kHeadUnroll + (q % kHeadUnroll) * heads_per_pass + sub;
+                    if (col_ok && h < H) colsum_flush8(q, dst + h * D);
                 }
             }
         }
@@ -457,13 +598,40 @@ dim3 grid_for_rounds(const QkPrepParams& p, int per_round) {
     return grid_for(p.tokens / p.seqlen * ((p.seqlen + per_round - 1) / per_round), 1);
 }
 
+// chunk slots of 8 columns per thread whose running sums the token kernel keeps in LDS: its NCH
+int token_sum_slots(int nchunks) {
+    const int need = (nchunks + 63) / 64;
+    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 10 ? 10 : nchunks <= 4 * 256 ? 4 : 8;
+}
+// ... and the head kernel: a slot per pass of 64 / G heads, in whole batches of kHeadUnroll passes
+int head_sum_slots(int num_heads, int head_dim) {
+    int group_log2 = 0;
+    while ((8 << group_log2) < head_dim) ++group_log2;
+    const int per_batch = (64 >> group_log2) * kHeadUnroll;
+    return (num_heads + per_batch - 1) / per_batch * kHeadUnroll;
+}
+
+// the grid of a smooth form (one workgroup per block of 4 parts of one batch) and the LDS of its column sums; hipErrorInvalidValue etc.
+// of the attribute call stay in hipGetLastError for the caller
+template <class K>
+bool smooth_launch_shape(K kfn, const QkPrepParams& p, int slots, dim3* grid, size_t* lds) {
+    *grid = grid_for(static_cast<int64_t>(p.batch) * p.part_blocks, 1);
+    *lds = p.colsum_part ? static_cast<size_t>(slots) * 8 * 256 * sizeof(float) : 0;
+    return *lds == 0 ||
+           hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(*lds)) == hipSuccess;
+}
+
 template <int DT_IN, int DT_OUT, int MODE>
 void launch_token(const QkPrepParams& p, hipStream_t stream) {
     const int nchunks = p.num_heads * p.head_dim / 8;              // <= 2048, checked by la_qk_prep
     const int need = (nchunks + 63) / 64;                          // chunks per lane with one wave per token
 #define LA_QK_PREP_TOKEN(NCH, WG) \
-    hipLaunchKernelGGL((la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>), \
-                       MODE ? grid_for_rounds(p, WG ? 1 : 4) : grid_for(p.tokens, WG ? 1 : 4), dim3(256), 0, stream, p)
+    do { \
+        dim3 grid = MODE ? grid_for_rounds(p, WG ? 1 : 4) : grid_for(p.tokens, WG ? 1 : 4); \
+        size_t lds = 0; \
+        if (MODE >= 3 && !smooth_launch_shape(la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>, p, NCH, &grid, &lds)) return; \
+        hipLaunchKernelGGL((la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>), grid, dim3(256), lds, stream, p); \
+    } while (0)
     if (need <= 1) LA_QK_PREP_TOKEN(1, false);
     else if (need <= 2) LA_QK_PREP_TOKEN(2, false);
     else if (need <= 4) LA_QK_PREP_TOKEN(4, false);
@@ -481,8 +649,11 @@ void launch_typed(const QkPrepParams& p, hipStream_t stream) {
     } else {
         int group_log2 = 0;
         while ((8 << group_log2) < p.head_dim) ++group_log2;       // head_dim <= 256: at most 5
-        hipLaunchKernelGGL((la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>), MODE ? grid_for_rounds(p, 4) : grid_for(p.tokens, 4), dim3(256), 0,
-                           stream, p, group_log2);
+        dim3 grid = MODE ? grid_for_rounds(p, 4) : grid_for(p.tokens, 4);
+        size_t lds = 0;
+        if (MODE >= 3 && !smooth_launch_shape(la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>, p, head_sum_slots(p.num_heads, p.head_dim), &grid, &lds))
+            return;
+        hipLaunchKernelGGL((la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>), grid, dim3(256), lds, stream, p, group_log2);
     }
 }
 
@@ -498,7 +669,46 @@ void launch_in_fp8(const QkPrepParams& p, hipStream_t stream) {
     else launch_typed<DT_IN, 2, 2>(p, stream);
 }
 
+// mean[b][h][d] = (part[0][b][h][d] + part[1][b][h][d] + ...) / seqlen, added in index order: one thread per column
+__global__ void __launch_bounds__(256) la_colsum_finish_kernel(const float* __restrict__ part, int n_parts, int64_t cols, int head_dim,
+                                                                 int num_heads, float seqlen, float* __restrict__ mean, int64_t m_bs,
+                                                                 int64_t m_hs) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (c >= cols) return;
+    float acc = 0.f;
+    for (int q = 0; q < n_parts; ++q) acc += part[q * cols + c];
+    const int64_t bh = c / head_dim, b = bh / num_heads;
+    mean[b * m_bs + (bh - b * num_heads) * m_hs + (c - bh * head_dim)] = acc / seqlen;
+}
+
 }  // namespace
+
+int qk_prep_sum_slots(const QkPrepParams& p) {
+    return p.norm_mode == 1 ? token_sum_slots(p.num_heads * p.head_dim / 8) : head_sum_slots(p.num_heads, p.head_dim);
+}
+
+hipError_t launch_qk_prep_smooth(const QkPrepParams& p, int in_dtype, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (p.out) {
+        if (in_dtype == 0) launch_typed<0, 2, 3>(p, stream);
+        else if (in_dtype == 1) launch_typed<1, 2, 3>(p, stream);
+        else launch_typed<3, 2, 3>(p, stream);
+    } else {
+        if (in_dtype == 0) launch_typed<0, 2, 4>(p, stream);
+        else if (in_dtype == 1) launch_typed<1, 2, 4>(p, stream);
+        else launch_typed<3, 2, 4>(p, stream);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean,
+                                int64_t m_bs, int64_t m_hs, hipStream_t stream) {
+    (void)hipGetLastError();
+    const int64_t cols = static_cast<int64_t>(batch) * num_heads * head_dim;
+    hipLaunchKernelGGL(la_colsum_finish_kernel, dim3(static_cast<unsigned>((cols + 255) / 256)), dim3(256), 0, stream, part, n_parts, cols,
+                       head_dim, num_heads, static_cast<float>(seqlen), mean, m_bs, m_hs);
+    return hipGetLastError();
+}
 
 hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
     (void)hipGetLastError();

@@ -9,7 +9,11 @@ cast to bf16 / fp16 (``la_qk_prep``), in place of the ten-odd eager passes with 
 
 The e4m3 form (``la_qk_prep_fp8``) is the producer of the fp8 forward's operands: ``qk_prep_fp8`` (scale, clamp, cast to
 ``float8_e4m3fn`` at the store), ``qk_prep_amax`` (the per-head amax pass alone), ``descale_from_amax`` and ``E4m3Scales``, which keeps
-the buffers of one tensor and returns ``(x8, descale)``; the descales then go into the attention call as ``q/k/v_descale``."""
+the buffers of one tensor and returns ``(x8, descale)``; the descales then go into the attention call as ``q/k/v_descale``.
+
+K smoothing (``la_qk_prep_smooth``): ``qk_prep_smooth`` subtracts a per-head vector from the keys before it quantizes them and collects
+the column sums that vector is made from (``qk_prep_colmean``) and the ``q . c`` row dots that undo its shift of the LSE
+(``lse_unshift``); ``SmoothedQK`` keeps the buffers of one layer's q and k."""
 from __future__ import annotations
 
 import ctypes
@@ -365,6 +369,279 @@ class E4m3Scales:
         return self.out, self.descale
 
 
+# ---- K smoothing: la_qk_prep_smooth ----------------------------------------------------------------------------------------------------------
+def qk_prep_smooth_parts(seqlen: int, num_heads: int, head_dim: int) -> Tuple[int, int]:
+    """``(n_parts, rows_per_part)`` of the column partial sums of ``qk_prep_smooth`` for a shape (``la_qk_prep_smooth_parts`` and
+    ``la_qk_prep_smooth_part_rows``): part p holds rows ``[p * rows_per_part, (p + 1) * rows_per_part)`` of each batch."""
+    lib = _cabi.load()
+    n = lib.la_qk_prep_smooth_parts(int(seqlen), int(num_heads), int(head_dim))
+    r = lib.la_qk_prep_smooth_part_rows(int(seqlen), int(num_heads), int(head_dim))
+    if n <= 0 or r <= 0:
+        raise ValueError(f"la_qk_prep_smooth_parts({seqlen}, {num_heads}, {head_dim}): {_cabi.status_string(min(n, r))}")
+    return n, r
+
+
+def _f32(name, t, shape, device):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{name} must be fp32 {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, shift, descale, amax, heads_per_scale, colsum_part,
+                         dot_vec, heads_per_dot, dot_out, out, store):
+    """One ``la_qk_prep_smooth`` call. ``store``: quantize into ``out`` (allocated when None)."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise ValueError("x must live on a GPU (there is no CPU path; qk_prep_smooth_reference is the formula in torch)")
+    if x.dtype not in _IN_DTYPES:
+        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
+    if norm not in _NORM_MODES:
+        raise ValueError('norm: "token", "head" or None')
+    mode = _NORM_MODES[norm]
+    B, S, H, D = x.shape
+    hps, hpd = int(heads_per_scale), int(heads_per_dot)
+    if hps < 1 or H % hps:
+        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
+    for name, t in (("descale", descale), ("amax_out", amax)):
+        if t is not None:
+            _f32(name, t, (B, H // hps), x.device)
+    if shift is not None:
+        _f32("shift", shift, (B, H, D), x.device)
+        if shift.stride(2) != 1:
+            raise ValueError("the last dimension of shift must be contiguous")
+    if dot_vec is not None:
+        if hpd < 1 or H % hpd:
+            raise ValueError(f"heads_per_dot must be a divisor of the {H} heads, got {heads_per_dot}")
+        _f32("dot_vec", dot_vec, (B, H // hpd, D), x.device)
+        if dot_vec.stride(2) != 1:
+            raise ValueError("the last dimension of dot_vec must be contiguous")
+        if dot_out is None:
+            dot_out = torch.empty((B, H, S), dtype=torch.float32, device=x.device)
+        _f32("dot_out", dot_out, (B, H, S), x.device)
+        if not dot_out.is_contiguous():
+            raise ValueError("dot_out must be contiguous")
+    elif dot_out is not None:
+        raise ValueError("dot_out needs dot_vec")
+    if B * S == 0:
+        return out
+    if colsum_part is not None:
+        n_parts, _ = qk_prep_smooth_parts(S, H, D)
+        _f32("colsum_part", colsum_part, (n_parts, B, H, D), x.device)
+        if not colsum_part.is_contiguous():
+            raise ValueError("colsum_part must be contiguous")
+    if store:
+        if out is None:
+            out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
+        if out.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    elif amax is None and colsum_part is None and dot_out is None:
+        raise ValueError("a pass that stores nothing needs amax_out, colsum_part or dot_vec")
+    if x.stride(-1) != 1 or (store and out.stride(-1) != 1):
+        raise ValueError("the last dimension of x and out must be contiguous")
+    if weight is not None and mode != _cabi.LA_NORM_NONE:
+        want = H * D if mode == _cabi.LA_NORM_TOKEN else D
+        if weight.dtype != torch.float32 or weight.numel() != want or not weight.is_contiguous() or weight.device != x.device:
+            raise ValueError(f"weight must be contiguous fp32 with {want} elements on {x.device} "
+                             f"(got {weight.dtype}, {tuple(weight.shape)}, {weight.device})")
+    a = _cabi.LaQkPrepSmoothArgs()
+    a.struct_size = ctypes.sizeof(_cabi.LaQkPrepSmoothArgs)
+    a.in_dtype, a.norm_mode, a.heads_per_scale, a.heads_per_dot = _IN_DTYPES[x.dtype], mode, hps, hpd
+    a.x = x.data_ptr()
+    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
+    if store:
+        a.out = out.data_ptr()
+        a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
+        if descale is not None:
+            a.descale, a.descale_batch_stride, a.descale_head_stride = descale.data_ptr(), descale.stride(0), descale.stride(1)
+    if amax is not None:
+        a.amax, a.amax_batch_stride, a.amax_head_stride = amax.data_ptr(), amax.stride(0), amax.stride(1)
+    if shift is not None:
+        a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
+    if colsum_part is not None:
+        a.colsum_part = colsum_part.data_ptr()
+    if dot_vec is not None:
+        a.dot_vec, a.dot_vec_batch_stride, a.dot_vec_head_stride = dot_vec.data_ptr(), dot_vec.stride(0), dot_vec.stride(1)
+        a.dot_out = dot_out.data_ptr()
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
+    a.eps, a.pos_offset = float(eps), int(pos_offset)
+    if tables is not None:
+        for i, (t, n) in enumerate(zip(tables, axis_pairs)):
+            if t.device != x.device:
+                raise ValueError(f"rope table {i} lives on {t.device}, x on {x.device}: build the tables with device=x.device")
+            a.rope_table[i] = t.data_ptr() if n > 0 else None
+            a.axis_extent[i], a.axis_pairs[i] = t.shape[0], n
+    with torch.cuda.device(x.device):
+        rc = _cabi.load().la_qk_prep_smooth(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_qk_prep_smooth: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()}, out strides "
+                           f"{out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, heads_per_dot {hpd}, shift "
+                           f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}, pos_offset {pos_offset}, "
+                           f"{S} rows on a grid of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]})")
+    return out
+
+
+def qk_prep_smooth(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+                   norm: Optional[str] = "token", pos_offset: int = 0, *, shift: Optional[torch.Tensor] = None,
+                   descale: Optional[torch.Tensor] = None, amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1,
+                   colsum_part: Optional[torch.Tensor] = None, dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1,
+                   dot_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   quantize: bool = True) -> Optional[torch.Tensor]:
+    """``qk_prep_fp8`` with K smoothing (``la_qk_prep_smooth``). With y the fp32 value ``qk_prep`` would round:
+
+    shift         fp32 (B, H, D): ``out`` and ``amax_out`` are taken from ``y - shift[b, h]``. Subtracting one vector from every key
+                  of a head changes neither P nor O nor the skip vote; the LSE moves by ``-softmax_scale * (q . shift)``.
+    colsum_part   fp32 (n_parts, B, H, D) contiguous, ``n_parts`` from ``qk_prep_smooth_parts``: the sums of the UNSHIFTED y over the
+                  rows of each part, bit-reproducible (``colsum_finish`` makes the mean of them).
+    dot_vec       fp32 (B, H // heads_per_dot, D): ``dot_out[b, h, s] = sum_d y[b, s, h, d] * dot_vec[b, h // heads_per_dot, d]`` of the
+                  unshifted, unquantized y, fp32 (B, H, S) - the layout of the LSE. For q, ``dot_vec`` is the shift given for k and
+                  ``heads_per_dot`` = H_q // H_kv; ``lse_unshift`` then restores the LSE. ``dot_out`` None: allocated; read it from
+                  the ``dot_out`` you pass.
+    quantize      False: nothing is stored (a sums-only, dots-only or amax-only pass), returns None.
+    Everything else as ``qk_prep_fp8``; with ``shift``, ``colsum_part`` and ``dot_vec`` all None it is ``qk_prep_fp8``, bit for bit."""
+    tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
+    if not quantize and out is not None:
+        raise ValueError("quantize=False stores nothing: out must be None")
+    return _qk_prep_smooth_impl(x, weight, eps, tabs, pairs, norm, pos_offset, shift, descale, amax_out, heads_per_scale, colsum_part,
+                                dot_vec, heads_per_dot, dot_out, out, bool(quantize))
+
+
+def colsum_finish(colsum_part: torch.Tensor, seqlen: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mean[b, h, d] = (part[0, b, h, d] + part[1, b, h, d] + ...) / seqlen``, added in index order (``la_colsum_finish``)."""
+    if colsum_part.dim() != 4 or colsum_part.dtype != torch.float32 or not colsum_part.is_contiguous() or not colsum_part.is_cuda:
+        raise ValueError("colsum_part must be contiguous fp32 (n_parts, B, H, D) on a GPU")
+    n_parts, B, H, D = colsum_part.shape
+    if out is None:
+        out = torch.empty((B, H, D), dtype=torch.float32, device=colsum_part.device)
+    _f32("out", out, (B, H, D), colsum_part.device)
+    if out.stride(2) != 1:
+        raise ValueError("the last dimension of out must be contiguous")
+    with torch.cuda.device(colsum_part.device):
+        rc = _cabi.load().la_colsum_finish(colsum_part.data_ptr(), n_parts, B, H, D, int(seqlen), out.data_ptr(), out.stride(0), out.stride(1),
+                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_colsum_finish: {_cabi.status_string(rc)} (parts {tuple(colsum_part.shape)}, seqlen {seqlen})")
+    return out
+
+
+def qk_prep_colmean(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
+                    norm: Optional[str] = "token", pos_offset: int = 0, *, colsum_part: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mean of y over the rows, fp32 (B, H, D): the sums-only pass of ``qk_prep_smooth`` plus ``colsum_finish``. x is read once and
+    nothing of its size is written. ``colsum_part`` / ``out``: buffers to reuse (None: allocated)."""
+    B, S, H, D = x.shape
+    if colsum_part is None:
+        colsum_part = torch.empty((qk_prep_smooth_parts(S, H, D)[0], B, H, D), dtype=torch.float32, device=x.device)
+    qk_prep_smooth(x, weight, eps, tables, norm, pos_offset, colsum_part=colsum_part, quantize=False)
+    return colsum_finish(colsum_part, S, out=out)
+
+
+def qk_prep_smooth_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                             tables: Optional[RopeTables] = None, norm: Optional[str] = "token", pos_offset: int = 0, *,
+                             shift: Optional[torch.Tensor] = None, descale: Optional[torch.Tensor] = None, heads_per_scale: int = 1,
+                             dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1):
+    """The formula of ``qk_prep_smooth`` in torch fp64, with ``y = qk_prep_reference(...)``: ``(clamp((y - shift) / descale, -448, 448)``
+    UNROUNDED, the amax (B, H // heads_per_scale) of ``|y - shift|``, the mean (B, H, D) of y over the rows, the row dots (B, H, S) of y
+    with ``dot_vec`` or None``)``, all fp64."""
+    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset)
+    B, S, H, D = y.shape
+    hps, hpd = int(heads_per_scale), int(heads_per_dot)
+    if hps < 1 or H % hps:
+        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
+    mean = y.mean(dim=1)
+    dots = None
+    if dot_vec is not None:
+        if hpd < 1 or H % hpd:
+            raise ValueError(f"heads_per_dot must be a divisor of the {H} heads, got {heads_per_dot}")
+        dots = torch.einsum("bshd,bhd->bhs", y, dot_vec.double().to(y.device).repeat_interleave(hpd, dim=1))
+    z = y if shift is None else y - shift.double().to(y.device)[:, None]
+    amax = z.abs().reshape(B, S, H // hps, hps * D).amax(dim=(1, 3))
+    if descale is not None:
+        z = z / descale.double().to(y.device).repeat_interleave(hps, dim=1)[:, None, :, None]
+    return z.clamp(-E4M3_MAX, E4M3_MAX), amax, mean, dots
+
+
+def lse_unshift(lse: torch.Tensor, dot: torch.Tensor, softmax_scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``lse + softmax_scale * dot``: the LSE of the unshifted keys from the LSE the attention call returned for keys shifted by c and
+    ``dot`` = q . c (``qk_prep_smooth(..., dot_vec=c)`` on the q side), both (B, H, S) fp32. ``softmax_scale`` is the one given to the
+    attention call (its default is ``head_dim ** -0.5``). One torch add: no host sync, captures into a HIP graph. Needed wherever the
+    LSE is used - e.g. the merge of the text + video recipe; O needs nothing."""
+    return torch.add(lse, dot, alpha=float(softmax_scale), out=out)
+
+
+class SmoothedQK:
+    """The buffers of one layer's q and k across calls, with the keys mean-shifted before they are quantized:
+    ``q8, k8, dq, dk, lse_shift = smoothed.pair(xq, xk, wq, wk, eps, tables, norm)``. ``q8, k8`` e4m3, ``dq, dk`` the descales for the
+    attention call, ``lse_shift`` (B, H_q, S) = q . c for ``lse_unshift`` (O needs no correction). k is prepared BEFORE q: q's dots need
+    the shift k used. V keeps using ``E4m3Scales``.
+
+    mode "current"   k: the column-mean pass, the amax pass of ``y - mean``, the quantizing pass (three reads of xk);
+                     q: the amax pass, the quantizing pass with the dots (two reads of xq).
+    mode "delayed"   one read of each tensor: step t shifts by step t - 1's mean and scales by step t - 1's amaxes, and collects its own
+                     part sums and amaxes in the same pass; the finish kernel then makes the mean for step t + 1. ANY shift vector is
+                     exact, so a stale mean costs no correctness - only the amax may outgrow ``margin``. The first call has no
+                     history and runs as "current".
+    Buffers are allocated by the first call and reused: no host sync, no allocation after it; a call overwrites the last results."""
+
+    def __init__(self, mode: str = "current", margin: float = 1.0, heads_per_scale: Optional[int] = None):
+        if mode not in ("current", "delayed"):
+            raise ValueError('mode: "current" or "delayed"')
+        if not margin > 0:
+            raise ValueError("margin must be positive")
+        self.mode, self.margin, self.heads_per_scale = mode, float(margin), heads_per_scale
+        self.q8 = self.k8 = None
+        self.calls = 0
+
+    def _allocate(self, xq, xk, hps):
+        dev = xk.device
+        B, S, Hk, D = xk.shape
+        Hq = xq.shape[2]
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.q8 = torch.empty(xq.shape, dtype=torch.float8_e4m3fn, device=dev)
+        self.k8 = torch.empty(xk.shape, dtype=torch.float8_e4m3fn, device=dev)
+        self.amax_q, self.amax_k = torch.zeros((B, Hq // hps), **f32), torch.zeros((B, Hk), **f32)
+        self.dq, self.dk = torch.empty_like(self.amax_q), torch.empty_like(self.amax_k)
+        self.part = torch.empty((qk_prep_smooth_parts(S, Hk, D)[0], B, Hk, D), **f32)
+        self.mean = torch.empty((B, Hk, D), **f32)
+        self.lse_shift = torch.empty((B, Hq, xq.shape[1]), **f32)
+
+    def pair(self, xq, xk, wq=None, wk=None, eps=1e-6, tables=None, norm="token", pos_offset=0):
+        Hq, Hk = xq.shape[2], xk.shape[2]
+        if Hq % Hk:
+            raise ValueError(f"{Hq} query heads are no multiple of {Hk} key heads")
+        hps = Hq // Hk if self.heads_per_scale is None else int(self.heads_per_scale)
+        if hps != Hq // Hk:
+            raise ValueError(f"heads_per_scale of q must be H_q // H_kv = {Hq // Hk} (the attention call takes descales per kv head)")
+        first = self.q8 is None or self.q8.shape != xq.shape or self.k8.shape != xk.shape or self.k8.device != xk.device
+        if first:
+            self._allocate(xq, xk, hps)
+        args_q, args_k = (xq, wq, eps, tables, norm, pos_offset), (xk, wk, eps, tables, norm, pos_offset)
+        if first or self.mode == "current":
+            qk_prep_colmean(*args_k, colsum_part=self.part, out=self.mean)
+            self.amax_k.zero_()
+            qk_prep_smooth(*args_k, shift=self.mean, amax_out=self.amax_k, quantize=False)
+            descale_from_amax(self.amax_k, self.margin, out=self.dk)
+            qk_prep_smooth(*args_k, shift=self.mean, descale=self.dk, out=self.k8)
+            self.amax_q.zero_()
+            qk_prep_amax(*args_q, amax_out=self.amax_q, heads_per_scale=hps)
+            descale_from_amax(self.amax_q, self.margin, out=self.dq)
+            qk_prep_smooth(*args_q, descale=self.dq, heads_per_scale=hps, dot_vec=self.mean, heads_per_dot=hps, dot_out=self.lse_shift,
+                           out=self.q8)
+        else:
+            descale_from_amax(self.amax_k, self.margin, out=self.dk)
+            descale_from_amax(self.amax_q, self.margin, out=self.dq)
+            self.amax_k.zero_()
+            self.amax_q.zero_()
+            qk_prep_smooth(*args_k, shift=self.mean, descale=self.dk, amax_out=self.amax_k, colsum_part=self.part, out=self.k8)
+            qk_prep_smooth(*args_q, descale=self.dq, amax_out=self.amax_q, heads_per_scale=hps, dot_vec=self.mean, heads_per_dot=hps,
+                           dot_out=self.lse_shift, out=self.q8)
+            colsum_finish(self.part, xk.shape[1], out=self.mean)          # behind q's read of the mean this step used
+        self.calls += 1
+        return self.q8, self.k8, self.dq, self.dk, self.lse_shift
+
+
 # ---- op registration: torch.ops.lite_attention.qk_prep, beside fwd / fwd_combine ---------------------------------------------------------
 _QK_PREP_SCHEMA = ("qk_prep(Tensor x, Tensor? weight = None, float eps = 1e-6, Tensor[]? tables = None, int[]? axis_pairs = None, "
                    "str? norm = \"token\", int pos_offset = 0, Tensor(out!)? out = None, ScalarType? out_dtype = None) -> Tensor(out!)")
@@ -402,6 +679,29 @@ def _qk_prep_fp8_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, no
     return out if out is not None else torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
 
 
+_QK_PREP_SMOOTH_SCHEMA = ("qk_prep_smooth(Tensor x, Tensor? weight = None, float eps = 1e-6, Tensor[]? tables = None, "
+                          "int[]? axis_pairs = None, str? norm = \"token\", int pos_offset = 0, Tensor? shift = None, Tensor? descale = None, "
+                          "Tensor(amax!)? amax_out = None, int heads_per_scale = 1, Tensor(part!)? colsum_part = None, "
+                          "Tensor? dot_vec = None, int heads_per_dot = 1, Tensor(dots!)? dot_out = None, Tensor(out!)? out = None) "
+                          "-> Tensor(out!)")
+
+
+def _qk_prep_smooth_op(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, shift=None, descale=None,
+                       amax_out=None, heads_per_scale=1, colsum_part=None, dot_vec=None, heads_per_dot=1, dot_out=None, out=None):
+    """The quantizing form (the op returns a tensor); with ``dot_vec`` it wants ``dot_out`` too."""
+    tabs, pairs = _unpack_tables(None if tables is None else (tables, axis_pairs or ()), x.shape[-1])
+    if dot_vec is not None and dot_out is None:
+        raise ValueError("the op writes the dots into dot_out: give it")
+    return _qk_prep_smooth_impl(x, weight, eps, tabs, pairs, norm, pos_offset, shift, descale, amax_out, heads_per_scale, colsum_part,
+                                dot_vec, heads_per_dot, dot_out, out, True)
+
+
+def _qk_prep_smooth_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, shift=None, descale=None,
+                         amax_out=None, heads_per_scale=1, colsum_part=None, dot_vec=None, heads_per_dot=1, dot_out=None, out=None):
+    """Shape and dtype only."""
+    return out if out is not None else torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+
+
 def _register_op():
     global _op_lib
     if _op_lib is not None:
@@ -414,6 +714,9 @@ def _register_op():
     lib.define(_QK_PREP_FP8_SCHEMA)
     lib.impl("qk_prep_fp8", _qk_prep_fp8_op, "CUDA")
     lib.impl("qk_prep_fp8", _qk_prep_fp8_meta, "Meta")
+    lib.define(_QK_PREP_SMOOTH_SCHEMA)
+    lib.impl("qk_prep_smooth", _qk_prep_smooth_op, "CUDA")
+    lib.impl("qk_prep_smooth", _qk_prep_smooth_meta, "Meta")
     _op_lib = lib
 
 
