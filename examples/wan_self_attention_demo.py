@@ -10,7 +10,8 @@ per layer, the skip state carried across denoising steps.
 
 `--fused-prep` (`fused_prep=True` on the modules): RMSNorm, RoPE and the bf16 cast of q and k run as ONE pass each (`qk_prep`) instead of
 the eager lines below. `--fp8 --smooth-k`: each key head's mean over the tokens is subtracted before the e4m3 cast (`SmoothedQK`); the
-output needs no correction.
+output needs no correction. `--fp8 --smooth-v` (combinable with `--smooth-k`): the same for V (`SmoothedV`); the mean is added back to
+the attention output by the restoring pass, which also replaces the block's `.float()` (`out_dtype=torch.float32`).
 
 Prints, per denoising step, the fraction of tiles skipped and the error against the same block with skipping disabled.
 """
@@ -26,6 +27,7 @@ from lite_attention import LiteAttention  # noqa: E402  (same import line as the
 from lite_attention import qk_prep, rope_tables  # noqa: E402  (the fused q / k prologue: fused_prep=True)
 from lite_attention import E4m3Scales  # noqa: E402  (its e4m3 form with per-head scales: fp8=True)
 from lite_attention import SmoothedQK  # noqa: E402  (... with the keys mean-shifted before they are quantized: smooth_k=True)
+from lite_attention import SmoothedV  # noqa: E402  (... and V: smooth_v=True; the attention call adds the mean back to its output)
 
 
 class RMSNorm(nn.Module):
@@ -62,7 +64,7 @@ def rope_3d(x, grid, theta=10000.0):
 
 class WanLikeSelfAttention(nn.Module):
     def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1, fused_prep=False, *, fp8=False,
-                 fp8_mode="current", fp8_margin=1.0, smooth_k=False):
+                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False):
         super().__init__()
         assert dim % num_heads == 0
         self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
@@ -72,6 +74,9 @@ class WanLikeSelfAttention(nn.Module):
         # smooth_k: q and k go through one SmoothedQK instead (k first, q with the dots that would restore the LSE); v as before
         assert fp8 or not smooth_k, "smooth_k is a form of the fp8 path"
         self.smoothed = SmoothedQK(mode=fp8_mode, margin=fp8_margin) if smooth_k else None
+        # smooth_v: v goes through a SmoothedV; the attention call restores O (v_shift) and hands it on in fp32 (out_dtype)
+        assert fp8 or not smooth_v, "smooth_v is a form of the fp8 path"
+        self.smoothed_v = SmoothedV(mode=fp8_mode, margin=fp8_margin) if smooth_v else None
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
         # the recipe: ONE LiteAttention per attention layer (its skip lists are that layer's state)
@@ -87,6 +92,10 @@ class WanLikeSelfAttention(nn.Module):
             else:
                 q, dq = self.scales[0](self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables)
                 k, dk = self.scales[1](self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables)
+            if self.smoothed_v is not None:                         # the block's .float() becomes the restoring pass' out_dtype
+                v, dv, v_shift = self.smoothed_v(self.v(x).view(b, s, n, d))
+                return self.o(self.lite_attention(q, k, v, q_descale=dq, k_descale=dk, v_descale=dv, v_shift=v_shift,
+                                                  out_dtype=torch.float32).flatten(2))
             v, dv = self.scales[2](self.v(x).view(b, s, n, d), norm=None)
             return self.o(self.lite_attention(q, k, v, q_descale=dq, k_descale=dk, v_descale=dv).float().flatten(2))
         if self.fused_prep:                                         # norm + rope + cast of q and of k: one pass each
@@ -144,11 +153,11 @@ class WanLikeCrossAttention(nn.Module):
 
 
 def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False, *,
-        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False):
+        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False):
     torch.manual_seed(seed)
     dim, grid = heads * 128, (frames, height, width)
     S = frames * height * width
-    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k)
+    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v)
     sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep, **kw).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
     # under which tokens of the same frame attend to each other
@@ -182,6 +191,10 @@ if __name__ == "__main__":
     ap.add_argument("--fp8-mode", choices=("current", "delayed"), default="current")
     ap.add_argument("--fp8-margin", type=float, default=1.0)
     ap.add_argument("--smooth-k", action="store_true", help="with --fp8: subtract each key head's mean before the e4m3 cast (SmoothedQK)")
+    ap.add_argument("--smooth-v", action="store_true", help="with --fp8: subtract each V head's mean before the e4m3 cast (SmoothedV); "
+                    "the attention call adds it back and returns fp32")
     a = ap.parse_args()
+    if (a.smooth_k or a.smooth_v) and not a.fp8:
+        ap.error("--smooth-k and --smooth-v need --fp8")
     run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep, fp8=a.fp8, fp8_mode=a.fp8_mode,
-        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k)
+        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v)

@@ -29,6 +29,10 @@
  *   la_qk_prep_smooth     <- nothing: la_qk_prep_fp8 that can subtract a per-head vector from k before quantizing ("smooth K"), with
  *                            the deterministic column sums that vector is made from (la_colsum_finish) and the q . c row dots that
  *                            undo its shift of the LSE
+ *   la_v_colstats         <- nothing: mean and exact amax of V - mean in one read of V (with la_v_colstats_finish), for a V that is
+ *                            quantized mean-shifted ("smooth V")
+ *   la_attn_unshift       <- nothing: adds that mean back to the attention output (exact: the rows of P sum to 1), restores the LSE
+ *                            of smoothed keys and casts, in one read of O
  *
  * Rules of the boundary:
  *   - plain C: pointers, sizes, scalars. No torch types, no C++ types, no exceptions.
@@ -48,7 +52,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows) and la_colsum_finish were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish) and la_attn_unshift were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -482,6 +486,84 @@ int la_qk_prep_smooth_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_
 /* Errors: NULL part / mean_out LA_ERR_NULL_ARG; a non-positive size LA_ERR_SHAPE; a negative stride or a pointer off 4 bytes LA_ERR_STRIDE. */
 int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
                      float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride, void* stream);
+
+/* V smoothing: the twin of K smoothing for the one operand that is quantized as it leaves its projection. la_fwd divides by its own
+ * row sum, so the rows of P sum to 1 over whatever keys a row visits - with skip lists, with split keys and after an LSE merge - and
+ *   P (V - 1 m^T) + 1 m^T = P V     for any vector m[b][h_kv][:].
+ * V is quantized as V - m (la_qk_prep_smooth with LA_NORM_NONE, shift = m, descale), la_fwd runs unchanged on the shifted codes, and
+ * la_attn_unshift adds m to O in fp32: the rounding of V and of the e4m3 P is paid on the centred values only.
+ *
+ * la_v_colstats: x (B, S, H, D) bf16 / fp16 / fp32 by its strides (elements), last dimension contiguous, head_dim % 8 == 0 and <= 256;
+ * no norm, no rope, no weight. stat_part fp32 [n_parts, 3, B, H, D] contiguous: stat_part[p][0 / 1 / 2][b][h][d] = the SUM, MINIMUM and
+ * MAXIMUM of float(x[b][s][h][d]) over rows s in [p R, (p + 1) R), n_parts = la_v_colstats_parts(S, H, D), R =
+ * la_v_colstats_part_rows(S, H, D) = max(16, ceil(S * (H * D / 8) / 131072)): pure functions of (S, H, D), not of the device, the grid
+ * or the timing. The sum is added in row order from 0.0f; no float atomics: two launches agree bit for bit. A part without rows is
+ * written as 0, +inf, -inf; every element is written. A NaN in a column makes that column's sum NaN; minimum and maximum skip it.
+ * One read of x.
+ * la_v_colstats_finish: mean_out[b][h][d] = (sum_0 + sum_1 + ...) / S, added in index order; amax_out[b][h] = max over d of
+ * max(|fl(vmax - mean)|, |fl(mean - vmin)|), one fp32 subtraction each, taken as the unsigned maximum of the bit patterns (a NaN mean
+ * makes that head's amax NaN and no other's). Rounding is monotone, so this is the largest |fl(x - mean)| over the rows: the bits
+ * la_qk_prep_smooth reports with shift = mean_out, LA_NORM_NONE, a zeroed amax and out = NULL - mean and exact amax for one read of x
+ * instead of two. amax_out is WRITTEN, not accumulated; NULL: not wanted. mean_out fp32 [B, H, D] and amax_out fp32 [B, H] by their
+ * strides (elements); n_parts / batch / num_heads / head_dim describe stat_part.
+ * Errors of la_v_colstats (all before any HIP call), in this order: NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; NULL x or
+ * stat_part LA_ERR_NULL_ARG; in_dtype LA_ERR_DTYPE; a non-positive size LA_ERR_SHAPE; head_dim % 8 != 0 or above 256 LA_ERR_HEAD_DIM; a
+ * negative stride, x or stat_part off a 16-byte boundary, or a used x stride (seqlen > 1: row, num_heads > 1: head, batch > 1: batch)
+ * that takes a row, head or batch start off one, LA_ERR_STRIDE. Of la_v_colstats_finish: NULL part / mean_out LA_ERR_NULL_ARG; a
+ * non-positive size LA_ERR_SHAPE; head_dim above 256 LA_ERR_HEAD_DIM; a negative stride or a pointer off 4 bytes LA_ERR_STRIDE.
+ * NOT detected: a stat_part shorter than n_parts * 3 * B * H * D floats, buffers that overlap. */
+typedef struct la_v_colstats_args {
+    uint32_t struct_size;        /* = sizeof(la_v_colstats_args)                                  */
+    int32_t  in_dtype;           /* la_dtype of x: LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32  */
+    const void* x;               /* (B, S, H, D), last dimension contiguous                       */
+    float*      stat_part;       /* fp32 [n_parts, 3, B, H, D] contiguous                         */
+    int64_t x_batch_stride, x_row_stride, x_head_stride;          /* in elements                  */
+    int32_t batch, seqlen, num_heads, head_dim;
+} la_v_colstats_args;
+int la_v_colstats(const la_v_colstats_args* args, void* stream);
+/* Parts and rows per part of stat_part for a shape: pure functions of their arguments (LA_ERR_SHAPE for a non-positive one). */
+int la_v_colstats_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim);
+int la_v_colstats_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim);
+int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
+                         float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride,
+                         float* amax_out, int64_t amax_batch_stride, int64_t amax_head_stride, void* stream);
+
+/* la_attn_unshift: the restoring pass, one read of the attention output.
+ *   out[b][s][h][:]  = round_to_out_dtype(float(o[b][s][h][:]) + shift[b][h / heads_per_vec][:])     one fp32 addition, one rounding
+ *   lse_out[b][h][s] = fmaf(softmax_scale, lse_dot[b][h][s], lse[b][h][s])                            only when lse_dot is given
+ * o bf16 / fp16 (B, S, H, D) by its strides - what la_fwd returns; out bf16, fp16 or fp32 by its OWN strides (e.g. the (B, S, H * D)
+ * fp32 tensor an output projection reads). out may BE o (equal element sizes and strides: a chunk of 8 elements is read completely
+ * before it is written, by the one thread that touches it); any other overlap of the two is NOT detected. shift fp32 [B, H_kv, D] by
+ * its strides, heads_per_vec = H_q / H_kv (GQA / MQA); NULL: nothing is added (a cast / LSE pass). lse, lse_dot, lse_out fp32 [B, H, S]
+ * contiguous (the layout of la_fwd's lse):
+ *   lse       optional. When given, a row whose lse is +inf or -inf is written as ZEROS and its lse_out is its lse: la_fwd's empty sum
+ *             (seqlen_k == 0 gives O = 0, LSE = +inf; an empty partial -inf) - no weights carry the shift. A NaN lse takes the normal path.
+ *   lse_dot / lse_out   both or neither, and only with lse: la_qk_prep_smooth's q . c row dots and the LSE of the unshifted keys (K
+ *             smoothing undone in the same pass). lse_out may be lse (an element is read and written by one thread).
+ * Errors (all before any HIP call), in this order: NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; NULL o or out, exactly one
+ * of lse_dot / lse_out, or the two without lse, LA_ERR_NULL_ARG; o_dtype not bf16 / fp16 or out_dtype not bf16 / fp16 / fp32
+ * LA_ERR_DTYPE; a non-positive size, or (with shift) heads_per_vec below 1 or not a divisor of num_heads, LA_ERR_SHAPE; head_dim % 8 != 0
+ * LA_ERR_HEAD_DIM; a negative stride, o, out or shift off a 16-byte boundary, a used stride of them that takes a row, head or batch
+ * start off one, or lse / lse_dot / lse_out off a 4-byte boundary, LA_ERR_STRIDE. */
+typedef struct la_attn_unshift_args {
+    uint32_t struct_size;        /* = sizeof(la_attn_unshift_args)                                */
+    int32_t  o_dtype;            /* la_dtype of o: LA_DTYPE_BF16 or LA_DTYPE_FP16                 */
+    int32_t  out_dtype;          /* la_dtype of out: LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32 */
+    int32_t  heads_per_vec;      /* query heads that share one shift row: H_q / H_kv              */
+    const void* o;               /* (B, S, H, D), last dimension contiguous                       */
+    void*       out;             /* (B, S, H, D) by its own strides; may be o                     */
+    int64_t o_batch_stride, o_row_stride, o_head_stride;          /* in elements                  */
+    int64_t out_batch_stride, out_row_stride, out_head_stride;
+    int32_t batch, seqlen, num_heads, head_dim;
+    const float* shift;          /* fp32 [B, H / heads_per_vec, D] by the strides below; NULL = no shift */
+    int64_t shift_batch_stride, shift_head_stride;
+    const float* lse;            /* fp32 [B, H, S] contiguous; NULL = no empty-row rule           */
+    const float* lse_dot;        /* fp32 [B, H, S] contiguous; given exactly when lse_out is      */
+    float*       lse_out;        /* fp32 [B, H, S] contiguous; may be lse                         */
+    float   softmax_scale;       /* the one given to la_fwd                                       */
+    int32_t reserved0;           /* 0                                                              */
+} la_attn_unshift_args;
+int la_attn_unshift(const la_attn_unshift_args* args, void* stream);
 
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)

@@ -26,6 +26,8 @@ if not _BUILDING:
     from .qk_prep import E4m3Scales, descale_from_amax, qk_prep_amax, qk_prep_fp8, qk_prep_fp8_reference  # noqa: E402
     from .qk_prep import (SmoothedQK, colsum_finish, lse_unshift, qk_prep_colmean, qk_prep_smooth, qk_prep_smooth_parts,  # noqa: E402
                           qk_prep_smooth_reference)
+    from .v_prep import (SmoothedV, attn_unshift, attn_unshift_reference, v_colstats, v_colstats_parts,  # noqa: E402
+                         v_colstats_reference, v_shift_as_bias)
     from .parallel import (HeadShardedLiteAttention, RingSeqParallelLiteAttention,  # noqa: E402
                            UlyssesLiteAttention)
 
@@ -36,4 +38,5 @@ __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flas
            "qk_prep", "qk_prep_reference", "rope_tables", "wan_rope_parts", "RopeTables",
            "qk_prep_fp8", "qk_prep_amax", "descale_from_amax", "qk_prep_fp8_reference", "E4m3Scales",
            "qk_prep_smooth", "qk_prep_colmean", "colsum_finish", "qk_prep_smooth_parts", "qk_prep_smooth_reference", "lse_unshift", "SmoothedQK",
+           "v_colstats", "v_colstats_parts", "v_colstats_reference", "attn_unshift", "attn_unshift_reference", "v_shift_as_bias", "SmoothedV",
            "HeadShardedLiteAttention", "UlyssesLiteAttention", "RingSeqParallelLiteAttention", "__version__"]

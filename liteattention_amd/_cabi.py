@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "la_status_string", "la_last_hip_error", "la_blockmask_to_lists", "la_device_slots", "la_build_info", "la_combine_list",
     "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error", "la_qk_prep", "la_qk_prep_fp8",
     "la_qk_prep_smooth", "la_qk_prep_smooth_parts", "la_qk_prep_smooth_part_rows", "la_colsum_finish",
+    "la_v_colstats", "la_v_colstats_parts", "la_v_colstats_part_rows", "la_v_colstats_finish", "la_attn_unshift",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -97,6 +98,30 @@ class LaQkPrepSmoothArgs(ctypes.Structure):
         ("colsum_part", ctypes.c_void_p),
         ("dot_vec", ctypes.c_void_p), ("dot_vec_batch_stride", ctypes.c_int64), ("dot_vec_head_stride", ctypes.c_int64),
         ("dot_out", ctypes.c_void_p), ("heads_per_dot", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+    ]
+
+
+class LaVColstatsArgs(ctypes.Structure):
+    """Mirror of ``la_v_colstats_args`` (field order and types must match the header)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("in_dtype", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("stat_part", ctypes.c_void_p),
+        ("x_batch_stride", ctypes.c_int64), ("x_row_stride", ctypes.c_int64), ("x_head_stride", ctypes.c_int64),
+        ("batch", ctypes.c_int32), ("seqlen", ctypes.c_int32), ("num_heads", ctypes.c_int32), ("head_dim", ctypes.c_int32),
+    ]
+
+
+class LaAttnUnshiftArgs(ctypes.Structure):
+    """Mirror of ``la_attn_unshift_args`` (field order and types must match the header)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("o_dtype", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("heads_per_vec", ctypes.c_int32),
+        ("o", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("o_batch_stride", ctypes.c_int64), ("o_row_stride", ctypes.c_int64), ("o_head_stride", ctypes.c_int64),
+        ("out_batch_stride", ctypes.c_int64), ("out_row_stride", ctypes.c_int64), ("out_head_stride", ctypes.c_int64),
+        ("batch", ctypes.c_int32), ("seqlen", ctypes.c_int32), ("num_heads", ctypes.c_int32), ("head_dim", ctypes.c_int32),
+        ("shift", ctypes.c_void_p), ("shift_batch_stride", ctypes.c_int64), ("shift_head_stride", ctypes.c_int64),
+        ("lse", ctypes.c_void_p), ("lse_dot", ctypes.c_void_p), ("lse_out", ctypes.c_void_p),
+        ("softmax_scale", ctypes.c_float), ("reserved0", ctypes.c_int32),
     ]
 
 
@@ -225,6 +250,17 @@ def load() -> ctypes.CDLL:
     lib.la_colsum_finish.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     lib.la_colsum_finish.restype = ctypes.c_int
+    lib.la_v_colstats.argtypes = [ctypes.POINTER(LaVColstatsArgs), ctypes.c_void_p]
+    lib.la_v_colstats.restype = ctypes.c_int
+    for fn in (lib.la_v_colstats_parts, lib.la_v_colstats_part_rows):
+        fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        fn.restype = ctypes.c_int
+    lib.la_v_colstats_finish.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_void_p]
+    lib.la_v_colstats_finish.restype = ctypes.c_int
+    lib.la_attn_unshift.argtypes = [ctypes.POINTER(LaAttnUnshiftArgs), ctypes.c_void_p]
+    lib.la_attn_unshift.restype = ctypes.c_int
     lib.la_device_slots.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.la_device_slots.restype = ctypes.c_int
     lib.la_status_string.argtypes = [ctypes.c_int]

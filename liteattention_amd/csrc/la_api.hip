@@ -650,4 +650,92 @@ int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t 
     return LA_OK;
 }
 
+// ---- V smoothing (la_prep_v.hip) ---------------------------------------------------------------------------------------------------
+int la_v_colstats_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
+    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
+    return la::v_colstats_parts(seqlen, num_heads, head_dim);
+}
+
+int la_v_colstats_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
+    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
+    return la::v_colstats_part_rows(seqlen, num_heads, head_dim);
+}
+
+// Every row, head and batch start of a (B, S, H, D) tensor on a 16-byte boundary: the pointer, and every stride that is used, in units
+// of 16 / element size
+static bool rows16(const void* ptr, int32_t dtype, int64_t bs, int64_t rs, int64_t hs, int32_t batch, int32_t seqlen, int32_t num_heads) {
+    const int64_t unit = dtype == LA_DTYPE_FP32 ? 4 : 8;
+    return bs >= 0 && rs >= 0 && hs >= 0 && aligned16(ptr) && (seqlen == 1 || rs % unit == 0) && (num_heads == 1 || hs % unit == 0) &&
+           (batch == 1 || bs % unit == 0);
+}
+
+int la_v_colstats(const la_v_colstats_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_v_colstats_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || !a->stat_part) return LA_ERR_NULL_ARG;
+    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
+    if (!rows16(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
+        !aligned16(a->stat_part)) return LA_ERR_STRIDE;
+    la::VColstatsParams p = {};
+    p.x = a->x; p.stat_part = a->stat_part;
+    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    p.n_parts = la::v_colstats_parts(a->seqlen, a->num_heads, a->head_dim);
+    p.part_rows = la::v_colstats_part_rows(a->seqlen, a->num_heads, a->head_dim);
+    // one thread per (part, batch, head, chunk of 8 columns), 256 per workgroup
+    if (static_cast<int64_t>(p.n_parts) * a->batch * a->num_heads * (a->head_dim / 8) > 0x7fffffffLL * 256) return LA_ERR_SHAPE;
+    const hipError_t err = la::launch_v_colstats(p, a->in_dtype, static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
+int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
+                         float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride, float* amax_out, int64_t amax_batch_stride,
+                         int64_t amax_head_stride, void* stream_) {
+    if (!part || !mean_out) return LA_ERR_NULL_ARG;
+    if (n_parts <= 0 || batch <= 0 || num_heads <= 0 || head_dim <= 0 || seqlen <= 0) return LA_ERR_SHAPE;
+    if (head_dim > 256) return LA_ERR_HEAD_DIM;                                   // one thread of a workgroup per column of a head
+    if (mean_batch_stride < 0 || mean_head_stride < 0 || amax_batch_stride < 0 || amax_head_stride < 0 ||
+        ((reinterpret_cast<uintptr_t>(part) | reinterpret_cast<uintptr_t>(mean_out) | reinterpret_cast<uintptr_t>(amax_out)) & 3u))
+        return LA_ERR_STRIDE;
+    if (static_cast<int64_t>(batch) * num_heads > 0x7fffffffLL) return LA_ERR_SHAPE;                       // one workgroup per head
+    const hipError_t err = la::launch_v_colstats_finish(part, n_parts, batch, num_heads, head_dim, seqlen, mean_out, mean_batch_stride,
+                                                        mean_head_stride, amax_out, amax_batch_stride, amax_head_stride,
+                                                        static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
+int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_attn_unshift_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->o || !a->out) return LA_ERR_NULL_ARG;
+    if ((a->lse_dot != nullptr) != (a->lse_out != nullptr) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
+    if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
+    if (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16 && a->out_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
+    if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
+    if (!rows16(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, a->seqlen, a->num_heads) ||
+        !rows16(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen, a->num_heads))
+        return LA_ERR_STRIDE;
+    if (a->shift && !rows16(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
+                            a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
+    if ((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out)) & 3u)
+        return LA_ERR_STRIDE;
+    la::AttnUnshiftParams p = {};
+    p.o = a->o; p.out = a->out; p.shift = a->shift; p.lse = a->lse; p.lse_dot = a->lse_dot; p.lse_out = a->lse_out;
+    p.o_bs = a->o_batch_stride; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
+    p.out_bs = a->out_batch_stride; p.out_rs = a->out_row_stride; p.out_hs = a->out_head_stride;
+    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
+    p.softmax_scale = a->softmax_scale;
+    const hipError_t err = la::launch_attn_unshift(p, a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
+    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+    return LA_OK;
+}
+
 }  // extern "C"

@@ -157,4 +157,40 @@ hipError_t launch_qk_prep_smooth(const QkPrepParams& p, int in_dtype, hipStream_
 hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean,
                                 int64_t m_bs, int64_t m_hs, hipStream_t stream);
 
+// la_v_colstats / la_attn_unshift (la_prep_v.hip): checked and filled by la_api.hip. Strides in elements.
+struct VColstatsParams {
+    const void* x;               // (B, S, H, D) by x_bs / x_rs / x_hs
+    float* stat_part;            // [n_parts, 3, B, H, D] contiguous: sum, minimum, maximum over the rows of each part
+    int64_t x_bs, x_rs, x_hs;
+    int batch, seqlen, num_heads, head_dim;
+    int n_parts, part_rows;
+};
+// Rows of a part: about kVColstatsThreads threads of 8 columns each (two waves per SIMD on 256 compute units), never fewer than 16
+// rows per part. The one place the row -> part map of la_v_colstats is decided: a function of (S, H, D) alone.
+constexpr int64_t kVColstatsThreads = 131072;
+inline int v_colstats_part_rows(int seqlen, int num_heads, int head_dim) {
+    const int64_t chunks = static_cast<int64_t>(num_heads) * ((head_dim + 7) / 8);
+    const int64_t r = (static_cast<int64_t>(seqlen) * chunks + kVColstatsThreads - 1) / kVColstatsThreads;
+    return r < 16 ? 16 : (r > 0x7fffffffLL ? 0x7fffffff : static_cast<int>(r));
+}
+inline int v_colstats_parts(int seqlen, int num_heads, int head_dim) {
+    const int64_t r = v_colstats_part_rows(seqlen, num_heads, head_dim);
+    return static_cast<int>((static_cast<int64_t>(seqlen) + r - 1) / r);
+}
+hipError_t launch_v_colstats(const VColstatsParams& p, int in_dtype, hipStream_t stream);      // in_dtype: 0 bf16, 1 fp16, 3 fp32
+hipError_t launch_v_colstats_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean,
+                                    int64_t m_bs, int64_t m_hs, float* amax, int64_t a_bs, int64_t a_hs, hipStream_t stream);
+struct AttnUnshiftParams {
+    const void* o;               // bf16 / fp16 (B, S, H, D) by o_bs / o_rs / o_hs
+    void* out;                   // bf16 / fp16 / fp32 by out_bs / out_rs / out_hs; may be o
+    const float* shift;          // [B, H / heads_per_vec, D] by sh_bs / sh_hs; NULL = nothing added
+    const float* lse;            // [B, H, S] contiguous; NULL = no empty-row rule
+    const float* lse_dot;        // [B, H, S]; given exactly when lse_out is
+    float* lse_out;              // [B, H, S]; may be lse
+    int64_t o_bs, o_rs, o_hs, out_bs, out_rs, out_hs, sh_bs, sh_hs;
+    int batch, seqlen, num_heads, head_dim, heads_per_vec;
+    float softmax_scale;
+};
+hipError_t launch_attn_unshift(const AttnUnshiftParams& p, int o_dtype, int out_dtype, hipStream_t stream);   // 0 bf16, 1 fp16, 3 fp32 (out only)
+
 }  // namespace la

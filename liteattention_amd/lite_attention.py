@@ -180,7 +180,8 @@ class LiteAttention:
     def __call__(self, query: Tensor, key: Tensor, value: Tensor, scale: Optional[float] = None,
                  return_softmax_lse: bool = False, must_do_list: list = None, must_skip_list: list = None, *,
                  q_descale: Optional[Tensor] = None, k_descale: Optional[Tensor] = None,
-                 v_descale: Optional[Tensor] = None) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+                 v_descale: Optional[Tensor] = None, v_shift: Optional[Tensor] = None, lse_shift: Optional[Tensor] = None,
+                 out_dtype: Optional[torch.dtype] = None) -> Union[Tensor, Tuple[Tensor, Tensor]]:
         """One attention call of a denoising step (:244-291).
 
         query (B, S, H, D) bf16; key/value (B, Sk, H, D). Returns out (B, S, H, D) — the reference
@@ -188,7 +189,15 @@ class LiteAttention:
         ``must_do_list``: token ranges ``[start0, end0, ...]`` (descending) never dropped;
         ``must_skip_list``: token ranges dropped from the start, applied when the lists are (re)built.
         ``q/k/v_descale`` (keyword-only extension; the reference class cannot pass them): fp32
-        ``(batch, nheads_k)`` dequantisation scales for e4m3 inputs, as ``flash_attn_func`` takes them."""
+        ``(batch, nheads_k)`` dequantisation scales for e4m3 inputs, as ``flash_attn_func`` takes them.
+        ``v_shift`` / ``lse_shift`` / ``out_dtype`` (keyword-only extension): the restoring pass of V and K smoothing
+        (``attn_unshift``), applied to what the forward returns - behind its internal split-KV merge. ``v_shift`` fp32
+        (batch, nheads_k, D): the vector subtracted from V (``SmoothedV``), added back to O; rows without keys stay 0.
+        ``lse_shift`` fp32 (batch, nheads, S): ``q . c`` of ``SmoothedQK``, folded into the returned LSE. ``out_dtype``:
+        bf16 / fp16 / fp32 of the returned O (fp32: what an output projection reads)."""
+        restore = v_shift is not None or lse_shift is not None or out_dtype is not None
+        if restore:
+            self._check_restore(query, key, value, v_shift, lse_shift, out_dtype)
         read_list, write_list = self._get_read_write_lists(query, key, must_skip_list)
         must_do = None
         if read_list is not None:
@@ -202,13 +211,42 @@ class LiteAttention:
             # the reference's heuristic (flash_api.cpp:437, heuristics.h:25-58; the reference class passes nothing, i.e. 1: its default
             # build has no split kernel, hopper/setup.py:48)
             extra["num_splits"] = -1
+        # the restoring pass reads the LSE for its empty-row rule: ask the forward for it whenever a shift is given
+        want_lse = return_softmax_lse or v_shift is not None or lse_shift is not None
         output = flash_attn_func(q=query, k=key, v=value, softmax_scale=scale, attn_read_list=read_list,
                                  attn_must_do_list=must_do, attn_write_list=write_list, thr=self._take_threshold(read_list is not None),
-                                 return_softmax_lse=return_softmax_lse, **extra)
+                                 return_softmax_lse=want_lse, **extra)
         if read_list is not None and _verbose():
             self._last_percentage = self.calc_percentage(read_list[: query.shape[0]])
             print(f"[Info]: Percentage of tiles skipped: {1.0 - self._last_percentage:.2%}")
+        if restore:
+            output = self._restore(output, want_lse, return_softmax_lse, scale, v_shift, lse_shift, out_dtype)
         return output
+
+    @staticmethod
+    def _check_restore(query, key, value, v_shift, lse_shift, out_dtype):
+        """The arguments of the restoring pass, before anything is launched."""
+        B, S, H = query.shape[0], query.shape[1], query.shape[2]
+        if v_shift is not None and (v_shift.dtype != torch.float32 or tuple(v_shift.shape) != (B, key.shape[2], value.shape[3])):
+            raise ValueError(f"v_shift must be fp32 (batch, nheads_k, D) = {(B, key.shape[2], value.shape[3])}, got {v_shift.dtype} "
+                             f"{tuple(v_shift.shape)}")
+        if lse_shift is not None and (lse_shift.dtype != torch.float32 or tuple(lse_shift.shape) != (B, H, S)):
+            raise ValueError(f"lse_shift must be fp32 (batch, nheads, S) = {(B, H, S)}, got {lse_shift.dtype} {tuple(lse_shift.shape)}")
+        if out_dtype not in (None, torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"out_dtype: bf16, fp16 or fp32, got {out_dtype}")
+
+    @staticmethod
+    def _restore(output, have_lse, return_lse, scale, v_shift, lse_shift, out_dtype):
+        from .v_prep import attn_unshift
+        o, lse = output if have_lse else (output, None)
+        in_place = out_dtype is None or out_dtype == o.dtype
+        fix_lse = lse_shift is not None and return_lse
+        if v_shift is None and in_place and not fix_lse:        # an LSE shift nobody asked the LSE of: nothing to do
+            return (o, lse) if return_lse else o
+        res = attn_unshift(o, v_shift, lse=lse, lse_dot=lse_shift if fix_lse else None, softmax_scale=scale, out=o if in_place else None,
+                           out_dtype=out_dtype, lse_out=lse if fix_lse else None)
+        out = res[0] if fix_lse else res
+        return (out, lse) if return_lse else out
 
     def call_windowed(self, query: Tensor, key: Tensor, value: Tensor, q_windows, window_hook=None,
                       scale: Optional[float] = None, return_softmax_lse: bool = False, must_do_list: list = None,
@@ -372,11 +410,17 @@ class SeqParallelLiteAttention:
 
     def __call__(self, query: Tensor, key: Tensor, value: Tensor, split_idx: int, scale: Optional[float] = None,
                  return_softmax_lse: bool = False, *, q_descale: Optional[Tensor] = None, k_descale: Optional[Tensor] = None,
-                 v_descale: Optional[Tensor] = None) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+                 v_descale: Optional[Tensor] = None, v_shift: Optional[Tensor] = None, lse_shift: Optional[Tensor] = None,
+                 out_dtype: Optional[torch.dtype] = None) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+        """``v_shift`` / ``lse_shift`` / ``out_dtype`` as ``LiteAttention.__call__``: this shard's output and LSE are restored HERE, before
+        the caller merges the shards by LSE - the shards' V means differ, and a merge would weight them."""
         assert split_idx < self.num_nodes, "split_idx must be less than num_nodes"
         kw = {}
+        for name, val in (("v_shift", v_shift), ("lse_shift", lse_shift), ("out_dtype", out_dtype)):      # only when given
+            if val is not None:
+                kw[name] = val
         if q_descale is not None or k_descale is not None or v_descale is not None:       # keyword-only extension, as LiteAttention.__call__
-            kw = dict(q_descale=q_descale, k_descale=k_descale, v_descale=v_descale)
+            kw.update(q_descale=q_descale, k_descale=k_descale, v_descale=v_descale)
         if return_softmax_lse and self.exact_fp8_lse and query.dtype == torch.float8_e4m3fn:
             from .flash_attn_interface import fwd_flags
             from ._cabi import LA_FLAG_FP8_ENCODED_P, LA_FLAG_FP8_MFMA_ROWSUM

@@ -575,7 +575,7 @@ class SmoothedQK:
     """The buffers of one layer's q and k across calls, with the keys mean-shifted before they are quantized:
     ``q8, k8, dq, dk, lse_shift = smoothed.pair(xq, xk, wq, wk, eps, tables, norm)``. ``q8, k8`` e4m3, ``dq, dk`` the descales for the
     attention call, ``lse_shift`` (B, H_q, S) = q . c for ``lse_unshift`` (O needs no correction). k is prepared BEFORE q: q's dots need
-    the shift k used. V keeps using ``E4m3Scales``.
+    the shift k used. V: ``E4m3Scales``, or ``SmoothedV`` (v_prep.py).
 
     mode "current"   k: the column-mean pass, the amax pass of ``y - mean``, the quantizing pass (three reads of xk);
                      q: the amax pass, the quantizing pass with the dots (two reads of xq).

@@ -1,0 +1,365 @@
+"""V smoothing for the e4m3 forward. The kernel divides by its own row sum, so the rows of P sum to 1 over whatever keys a row visits -
+with skip lists, with split keys and after an LSE merge - and ``P (V - 1 m^T) + 1 m^T = P V`` for any vector m per (batch, kv-head). V is
+quantized as ``V - m``, the forward runs unchanged on the shifted codes, and m is added back to O in fp32:
+
+    sv = SmoothedV()                                   # one per layer
+    v8, dv, shift = sv(v_proj.view(b, s, n, d))        # e4m3 V - mean, its descale, the mean
+    o, lse = flash_attn_func(q8, k8, v8, q_descale=dq, k_descale=dk, v_descale=dv, return_softmax_lse=True)
+    o = sv.finish(o, lse=lse, out_dtype=torch.float32) # O + mean, as the fp32 the output projection reads
+
+``v_colstats`` (``la_v_colstats`` + ``la_v_colstats_finish``) makes the mean and the exact amax of ``V - mean`` in ONE read of V;
+``attn_unshift`` (``la_attn_unshift``) is the restoring pass, which also undoes K smoothing's shift of the LSE (``lse_unshift``, fused)
+and casts. ``v_colstats_reference`` / ``attn_unshift_reference`` are the formulas in torch fp64; ``v_shift_as_bias`` folds the shift
+into the bias of the output projection instead."""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Tuple
+
+import torch
+
+from . import _cabi
+from .qk_prep import _IN_DTYPES, _f32, descale_from_amax, qk_prep_smooth
+
+_UNSHIFT_OUT_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}
+_UNSHIFT_IN_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16}
+
+
+def v_colstats_parts(seqlen: int, num_heads: int, head_dim: int) -> Tuple[int, int]:
+    """``(n_parts, rows_per_part)`` of ``v_colstats``'s partial statistics for a shape (``la_v_colstats_parts`` and
+    ``la_v_colstats_part_rows``): part p holds rows ``[p * rows_per_part, (p + 1) * rows_per_part)`` of each batch. Pure functions of
+    the shape: ``rows_per_part = max(16, ceil(S * H * D / 8 / 131072))``."""
+    lib = _cabi.load()
+    n = lib.la_v_colstats_parts(int(seqlen), int(num_heads), int(head_dim))
+    r = lib.la_v_colstats_part_rows(int(seqlen), int(num_heads), int(head_dim))
+    if n <= 0 or r <= 0:
+        raise ValueError(f"la_v_colstats_parts({seqlen}, {num_heads}, {head_dim}): {_cabi.status_string(min(n, r))}")
+    return n, r
+
+
+def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mean_out: Optional[torch.Tensor] = None,
+               amax_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(mean, amax)`` of ``x`` (B, S, H, D) bf16 / fp16 / fp32 on the GPU in one read of it: ``mean`` fp32 (B, H, D) over the rows,
+    ``amax`` fp32 (B, H) = the largest ``|fl(x - mean)|`` of the head - bit for bit what ``qk_prep_smooth(x, norm=None, shift=mean,
+    amax_out=zeros, quantize=False)`` reports, without the second read. ``x`` may be any view whose last dimension is contiguous and
+    whose rows, heads and batches start on 16-byte boundaries (the V slice of a fused projection); ``head_dim % 8 == 0``, at most 256.
+    Deterministic (no float atomics). A NaN in a column makes that column's mean and the head's amax NaN.
+
+    stat_part    fp32 (n_parts, 3, B, H, D) contiguous work buffer, ``n_parts`` from ``v_colstats_parts``; None: allocated.
+    mean_out / amax_out   buffers to write (amax is WRITTEN, not accumulated); None: allocated.
+    No host sync; with the three buffers given, no allocation; captures into a HIP graph."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise ValueError("x must live on a GPU (there is no CPU path; v_colstats_reference is the formula in torch)")
+    if x.dtype not in _IN_DTYPES:
+        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
+    if x.stride(-1) != 1:
+        raise ValueError("the last dimension of x must be contiguous")
+    B, S, H, D = x.shape
+    if B * S * H * D == 0:
+        raise ValueError(f"x must not be empty, got {tuple(x.shape)}")
+    n_parts, _ = v_colstats_parts(S, H, D)
+    if stat_part is None:
+        stat_part = torch.empty((n_parts, 3, B, H, D), dtype=torch.float32, device=x.device)
+    _f32("stat_part", stat_part, (n_parts, 3, B, H, D), x.device)
+    if not stat_part.is_contiguous():
+        raise ValueError("stat_part must be contiguous")
+    if mean_out is None:
+        mean_out = torch.empty((B, H, D), dtype=torch.float32, device=x.device)
+    _f32("mean_out", mean_out, (B, H, D), x.device)
+    if mean_out.stride(2) != 1:
+        raise ValueError("the last dimension of mean_out must be contiguous")
+    if amax_out is None:
+        amax_out = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    _f32("amax_out", amax_out, (B, H), x.device)
+    a = _cabi.LaVColstatsArgs()
+    a.struct_size = ctypes.sizeof(_cabi.LaVColstatsArgs)
+    a.in_dtype = _IN_DTYPES[x.dtype]
+    a.x, a.stat_part = x.data_ptr(), stat_part.data_ptr()
+    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    lib = _cabi.load()
+    with torch.cuda.device(x.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        rc = lib.la_v_colstats(ctypes.byref(a), stream)
+        if rc != _cabi.LA_OK:
+            raise RuntimeError(f"la_v_colstats: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()})")
+        rc = lib.la_v_colstats_finish(stat_part.data_ptr(), n_parts, B, H, D, S, mean_out.data_ptr(), mean_out.stride(0), mean_out.stride(1),
+                                      amax_out.data_ptr(), amax_out.stride(0), amax_out.stride(1), stream)
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_v_colstats_finish: {_cabi.status_string(rc)} (parts {tuple(stat_part.shape)}, seqlen {S})")
+    return mean_out, amax_out
+
+
+def v_colstats_reference(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The formula of ``v_colstats`` in torch fp64, on whatever device ``x`` lives on: ``(mean`` (B, H, D) over the rows, ``amax`` (B, H)
+    of ``|x - mean|)``."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    y = x.double()
+    mean = y.mean(dim=1)
+    return mean, (y - mean[:, None]).abs().amax(dim=(1, 3))
+
+
+def _check_unshift(o, shift, lse, lse_dot):
+    """Shapes and dtypes of the restoring pass (device-free: LiteAttention checks with it before the forward). Returns heads_per_vec."""
+    if o.dim() != 4:
+        raise ValueError(f"o must be (B, S, H, D), got {tuple(o.shape)}")
+    B, S, H, D = o.shape
+    hpv = 1
+    if shift is not None:
+        if shift.dim() != 3 or shift.dtype != torch.float32 or shift.shape[0] != B or shift.shape[2] != D or shift.shape[1] < 1 or \
+                H % shift.shape[1]:
+            raise ValueError(f"shift must be fp32 (B, H_kv, D) = ({B}, a divisor of {H}, {D}), got {shift.dtype} {tuple(shift.shape)}")
+        if shift.stride(2) != 1:
+            raise ValueError("the last dimension of shift must be contiguous")
+        hpv = H // shift.shape[1]
+    for name, t in (("lse", lse), ("lse_dot", lse_dot)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, H, S)):
+            raise ValueError(f"{name} must be fp32 (B, H, S) = {(B, H, S)}, got {t.dtype} {tuple(t.shape)}")
+    if lse_dot is not None and lse is None:
+        raise ValueError("lse_dot needs lse")
+    return hpv
+
+
+def attn_unshift(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
+                 lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                 out_dtype: Optional[torch.dtype] = None, lse_out: Optional[torch.Tensor] = None):
+    """The restoring pass of V (and K) smoothing in one read of the attention output (``la_attn_unshift``):
+
+        out[b, s, h]     = round(float(o[b, s, h]) + shift[b, h // (H_q // H_kv)])        one fp32 addition, one rounding
+        lse_out[b, h, s] = lse[b, h, s] + softmax_scale * lse_dot[b, h, s]                 (one fma) only with ``lse_dot``
+
+    o          bf16 / fp16 (B, S, H, D), what the attention call returned for the shifted V.
+    shift      fp32 (B, H_kv, D), the vector subtracted from V; None: nothing is added (a cast / LSE pass).
+    lse        fp32 (B, H, S) of the call. When given, a row whose lse is +-inf (the forward's empty sum: ``seqlen_k == 0`` gives O = 0,
+               LSE = +inf) stays zeros and keeps its lse - no weights carry the shift. A NaN lse takes the normal path.
+    lse_dot    fp32 (B, H, S), ``q . c`` of ``qk_prep_smooth`` / ``SmoothedQK``: ``lse_unshift`` fused. Needs ``lse``;
+               ``softmax_scale`` is the one of the attention call (default ``head_dim ** -0.5``). ``lse_out``: where to (may be
+               ``lse``); None: allocated.
+    out        bf16, fp16 or fp32 by its own strides - e.g. a ``(B, S, H, D)`` view of the (B, S, H * D) fp32 tensor the output
+               projection reads; may be ``o`` itself (in place); None: a new contiguous tensor of ``out_dtype`` (default ``o.dtype``).
+               Any other overlap of ``out`` and ``o`` is an error nobody detects.
+    Returns ``out``, or ``(out, lse_out)`` with ``lse_dot``. No host sync; no allocation when ``out`` (and ``lse_out``) are given;
+    captures into a HIP graph."""
+    hpv = _check_unshift(o, shift, lse, lse_dot)
+    if not o.is_cuda:
+        raise ValueError("o must live on a GPU (there is no CPU path; attn_unshift_reference is the formula in torch)")
+    if o.dtype not in _UNSHIFT_IN_DTYPES:
+        raise TypeError(f"o: bf16 or fp16, got {o.dtype}")
+    B, S, H, D = o.shape
+    if out is None:
+        out = torch.empty((B, S, H, D), dtype=o.dtype if out_dtype is None else out_dtype, device=o.device)
+    elif out_dtype is not None and out.dtype != out_dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype says {out_dtype}")
+    if out.dtype not in _UNSHIFT_OUT_DTYPES:
+        raise TypeError(f"out: bf16, fp16 or fp32, got {out.dtype}")
+    if out.shape != o.shape or out.device != o.device:
+        raise ValueError(f"out must be {tuple(o.shape)} on {o.device}, got {tuple(out.shape)} on {out.device}")
+    if o.stride(-1) != 1 or out.stride(-1) != 1:
+        raise ValueError("the last dimension of o and out must be contiguous")
+    for name, t in (("shift", shift), ("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out)):
+        if t is not None and t.device != o.device:
+            raise ValueError(f"{name} lives on {t.device}, o on {o.device}")
+    if lse_dot is not None:
+        if lse_out is None:
+            lse_out = torch.empty((B, H, S), dtype=torch.float32, device=o.device)
+        _f32("lse_out", lse_out, (B, H, S), o.device)
+    elif lse_out is not None:
+        raise ValueError("lse_out needs lse_dot")
+    for name, t in (("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if B * S * H * D == 0:
+        return out if lse_dot is None else (out, lse_out.copy_(lse))
+    a = _cabi.LaAttnUnshiftArgs()
+    a.struct_size = ctypes.sizeof(_cabi.LaAttnUnshiftArgs)
+    a.o_dtype, a.out_dtype, a.heads_per_vec = _UNSHIFT_IN_DTYPES[o.dtype], _UNSHIFT_OUT_DTYPES[out.dtype], hpv
+    a.o, a.out = o.data_ptr(), out.data_ptr()
+    a.o_batch_stride, a.o_row_stride, a.o_head_stride = o.stride(0), o.stride(1), o.stride(2)
+    a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    if shift is not None:
+        a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
+    if lse is not None:
+        a.lse = lse.data_ptr()
+    if lse_dot is not None:
+        a.lse_dot, a.lse_out = lse_dot.data_ptr(), lse_out.data_ptr()
+        a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
+    with torch.cuda.device(o.device):
+        rc = _cabi.load().la_attn_unshift(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_attn_unshift: {_cabi.status_string(rc)} (o {tuple(o.shape)} strides {o.stride()}, out {out.dtype} strides "
+                           f"{out.stride()}, shift {None if shift is None else (tuple(shift.shape), shift.stride())})")
+    return out if lse_dot is None else (out, lse_out)
+
+
+def attn_unshift_reference(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
+                           lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+    """The formula of ``attn_unshift`` in torch fp64, UNROUNDED, on whatever device ``o`` lives on: ``out``, or ``(out, lse_out)`` with
+    ``lse_dot``. The product ``softmax_scale * lse_dot`` takes the scale as the fp32 the kernel is handed."""
+    hpv = _check_unshift(o, shift, lse, lse_dot)
+    out = o.double()
+    if shift is not None:
+        out = out + shift.double().to(o.device).repeat_interleave(hpv, dim=1)[:, None]
+    if lse is not None:
+        out = torch.where(lse.to(o.device).isinf().transpose(1, 2)[..., None], torch.zeros_like(out), out)
+    if lse_dot is None:
+        return out
+    scale = float(torch.tensor(o.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale, dtype=torch.float32))
+    l64 = lse.double()
+    return out, torch.where(l64.isinf(), l64, l64 + scale * lse_dot.double())
+
+
+def v_shift_as_bias(weight: torch.Tensor, bias: Optional[torch.Tensor], shift: torch.Tensor,
+                    dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The zero-pass alternative to ``attn_unshift`` when nothing between the attention and its output projection needs the true O:
+    the bias ``b' = b + W . flatten(shift repeated per q-head)`` under which ``F.linear(O_shifted.flatten(2), W, b')`` equals
+    ``F.linear((O_shifted + shift).flatten(2), W, b)``.
+
+    weight (out_features, H_q * D); bias (out_features,) or None; shift (1, H_kv, D) or (H_kv, D) - ONE batch's vector; H_q / H_kv is
+    taken from the two shapes. Computed in ``promote_types(weight.dtype, float32)`` and returned so unless ``dtype`` is given. Pure
+    torch, no host sync. It does NOT apply
+      * to B > 1 with per-batch shifts (a bias is one vector; use ``attn_unshift``, or one bias per batch element by hand);
+      * where partial outputs whose shifts differ are merged by LSE (sequence-parallel shards, the text + video recipe): each partial
+        must be restored BEFORE the merge - the merge weights the shifts too;
+      * to rows with an empty key set (their O is 0, not ``shift``), nor where anything between reads O."""
+    if shift.dim() == 3:
+        if shift.shape[0] != 1:
+            raise ValueError(f"v_shift_as_bias folds ONE batch's shift into the bias, got shift {tuple(shift.shape)}: per-batch shifts need "
+                             "attn_unshift")
+        shift = shift[0]
+    if shift.dim() != 2 or weight.dim() != 2:
+        raise ValueError(f"weight (out_features, H_q * D) and shift (H_kv, D), got {tuple(weight.shape)} and {tuple(shift.shape)}")
+    hkv, d = shift.shape
+    if weight.shape[1] % (hkv * d):
+        raise ValueError(f"the {weight.shape[1]} input features of weight are no multiple of H_kv * D = {hkv * d}")
+    work = torch.promote_types(weight.dtype, torch.float32)
+    vec = shift.to(device=weight.device, dtype=work).repeat_interleave(weight.shape[1] // (hkv * d), dim=0).reshape(-1)
+    res = torch.mv(weight.to(work), vec)
+    if bias is not None:
+        res = res + bias.to(work)
+    return res if dtype is None else res.to(dtype)
+
+
+class SmoothedV:
+    """The buffers of one layer's V across calls, mean-shifted before it is quantized: ``v8, dv, shift = sv(xv)`` - ``v8`` e4m3 of
+    ``xv - shift``, ``dv`` its descale for the attention call, ``shift`` fp32 (B, H_kv, D) - and ``sv.finish(o, ...)`` adds the shift
+    back to what the attention call returned (``attn_unshift``).
+
+    mode "current"   ``v_colstats`` (mean and exact amax of ``xv - mean``), ``descale_from_amax``, the quantizing pass
+                     (``qk_prep_smooth`` with ``norm=None``): two reads of xv.
+    mode "delayed"   step t quantizes with step t - 1's mean and descale and runs ``v_colstats`` on the same input for step t + 1. ANY
+                     shift is exact, so a stale mean costs range only (what outgrows ``margin`` saturates at +-448), as ``SmoothedQK``
+                     documents. The first call has no history and runs as "current".
+    Buffers are allocated by the first call and reused: no host sync, no allocation after it; a call overwrites the last results,
+    ``shift`` included - call ``finish`` before the next ``sv(xv)``."""
+
+    def __init__(self, mode: str = "current", margin: float = 1.0):
+        if mode not in ("current", "delayed"):
+            raise ValueError('mode: "current" or "delayed"')
+        if not margin > 0:
+            raise ValueError("margin must be positive")
+        self.mode, self.margin = mode, float(margin)
+        self.v8 = self.shift = self.out = None
+        self.calls = 0
+
+    def _allocate(self, xv):
+        B, S, H, D = xv.shape
+        f32 = dict(dtype=torch.float32, device=xv.device)
+        self.v8 = torch.empty(xv.shape, dtype=torch.float8_e4m3fn, device=xv.device)
+        self.part = torch.empty((v_colstats_parts(S, H, D)[0], 3, B, H, D), **f32)
+        self.shift, self.amax, self.dv = torch.empty((B, H, D), **f32), torch.empty((B, H), **f32), torch.empty((B, H), **f32)
+        if self.mode == "delayed":                               # this step's statistics, for the next step
+            self.next_mean, self.next_amax = torch.empty_like(self.shift), torch.empty_like(self.amax)
+        self.out = None
+
+    def __call__(self, xv: torch.Tensor):
+        if xv.dim() != 4:
+            raise ValueError(f"xv must be (B, S, H, D), got {tuple(xv.shape)}")
+        first = self.v8 is None or self.v8.shape != xv.shape or self.v8.device != xv.device
+        if first:
+            self._allocate(xv)
+        if self.mode == "current":
+            v_colstats(xv, stat_part=self.part, mean_out=self.shift, amax_out=self.amax)
+        else:
+            if first:
+                v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax)
+            self.shift.copy_(self.next_mean)
+            self.amax.copy_(self.next_amax)
+        descale_from_amax(self.amax, self.margin, out=self.dv)
+        qk_prep_smooth(xv, norm=None, shift=self.shift, descale=self.dv, out=self.v8)
+        if self.mode == "delayed":
+            v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax)
+        self.calls += 1
+        return self.v8, self.dv, self.shift
+
+    def finish(self, o: torch.Tensor, lse: Optional[torch.Tensor] = None, lse_dot: Optional[torch.Tensor] = None,
+               softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+        """``attn_unshift(o, shift, ...)`` with the shift of the last call. ``out`` None: ``o`` itself when ``out_dtype`` is None or
+        ``o.dtype`` (in place: the attention call's result is overwritten), else a buffer of ``out_dtype`` this object keeps. With
+        ``lse_dot`` (K smoothed too) the LSE is restored in place and ``(out, lse)`` is returned. Pass ``lse`` whenever the call may
+        have had no keys."""
+        if self.shift is None:
+            raise RuntimeError("finish() before the first call: there is no shift yet")
+        if out is None:
+            if out_dtype is None or out_dtype == o.dtype:
+                out = o
+            else:
+                if self.out is None or self.out.shape != o.shape or self.out.dtype != out_dtype or self.out.device != o.device:
+                    self.out = torch.empty(o.shape, dtype=out_dtype, device=o.device)
+                out = self.out
+        return attn_unshift(o, self.shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, out=out, out_dtype=out_dtype,
+                            lse_out=lse if lse_dot is not None else None)
+
+
+# ---- op registration: torch.ops.lite_attention.v_colstats / attn_unshift, beside qk_prep_smooth ------------------------------------------
+_V_COLSTATS_SCHEMA = ("v_colstats(Tensor x, Tensor(part!)? stat_part = None, Tensor(mean!)? mean_out = None, "
+                      "Tensor(amax!)? amax_out = None) -> (Tensor(mean!), Tensor(amax!))")
+_ATTN_UNSHIFT_SCHEMA = ("attn_unshift(Tensor o, Tensor? shift = None, Tensor? lse = None, Tensor? lse_dot = None, "
+                        "float? softmax_scale = None, Tensor(out!)? out = None, ScalarType? out_dtype = None, "
+                        "Tensor(lse_out!)? lse_out = None) -> Tensor(out!)")
+_op_lib = None
+
+
+def _v_colstats_op(x, stat_part=None, mean_out=None, amax_out=None):
+    return v_colstats(x, stat_part=stat_part, mean_out=mean_out, amax_out=amax_out)
+
+
+def _v_colstats_meta(x, stat_part=None, mean_out=None, amax_out=None):
+    """Shapes and dtypes only (fake-tensor tracing treats the op as opaque)."""
+    B, _, H, D = x.shape
+    return (mean_out if mean_out is not None else torch.empty((B, H, D), dtype=torch.float32, device=x.device),
+            amax_out if amax_out is not None else torch.empty((B, H), dtype=torch.float32, device=x.device))
+
+
+def _attn_unshift_op(o, shift=None, lse=None, lse_dot=None, softmax_scale=None, out=None, out_dtype=None, lse_out=None):
+    """The op returns ``out``; with ``lse_dot`` it wants ``lse_out`` too and writes the LSE there."""
+    if lse_dot is not None and lse_out is None:
+        raise ValueError("the op writes the LSE into lse_out: give it")
+    res = attn_unshift(o, shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, out=out, out_dtype=out_dtype, lse_out=lse_out)
+    return res if lse_dot is None else res[0]
+
+
+def _attn_unshift_meta(o, shift=None, lse=None, lse_dot=None, softmax_scale=None, out=None, out_dtype=None, lse_out=None):
+    """Shape and dtype only."""
+    return out if out is not None else torch.empty(o.shape, dtype=o.dtype if out_dtype is None else out_dtype, device=o.device)
+
+
+def _register_op():
+    global _op_lib
+    if _op_lib is not None:
+        return
+    from . import flash_attn_interface  # noqa: F401  (defines the library this is a fragment of)
+    lib = torch.library.Library("lite_attention", "FRAGMENT")
+    lib.define(_V_COLSTATS_SCHEMA)
+    lib.impl("v_colstats", _v_colstats_op, "CUDA")
+    lib.impl("v_colstats", _v_colstats_meta, "Meta")
+    lib.define(_ATTN_UNSHIFT_SCHEMA)
+    lib.impl("attn_unshift", _attn_unshift_op, "CUDA")
+    lib.impl("attn_unshift", _attn_unshift_meta, "Meta")
+    _op_lib = lib
+
+
+_register_op()
