@@ -17,6 +17,25 @@ thread_local int g_last_hip_error = 0;     // per-thread error detail of the las
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// the tail of every entry point that launches: the HIP error, if any, goes to la_last_hip_error()
+int launch_status(hipError_t err) {
+    if (err == hipSuccess) return LA_OK;
+    g_last_hip_error = static_cast<int>(err);
+    return LA_ERR_LAUNCH;
+}
+
+// Every row, head and batch start of a (batch, seqlen, heads, D) tensor on a boundary of `align` bytes: the pointer, and every stride
+// that is used, a multiple of `unit` elements (a row of 8 elements is 16 bytes of bf16 / fp16, two 16-byte halves of fp32, 8 bytes of
+// e4m3). No stride is negative.
+bool rows_aligned(const void* ptr, unsigned align, int64_t unit, int64_t bs, int64_t rs, int64_t hs, int batch, int seqlen, int heads) {
+    return bs >= 0 && rs >= 0 && hs >= 0 && (reinterpret_cast<uintptr_t>(ptr) & (align - 1)) == 0 && (seqlen <= 1 || rs % unit == 0) &&
+           (heads <= 1 || hs % unit == 0) && (batch <= 1 || bs % unit == 0);
+}
+// ... with unit and alignment from the la_dtype: 16-byte rows, 8-byte rows of e4m3
+bool rows_aligned(const void* ptr, int32_t dtype, int64_t bs, int64_t rs, int64_t hs, int batch, int seqlen, int heads) {
+    return rows_aligned(ptr, dtype == LA_DTYPE_FP8_E4M3 ? 8u : 16u, dtype == LA_DTYPE_FP32 ? 4 : 8, bs, rs, hs, batch, seqlen, heads);
+}
+
 // Kernel selection is a pure function of the arguments (no environment variables, no process-wide statics):
 //   bf16 / fp16 head_dim 128: the 256-row hand-scheduled kernel (x64) unless LA_FLAG_KERNEL_128ROW asks for the 128-row one (v2);
 //   head_dim 256: the hand-scheduled kernel in its 32-rows-per-wave form (q-tile 128) unless LA_FLAG_KERNEL_128ROW asks for the
@@ -211,8 +230,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
         hipError_t e1 = hipSuccess;
         if (e0 == hipSuccess && varlen && a->lse != nullptr && a->total_q > 0)            // +inf = 0x7f800000 is not a memset byte pattern
             e1 = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->lse), 0x7f800000, static_cast<size_t>(a->total_q) * a->num_heads, stream);
-        if (e0 != hipSuccess || e1 != hipSuccess) { g_last_hip_error = static_cast<int>(e0 != hipSuccess ? e0 : e1); return LA_ERR_LAUNCH; }
-        return LA_OK;
+        return launch_status(e0 != hipSuccess ? e0 : e1);
     }
 
     la::FwdParams p{};
@@ -313,8 +331,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
             if (e == hipSuccess)
                 e = la::launch_combine(o_part, true, false, lse_part, p.o, a->lse, f8d.n, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v, stream, false,
                                        p.o_batch_stride, p.o_row_stride, p.o_head_stride);
-            if (e != hipSuccess) { g_last_hip_error = static_cast<int>(e); return LA_ERR_LAUNCH; }
-            return LA_OK;
+            return launch_status(e);
         }
         // 1) V -> pre-transposed, pre-swizzled V^T tiles in the caller's workspace; 2) forward on (Q, K, V^T)
         hipError_t e8 = hipSuccess;
@@ -325,8 +342,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
             p.v = static_cast<const uint16_t*>(a->workspace);
             e8 = la::launch_fwd_x64_fp8(p, a->read_list != nullptr, p_mode, a->head_dim, stream);
         }
-        if (e8 != hipSuccess) { g_last_hip_error = static_cast<int>(e8); return LA_ERR_LAUNCH; }
-        return LA_OK;
+        return launch_status(e8);
     }
     // every instantiated head_dim: the hand-scheduled x64 kernel unless LA_FLAG_KERNEL_128ROW (the hipcc-scheduled template: 64 / 128 / 256)
     const bool skipable = a->read_list != nullptr;                                      // is_skipable, flash_api.cpp:931
@@ -358,7 +374,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
             ps.o_batch_stride = static_cast<int64_t>(p.seqlen_q) * ps.o_row_stride;
             ps.lse = lse_part + s * (d.lse_bytes / 4);
             err = la::launch_fwd_x64(ps, a->head_dim, false, f16, stream);
-            if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
+            if (err != hipSuccess) return launch_status(err);
         }
         err = la::launch_combine(o_part, true, f16, lse_part, p.o, a->lse, d.n, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v, stream, false,
                                  p.o_batch_stride, p.o_row_stride, p.o_head_stride);
@@ -367,11 +383,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     } else {
         err = la::launch_fwd_bf16_v2(p, a->head_dim, skipable, f16, stream);
     }
-    if (err != hipSuccess) {
-        g_last_hip_error = static_cast<int>(err);
-        return LA_ERR_LAUNCH;
-    }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
@@ -384,8 +396,7 @@ int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_ba
     if (rows > 0x7fffffffLL) return LA_ERR_SHAPE;
     const hipError_t err = la::launch_skip_list_stats(list, list_elem_size, static_cast<int>(rows), k_tiles, out_counts,
                                                       static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_skip_list_stats(const int32_t* list, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
@@ -405,8 +416,7 @@ int la_blockmask_to_lists_ex(const uint8_t* blockmask, int64_t mask_batch_stride
     const hipError_t err = la::launch_blockmask_to_lists(blockmask, mask_batch_stride, mask_head_stride, batch, num_heads, q_tiles,
                                                          k_tiles, q_tiles_valid, k_tiles_valid, lists, list_elem_size, empty_rows,
                                                          static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_blockmask_to_lists(const uint8_t* blockmask, int64_t mask_batch_stride, int64_t mask_head_stride, int32_t batch,
@@ -440,8 +450,7 @@ int la_combine(const void* o_partial, int32_t partial_is_16bit, const float* lse
     const hipError_t err = la::launch_combine(o_partial, partial_is_16bit != 0, o_dtype == LA_DTYPE_FP16, lse_partial, static_cast<uint16_t*>(o), lse,
                                               num_splits, batch, seqlen_q, num_heads, head_dim_v,
                                               static_cast<hipStream_t>(stream_), o_dtype == LA_DTYPE_FP32);
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_combine_list(const void* const* o_partials, int32_t partial_is_16bit, const float* const* lse_partials, void* o, int32_t o_dtype,
@@ -459,8 +468,7 @@ int la_combine_list(const void* const* o_partials, int32_t partial_is_16bit, con
     const hipError_t err = la::launch_combine_list(o_partials, partial_is_16bit != 0, o_dtype == LA_DTYPE_FP16, lse_partials, static_cast<uint16_t*>(o),
                                                    lse, num_splits, batch, seqlen_q, num_heads, head_dim_v, static_cast<hipStream_t>(stream_),
                                                    o_dtype == LA_DTYPE_FP32);
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride, int64_t out_row_stride, int64_t out_head_stride,
@@ -483,14 +491,13 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
     const hipError_t err = la::launch_output_error(out, out_dtype, out_batch_stride, out_row_stride, out_head_stride, ref, ref_dtype,
                                                    ref_batch_stride, ref_row_stride, ref_head_stride, batch, seqlen, num_heads, head_dim,
                                                    rows_per_bin, stats, static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 }  // extern "C"
 
-// What la_qk_prep and la_qk_prep_fp8 check alike, from the norm mode on, and the kernel parameters they share. A: either argument
-// struct (the same field names). out_dtype: la_dtype of out (LA_DTYPE_FP8_E4M3: 8 elements = 8 bytes, row starts on 8-byte boundaries).
+// What la_qk_prep, la_qk_prep_fp8 and la_qk_prep_smooth check alike, from the norm mode on, and the kernel parameters they share. A: any
+// of the three argument structs (the same field names). out_dtype: la_dtype of out (LA_DTYPE_FP8_E4M3: 8 elements = 8 bytes, row starts on 8-byte boundaries).
 template <class A>
 static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParams& p) {
     if (a->norm_mode != LA_NORM_NONE && a->norm_mode != LA_NORM_TOKEN && a->norm_mode != LA_NORM_HEAD) return LA_ERR_UNSUPPORTED;
@@ -499,14 +506,9 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParam
     // LA_NORM_TOKEN: the token stays in registers from the load to the store - of one wave up to 5120 elements, of the four waves of a
     // workgroup up to 8 chunks of 8 elements per lane
     if (a->norm_mode == LA_NORM_TOKEN && static_cast<int64_t>(a->num_heads) * a->head_dim > 16384) return LA_ERR_UNSUPPORTED;
-    // every row start is a 16-byte boundary: the pointer, and every stride that is used, in units of 16 / element size; the kernels
-    // keep a chunk's offset from its token's start in 32 bits
-    // (e4m3: 8 elements are 8 bytes, stored at once - an 8-byte boundary)
+    // every row start is aligned (rows_aligned), and the kernels keep a chunk's offset from its token's start in 32 bits
     const auto strides_ok = [&](const void* ptr, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
-        const int64_t unit = d == LA_DTYPE_FP32 ? 4 : 8;
-        const bool ptr_ok = d == LA_DTYPE_FP8_E4M3 ? (reinterpret_cast<uintptr_t>(ptr) & 7u) == 0 : aligned16(ptr);
-        return bs >= 0 && rs >= 0 && hs >= 0 && ptr_ok && (a->seqlen == 1 || rs % unit == 0) && (a->num_heads == 1 || hs % unit == 0) &&
-               (a->batch == 1 || bs % unit == 0) && hs <= (0x7fffffffLL - a->head_dim) / a->num_heads;
+        return rows_aligned(ptr, d, bs, rs, hs, a->batch, a->seqlen, a->num_heads) && hs <= (0x7fffffffLL - a->head_dim) / a->num_heads;
     };
     if (!strides_ok(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride) ||
         (a->out && !strides_ok(a->out, out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride))) return LA_ERR_STRIDE;
@@ -545,6 +547,30 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParam
     return LA_OK;
 }
 
+// The scale fields, which la_qk_prep_fp8 and la_qk_prep_smooth check and fill alike, in the three places their order of checks has: the
+// group size with the other shapes, the strides and pointers with the other strides, both before the shared checks ...
+template <class A>
+static bool qk_prep_scale_groups_ok(const A* a) {
+    return a->num_heads > 0 && a->heads_per_scale >= 1 && a->num_heads % a->heads_per_scale == 0;
+}
+template <class A>
+static bool qk_prep_scale_strides_ok(const A* a) {
+    return a->descale_batch_stride >= 0 && a->descale_head_stride >= 0 && a->amax_batch_stride >= 0 && a->amax_head_stride >= 0 &&
+           ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u) == 0;
+}
+// ... and behind them the limit of heads and the fill, with everything shared with la_qk_prep
+template <class A>
+static int qk_prep_e4m3_check_and_fill(const A* a, la::QkPrepParams& p) {
+    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, p);
+    if (rc != LA_OK) return rc;
+    if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;      // a workgroup keeps every head's scale and maximum in LDS
+    p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
+    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
+    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
+    p.heads_per_scale = a->heads_per_scale;
+    return LA_OK;
+}
+
 extern "C" {
 
 int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
@@ -556,9 +582,7 @@ int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
     la::QkPrepParams p;
     const int rc = qk_prep_check_and_fill(a, a->out_dtype, p);
     if (rc != LA_OK) return rc;
-    const hipError_t err = la::launch_qk_prep(p, a->in_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(la::launch_qk_prep(p, a->in_dtype, a->out_dtype, 0, static_cast<hipStream_t>(stream_)));
 }
 
 int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream_) {
@@ -566,20 +590,12 @@ int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream_) {
     if (a->struct_size != sizeof(la_qk_prep_fp8_args)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax)) return LA_ERR_NULL_ARG;
     if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
-    if (a->num_heads <= 0 || a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
-    if (a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 || a->amax_head_stride < 0 ||
-        ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u)) return LA_ERR_STRIDE;
+    if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
+    if (!qk_prep_scale_strides_ok(a)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
-    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, p);
+    const int rc = qk_prep_e4m3_check_and_fill(a, p);
     if (rc != LA_OK) return rc;
-    if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;      // a workgroup keeps every head's scale and maximum in LDS
-    p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
-    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
-    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
-    p.heads_per_scale = a->heads_per_scale;
-    const hipError_t err = la::launch_qk_prep_fp8(p, a->in_dtype, static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(la::launch_qk_prep(p, a->in_dtype, LA_DTYPE_FP8_E4M3, a->out ? 1 : 2, static_cast<hipStream_t>(stream_)));
 }
 
 int la_qk_prep_smooth_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
@@ -598,43 +614,30 @@ int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream_) {
     if (!a->x || (!a->out && !a->amax && !a->colsum_part && !a->dot_out)) return LA_ERR_NULL_ARG;
     if ((a->dot_out != nullptr) != (a->dot_vec != nullptr)) return LA_ERR_NULL_ARG;
     if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
-    if (a->num_heads <= 0 || a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
+    if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
     if (a->dot_vec && (a->heads_per_dot < 1 || a->num_heads % a->heads_per_dot != 0)) return LA_ERR_SHAPE;
-    if (a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 || a->amax_head_stride < 0 ||
-        ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax) | reinterpret_cast<uintptr_t>(a->dot_out)) & 3u))
-        return LA_ERR_STRIDE;
+    if (!qk_prep_scale_strides_ok(a) || (reinterpret_cast<uintptr_t>(a->dot_out) & 3u)) return LA_ERR_STRIDE;
     // shift and dot_vec rows are read 16 bytes at a time, the part sums are written so
-    const auto rows16 = [&](const float* ptr, int64_t bs, int64_t hs, int heads) {
-        return bs >= 0 && hs >= 0 && aligned16(ptr) && (a->batch <= 1 || bs % 4 == 0) && (heads <= 1 || hs % 4 == 0);
-    };
-    if ((a->shift && !rows16(a->shift, a->shift_batch_stride, a->shift_head_stride, a->num_heads)) ||
-        (a->dot_vec && !rows16(a->dot_vec, a->dot_vec_batch_stride, a->dot_vec_head_stride, a->num_heads / a->heads_per_dot)) ||
+    if ((a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1, a->num_heads)) ||
+        (a->dot_vec && !rows_aligned(a->dot_vec, LA_DTYPE_FP32, a->dot_vec_batch_stride, 0, a->dot_vec_head_stride, a->batch, 1,
+                                     a->num_heads / a->heads_per_dot)) ||
         !aligned16(a->colsum_part)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
-    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, p);
+    const int rc = qk_prep_e4m3_check_and_fill(a, p);
     if (rc != LA_OK) return rc;
-    if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;
     // a thread keeps the running sums of its columns in LDS: at most 16 chunks of 8
     if (a->colsum_part && la::qk_prep_sum_slots(p) > la::kQkPrepSumSlots) return LA_ERR_UNSUPPORTED;
-    p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
-    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
-    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
-    p.heads_per_scale = a->heads_per_scale;
     p.batch = a->batch;
-    const hipStream_t stream = static_cast<hipStream_t>(stream_);
-    hipError_t err;
-    if (!a->shift && !a->colsum_part && !a->dot_vec) {              // nothing added: la_qk_prep_fp8's own kernels
-        err = la::launch_qk_prep_fp8(p, a->in_dtype, stream);
-    } else {
+    int mode = a->out ? 1 : 2;                                      // nothing added: la_qk_prep_fp8's own kernels
+    if (a->shift || a->colsum_part || a->dot_vec) {
+        mode += 2;
         p.shift = a->shift; p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
         p.colsum_part = a->colsum_part;
         p.dot_vec = a->dot_vec; p.dv_bs = a->dot_vec_batch_stride; p.dv_hs = a->dot_vec_head_stride;
         p.heads_per_dot = a->dot_vec ? a->heads_per_dot : 1; p.dot_out = a->dot_out;
         p.part_rows = la::qk_prep_part_rows(a->seqlen); p.part_blocks = la::qk_prep_part_blocks(a->seqlen);
-        err = la::launch_qk_prep_smooth(p, a->in_dtype, stream);
     }
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(la::launch_qk_prep(p, a->in_dtype, LA_DTYPE_FP8_E4M3, mode, static_cast<hipStream_t>(stream_)));
 }
 
 int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
@@ -646,8 +649,7 @@ int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t 
     if (static_cast<int64_t>(batch) * num_heads * head_dim > 0x7fffffffLL * 256) return LA_ERR_SHAPE;      // one thread per column
     const hipError_t err = la::launch_colsum_finish(part, n_parts, batch, num_heads, head_dim, seqlen, mean_out, mean_batch_stride,
                                                     mean_head_stride, static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 // ---- V smoothing (la_prep_v.hip) ---------------------------------------------------------------------------------------------------
@@ -661,14 +663,6 @@ int la_v_colstats_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim)
     return la::v_colstats_part_rows(seqlen, num_heads, head_dim);
 }
 
-// Every row, head and batch start of a (B, S, H, D) tensor on a 16-byte boundary: the pointer, and every stride that is used, in units
-// of 16 / element size
-static bool rows16(const void* ptr, int32_t dtype, int64_t bs, int64_t rs, int64_t hs, int32_t batch, int32_t seqlen, int32_t num_heads) {
-    const int64_t unit = dtype == LA_DTYPE_FP32 ? 4 : 8;
-    return bs >= 0 && rs >= 0 && hs >= 0 && aligned16(ptr) && (seqlen == 1 || rs % unit == 0) && (num_heads == 1 || hs % unit == 0) &&
-           (batch == 1 || bs % unit == 0);
-}
-
 int la_v_colstats(const la_v_colstats_args* a, void* stream_) {
     if (!a) return LA_ERR_NULL_ARG;
     if (a->struct_size != sizeof(la_v_colstats_args)) return LA_ERR_STRUCT_SIZE;
@@ -676,7 +670,7 @@ int la_v_colstats(const la_v_colstats_args* a, void* stream_) {
     if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
-    if (!rows16(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
+    if (!rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
         !aligned16(a->stat_part)) return LA_ERR_STRIDE;
     la::VColstatsParams p = {};
     p.x = a->x; p.stat_part = a->stat_part;
@@ -687,8 +681,7 @@ int la_v_colstats(const la_v_colstats_args* a, void* stream_) {
     // one thread per (part, batch, head, chunk of 8 columns), 256 per workgroup
     if (static_cast<int64_t>(p.n_parts) * a->batch * a->num_heads * (a->head_dim / 8) > 0x7fffffffLL * 256) return LA_ERR_SHAPE;
     const hipError_t err = la::launch_v_colstats(p, a->in_dtype, static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
@@ -704,8 +697,7 @@ int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int3
     const hipError_t err = la::launch_v_colstats_finish(part, n_parts, batch, num_heads, head_dim, seqlen, mean_out, mean_batch_stride,
                                                         mean_head_stride, amax_out, amax_batch_stride, amax_head_stride,
                                                         static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
@@ -718,10 +710,10 @@ int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!rows16(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, a->seqlen, a->num_heads) ||
-        !rows16(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen, a->num_heads))
+    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, a->seqlen, a->num_heads) ||
+        !rows_aligned(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen, a->num_heads))
         return LA_ERR_STRIDE;
-    if (a->shift && !rows16(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
+    if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
                             a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
     if ((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out)) & 3u)
         return LA_ERR_STRIDE;
@@ -734,8 +726,7 @@ int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
     p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
     p.softmax_scale = a->softmax_scale;
     const hipError_t err = la::launch_attn_unshift(p, a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
-    if (err != hipSuccess) { g_last_hip_error = static_cast<int>(err); return LA_ERR_LAUNCH; }
-    return LA_OK;
+    return launch_status(err);
 }
 
 }  // extern "C"

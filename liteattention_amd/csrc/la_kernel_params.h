@@ -144,8 +144,9 @@ struct QkPrepParams {
 };
 constexpr int kQkPrepScaleSlots = 1024;      // heads whose scale and running amax a workgroup keeps in LDS (la_qk_prep_fp8)
 constexpr int kQkPrepSumSlots = 16;          // chunks of 8 columns a thread keeps running column sums for in LDS (la_qk_prep_smooth): 128 KiB
-hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream);   // dtypes: 0 bf16, 1 fp16, 3 fp32 (in only)
-hipError_t launch_qk_prep_fp8(const QkPrepParams& p, int in_dtype, hipStream_t stream);      // out e4m3; p.out == NULL: the amax pass alone
+// dtypes: 0 bf16, 1 fp16, 3 fp32 (in only), 2 e4m3 (out only). mode: 0 la_qk_prep (16-bit out); la_qk_prep_fp8: 1 quantize, 2 the amax pass
+// alone (p.out == NULL); la_qk_prep_smooth with a shift, column sums or row dots: 3 with out, 4 without
+hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, int mode, hipStream_t stream);
 // la_qk_prep_smooth: rows of a part and blocks of 4 parts for a sequence length - the one place the row -> part map is decided
 inline int qk_prep_part_rows(int seqlen) { const int r = static_cast<int>((static_cast<int64_t>(seqlen) + 1023) / 1024); return r < 16 ? 16 : r; }
 inline int qk_prep_part_blocks(int seqlen) {
@@ -153,7 +154,6 @@ inline int qk_prep_part_blocks(int seqlen) {
     return static_cast<int>(((static_cast<int64_t>(seqlen) + r - 1) / r + 3) / 4);
 }
 int qk_prep_sum_slots(const QkPrepParams& p);      // chunks per thread the column sums of this shape need (<= kQkPrepSumSlots or unsupported)
-hipError_t launch_qk_prep_smooth(const QkPrepParams& p, int in_dtype, hipStream_t stream);   // out e4m3 or NULL, plus shift / column sums / row dots
 hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean,
                                 int64_t m_bs, int64_t m_hs, hipStream_t stream);
 

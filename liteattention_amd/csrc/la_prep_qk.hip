@@ -60,89 +60,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "la_kernel_params.h"
+#include "la_prep_common.h"
 
 namespace la {
 namespace {
 
-typedef unsigned int pq_u32x4 __attribute__((ext_vector_type(4)));
-typedef float pq_f32x4 __attribute__((ext_vector_type(4)));
-typedef float pq_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int pq_u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 pq_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pq_bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kMaxGrid = 2048;             // workgroups: 8 per compute unit; the rest of the tokens by grid stride
 constexpr int kRotRow = 128;               // pairs of one token's rotation row (head_dim <= 256)
 constexpr int kHeadUnroll = 4;             // passes of the head kernel whose loads are issued together
-
-template <int DT> struct PrepLoad;         // DT: la_dtype; raw = 8 consecutive elements as loaded (what a lane keeps of a chunk), to_float -> fp32
-template <> struct PrepLoad<0> {           // bf16
-    typedef pq_u32x4 raw;
-    static __device__ __forceinline__ raw zero() { return raw{0u, 0u, 0u, 0u}; }
-    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
-        return *reinterpret_cast<const pq_u32x4*>(static_cast<const uint16_t*>(base) + off);
-    }
-    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = __uint_as_float(w[i] << 16);
-            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-};
-template <> struct PrepLoad<1> {           // fp16
-    typedef pq_f16x8 raw;
-    static __device__ __forceinline__ raw zero() { return raw{0, 0, 0, 0, 0, 0, 0, 0}; }
-    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
-        return *reinterpret_cast<const pq_f16x8*>(static_cast<const uint16_t*>(base) + off);
-    }
-    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = static_cast<float>(w[i]);
-    }
-};
-template <> struct PrepLoad<3> {           // fp32
-    struct raw { pq_f32x4 a, c; };
-    static __device__ __forceinline__ raw zero() { return raw{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}; }
-    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
-        const float* q = static_cast<const float*>(base) + off;
-        return raw{*reinterpret_cast<const pq_f32x4*>(q), *reinterpret_cast<const pq_f32x4*>(q + 4)};
-    }
-    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x[i] = w.a[i]; x[4 + i] = w.c[i]; }
-    }
-};
-
-template <int DT> struct PrepStore;        // fp32 -> 8 elements, round to nearest even, one 16-byte store
-template <> struct PrepStore<0> {
-    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        pq_bf16x8 w;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = static_cast<__bf16>(y[i]);
-        *reinterpret_cast<pq_bf16x8*>(static_cast<uint16_t*>(base) + off) = w;
-    }
-};
-template <> struct PrepStore<1> {
-    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        pq_f16x8 w;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = static_cast<_Float16>(y[i]);
-        *reinterpret_cast<pq_f16x8*>(static_cast<uint16_t*>(base) + off) = w;
-    }
-};
-
-template <> struct PrepStore<2> {           // e4m3: y is inside +-448 or NaN (scale_clamp8); 8 bytes, one 8-byte store
-    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        int lo = 0, hi = 0;
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
-        *reinterpret_cast<pq_u32x2*>(static_cast<uint8_t*>(base) + off) = pq_u32x2{static_cast<unsigned>(lo), static_cast<unsigned>(hi)};
-    }
-};
 
 // What follows y: 0 the 16-bit store of la_qk_prep; 1 amax + scale + clamp + e4m3 store; 2 amax alone (x is read, nothing is written);
 // 3 / 4 la_qk_prep_smooth: 1 / 2 of y - shift, plus the column sums and row dots of y (each on when its pointer is given)
@@ -169,23 +97,8 @@ __device__ __forceinline__ void colsum_flush8(int slot, float* dst) {
     *reinterpret_cast<pq_f32x4*>(dst + 4) = pq_f32x4{t[1024], t[1280], t[1536], t[1792]};
 }
 
-__device__ __forceinline__ void load_f32x8(const float* __restrict__ src, float (&w)[8]) {
-    const pq_f32x4 a = *reinterpret_cast<const pq_f32x4*>(src), c = *reinterpret_cast<const pq_f32x4*>(src + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { w[i] = a[i]; w[4 + i] = c[i]; }
-}
-
 __device__ __forceinline__ float dot8(const float (&y)[8], const float (&c)[8]) {
     return ((y[0] * c[0] + y[1] * c[1]) + (y[2] * c[2] + y[3] * c[3])) + ((y[4] * c[4] + y[5] * c[5]) + (y[6] * c[6] + y[7] * c[7]));
-}
-
-__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
-
-__device__ __forceinline__ unsigned absmax8(const float (&y)[8]) {
-    unsigned m = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) m = umax(m, __float_as_uint(y[i]) & 0x7fffffffu);
-    return m;
 }
 
 __device__ __forceinline__ void scale_clamp8(float (&y)[8], float inv) {
@@ -220,12 +133,6 @@ __device__ __forceinline__ void scale_turn(const QkPrepParams& p, unsigned* am_t
 
 __device__ __forceinline__ float sum_squares8(const float (&v)[8]) {
     return ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) + ((v[4] * v[4] + v[5] * v[5]) + (v[6] * v[6] + v[7] * v[7]));
-}
-
-__device__ __forceinline__ void load_weight8(const float* __restrict__ weight, int idx, float (&w)[8]) {
-    const pq_f32x4 a = *reinterpret_cast<const pq_f32x4*>(weight + idx), c = *reinterpret_cast<const pq_f32x4*>(weight + idx + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { w[i] = a[i]; w[4 + i] = c[i]; }
 }
 
 // LDS accesses of ONE wave before / after this point stay on their side of it (the hardware runs them in order)
@@ -400,7 +307,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
                 PrepLoad<DT_IN>::to_float(v[i], y);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) w[j] = 1.f;
-                if (weight) load_weight8(weight, (first + kLanes * i) * 8, w);      // 4 H D bytes every token rereads: they stay in L1 / L2
+                if (weight) load_f32x8(weight + (first + kLanes * i) * 8, w);       // 4 H D bytes every token rereads: they stay in L1 / L2
                 if (rotate) scale_rotate8<true>(y, r, w, col[i], rot_pairs, row);
                 else scale_rotate8<false>(y, r, w, col[i], rot_pairs, row);
                 if constexpr (POL::kSmooth) {                      // sums and dots see y, the maximum and the store y - shift
@@ -472,7 +379,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
     float w[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) w[j] = 1.f;
-    if (norm && p.weight && col_ok) load_weight8(p.weight, e, w);
+    if (norm && p.weight && col_ok) load_f32x8(p.weight + e, w);
     RotStage rs;
     rs.init(p, lane);
 
@@ -588,85 +495,66 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
     if constexpr (POL::kScaled) scale_turn<false>(p, am_tab, inv_tab, cur_b, -1);
 }
 
-dim3 grid_for(int64_t tokens, int tokens_per_block) {
-    const int64_t blocks = (tokens + tokens_per_block - 1) / tokens_per_block;
+// The token kernel of a shape: NCH chunks of 8 per lane, one wave per token up to 10 of them (5120 elements), above that the four waves
+// of the workgroup share the token (WG; nchunks <= 2048, checked by la_qk_prep). The launch and the LDS of the column sums read it here.
+struct TokenShape { int nch; bool wg; };
+TokenShape token_shape(int nchunks) {
+    const int need = (nchunks + 63) / 64;                          // chunks per lane with one wave per token
+    for (const int nch : {1, 2, 4, 8, 10})
+        if (need <= nch) return {nch, false};
+    return {nchunks <= 4 * 256 ? 4 : 8, true};
+}
+// ... and of the head kernel: a head's chunks sit on G = 1 << group_log2 lanes (head_dim <= 256: at most 5)
+int head_group_log2(int head_dim) {
+    int group_log2 = 0;
+    while ((8 << group_log2) < head_dim) ++group_log2;
+    return group_log2;
+}
+
+// Workgroups of a launch whose workgroup takes per_wg rows at a time (4: one per wave; 1: its waves share one). Mode 0: one per per_wg
+// tokens; the e4m3 forms: one per round of per_wg tokens of ONE batch; the smooth forms: one per block of 4 parts of one batch.
+dim3 grid_for(const QkPrepParams& p, int mode, int per_wg) {
+    const int64_t blocks = mode == 0 ? (p.tokens + per_wg - 1) / per_wg
+                                     : p.tokens / p.seqlen * (mode >= 3 ? p.part_blocks : (p.seqlen + per_wg - 1) / per_wg);
     return dim3(static_cast<unsigned>(blocks < kMaxGrid ? blocks : kMaxGrid));
 }
 
-// workgroups of an e4m3 form: one per round of `per_round` tokens of one batch
-dim3 grid_for_rounds(const QkPrepParams& p, int per_round) {
-    return grid_for(p.tokens / p.seqlen * ((p.seqlen + per_round - 1) / per_round), 1);
-}
-
-// chunk slots of 8 columns per thread whose running sums the token kernel keeps in LDS: its NCH
-int token_sum_slots(int nchunks) {
-    const int need = (nchunks + 63) / 64;
-    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : need <= 10 ? 10 : nchunks <= 4 * 256 ? 4 : 8;
-}
-// ... and the head kernel: a slot per pass of 64 / G heads, in whole batches of kHeadUnroll passes
-int head_sum_slots(int num_heads, int head_dim) {
-    int group_log2 = 0;
-    while ((8 << group_log2) < head_dim) ++group_log2;
-    const int per_batch = (64 >> group_log2) * kHeadUnroll;
-    return (num_heads + per_batch - 1) / per_batch * kHeadUnroll;
-}
-
-// the grid of a smooth form (one workgroup per block of 4 parts of one batch) and the LDS of its column sums; hipErrorInvalidValue etc.
-// of the attribute call stay in hipGetLastError for the caller
-template <class K>
-bool smooth_launch_shape(K kfn, const QkPrepParams& p, int slots, dim3* grid, size_t* lds) {
-    *grid = grid_for(static_cast<int64_t>(p.batch) * p.part_blocks, 1);
-    *lds = p.colsum_part ? static_cast<size_t>(slots) * 8 * 256 * sizeof(float) : 0;
-    return *lds == 0 ||
-           hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(*lds)) == hipSuccess;
-}
-
-template <int DT_IN, int DT_OUT, int MODE>
-void launch_token(const QkPrepParams& p, hipStream_t stream) {
-    const int nchunks = p.num_heads * p.head_dim / 8;              // <= 2048, checked by la_qk_prep
-    const int need = (nchunks + 63) / 64;                          // chunks per lane with one wave per token
-#define LA_QK_PREP_TOKEN(NCH, WG) \
-    do { \
-        dim3 grid = MODE ? grid_for_rounds(p, WG ? 1 : 4) : grid_for(p.tokens, WG ? 1 : 4); \
-        size_t lds = 0; \
-        if (MODE >= 3 && !smooth_launch_shape(la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>, p, NCH, &grid, &lds)) return; \
-        hipLaunchKernelGGL((la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>), grid, dim3(256), lds, stream, p); \
-    } while (0)
-    if (need <= 1) LA_QK_PREP_TOKEN(1, false);
-    else if (need <= 2) LA_QK_PREP_TOKEN(2, false);
-    else if (need <= 4) LA_QK_PREP_TOKEN(4, false);
-    else if (need <= 8) LA_QK_PREP_TOKEN(8, false);
-    else if (need <= 10) LA_QK_PREP_TOKEN(10, false);
-    else if (nchunks <= 4 * 256) LA_QK_PREP_TOKEN(4, true);        // one workgroup per token
-    else LA_QK_PREP_TOKEN(8, true);
-#undef LA_QK_PREP_TOKEN
+// One launch. A smooth form that sums columns asks for their dynamic LDS first; hipErrorInvalidValue etc. of that call stay in
+// hipGetLastError for the caller.
+template <int MODE, class K, class... Extra>
+void launch_kernel(K kfn, const QkPrepParams& p, int per_wg, hipStream_t stream, Extra... extra) {
+    const size_t lds = MODE >= 3 && p.colsum_part ? static_cast<size_t>(qk_prep_sum_slots(p)) * 8 * 256 * sizeof(float) : 0;
+    if (lds != 0 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
+        return;
+    hipLaunchKernelGGL(kfn, grid_for(p, MODE, per_wg), dim3(256), lds, stream, p, extra...);
 }
 
 template <int DT_IN, int DT_OUT, int MODE>
 void launch_typed(const QkPrepParams& p, hipStream_t stream) {
     if (p.norm_mode == 1) {
-        launch_token<DT_IN, DT_OUT, MODE>(p, stream);
+        const TokenShape ts = token_shape(p.num_heads * p.head_dim / 8);
+#define LA_QK_PREP_TOKEN(NCH, WG) \
+        if (ts.nch == NCH && ts.wg == WG) launch_kernel<MODE>(la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>, p, WG ? 1 : 4, stream)
+        LA_QK_PREP_TOKEN(1, false);
+        LA_QK_PREP_TOKEN(2, false);
+        LA_QK_PREP_TOKEN(4, false);
+        LA_QK_PREP_TOKEN(8, false);
+        LA_QK_PREP_TOKEN(10, false);
+        LA_QK_PREP_TOKEN(4, true);
+        LA_QK_PREP_TOKEN(8, true);
+#undef LA_QK_PREP_TOKEN
     } else {
-        int group_log2 = 0;
-        while ((8 << group_log2) < p.head_dim) ++group_log2;       // head_dim <= 256: at most 5
-        dim3 grid = MODE ? grid_for_rounds(p, 4) : grid_for(p.tokens, 4);
-        size_t lds = 0;
-        if (MODE >= 3 && !smooth_launch_shape(la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>, p, head_sum_slots(p.num_heads, p.head_dim), &grid, &lds))
-            return;
-        hipLaunchKernelGGL((la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>), grid, dim3(256), lds, stream, p, group_log2);
+        launch_kernel<MODE>(la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>, p, 4, stream, head_group_log2(p.head_dim));
     }
 }
 
-template <int DT_IN>
-void launch_in(const QkPrepParams& p, int out_dtype, hipStream_t stream) {
-    if (out_dtype == 0) launch_typed<DT_IN, 0, 0>(p, stream);
-    else launch_typed<DT_IN, 1, 0>(p, stream);
-}
-
-template <int DT_IN>
-void launch_in_fp8(const QkPrepParams& p, hipStream_t stream) {
-    if (p.out) launch_typed<DT_IN, 2, 1>(p, stream);
-    else launch_typed<DT_IN, 2, 2>(p, stream);
+// The input-type ladder, once: f(DT) with the la_dtype of x as a compile-time constant.
+template <class F>
+void with_in_dtype(int in_dtype, F f) {
+    if (in_dtype == 0) f(std::integral_constant<int, 0>());
+    else if (in_dtype == 1) f(std::integral_constant<int, 1>());
+    else f(std::integral_constant<int, 3>());
 }
 
 // mean[b][h][d] = (part[0][b][h][d] + part[1][b][h][d] + ...) / seqlen, added in index order: one thread per column
@@ -683,21 +571,30 @@ __global__ void __launch_bounds__(256) la_colsum_finish_kernel(const float* __re
 
 }  // namespace
 
+// chunk slots of 8 columns per thread whose running sums live in LDS: the token kernel's NCH; the head kernel's passes of 64 / G heads,
+// in whole batches of kHeadUnroll
 int qk_prep_sum_slots(const QkPrepParams& p) {
-    return p.norm_mode == 1 ? token_sum_slots(p.num_heads * p.head_dim / 8) : head_sum_slots(p.num_heads, p.head_dim);
+    if (p.norm_mode == 1) return token_shape(p.num_heads * p.head_dim / 8).nch;
+    const int per_batch = (64 >> head_group_log2(p.head_dim)) * kHeadUnroll;
+    return (p.num_heads + per_batch - 1) / per_batch * kHeadUnroll;
 }
 
-hipError_t launch_qk_prep_smooth(const QkPrepParams& p, int in_dtype, hipStream_t stream) {
+// Templates are instantiated in the order they are named, and that is the order of the kernels in the code object: the cases below keep
+// the order the kernels have had since each form was added, so that an assembly diff against an earlier build shows code changes only.
+hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
     (void)hipGetLastError();
-    if (p.out) {
-        if (in_dtype == 0) launch_typed<0, 2, 3>(p, stream);
-        else if (in_dtype == 1) launch_typed<1, 2, 3>(p, stream);
-        else launch_typed<3, 2, 3>(p, stream);
-    } else {
-        if (in_dtype == 0) launch_typed<0, 2, 4>(p, stream);
-        else if (in_dtype == 1) launch_typed<1, 2, 4>(p, stream);
-        else launch_typed<3, 2, 4>(p, stream);
-    }
+    if (mode == 3) with_in_dtype(in_dtype, [&](auto dt) { launch_typed<decltype(dt)::value, 2, 3>(p, stream); });
+    else if (mode == 4) with_in_dtype(in_dtype, [&](auto dt) { launch_typed<decltype(dt)::value, 2, 4>(p, stream); });
+    else if (mode == 0)
+        with_in_dtype(in_dtype, [&](auto dt) {
+            if (out_dtype == 0) launch_typed<decltype(dt)::value, 0, 0>(p, stream);
+            else launch_typed<decltype(dt)::value, 1, 0>(p, stream);
+        });
+    else
+        with_in_dtype(in_dtype, [&](auto dt) {
+            if (mode == 1) launch_typed<decltype(dt)::value, 2, 1>(p, stream);
+            else launch_typed<decltype(dt)::value, 2, 2>(p, stream);
+        });
     return hipGetLastError();
 }
 
@@ -707,22 +604,6 @@ hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int n
     const int64_t cols = static_cast<int64_t>(batch) * num_heads * head_dim;
     hipLaunchKernelGGL(la_colsum_finish_kernel, dim3(static_cast<unsigned>((cols + 255) / 256)), dim3(256), 0, stream, part, n_parts, cols,
                        head_dim, num_heads, static_cast<float>(seqlen), mean, m_bs, m_hs);
-    return hipGetLastError();
-}
-
-hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (in_dtype == 0) launch_in<0>(p, out_dtype, stream);
-    else if (in_dtype == 1) launch_in<1>(p, out_dtype, stream);
-    else launch_in<3>(p, out_dtype, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_qk_prep_fp8(const QkPrepParams& p, int in_dtype, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (in_dtype == 0) launch_in_fp8<0>(p, stream);
-    else if (in_dtype == 1) launch_in_fp8<1>(p, stream);
-    else launch_in_fp8<3>(p, stream);
     return hipGetLastError();
 }
 

@@ -28,79 +28,14 @@
 #include <stdint.h>
 
 #include "la_kernel_params.h"
+#include "la_prep_common.h"
 
 namespace la {
 namespace {
 
-typedef unsigned int pv_u32x4 __attribute__((ext_vector_type(4)));
-typedef float pv_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 pv_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pv_bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kRowsInFlight = 8;           // rows of a thread's chunk loaded before the first of them is added
 constexpr int kUnshiftMaxGrid = 8192;      // workgroups of la_attn_unshift_kernel (combine_kernel's cap); the rest by grid stride
 constexpr int64_t kUnshiftMaxTiles = 1 << 20;      // ... of la_attn_unshift_lse_kernel, one tile each; more tiles by grid stride
-
-template <int DT> struct VLoad;            // DT: la_dtype; raw = 8 consecutive elements as loaded, to_float -> fp32
-template <> struct VLoad<0> {              // bf16
-    typedef pv_u32x4 raw;
-    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
-        return *reinterpret_cast<const pv_u32x4*>(static_cast<const uint16_t*>(base) + off);
-    }
-    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = __uint_as_float(w[i] << 16);
-            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-};
-template <> struct VLoad<1> {              // fp16
-    typedef pv_f16x8 raw;
-    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
-        return *reinterpret_cast<const pv_f16x8*>(static_cast<const uint16_t*>(base) + off);
-    }
-    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = static_cast<float>(w[i]);
-    }
-};
-template <> struct VLoad<3> {              // fp32
-    struct raw { pv_f32x4 a, c; };
-    static __device__ __forceinline__ raw load(const void* base, int64_t off) {
-        const float* q = static_cast<const float*>(base) + off;
-        return raw{*reinterpret_cast<const pv_f32x4*>(q), *reinterpret_cast<const pv_f32x4*>(q + 4)};
-    }
-    static __device__ __forceinline__ void to_float(const raw& w, float (&x)[8]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x[i] = w.a[i]; x[4 + i] = w.c[i]; }
-    }
-};
-
-template <int DT> struct VStore;           // fp32 -> 8 elements, round to nearest even at the store
-template <> struct VStore<0> {
-    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        pv_bf16x8 w;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = static_cast<__bf16>(y[i]);
-        *reinterpret_cast<pv_bf16x8*>(static_cast<uint16_t*>(base) + off) = w;
-    }
-};
-template <> struct VStore<1> {
-    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        pv_f16x8 w;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = static_cast<_Float16>(y[i]);
-        *reinterpret_cast<pv_f16x8*>(static_cast<uint16_t*>(base) + off) = w;
-    }
-};
-template <> struct VStore<3> {
-    static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        float* q = static_cast<float*>(base) + off;
-        *reinterpret_cast<pv_f32x4*>(q) = pv_f32x4{y[0], y[1], y[2], y[3]};
-        *reinterpret_cast<pv_f32x4*>(q + 4) = pv_f32x4{y[4], y[5], y[6], y[7]};
-    }
-};
 
 __device__ __forceinline__ void take_row(const float (&v)[8], float (&sum)[8], float (&lo)[8], float (&hi)[8]) {
 #pragma unroll
@@ -131,29 +66,27 @@ __global__ void __launch_bounds__(256) la_v_colstats_kernel(const VColstatsParam
     for (int j = 0; j < 8; ++j) { sum[j] = 0.f; lo[j] = INFINITY; hi[j] = -INFINITY; }
     int64_t r = r0;
     for (; r + kRowsInFlight <= r1; r += kRowsInFlight) {
-        typename VLoad<DT>::raw w[kRowsInFlight];
+        typename PrepLoad<DT>::raw w[kRowsInFlight];
 #pragma unroll
-        for (int u = 0; u < kRowsInFlight; ++u) w[u] = VLoad<DT>::load(p.x, col0 + (r + u) * p.x_rs);
+        for (int u = 0; u < kRowsInFlight; ++u) w[u] = PrepLoad<DT>::load(p.x, col0 + (r + u) * p.x_rs);
 #pragma unroll
         for (int u = 0; u < kRowsInFlight; ++u) {
             float v[8];
-            VLoad<DT>::to_float(w[u], v);
+            PrepLoad<DT>::to_float(w[u], v);
             take_row(v, sum, lo, hi);
         }
     }
     for (; r < r1; ++r) {
         float v[8];
-        VLoad<DT>::to_float(VLoad<DT>::load(p.x, col0 + r * p.x_rs), v);
+        PrepLoad<DT>::to_float(PrepLoad<DT>::load(p.x, col0 + r * p.x_rs), v);
         take_row(v, sum, lo, hi);
     }
     const int64_t cols = static_cast<int64_t>(p.batch) * p.num_heads * p.head_dim;
     float* dst = p.stat_part + part * 3 * cols + (static_cast<int64_t>(b) * p.num_heads + h) * p.head_dim + ch * 8;
-    VStore<3>::store8(dst, 0, sum);
-    VStore<3>::store8(dst, cols, lo);
-    VStore<3>::store8(dst, 2 * cols, hi);
+    PrepStore<3>::store8(dst, 0, sum);
+    PrepStore<3>::store8(dst, cols, lo);
+    PrepStore<3>::store8(dst, 2 * cols, hi);
 }
-
-__device__ __forceinline__ unsigned pv_umax(unsigned a, unsigned b) { return a > b ? a : b; }
 
 __global__ void __launch_bounds__(256) la_v_colstats_finish_kernel(const float* __restrict__ part, int n_parts, int64_t cols, int head_dim,
                                                                      int num_heads, float seqlen, float* __restrict__ mean, int64_t m_bs,
@@ -179,25 +112,25 @@ __global__ void __launch_bounds__(256) la_v_colstats_finish_kernel(const float* 
         }
         const float mu = acc / seqlen;
         mean[b * m_bs + h * m_hs + d] = mu;
-        m = pv_umax(__float_as_uint(hi - mu) & 0x7fffffffu, __float_as_uint(mu - lo) & 0x7fffffffu);
+        m = umax(__float_as_uint(hi - mu) & 0x7fffffffu, __float_as_uint(mu - lo) & 0x7fffffffu);
     }
     if (amax == nullptr) return;
 #pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m = pv_umax(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), s, 64)));
+    for (int s = 32; s >= 1; s >>= 1) m = umax(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), s, 64)));
     if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)
-        amax[b * a_bs + h * a_hs] = __uint_as_float(pv_umax(pv_umax(wave_max[0], wave_max[1]), pv_umax(wave_max[2], wave_max[3])));
+        amax[b * a_bs + h * a_hs] = __uint_as_float(umax(umax(wave_max[0], wave_max[1]), umax(wave_max[2], wave_max[3])));
 }
 
 // 8 elements of a row: load, add the shift of the row's kv head, zero when the row is empty, round and store
 template <int DT_O, int DT_OUT>
 __device__ __forceinline__ void unshift_chunk(const AttnUnshiftParams& p, int b, int s, int h, int ch, bool empty) {
     float v[8];
-    VLoad<DT_O>::to_float(VLoad<DT_O>::load(p.o, b * p.o_bs + s * p.o_rs + h * p.o_hs + ch * 8), v);
+    PrepLoad<DT_O>::to_float(PrepLoad<DT_O>::load(p.o, b * p.o_bs + s * p.o_rs + h * p.o_hs + ch * 8), v);
     if (p.shift != nullptr) {
         float c[8];
-        VLoad<3>::to_float(VLoad<3>::load(p.shift, b * p.sh_bs + (h / p.heads_per_vec) * p.sh_hs + ch * 8), c);
+        load_f32x8(p.shift + b * p.sh_bs + (h / p.heads_per_vec) * p.sh_hs + ch * 8, c);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] += c[j];
     }
@@ -205,7 +138,7 @@ __device__ __forceinline__ void unshift_chunk(const AttnUnshiftParams& p, int b,
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    VStore<DT_OUT>::store8(p.out, b * p.out_bs + s * p.out_rs + h * p.out_hs + ch * 8, v);
+    PrepStore<DT_OUT>::store8(p.out, b * p.out_bs + s * p.out_rs + h * p.out_hs + ch * 8, v);
 }
 
 // Without lse: one thread = 8 consecutive d of one (b, s, h) row, grid stride over the rows in memory order.

@@ -93,43 +93,70 @@ def _unpack_tables(tables, head_dim):
     return tuple(tabs), pairs
 
 
-def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None):
+def _check_x(x, reference, name="x", dtypes=_IN_DTYPES, accepted="bf16, fp16 or fp32"):
+    """What every prologue pass asks of the (B, S, H, D) tensor it reads; ``reference``: the torch formula the message points to."""
     if x.dim() != 4:
-        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+        raise ValueError(f"{name} must be (B, S, H, D), got {tuple(x.shape)}")
     if not x.is_cuda:
-        raise ValueError("x must live on a GPU (there is no CPU path; qk_prep_reference is the formula in torch)")
-    if x.dtype not in _IN_DTYPES:
-        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
+        raise ValueError(f"{name} must live on a GPU (there is no CPU path; {reference} is the formula in torch)")
+    if x.dtype not in dtypes:
+        raise TypeError(f"{name}: {accepted}, got {x.dtype}")
+
+
+def _check_x_norm(x, norm, reference):
+    """``_check_x`` and the norm mode (``la_norm_mode``) of ``norm``."""
+    _check_x(x, reference)
     if norm not in _NORM_MODES:
         raise ValueError('norm: "token", "head" or None')
-    mode = _NORM_MODES[norm]
-    B, S, H, D = x.shape
-    if out is None:
-        if out_dtype is None:
-            out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.bfloat16
-        out = torch.empty((B, S, H, D), dtype=out_dtype, device=x.device)
-    elif out_dtype is not None and out.dtype != out_dtype:
-        raise TypeError(f"out is {out.dtype}, out_dtype says {out_dtype}")
-    if out.dtype not in _OUT_DTYPES:
-        raise TypeError(f"out: bf16 or fp16, got {out.dtype}")
-    if out.shape != x.shape or out.device != x.device:
-        raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    if x.stride(-1) != 1 or out.stride(-1) != 1:
-        raise ValueError("the last dimension of x and out must be contiguous")
-    if B * S == 0:
-        return out
+    return _NORM_MODES[norm]
+
+
+def _check_weight(x, weight, mode):
     if weight is not None and mode != _cabi.LA_NORM_NONE:
-        want = H * D if mode == _cabi.LA_NORM_TOKEN else D
+        want = x.shape[2] * x.shape[3] if mode == _cabi.LA_NORM_TOKEN else x.shape[3]
         if weight.dtype != torch.float32 or weight.numel() != want or not weight.is_contiguous() or weight.device != x.device:
             raise ValueError(f"weight must be contiguous fp32 with {want} elements on {x.device} "
                              f"(got {weight.dtype}, {tuple(weight.shape)}, {weight.device})")
-    a = _cabi.LaQkPrepArgs()
-    a.struct_size = ctypes.sizeof(_cabi.LaQkPrepArgs)
-    a.in_dtype, a.out_dtype, a.norm_mode = _IN_DTYPES[x.dtype], _OUT_DTYPES[out.dtype], mode
-    a.x, a.out = x.data_ptr(), out.data_ptr()
+
+
+def _f32(name, t, shape, device):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{name} must be fp32 {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _check_scales(x, heads_per_scale, descale, amax):
+    """The scale tensors of the e4m3 forms, fp32 (B, H // heads_per_scale) each. Returns heads_per_scale as an int."""
+    B, H, hps = x.shape[0], x.shape[2], int(heads_per_scale)
+    if hps < 1 or H % hps:
+        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
+    for name, t in (("descale", descale), ("amax_out", amax)):
+        if t is not None:
+            _f32(name, t, (B, H // hps), x.device)
+    return hps
+
+
+def _e4m3_out(x, out):
+    """``out`` of a quantizing pass (allocated when None), checked against ``x``."""
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    if out.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def _prep_args(struct, x, out, mode, weight, eps, pos_offset, tables, axis_pairs):
+    """A ``struct`` (one of the three argument structs) with the fields all three share filled in; ``out`` None: nothing is stored."""
+    a = struct()
+    a.struct_size = ctypes.sizeof(struct)
+    a.in_dtype, a.norm_mode = _IN_DTYPES[x.dtype], mode
+    a.x = x.data_ptr()
     a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
-    a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
-    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    if out is not None:
+        a.out = out.data_ptr()
+        a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = x.shape
     a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
     a.eps, a.pos_offset = float(eps), int(pos_offset)
     if tables is not None:
@@ -138,12 +165,52 @@ def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="
                 raise ValueError(f"rope table {i} lives on {t.device}, x on {x.device}: build the tables with device=x.device")
             a.rope_table[i] = t.data_ptr() if n > 0 else None
             a.axis_extent[i], a.axis_pairs[i] = t.shape[0], n
+    return a
+
+
+def _fill_scales(a, hps, descale, amax, store):
+    a.heads_per_scale = hps
+    if store and descale is not None:
+        a.descale, a.descale_batch_stride, a.descale_head_stride = descale.data_ptr(), descale.stride(0), descale.stride(1)
+    if amax is not None:
+        a.amax, a.amax_batch_stride, a.amax_head_stride = amax.data_ptr(), amax.stride(0), amax.stride(1)
+
+
+def _call(entry, x, detail, *args):
+    """``entry(*args, stream)`` of the library on the device and current stream of ``x``; a status other than LA_OK raises
+    ``RuntimeError`` with the status string and ``detail()``."""
     with torch.cuda.device(x.device):
-        rc = _cabi.load().la_qk_prep(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = getattr(_cabi.load(), entry)(*args, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_qk_prep: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()}, out strides {out.stride()}, "
-                           f"norm {norm!r}, pos_offset {pos_offset}, {S} rows on a grid of "
-                           f"{[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]})")
+        raise RuntimeError(f"{entry}: {_cabi.status_string(rc)} ({detail()})")
+
+
+def _call_prep(entry, a, x, pos_offset, detail):
+    """``_call`` of one of the three prologue entry points; ``detail()``: what the form adds between the strides of x and the grid."""
+    _call(entry, x, lambda: f"x {tuple(x.shape)} strides {x.stride()}, {detail()}, pos_offset {pos_offset}, {x.shape[1]} rows on a grid "
+                            f"of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]}", ctypes.byref(a))
+
+
+def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None):
+    mode = _check_x_norm(x, norm, "qk_prep_reference")
+    if out is None:
+        if out_dtype is None:
+            out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.bfloat16
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    elif out_dtype is not None and out.dtype != out_dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype says {out_dtype}")
+    if out.dtype not in _OUT_DTYPES:
+        raise TypeError(f"out: bf16 or fp16, got {out.dtype}")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    if x.stride(-1) != 1 or out.stride(-1) != 1:
+        raise ValueError("the last dimension of x and out must be contiguous")
+    if x.shape[0] * x.shape[1] == 0:
+        return out
+    _check_weight(x, weight, mode)
+    a = _prep_args(_cabi.LaQkPrepArgs, x, out, mode, weight, eps, pos_offset, tables, axis_pairs)
+    a.out_dtype = _OUT_DTYPES[out.dtype]
+    _call_prep("la_qk_prep", a, x, pos_offset, lambda: f"out strides {out.stride()}, norm {norm!r}")
     return out
 
 
@@ -207,67 +274,21 @@ _TINY = 2.0 ** -100        # the smallest amax a descale is made from: its recip
 
 def _qk_prep_fp8_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, descale, amax, heads_per_scale, out, store):
     """One ``la_qk_prep_fp8`` call. ``store``: quantize into ``out`` (allocated when None); otherwise the amax pass alone."""
-    if x.dim() != 4:
-        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
-    if not x.is_cuda:
-        raise ValueError("x must live on a GPU (there is no CPU path; qk_prep_fp8_reference is the formula in torch)")
-    if x.dtype not in _IN_DTYPES:
-        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
-    if norm not in _NORM_MODES:
-        raise ValueError('norm: "token", "head" or None')
-    mode = _NORM_MODES[norm]
-    B, S, H, D = x.shape
-    hps = int(heads_per_scale)
-    if hps < 1 or H % hps:
-        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
-    for name, t in (("descale", descale), ("amax_out", amax)):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, H // hps) or t.device != x.device):
-            raise ValueError(f"{name} must be fp32 {(B, H // hps)} on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    mode = _check_x_norm(x, norm, "qk_prep_fp8_reference")
+    hps = _check_scales(x, heads_per_scale, descale, amax)
     if store:
-        if out is None:
-            out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
-        if out.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+        out = _e4m3_out(x, out)
     elif amax is None:
         raise ValueError("the amax pass needs amax_out")
     if x.stride(-1) != 1 or (store and out.stride(-1) != 1):
         raise ValueError("the last dimension of x and out must be contiguous")
-    if B * S == 0:
+    if x.shape[0] * x.shape[1] == 0:
         return out
-    if weight is not None and mode != _cabi.LA_NORM_NONE:
-        want = H * D if mode == _cabi.LA_NORM_TOKEN else D
-        if weight.dtype != torch.float32 or weight.numel() != want or not weight.is_contiguous() or weight.device != x.device:
-            raise ValueError(f"weight must be contiguous fp32 with {want} elements on {x.device} "
-                             f"(got {weight.dtype}, {tuple(weight.shape)}, {weight.device})")
-    a = _cabi.LaQkPrepFp8Args()
-    a.struct_size = ctypes.sizeof(_cabi.LaQkPrepFp8Args)
-    a.in_dtype, a.norm_mode, a.heads_per_scale = _IN_DTYPES[x.dtype], mode, hps
-    a.x = x.data_ptr()
-    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
-    if store:
-        a.out = out.data_ptr()
-        a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
-        if descale is not None:
-            a.descale, a.descale_batch_stride, a.descale_head_stride = descale.data_ptr(), descale.stride(0), descale.stride(1)
-    if amax is not None:
-        a.amax, a.amax_batch_stride, a.amax_head_stride = amax.data_ptr(), amax.stride(0), amax.stride(1)
-    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
-    a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
-    a.eps, a.pos_offset = float(eps), int(pos_offset)
-    if tables is not None:
-        for i, (t, n) in enumerate(zip(tables, axis_pairs)):
-            if t.device != x.device:
-                raise ValueError(f"rope table {i} lives on {t.device}, x on {x.device}: build the tables with device=x.device")
-            a.rope_table[i] = t.data_ptr() if n > 0 else None
-            a.axis_extent[i], a.axis_pairs[i] = t.shape[0], n
-    with torch.cuda.device(x.device):
-        rc = _cabi.load().la_qk_prep_fp8(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_qk_prep_fp8: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()}, out strides "
-                           f"{out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, pos_offset {pos_offset}, {S} rows "
-                           f"on a grid of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]})")
+    _check_weight(x, weight, mode)
+    a = _prep_args(_cabi.LaQkPrepFp8Args, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs)
+    _fill_scales(a, hps, descale, amax, store)
+    _call_prep("la_qk_prep_fp8", a, x, pos_offset,
+               lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}")
     return out
 
 
@@ -381,30 +402,12 @@ def qk_prep_smooth_parts(seqlen: int, num_heads: int, head_dim: int) -> Tuple[in
     return n, r
 
 
-def _f32(name, t, shape, device):
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
-        raise ValueError(f"{name} must be fp32 {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-
-
 def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, shift, descale, amax, heads_per_scale, colsum_part,
                          dot_vec, heads_per_dot, dot_out, out, store):
     """One ``la_qk_prep_smooth`` call. ``store``: quantize into ``out`` (allocated when None)."""
-    if x.dim() != 4:
-        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
-    if not x.is_cuda:
-        raise ValueError("x must live on a GPU (there is no CPU path; qk_prep_smooth_reference is the formula in torch)")
-    if x.dtype not in _IN_DTYPES:
-        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
-    if norm not in _NORM_MODES:
-        raise ValueError('norm: "token", "head" or None')
-    mode = _NORM_MODES[norm]
+    mode = _check_x_norm(x, norm, "qk_prep_smooth_reference")
     B, S, H, D = x.shape
-    hps, hpd = int(heads_per_scale), int(heads_per_dot)
-    if hps < 1 or H % hps:
-        raise ValueError(f"heads_per_scale must be a divisor of the {H} heads, got {heads_per_scale}")
-    for name, t in (("descale", descale), ("amax_out", amax)):
-        if t is not None:
-            _f32(name, t, (B, H // hps), x.device)
+    hps, hpd = _check_scales(x, heads_per_scale, descale, amax), int(heads_per_dot)
     if shift is not None:
         _f32("shift", shift, (B, H, D), x.device)
         if shift.stride(2) != 1:
@@ -430,33 +433,15 @@ def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, s
         if not colsum_part.is_contiguous():
             raise ValueError("colsum_part must be contiguous")
     if store:
-        if out is None:
-            out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
-        if out.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+        out = _e4m3_out(x, out)
     elif amax is None and colsum_part is None and dot_out is None:
         raise ValueError("a pass that stores nothing needs amax_out, colsum_part or dot_vec")
     if x.stride(-1) != 1 or (store and out.stride(-1) != 1):
         raise ValueError("the last dimension of x and out must be contiguous")
-    if weight is not None and mode != _cabi.LA_NORM_NONE:
-        want = H * D if mode == _cabi.LA_NORM_TOKEN else D
-        if weight.dtype != torch.float32 or weight.numel() != want or not weight.is_contiguous() or weight.device != x.device:
-            raise ValueError(f"weight must be contiguous fp32 with {want} elements on {x.device} "
-                             f"(got {weight.dtype}, {tuple(weight.shape)}, {weight.device})")
-    a = _cabi.LaQkPrepSmoothArgs()
-    a.struct_size = ctypes.sizeof(_cabi.LaQkPrepSmoothArgs)
-    a.in_dtype, a.norm_mode, a.heads_per_scale, a.heads_per_dot = _IN_DTYPES[x.dtype], mode, hps, hpd
-    a.x = x.data_ptr()
-    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
-    if store:
-        a.out = out.data_ptr()
-        a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
-        if descale is not None:
-            a.descale, a.descale_batch_stride, a.descale_head_stride = descale.data_ptr(), descale.stride(0), descale.stride(1)
-    if amax is not None:
-        a.amax, a.amax_batch_stride, a.amax_head_stride = amax.data_ptr(), amax.stride(0), amax.stride(1)
+    _check_weight(x, weight, mode)
+    a = _prep_args(_cabi.LaQkPrepSmoothArgs, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs)
+    _fill_scales(a, hps, descale, amax, store)
+    a.heads_per_dot = hpd
     if shift is not None:
         a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
     if colsum_part is not None:
@@ -464,22 +449,9 @@ def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, s
     if dot_vec is not None:
         a.dot_vec, a.dot_vec_batch_stride, a.dot_vec_head_stride = dot_vec.data_ptr(), dot_vec.stride(0), dot_vec.stride(1)
         a.dot_out = dot_out.data_ptr()
-    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
-    a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
-    a.eps, a.pos_offset = float(eps), int(pos_offset)
-    if tables is not None:
-        for i, (t, n) in enumerate(zip(tables, axis_pairs)):
-            if t.device != x.device:
-                raise ValueError(f"rope table {i} lives on {t.device}, x on {x.device}: build the tables with device=x.device")
-            a.rope_table[i] = t.data_ptr() if n > 0 else None
-            a.axis_extent[i], a.axis_pairs[i] = t.shape[0], n
-    with torch.cuda.device(x.device):
-        rc = _cabi.load().la_qk_prep_smooth(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_qk_prep_smooth: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()}, out strides "
-                           f"{out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, heads_per_dot {hpd}, shift "
-                           f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}, pos_offset {pos_offset}, "
-                           f"{S} rows on a grid of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]})")
+    _call_prep("la_qk_prep_smooth", a, x, pos_offset,
+               lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, heads_per_dot {hpd}, shift "
+                       f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}")
     return out
 
 
@@ -518,11 +490,8 @@ def colsum_finish(colsum_part: torch.Tensor, seqlen: int, out: Optional[torch.Te
     _f32("out", out, (B, H, D), colsum_part.device)
     if out.stride(2) != 1:
         raise ValueError("the last dimension of out must be contiguous")
-    with torch.cuda.device(colsum_part.device):
-        rc = _cabi.load().la_colsum_finish(colsum_part.data_ptr(), n_parts, B, H, D, int(seqlen), out.data_ptr(), out.stride(0), out.stride(1),
-                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_colsum_finish: {_cabi.status_string(rc)} (parts {tuple(colsum_part.shape)}, seqlen {seqlen})")
+    _call("la_colsum_finish", colsum_part, lambda: f"parts {tuple(colsum_part.shape)}, seqlen {seqlen}", colsum_part.data_ptr(), n_parts, B, H,
+          D, int(seqlen), out.data_ptr(), out.stride(0), out.stride(1))
     return out
 
 
@@ -673,10 +642,14 @@ def _qk_prep_fp8_op(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm
     return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True)
 
 
+def _e4m3_meta(x, out):
+    """Shape and dtype only, of the two e4m3 ops."""
+    return out if out is not None else torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+
+
 def _qk_prep_fp8_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, descale=None, amax_out=None,
                       heads_per_scale=1, out=None):
-    """Shape and dtype only."""
-    return out if out is not None else torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    return _e4m3_meta(x, out)      # (named arguments: the dispatcher drops trailing arguments that equal their defaults)
 
 
 _QK_PREP_SMOOTH_SCHEMA = ("qk_prep_smooth(Tensor x, Tensor? weight = None, float eps = 1e-6, Tensor[]? tables = None, "
@@ -698,8 +671,7 @@ def _qk_prep_smooth_op(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, n
 
 def _qk_prep_smooth_meta(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, shift=None, descale=None,
                          amax_out=None, heads_per_scale=1, colsum_part=None, dot_vec=None, heads_per_dot=1, dot_out=None, out=None):
-    """Shape and dtype only."""
-    return out if out is not None else torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    return _e4m3_meta(x, out)
 
 
 def _register_op():

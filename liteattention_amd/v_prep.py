@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _cabi
-from .qk_prep import _IN_DTYPES, _f32, descale_from_amax, qk_prep_smooth
+from .qk_prep import _IN_DTYPES, _call, _check_x, _f32, descale_from_amax, qk_prep_smooth
 
 _UNSHIFT_OUT_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}
 _UNSHIFT_IN_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16}
@@ -48,12 +48,7 @@ def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mea
     stat_part    fp32 (n_parts, 3, B, H, D) contiguous work buffer, ``n_parts`` from ``v_colstats_parts``; None: allocated.
     mean_out / amax_out   buffers to write (amax is WRITTEN, not accumulated); None: allocated.
     No host sync; with the three buffers given, no allocation; captures into a HIP graph."""
-    if x.dim() != 4:
-        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
-    if not x.is_cuda:
-        raise ValueError("x must live on a GPU (there is no CPU path; v_colstats_reference is the formula in torch)")
-    if x.dtype not in _IN_DTYPES:
-        raise TypeError(f"x: bf16, fp16 or fp32, got {x.dtype}")
+    _check_x(x, "v_colstats_reference")
     if x.stride(-1) != 1:
         raise ValueError("the last dimension of x must be contiguous")
     B, S, H, D = x.shape
@@ -79,16 +74,9 @@ def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mea
     a.x, a.stat_part = x.data_ptr(), stat_part.data_ptr()
     a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
     a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
-    lib = _cabi.load()
-    with torch.cuda.device(x.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.la_v_colstats(ctypes.byref(a), stream)
-        if rc != _cabi.LA_OK:
-            raise RuntimeError(f"la_v_colstats: {_cabi.status_string(rc)} (x {tuple(x.shape)} strides {x.stride()})")
-        rc = lib.la_v_colstats_finish(stat_part.data_ptr(), n_parts, B, H, D, S, mean_out.data_ptr(), mean_out.stride(0), mean_out.stride(1),
-                                      amax_out.data_ptr(), amax_out.stride(0), amax_out.stride(1), stream)
-    if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_v_colstats_finish: {_cabi.status_string(rc)} (parts {tuple(stat_part.shape)}, seqlen {S})")
+    _call("la_v_colstats", x, lambda: f"x {tuple(x.shape)} strides {x.stride()}", ctypes.byref(a))
+    _call("la_v_colstats_finish", x, lambda: f"parts {tuple(stat_part.shape)}, seqlen {S}", stat_part.data_ptr(), n_parts, B, H, D, S,
+          mean_out.data_ptr(), mean_out.stride(0), mean_out.stride(1), amax_out.data_ptr(), amax_out.stride(0), amax_out.stride(1))
     return mean_out, amax_out
 
 
@@ -144,10 +132,7 @@ def attn_unshift(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
     Returns ``out``, or ``(out, lse_out)`` with ``lse_dot``. No host sync; no allocation when ``out`` (and ``lse_out``) are given;
     captures into a HIP graph."""
     hpv = _check_unshift(o, shift, lse, lse_dot)
-    if not o.is_cuda:
-        raise ValueError("o must live on a GPU (there is no CPU path; attn_unshift_reference is the formula in torch)")
-    if o.dtype not in _UNSHIFT_IN_DTYPES:
-        raise TypeError(f"o: bf16 or fp16, got {o.dtype}")
+    _check_x(o, "attn_unshift_reference", "o", _UNSHIFT_IN_DTYPES, "bf16 or fp16")
     B, S, H, D = o.shape
     if out is None:
         out = torch.empty((B, S, H, D), dtype=o.dtype if out_dtype is None else out_dtype, device=o.device)
@@ -187,11 +172,8 @@ def attn_unshift(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
     if lse_dot is not None:
         a.lse_dot, a.lse_out = lse_dot.data_ptr(), lse_out.data_ptr()
         a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
-    with torch.cuda.device(o.device):
-        rc = _cabi.load().la_attn_unshift(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_attn_unshift: {_cabi.status_string(rc)} (o {tuple(o.shape)} strides {o.stride()}, out {out.dtype} strides "
-                           f"{out.stride()}, shift {None if shift is None else (tuple(shift.shape), shift.stride())})")
+    _call("la_attn_unshift", o, lambda: f"o {tuple(o.shape)} strides {o.stride()}, out {out.dtype} strides {out.stride()}, shift "
+                                        f"{None if shift is None else (tuple(shift.shape), shift.stride())}", ctypes.byref(a))
     return out if lse_dot is None else (out, lse_out)
 
 
