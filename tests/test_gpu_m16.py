@@ -54,6 +54,14 @@ def test_score_staircases_on_the_16x16x32_body():
     assert " passed" in r.stdout and "failed" not in r.stdout
 
 
+def test_non_finite_containment_on_the_16x16x32_body():
+    """Another V image in LDS and a transposed running state: the step past the end of the walk and the item-to-item carry-over of
+    tests/test_gpu_nonfinite.py at head_dim 128, bf16 and fp16 (families A and B, the host split, the workspace)."""
+    r = _run(["tests/test_gpu_nonfinite.py", "-k", "d128 and not e4m3 and not v2 and not half"])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert " passed" in r.stdout and "failed" not in r.stdout
+
+
 def test_the_process_really_ran_the_16x16x32_kernel():
     """The kernel symbol is the same (la_fwd_x64_kernel<.., 128>): what tells the bodies apart is the instruction stream. The library on
     disk must hold 16x16x32 MFMAs in its gfx950 code object, and the product library none (it is all 32x32x16 / fp8 scaled)."""
