@@ -12,6 +12,9 @@ per layer, the skip state carried across denoising steps.
 the eager lines below. `--fp8 --smooth-k`: each key head's mean over the tokens is subtracted before the e4m3 cast (`SmoothedQK`); the
 output needs no correction. `--fp8 --smooth-v` (combinable with `--smooth-k`): the same for V (`SmoothedV`); the mean is added back to
 the attention output by the restoring pass, which also replaces the block's `.float()` (`out_dtype=torch.float32`).
+`--fp8 [--smooth-v] --v-tiles`: V is quantized straight into the V^T tiles the e4m3 forward stages (`v_prep_tiles`) and handed to the
+attention call as a `PreparedV`: the same codes, no e4m3 V tensor. (The block with skipping disabled is then never split over the
+keys; with a tensor V it is above 704 keys, so its rows agree with those of the tensor route to rounding there, bit for bit below.)
 
 Prints, per denoising step, the fraction of tiles skipped and the error against the same block with skipping disabled.
 """
@@ -64,19 +67,21 @@ def rope_3d(x, grid, theta=10000.0):
 
 class WanLikeSelfAttention(nn.Module):
     def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1, fused_prep=False, *, fp8=False,
-                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False):
+                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False):
         super().__init__()
         assert dim % num_heads == 0
         self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
         # fp8: q, k and v are produced in e4m3 by qk_prep_fp8, each with the per-head scales of its own E4m3Scales
         self.fp8 = fp8
-        self.scales = [E4m3Scales(mode=fp8_mode, margin=fp8_margin) for _ in range(3)] if fp8 else None
+        # v_tiles: v is quantized straight into the V^T tiles of the e4m3 forward (a PreparedV): no e4m3 V tensor, no prepare pass
+        assert fp8 or not v_tiles, "v_tiles is a form of the fp8 path"
+        self.scales = [E4m3Scales(mode=fp8_mode, margin=fp8_margin, tiles=v_tiles and i == 2) for i in range(3)] if fp8 else None
         # smooth_k: q and k go through one SmoothedQK instead (k first, q with the dots that would restore the LSE); v as before
         assert fp8 or not smooth_k, "smooth_k is a form of the fp8 path"
         self.smoothed = SmoothedQK(mode=fp8_mode, margin=fp8_margin) if smooth_k else None
         # smooth_v: v goes through a SmoothedV; the attention call restores O (v_shift) and hands it on in fp32 (out_dtype)
         assert fp8 or not smooth_v, "smooth_v is a form of the fp8 path"
-        self.smoothed_v = SmoothedV(mode=fp8_mode, margin=fp8_margin) if smooth_v else None
+        self.smoothed_v = SmoothedV(mode=fp8_mode, margin=fp8_margin, tiles=v_tiles) if smooth_v else None
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
         # the recipe: ONE LiteAttention per attention layer (its skip lists are that layer's state)
@@ -153,11 +158,11 @@ class WanLikeCrossAttention(nn.Module):
 
 
 def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False, *,
-        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False):
+        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False):
     torch.manual_seed(seed)
     dim, grid = heads * 128, (frames, height, width)
     S = frames * height * width
-    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v)
+    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v, v_tiles=v_tiles)
     sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep, **kw).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
     # under which tokens of the same frame attend to each other
@@ -193,8 +198,10 @@ if __name__ == "__main__":
     ap.add_argument("--smooth-k", action="store_true", help="with --fp8: subtract each key head's mean before the e4m3 cast (SmoothedQK)")
     ap.add_argument("--smooth-v", action="store_true", help="with --fp8: subtract each V head's mean before the e4m3 cast (SmoothedV); "
                     "the attention call adds it back and returns fp32")
+    ap.add_argument("--v-tiles", action="store_true", help="with --fp8: quantize V straight into the V^T tiles the e4m3 forward stages "
+                    "(v_prep_tiles through E4m3Scales / SmoothedV with tiles=True): no e4m3 V tensor, no prepare pass in the call")
     a = ap.parse_args()
-    if (a.smooth_k or a.smooth_v) and not a.fp8:
-        ap.error("--smooth-k and --smooth-v need --fp8")
+    if (a.smooth_k or a.smooth_v or a.v_tiles) and not a.fp8:
+        ap.error("--smooth-k, --smooth-v and --v-tiles need --fp8")
     run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep, fp8=a.fp8, fp8_mode=a.fp8_mode,
-        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v)
+        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v, v_tiles=a.v_tiles)

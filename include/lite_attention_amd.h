@@ -33,6 +33,9 @@
  *                            quantized mean-shifted ("smooth V")
  *   la_attn_unshift       <- nothing: adds that mean back to the attention output (exact: the rows of P sum to 1), restores the LSE
  *                            of smoothed keys and casts, in one read of O
+ *   la_v_prep_tiles       <- nothing: quantizes V as it leaves its projection straight into the V^T tiles la_fwd's e4m3 kernels stage
+ *                            (with la_v_tiles_bytes / la_v_tiles_workspace_bytes), for a la_fwd under LA_FLAG_V_PREPARED: the e4m3
+ *                            (B, S, Hk, D) tensor and la_fwd's own prepare pass over it drop out
  *
  * Rules of the boundary:
  *   - plain C: pointers, sizes, scalars. No torch types, no C++ types, no exceptions.
@@ -52,7 +55,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish) and la_attn_unshift were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes and la_v_tiles_workspace_bytes were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -564,6 +567,49 @@ typedef struct la_attn_unshift_args {
     int32_t reserved0;           /* 0                                                              */
 } la_attn_unshift_args;
 int la_attn_unshift(const la_attn_unshift_args* args, void* stream);
+
+/* fp8 V in one pass. la_fwd's e4m3 kernels do not read V (B, Sk, Hk, D): they stage pre-transposed, pre-swizzled V^T tiles
+ * [B, Hk, ceil(Sk / 64)][head_dim (96: 128 rows, the last 32 zeros)][64 keys] from the front of the workspace, which la_fwd's prepare pass
+ * writes from the e4m3 V unless LA_FLAG_V_PREPARED says they are there. la_v_prep_tiles writes the same bytes from V as its projection
+ * wrote it:
+ *   y  = float(x[b][s][h][d]) - shift[b][h][d]                       (shift NULL: y = float(x))
+ *   z  = clamp(y * (1 / descale[b][h]), -448, +448)                  one IEEE division per (b, h); a NaN stays a NaN
+ *   code = e4m3fn(z), round to nearest even
+ * - for every element the byte la_qk_prep_smooth (LA_NORM_NONE, no rope, heads_per_scale 1, the same shift and descale) stores, in the
+ * place la_fwd's prepare pass would put it; keys at and beyond seqlen are zeros. amax[b][h] = max(amax[b][h], max |y|) as the
+ * unsigned maximum of the bit patterns, la_qk_prep_fp8's semantics (zero it first for this call's maximum; any NaN wins; one integer
+ * atomicMax per workgroup, no float atomics: two launches write the same bytes). One read of x, one write of the tiles.
+ * The call that follows: la_fwd with dtype LA_DTYPE_FP8_E4M3, flags | LA_FLAG_V_PREPARED, workspace = tiles and workspace_bytes >=
+ * la_v_tiles_workspace_bytes(B, Hk, Sk, D), the descale given here as v_descale, and as v any 16-byte aligned buffer of B * Sk * Hk * D
+ * bytes with valid strides (it is checked, never read: the tile buffer itself will do). That workspace size serves every
+ * fixed-length, unsplit e4m3 la_fwd over these keys, with or without lists, with or without LA_FLAG_STATIC_SCHED: the tiles, then the
+ * ticket counters. A dense launch whose keys la_fwd would cut into runs (la_fwd_workspace_bytes() above that size) has no prepared
+ * form: la_fwd refuses it (LA_ERR_SEQLEN, or LA_ERR_WORKSPACE when the workspace is too small for the runs' partials).
+ * Errors of la_v_prep_tiles (all before any HIP call), in this order: NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; NULL x
+ * or tiles LA_ERR_NULL_ARG; in_dtype LA_ERR_DTYPE; a non-positive size LA_ERR_SHAPE; head_dim outside 64 / 96 / 128 / 192 / 256
+ * LA_ERR_HEAD_DIM; reserved0 != 0 LA_ERR_UNSUPPORTED; a negative stride, x, shift or tiles off a 16-byte boundary, a used stride of x or
+ * shift that takes a row, head or batch start off one, descale or amax off a 4-byte boundary, LA_ERR_STRIDE; more than 2^31 - 1 tiles
+ * (B * Hk * ceil(S / 64)) LA_ERR_SHAPE. NOT detected: a tiles buffer shorter than la_v_tiles_bytes(), buffers that overlap.
+ * la_v_tiles_bytes / la_v_tiles_workspace_bytes: B * Hk * ceil(Sk / 64) * 64 * (96: 128, else head_dim) bytes, and that plus the ticket
+ * counters; a non-positive batch / num_heads_k or a negative seqlen_k LA_ERR_SHAPE, another head_dim LA_ERR_HEAD_DIM (as int64_t). */
+typedef struct la_v_prep_tiles_args {
+    uint32_t struct_size;        /* = sizeof(la_v_prep_tiles_args)                                */
+    int32_t  in_dtype;           /* la_dtype of x: LA_DTYPE_BF16, LA_DTYPE_FP16 or LA_DTYPE_FP32  */
+    const void* x;               /* (B, S, Hk, D), last dimension contiguous                      */
+    int64_t x_batch_stride, x_row_stride, x_head_stride;          /* in elements                  */
+    int32_t batch, seqlen, num_heads, head_dim;                   /* num_heads: kv heads          */
+    const float* descale;        /* fp32 [B, Hk] by the strides below; NULL = 1.0                 */
+    int64_t descale_batch_stride, descale_head_stride;
+    const float* shift;          /* fp32 [B, Hk, D] by the strides below; NULL = no shift         */
+    int64_t shift_batch_stride, shift_head_stride;
+    float*  amax;                /* fp32 [B, Hk] by the strides below, accumulated; NULL = not wanted */
+    int64_t amax_batch_stride, amax_head_stride;
+    void*   tiles;               /* la_v_tiles_bytes() bytes, 16-byte aligned: the front of a la_fwd workspace */
+    int32_t reserved0;           /* 0                                                              */
+} la_v_prep_tiles_args;
+int la_v_prep_tiles(const la_v_prep_tiles_args* args, void* stream);
+int64_t la_v_tiles_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim);
+int64_t la_v_tiles_workspace_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim);
 
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error", "la_qk_prep", "la_qk_prep_fp8",
     "la_qk_prep_smooth", "la_qk_prep_smooth_parts", "la_qk_prep_smooth_part_rows", "la_colsum_finish",
     "la_v_colstats", "la_v_colstats_parts", "la_v_colstats_part_rows", "la_v_colstats_finish", "la_attn_unshift",
+    "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -122,6 +123,20 @@ class LaAttnUnshiftArgs(ctypes.Structure):
         ("shift", ctypes.c_void_p), ("shift_batch_stride", ctypes.c_int64), ("shift_head_stride", ctypes.c_int64),
         ("lse", ctypes.c_void_p), ("lse_dot", ctypes.c_void_p), ("lse_out", ctypes.c_void_p),
         ("softmax_scale", ctypes.c_float), ("reserved0", ctypes.c_int32),
+    ]
+
+
+class LaVPrepTilesArgs(ctypes.Structure):
+    """Mirror of ``la_v_prep_tiles_args`` (field order and types must match the header)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("in_dtype", ctypes.c_int32),
+        ("x", ctypes.c_void_p),
+        ("x_batch_stride", ctypes.c_int64), ("x_row_stride", ctypes.c_int64), ("x_head_stride", ctypes.c_int64),
+        ("batch", ctypes.c_int32), ("seqlen", ctypes.c_int32), ("num_heads", ctypes.c_int32), ("head_dim", ctypes.c_int32),
+        ("descale", ctypes.c_void_p), ("descale_batch_stride", ctypes.c_int64), ("descale_head_stride", ctypes.c_int64),
+        ("shift", ctypes.c_void_p), ("shift_batch_stride", ctypes.c_int64), ("shift_head_stride", ctypes.c_int64),
+        ("amax", ctypes.c_void_p), ("amax_batch_stride", ctypes.c_int64), ("amax_head_stride", ctypes.c_int64),
+        ("tiles", ctypes.c_void_p), ("reserved0", ctypes.c_int32),
     ]
 
 
@@ -261,6 +276,11 @@ def load() -> ctypes.CDLL:
     lib.la_v_colstats_finish.restype = ctypes.c_int
     lib.la_attn_unshift.argtypes = [ctypes.POINTER(LaAttnUnshiftArgs), ctypes.c_void_p]
     lib.la_attn_unshift.restype = ctypes.c_int
+    lib.la_v_prep_tiles.argtypes = [ctypes.POINTER(LaVPrepTilesArgs), ctypes.c_void_p]
+    lib.la_v_prep_tiles.restype = ctypes.c_int
+    for fn in (lib.la_v_tiles_bytes, lib.la_v_tiles_workspace_bytes):
+        fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        fn.restype = ctypes.c_int64
     lib.la_device_slots.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.la_device_slots.restype = ctypes.c_int
     lib.la_status_string.argtypes = [ctypes.c_int]

@@ -729,4 +729,41 @@ int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
     return launch_status(err);
 }
 
+// ---- fp8 V in one pass (la_prep_fp8.hip) -------------------------------------------------------------------------------------------
+int64_t la_v_tiles_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim) {
+    if (batch <= 0 || num_heads_k <= 0 || seqlen_k < 0) return LA_ERR_SHAPE;
+    if (la::tile_shape(head_dim, 1).block_m == 0) return LA_ERR_HEAD_DIM;
+    return static_cast<int64_t>(la::fp8_workspace_bytes(batch, num_heads_k, (seqlen_k + 63) / 64, head_dim));
+}
+
+int64_t la_v_tiles_workspace_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim) {
+    const int64_t tiles = la_v_tiles_bytes(batch, num_heads_k, seqlen_k, head_dim);
+    return tiles < 0 ? tiles : tiles + static_cast<int64_t>(kSchedWorkspaceBytes);      // what la_fwd asks for when it does not cut the keys into runs
+}
+
+int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_v_prep_tiles_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || !a->tiles) return LA_ERR_NULL_ARG;
+    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (la::tile_shape(a->head_dim, 1).block_m == 0) return LA_ERR_HEAD_DIM;     // the head dims the e4m3 forward has
+    if (a->reserved0 != 0) return LA_ERR_UNSUPPORTED;
+    if (!rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
+        (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1, a->num_heads)) ||
+        !aligned16(a->tiles) || a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 ||
+        a->amax_head_stride < 0 || ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u))
+        return LA_ERR_STRIDE;
+    la::VPrepTilesParams p = {};
+    p.k_tiles = (a->seqlen + 63) / 64;
+    if (static_cast<int64_t>(a->batch) * a->num_heads * p.k_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;      // one workgroup per tile
+    p.x = a->x; p.tiles = static_cast<uint8_t*>(a->tiles); p.descale = a->descale; p.shift = a->shift; p.amax = a->amax;
+    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
+    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
+    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
+    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    return launch_status(la::launch_v_prep_tiles(p, a->in_dtype, static_cast<hipStream_t>(stream_)));
+}
+
 }  // extern "C"

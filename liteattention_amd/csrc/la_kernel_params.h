@@ -94,6 +94,18 @@ size_t fp8_workspace_bytes(int batch, int num_heads_k, int k_tiles, int head_dim
 hipError_t launch_prep_v_fp8(const void* v, int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride,
                              void* vt, int batch, int seqlen_k, int num_heads_k, int k_tiles, int head_dim, hipStream_t stream,
                              const int* cu_seqlens_k = nullptr);
+// la_v_prep_tiles (la_prep_fp8.hip): the quantizing front end of the same tile writer - x as the projection wrote it -> the V^T tiles.
+// Checked and filled by la_api.hip. Strides in elements.
+struct VPrepTilesParams {
+    const void* x;               // (B, S, Hk, D) bf16 / fp16 / fp32 by x_bs / x_rs / x_hs
+    uint8_t* tiles;              // [B, Hk, Kt][D (96: 128)][64]: fp8_workspace_bytes(B, Hk, Kt, D) bytes
+    const float* descale;        // [B, Hk] by ds_bs / ds_hs; NULL = 1.0
+    const float* shift;          // [B, Hk, D] by sh_bs / sh_hs; NULL = none
+    float* amax;                 // [B, Hk] by am_bs / am_hs: running maximum of |x - shift| as its bit pattern; NULL = not wanted
+    int64_t x_bs, x_rs, x_hs, ds_bs, ds_hs, sh_bs, sh_hs, am_bs, am_hs;
+    int batch, seqlen, num_heads, head_dim, k_tiles;
+};
+hipError_t launch_v_prep_tiles(const VPrepTilesParams& p, int in_dtype, hipStream_t stream);      // in_dtype: 0 bf16, 1 fp16, 3 fp32
 hipError_t launch_empty_k_fill(uint16_t* o, float* lse, int64_t o_batch_stride, int64_t o_row_stride, int64_t o_head_stride,
                                int batch, int seqlen_q, int num_heads, int head_dim_v, hipStream_t stream);
 hipError_t launch_skip_list_stats(const void* list, int list_elem_size, int rows, int k_tiles, int64_t* out, hipStream_t stream);

@@ -1,4 +1,4 @@
-// la_prep_common.h — chunk I/O of the prologue passes (la_prep_qk.hip, la_prep_v.hip): a CHUNK is 8 consecutive elements of a row, one
+// la_prep_common.h — chunk I/O of the prologue passes (la_prep_qk.hip, la_prep_v.hip, la_v_prep_tiles in la_prep_fp8.hip): a CHUNK is 8 consecutive elements of a row, one
 // 16-byte load or store of 16-bit elements, two of fp32, one 8-byte store of e4m3; between the two everything is fp32. Everything
 // sits in the unnamed namespace of the including file and is inlined into its kernels: no symbol, no device code of its own.
 #pragma once
@@ -72,14 +72,18 @@ template <> struct PrepStore<1> {
         *reinterpret_cast<pq_f16x8*>(static_cast<uint16_t*>(base) + off) = w;
     }
 };
+// 8 values inside +-448 or NaN (the caller clamps) -> their 8 e4m3 bytes, element i in byte i: the hardware's round to nearest even
+__device__ __forceinline__ pq_u32x2 e4m3_pack8(const float (&y)[8]) {
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+    return pq_u32x2{static_cast<unsigned>(lo), static_cast<unsigned>(hi)};
+}
 template <> struct PrepStore<2> {           // e4m3: y is inside +-448 or NaN (the caller clamps); 8 bytes, one 8-byte store
     static __device__ __forceinline__ void store8(void* base, int64_t off, const float (&y)[8]) {
-        int lo = 0, hi = 0;
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
-        *reinterpret_cast<pq_u32x2*>(static_cast<uint8_t*>(base) + off) = pq_u32x2{static_cast<unsigned>(lo), static_cast<unsigned>(hi)};
+        *reinterpret_cast<pq_u32x2*>(static_cast<uint8_t*>(base) + off) = e4m3_pack8(y);
     }
 };
 template <> struct PrepStore<3> {           // fp32: two 16-byte stores
@@ -105,6 +109,16 @@ __device__ __forceinline__ unsigned absmax8(const float (&y)[8]) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) m = umax(m, __float_as_uint(y[i]) & 0x7fffffffu);
     return m;
+}
+
+// z = y * inv clamped to +-448, the step in front of the e4m3 conversion (inv = 1 / descale, one IEEE division by the caller)
+__device__ __forceinline__ void scale_clamp8(float (&y)[8], float inv) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        float z = y[i] * inv;
+        z = z > 448.f ? 448.f : z;                                 // a NaN fails both compares and stays
+        y[i] = z < -448.f ? -448.f : z;
+    }
 }
 
 }  // namespace

@@ -101,15 +101,6 @@ __device__ __forceinline__ float dot8(const float (&y)[8], const float (&c)[8]) 
     return ((y[0] * c[0] + y[1] * c[1]) + (y[2] * c[2] + y[3] * c[3])) + ((y[4] * c[4] + y[5] * c[5]) + (y[6] * c[6] + y[7] * c[7]));
 }
 
-__device__ __forceinline__ void scale_clamp8(float (&y)[8], float inv) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float z = y[i] * inv;
-        z = z > 448.f ? 448.f : z;                                 // a NaN fails both compares and stays
-        y[i] = z < -448.f ? -448.f : z;
-    }
-}
-
 // The workgroup leaves batch old_b (-1: none) and enters new_b (-1: none): the maxima its waves collected per head in am_tab go out,
 // one atomic per scale group, and the reciprocal scales of new_b come in. Every thread of the workgroup calls it at the same trip.
 template <bool STORE>

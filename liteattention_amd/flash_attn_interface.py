@@ -326,7 +326,8 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
             is_causal=False, window_size_left=-1, window_size_right=-1, attention_chunk=0, softcap=0.0,
             is_rotary_interleaved=False, scheduler_metadata=None, num_splits=0, pack_gqa=None, sm_margin=0,
             attn_read_list=None, attn_must_do_list=None, attn_write_list=None, thr=-3.0,
-            _must_do_is_1d: bool = False, _q_windows=None, _window_hook=None, _static_sched: bool = False, _flags: int = 0):
+            _must_do_is_1d: bool = False, _q_windows=None, _window_hook=None, _static_sched: bool = False, _flags: int = 0,
+            _v_prepared=None):
     """Host half of the op (flash_api.cpp:667-1249) for the non-causal, fixed-length subset (MHA / GQA / MQA) that
     ``LiteAttention.__call__`` reaches. Returns ``(out, softmax_lse, out_accum, softmax_lse_accum)``.
 
@@ -337,7 +338,11 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     windows compute). ``_static_sched`` sets LA_FLAG_STATIC_SCHED (per-item workgroups instead of persistent ones: a
     collective running beside the launch gets CUs as items retire); "after_first" sets it on every window but the first
     (no collective is in flight beside window 0). ``_flags``: extra ``LA_FLAG_*`` bits ORed into ``la_fwd_args.flags`` (tests / A/B:
-    LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM, LA_FLAG_FP8_ENCODED_P); kernel-selection bits that change the tile geometry are not accepted here."""
+    LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM, LA_FLAG_FP8_ENCODED_P); kernel-selection bits that change the tile geometry are not accepted here.
+    ``_v_prepared``: the ``v_prep.PreparedV`` whose ``as_v()`` is given as ``v``: the launches run on ITS workspace (nothing is
+    allocated here) under LA_FLAG_V_PREPARED, every window of them; what it has no form for is refused before any launch."""
+    if _v_prepared is not None:
+        _v_prepared.check_call(q, k, cu_seqlens_q, cu_seqlens_k, num_splits)
     if _flags & ~_EXTRA_FLAGS:
         raise ValueError("_flags accepts LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM and LA_FLAG_FP8_ENCODED_P only")
     if not q.is_cuda:
@@ -400,7 +405,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     # and ran the bf16 kernels; the sizes between run zero-padded on the next one, like the 2-byte types)
     D_kernel = kernel_head_dim(D, q.element_size(), host_flags)
     _check_out(out, (B, Sq, H, D), out_dtype, _OUT_MSG)
-    if D_kernel != D:
+    if D_kernel != D:                                        # (never with a PreparedV: it exists at the instantiated sizes only)
         # head_dim between the instantiated sizes: zero-pad the last dim (one extra pass over q, k, v; exact, see
         # kernel_head_dim), run the D_kernel kernel with the ORIGINAL softmax scale, slice the output
         res = mha_fwd(_pad_head_dim(q, D_kernel), _pad_head_dim(k, D_kernel), _pad_head_dim(v, D_kernel),
@@ -441,7 +446,10 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
                   read_ptr, write_ptr, must_ptr, _must_do_is_1d, thr)
     base_flags = _route_flags(_FIXED, host_flags, _flags, list_flags, is_fp8)
     a.flags = base_flags | (_cabi.LA_FLAG_STATIC_SCHED if _static_sched is True else 0)
-    workspace = _add_workspace(a, q.device, _FIXED)           # noqa: F841 - alive until the launches are enqueued
+    if _v_prepared is None:
+        workspace = _add_workspace(a, q.device, _FIXED)       # noqa: F841 - alive until the launches are enqueued
+    else:                                                     # the caller's buffer: the tiles are there, the ticket counters go behind them
+        a.workspace, a.workspace_bytes = _v_prepared.workspace.data_ptr(), _v_prepared.workspace.numel()
     windows = [(0, 0)] if _q_windows is None else [(int(b0), int(c0)) for b0, c0 in _q_windows]
     if _q_windows is not None and any(c0 <= 0 or b0 < 0 or b0 + c0 > q_tiles for b0, c0 in windows):
         raise RuntimeError(f"q-tile windows must lie inside [0, {q_tiles}) with positive counts; got {windows}")
@@ -449,7 +457,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     with torch.cuda.device(q.device):                                                             # CUDAGuard :885
         for i, (w_begin, w_count) in enumerate(windows):
             a.q_tile_begin, a.q_tile_count = w_begin, w_count
-            a.flags = base_flags | (_cabi.LA_FLAG_V_PREPARED if (is_fp8 and i > 0) else 0) | \
+            a.flags = base_flags | (_cabi.LA_FLAG_V_PREPARED if (is_fp8 and (i > 0 or _v_prepared is not None)) else 0) | \
                       (_cabi.LA_FLAG_STATIC_SCHED if (_static_sched is True or (_static_sched == "after_first" and i > 0))
                        else 0)                                                   # V^T tiles prepared by window 0
             _launch(lib, a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _FIXED)   # :1219
@@ -749,6 +757,24 @@ class FlashAttnFunc(torch.autograd.Function):
                                   "sets FLASH_ATTENTION_DISABLE_BACKWARD, hopper/setup.py:47)")
 
 
+def _flash_attn_func_prepared_v(q, k, pv, softmax_scale, causal, qv, q_descale, k_descale, v_descale, window_size, attention_chunk,
+                                softcap, num_splits, pack_gqa, sm_margin, attn_read_list, attn_must_do_list, attn_write_list, thr,
+                                return_softmax_lse):
+    """``flash_attn_func`` for a ``PreparedV``: ``mha_fwd`` directly (the op's schema has no such argument), forward only."""
+    from .v_prep import PreparedV
+    if not isinstance(pv, PreparedV):
+        raise TypeError(f"v must be a tensor or a PreparedV, got {type(pv).__name__}")
+    pv.check_call(q, k, num_splits=num_splits)
+    q, k = maybe_contiguous(q), maybe_contiguous(k)
+    out, softmax_lse, *_ = mha_fwd(
+        q, k, pv.as_v(), q_v=qv, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale, softmax_scale=softmax_scale,
+        is_causal=causal, window_size_left=window_size[0], window_size_right=window_size[1], attention_chunk=attention_chunk,
+        softcap=softcap, num_splits=num_splits, pack_gqa=pack_gqa, sm_margin=sm_margin, attn_read_list=attn_read_list,
+        attn_must_do_list=attn_must_do_list, attn_write_list=attn_write_list, thr=thr,
+        _must_do_is_1d=attn_must_do_list is not None and attn_must_do_list.dim() == 1, _v_prepared=pv)
+    return (out, softmax_lse) if return_softmax_lse else out
+
+
 def flash_attn_func(q, k, v, softmax_scale=None, causal=False, qv=None, q_descale=None, k_descale=None,
                     v_descale=None, window_size=(-1, -1), attention_chunk=0, softcap=0.0, num_splits=1,
                     pack_gqa=None, deterministic=False, sm_margin=0, attn_read_list=None,
@@ -758,7 +784,14 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal=False, qv=None, q_descal
     q: (batch, seqlen, nheads, headdim); k, v: (batch, seqlen_k, nheads, headdim). Returns ``out``
     (batch, seqlen, nheads, headdim) or ``(out, softmax_lse)`` with softmax_lse (batch, nheads, seqlen)
     fp32. With ``attn_read_list``/``attn_write_list`` the K-tile loop walks the read list and the skip
-    decisions of this call are serialised into the write list (QK-Skip)."""
+    decisions of this call are serialised into the write list (QK-Skip).
+
+    ``v`` may be a ``v_prep.PreparedV`` (e4m3 q and k; fixed-length, unsplit calls at head_dim 64 / 96 / 128 / 192 / 256): the call
+    goes to ``mha_fwd`` directly and launches on the PreparedV's workspace. ``v_descale`` is still the caller's to pass."""
+    if not isinstance(v, torch.Tensor):
+        return _flash_attn_func_prepared_v(q, k, v, softmax_scale, causal, qv, q_descale, k_descale, v_descale, window_size,
+                                           attention_chunk, softcap, num_splits, pack_gqa, sm_margin, attn_read_list,
+                                           attn_must_do_list, attn_write_list, thr, return_softmax_lse)
     return FlashAttnFunc.apply(q, k, v, softmax_scale, causal, qv, q_descale, k_descale, v_descale, window_size,
                                attention_chunk, softcap, num_splits, pack_gqa, deterministic, sm_margin,
                                attn_read_list, attn_must_do_list, attn_write_list, thr, return_softmax_lse)

@@ -194,7 +194,12 @@ class LiteAttention:
         (``attn_unshift``), applied to what the forward returns - behind its internal split-KV merge. ``v_shift`` fp32
         (batch, nheads_k, D): the vector subtracted from V (``SmoothedV``), added back to O; rows without keys stay 0.
         ``lse_shift`` fp32 (batch, nheads, S): ``q . c`` of ``SmoothedQK``, folded into the returned LSE. ``out_dtype``:
-        bf16 / fp16 / fp32 of the returned O (fp32: what an output projection reads)."""
+        bf16 / fp16 / fp32 of the returned O (fp32: what an output projection reads).
+        ``value`` may be a ``v_prep.PreparedV`` (``v_prep_tiles``, ``SmoothedV(tiles=True)``): e4m3 query / key, the launch runs on
+        its workspace and a dense call is never split over the keys."""
+        tiles = not isinstance(value, Tensor)
+        if tiles:
+            value.check_call(query, key)
         restore = v_shift is not None or lse_shift is not None or out_dtype is not None
         if restore:
             self._check_restore(query, key, value, v_shift, lse_shift, out_dtype)
@@ -205,7 +210,7 @@ class LiteAttention:
         extra = {}
         if q_descale is not None or k_descale is not None or v_descale is not None:      # only when given: the host-logic
             extra = dict(q_descale=q_descale, k_descale=k_descale, v_descale=v_descale)     # tests record the exact call
-        if read_list is None:
+        if read_list is None and not tiles:
             # dense calls (enable_skip_optimization(False): the t2t / t2v / v2t calls of the text + video recipe, README.md:225-246) may be
             # split over the keys when they have fewer items than the device has workgroup slots: num_splits = -1 lets the op decide by
             # the reference's heuristic (flash_api.cpp:437, heuristics.h:25-58; the reference class passes nothing, i.e. 1: its default
@@ -213,15 +218,29 @@ class LiteAttention:
             extra["num_splits"] = -1
         # the restoring pass reads the LSE for its empty-row rule: ask the forward for it whenever a shift is given
         want_lse = return_softmax_lse or v_shift is not None or lse_shift is not None
-        output = flash_attn_func(q=query, k=key, v=value, softmax_scale=scale, attn_read_list=read_list,
-                                 attn_must_do_list=must_do, attn_write_list=write_list, thr=self._take_threshold(read_list is not None),
-                                 return_softmax_lse=want_lse, **extra)
+        if tiles:
+            output = self._fwd_prepared_v(query, key, value, scale, read_list, write_list, must_do, want_lse, **extra)
+        else:
+            output = flash_attn_func(q=query, k=key, v=value, softmax_scale=scale, attn_read_list=read_list,
+                                     attn_must_do_list=must_do, attn_write_list=write_list, thr=self._take_threshold(read_list is not None),
+                                     return_softmax_lse=want_lse, **extra)
         if read_list is not None and _verbose():
             self._last_percentage = self.calc_percentage(read_list[: query.shape[0]])
             print(f"[Info]: Percentage of tiles skipped: {1.0 - self._last_percentage:.2%}")
         if restore:
             output = self._restore(output, want_lse, return_softmax_lse, scale, v_shift, lse_shift, out_dtype)
         return output
+
+    def _fwd_prepared_v(self, query, key, value, scale, read_list, write_list, must_do, want_lse, q_windows=None, window_hook=None,
+                        static_sched=False, **descales):
+        """The forward for a ``PreparedV``: ``mha_fwd`` directly, as ``call_windowed`` reaches it, on the PreparedV's workspace."""
+        from .flash_attn_interface import mha_fwd
+        q, k = [x if x.stride(-1) == 1 else x.contiguous() for x in (query, key)]
+        out, lse, *_ = mha_fwd(q, k, value.as_v(), softmax_scale=scale, attn_read_list=read_list, attn_must_do_list=must_do,
+                               attn_write_list=write_list, thr=self._take_threshold(read_list is not None), _must_do_is_1d=True,
+                               _q_windows=q_windows, _window_hook=window_hook, _static_sched=static_sched, _v_prepared=value,
+                               **descales)
+        return (out, lse) if want_lse else out
 
     @staticmethod
     def _check_restore(query, key, value, v_shift, lse_shift, out_dtype):
@@ -258,10 +277,16 @@ class LiteAttention:
         is enqueued — the head-sharded driver starts the xGMI all-gather of those rows there. The reference has one
         launch per call (flash_fwd_launch_template.h:359) and no such entry point."""
         from .flash_attn_interface import mha_fwd
+        tiles = not isinstance(value, Tensor)
+        if tiles:
+            value.check_call(query, key)
         read_list, write_list = self._get_read_write_lists(query, key, must_skip_list)
         must_do = None
         if read_list is not None:
             must_do = self._must_do_device_row(must_do_list, query, read_list.shape[3])
+        if tiles:
+            return self._fwd_prepared_v(query, key, value, scale, read_list, write_list, must_do, return_softmax_lse, q_windows,
+                                        window_hook, static_sched, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale)
         q, k, v = [x if x.stride(-1) == 1 else x.contiguous() for x in (query, key, value)]
         out, lse, *_ = mha_fwd(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
                                softmax_scale=scale, attn_read_list=read_list, attn_must_do_list=must_do,

@@ -353,29 +353,41 @@ class E4m3Scales:
     mode "delayed"   step t quantizes with the descale made from step t - 1's amax and collects its own amax in the same pass: one
                      read of x. The first call has no history and runs the amax pass. ``margin`` > 1 leaves headroom for the growth
                      of amax from one step to the next (what exceeds it saturates at +-448).
+    tiles=True       for a V only the attention call reads (``norm=None``, no weight, no tables, ``heads_per_scale`` 1): the quantizing
+                     pass is ``v_prep.v_prep_tiles`` and ``x8`` a ``PreparedV`` - the V^T tiles of the e4m3 forward, no e4m3 tensor.
     The buffers (amax, descale, the e4m3 result) are allocated by the first call and reused: no host sync, no allocation after
     it - the result of a call is overwritten by the next one."""
 
     _amax_pass = staticmethod(qk_prep_amax)
     _quant_pass = staticmethod(qk_prep_fp8)
 
-    def __init__(self, mode: str = "current", margin: float = 1.0, heads_per_scale: int = 1):
+    def __init__(self, mode: str = "current", margin: float = 1.0, heads_per_scale: int = 1, tiles: bool = False):
         if mode not in ("current", "delayed"):
             raise ValueError('mode: "current" or "delayed"')
         if not margin > 0:
             raise ValueError("margin must be positive")
-        self.mode, self.margin, self.heads_per_scale = mode, float(margin), int(heads_per_scale)
+        if tiles and int(heads_per_scale) != 1:
+            raise ValueError("tiles=True takes one descale per kv head (heads_per_scale 1), as the attention call does")
+        self.mode, self.margin, self.heads_per_scale, self.tiles = mode, float(margin), int(heads_per_scale), bool(tiles)
         self.amax = self.descale = self.out = None
         self.calls = 0
 
     def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0):
         B, S, H, D = x.shape
         hps = self.heads_per_scale
+        if self.tiles:
+            from . import v_prep                                     # (v_prep imports this module)
+            if norm is not None or weight is not None or tables is not None:
+                raise ValueError("tiles=True quantizes V as its projection wrote it: norm=None, no weight, no tables")
         first = self.amax is None or self.out.shape != x.shape or self.out.device != x.device
         if first:
             self.amax = torch.zeros((B, H // hps), dtype=torch.float32, device=x.device)
             self.descale = torch.empty_like(self.amax)
-            self.out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
+            if self.tiles:
+                self.out = v_prep.PreparedV(torch.empty(v_prep.v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=x.device),
+                                            x.shape, self.descale)
+            else:
+                self.out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
         if first or self.mode == "current":
             self.amax.zero_()
             self._amax_pass(x, weight, eps, tables, norm, pos_offset, amax_out=self.amax, heads_per_scale=hps)
@@ -384,8 +396,11 @@ class E4m3Scales:
         if self.mode == "delayed":                               # this step's amax, for the next step's descale
             self.amax.zero_()
             collect = self.amax
-        self._quant_pass(x, weight, eps, tables, norm, pos_offset, descale=self.descale, amax_out=collect, heads_per_scale=hps,
-                         out=self.out)
+        if self.tiles:
+            v_prep.v_prep_tiles(x, descale=self.descale, amax_out=collect, out=self.out)
+        else:
+            self._quant_pass(x, weight, eps, tables, norm, pos_offset, descale=self.descale, amax_out=collect, heads_per_scale=hps,
+                             out=self.out)
         self.calls += 1
         return self.out, self.descale
 

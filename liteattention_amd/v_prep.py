@@ -10,7 +10,11 @@ quantized as ``V - m``, the forward runs unchanged on the shifted codes, and m i
 ``v_colstats`` (``la_v_colstats`` + ``la_v_colstats_finish``) makes the mean and the exact amax of ``V - mean`` in ONE read of V;
 ``attn_unshift`` (``la_attn_unshift``) is the restoring pass, which also undoes K smoothing's shift of the LSE (``lse_unshift``, fused)
 and casts. ``v_colstats_reference`` / ``attn_unshift_reference`` are the formulas in torch fp64; ``v_shift_as_bias`` folds the shift
-into the bias of the output projection instead."""
+into the bias of the output projection instead.
+
+``v_prep_tiles`` (``la_v_prep_tiles``) is the quantizing pass for a V that only the attention call reads: it writes the e4m3 codes
+straight into the V^T tiles the e4m3 forward stages and returns a ``PreparedV``, which ``flash_attn_func`` / ``LiteAttention`` take in
+the place of ``v``; ``SmoothedV(tiles=True)`` and ``E4m3Scales(tiles=True)`` run it."""
 from __future__ import annotations
 
 import ctypes
@@ -19,7 +23,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _cabi
-from .qk_prep import _IN_DTYPES, _call, _check_x, _f32, descale_from_amax, qk_prep_smooth
+from .qk_prep import _IN_DTYPES, _call, _check_scales, _check_x, _f32, descale_from_amax, qk_prep_smooth
 
 _UNSHIFT_OUT_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}
 _UNSHIFT_IN_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16}
@@ -225,6 +229,144 @@ def v_shift_as_bias(weight: torch.Tensor, bias: Optional[torch.Tensor], shift: t
     return res if dtype is None else res.to(dtype)
 
 
+# ---- fp8 V in one pass: la_v_prep_tiles ------------------------------------------------------------------------------------------------
+TILE_HEAD_DIMS = (64, 96, 128, 192, 256)      # the head dims the e4m3 forward has kernels for: the tile layouts there are
+
+
+def v_tiles_bytes(batch: int, num_heads_k: int, seqlen_k: int, head_dim: int) -> Tuple[int, int]:
+    """``(la_v_tiles_bytes, la_v_tiles_workspace_bytes)`` of a (B, Sk, Hk, D) V: the bytes of its V^T tiles, and of the workspace (the
+    tiles, then the ticket counters) every fixed-length, unsplit e4m3 ``la_fwd`` over these keys accepts. Pure host functions."""
+    lib = _cabi.load()
+    args = (int(batch), int(num_heads_k), int(seqlen_k), int(head_dim))
+    tiles, ws = lib.la_v_tiles_bytes(*args), lib.la_v_tiles_workspace_bytes(*args)
+    if tiles < 0 or ws < 0:
+        raise ValueError(f"la_v_tiles_bytes{args}: {_cabi.status_string(int(min(tiles, ws)))}")
+    return int(tiles), int(ws)
+
+
+class PreparedV:
+    """A V that exists only as the V^T tiles of the e4m3 forward: what ``v_prep_tiles`` returns and ``flash_attn_func``,
+    ``LiteAttention.__call__`` and ``LiteAttention.call_windowed`` accept as ``v`` / ``value``.
+
+    workspace   1-D uint8, at least ``v_tiles_bytes(...)[1]`` bytes, 16-byte aligned: the tiles at its front, the forward's ticket
+                counters behind them. The attention call launches ON this buffer (LA_FLAG_V_PREPARED, no allocation of its own); it
+                belongs to whoever made it and must stay untouched until the attention calls that read it have run.
+    shape       the logical ``(B, Sk, Hk, D)``; ``device`` is the workspace's.
+    descale     the fp32 (B, Hk) descale it was quantized with (None: 1.0) - what the attention call wants as ``v_descale``."""
+
+    __slots__ = ("workspace", "shape", "descale")
+
+    def __init__(self, workspace: torch.Tensor, shape, descale: Optional[torch.Tensor] = None):
+        shape = torch.Size(int(n) for n in shape)
+        if len(shape) != 4 or min(shape) <= 0:
+            raise ValueError(f"shape must be a non-empty (B, Sk, Hk, D), got {tuple(shape)}")
+        if shape[3] not in TILE_HEAD_DIMS:
+            raise NotImplementedError(f"V^T tiles exist for head_dim {TILE_HEAD_DIMS}, got {shape[3]} (a head_dim between them runs "
+                                      "zero-padded: quantize into an e4m3 tensor instead)")
+        need = v_tiles_bytes(shape[0], shape[2], shape[1], shape[3])[1]
+        if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < need:
+            raise ValueError(f"workspace must be a contiguous 1-D uint8 tensor of at least {need} bytes, got {workspace.dtype} "
+                             f"{tuple(workspace.shape)}")
+        if workspace.data_ptr() % 16:
+            raise ValueError("workspace must start on a 16-byte boundary")
+        self.workspace, self.shape, self.descale = workspace, shape, descale
+
+    @property
+    def device(self) -> torch.device:
+        return self.workspace.device
+
+    def as_v(self) -> torch.Tensor:
+        """An e4m3 (B, Sk, Hk, D) view of the front of the workspace: a buffer that passes the checks ``la_fwd`` makes of ``v`` (under
+        LA_FLAG_V_PREPARED it is never read). Its bytes are tile bytes, NOT the codes in this order."""
+        B, S, H, D = self.shape
+        return self.workspace[: B * S * H * D].view(torch.float8_e4m3fn).view(B, S, H, D)
+
+    def check_call(self, q, k, cu_seqlens_q=None, cu_seqlens_k=None, num_splits: int = 1):
+        """Refuse, before anything is launched, the attention calls this V has no form for. Needs no device."""
+        if cu_seqlens_q is not None or cu_seqlens_k is not None or q.dim() != 4 or k.dim() != 4:
+            raise NotImplementedError("a PreparedV serves fixed-length (B, S, H, D) calls only: the tiles of a packed variable-length "
+                                      "batch are laid out by its cu_seqlens")
+        if q.dtype != torch.float8_e4m3fn or k.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"a PreparedV holds e4m3 tiles: q and k must be float8_e4m3fn, got {q.dtype} and {k.dtype}")
+        if num_splits not in (0, 1):
+            raise NotImplementedError("split-KV (num_splits > 1, or the host's choice -1) cuts the e4m3 V by rows, and a PreparedV has "
+                                      "no such tensor")
+        B, Sk, Hk, D = self.shape
+        if tuple(k.shape) != (B, Sk, Hk, D) or q.shape[0] != B or q.shape[3] != D:
+            raise ValueError(f"the PreparedV was made for k (B, Sk, Hk, D) = {(B, Sk, Hk, D)} and q (B, *, *, {D}), got k "
+                             f"{tuple(k.shape)} and q {tuple(q.shape)}")
+        if q.device != self.device or k.device != self.device:
+            raise ValueError(f"the PreparedV lives on {self.device}, q on {q.device}, k on {k.device}")
+
+
+def v_prep_tiles(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                 amax_out: Optional[torch.Tensor] = None, out=None) -> PreparedV:
+    """Quantize ``x`` (B, Sk, Hk, D) bf16 / fp16 / fp32 straight into the V^T tiles of the e4m3 forward (``la_v_prep_tiles``): one read
+    of ``x``, one write of the tiles - the e4m3 (B, Sk, Hk, D) tensor of ``qk_prep_smooth(x, norm=None, ...)`` and the prepare pass the
+    attention call runs over it drop out. Every code is the byte that pass would store:
+
+        code = e4m3(clamp((float(x) - shift[b, h]) / descale[b, h], -448, 448))
+
+    descale    fp32 (B, Hk); None: 1.0.       shift   fp32 (B, Hk, D), last dimension contiguous; None: none.
+    amax_out   fp32 (B, Hk), ACCUMULATED as in ``qk_prep_fp8``: the running maximum of ``|x - shift|`` (zero it for this call's).
+    out        a ``PreparedV`` of this shape, or its 1-D uint8 workspace (at least ``v_tiles_bytes(B, Hk, Sk, D)[1]`` bytes, 16-byte
+               aligned), to write into; None: allocated.
+    ``x`` may be any view whose last dimension is contiguous and whose rows, heads and batches start on 16-byte boundaries (the V
+    slice of a fused projection); head_dim 64, 96, 128, 192 or 256. No host sync; with ``out`` given, no allocation; captures into
+    a HIP graph; two calls write the same bytes."""
+    _check_x(x, "v_prep_tiles_reference")
+    if x.stride(-1) != 1:
+        raise ValueError("the last dimension of x must be contiguous")
+    B, S, H, D = x.shape
+    if B * S * H * D == 0:
+        raise ValueError(f"x must not be empty, got {tuple(x.shape)}")
+    _check_scales(x, 1, descale, amax_out)
+    if shift is not None:
+        _f32("shift", shift, (B, H, D), x.device)
+        if shift.stride(2) != 1:
+            raise ValueError("the last dimension of shift must be contiguous")
+    if isinstance(out, PreparedV):
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError(f"out was made for {tuple(out.shape)} on {out.device}, x is {tuple(x.shape)} on {x.device}")
+        out.descale = descale
+        pv = out
+    else:
+        if out is None:
+            out = torch.empty(v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=x.device)
+        elif out.device != x.device:
+            raise ValueError(f"out lives on {out.device}, x on {x.device}")
+        pv = PreparedV(out, x.shape, descale)
+    a = _cabi.LaVPrepTilesArgs()
+    a.struct_size = ctypes.sizeof(_cabi.LaVPrepTilesArgs)
+    a.in_dtype = _IN_DTYPES[x.dtype]
+    a.x, a.tiles = x.data_ptr(), pv.workspace.data_ptr()
+    a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    if descale is not None:
+        a.descale, a.descale_batch_stride, a.descale_head_stride = descale.data_ptr(), descale.stride(0), descale.stride(1)
+    if shift is not None:
+        a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
+    if amax_out is not None:
+        a.amax, a.amax_batch_stride, a.amax_head_stride = amax_out.data_ptr(), amax_out.stride(0), amax_out.stride(1)
+    _call("la_v_prep_tiles", x, lambda: f"x {tuple(x.shape)} strides {x.stride()}, shift "
+                                        f"{None if shift is None else shift.stride()}", ctypes.byref(a))
+    return pv
+
+
+def v_prep_tiles_reference(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None,
+                           shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The e4m3 codes ``v_prep_tiles`` puts into the tiles, in (B, Sk, Hk, D) order, by the same fp32 steps in torch on whatever device
+    ``x`` lives on: one subtraction, one multiplication by the fp32 ``1 / descale``, the clamp, torch's round-to-nearest-even cast."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
+    y = x.float()
+    if shift is not None:
+        y = y - shift.to(y.device)[:, None]
+    if descale is not None:
+        y = y * (1.0 / descale.to(y.device))[:, None, :, None]
+    return y.clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+
+
 class SmoothedV:
     """The buffers of one layer's V across calls, mean-shifted before it is quantized: ``v8, dv, shift = sv(xv)`` - ``v8`` e4m3 of
     ``xv - shift``, ``dv`` its descale for the attention call, ``shift`` fp32 (B, H_kv, D) - and ``sv.finish(o, ...)`` adds the shift
@@ -235,22 +377,27 @@ class SmoothedV:
     mode "delayed"   step t quantizes with step t - 1's mean and descale and runs ``v_colstats`` on the same input for step t + 1. ANY
                      shift is exact, so a stale mean costs range only (what outgrows ``margin`` saturates at +-448), as ``SmoothedQK``
                      documents. The first call has no history and runs as "current".
+    tiles=True       the quantizing pass is ``v_prep_tiles``: ``v8`` is a ``PreparedV`` (the V^T tiles of the e4m3 forward, no e4m3
+                     tensor), which the attention call takes as ``v``. Head_dim 64, 96, 128, 192 or 256.
     Buffers are allocated by the first call and reused: no host sync, no allocation after it; a call overwrites the last results,
     ``shift`` included - call ``finish`` before the next ``sv(xv)``."""
 
-    def __init__(self, mode: str = "current", margin: float = 1.0):
+    def __init__(self, mode: str = "current", margin: float = 1.0, tiles: bool = False):
         if mode not in ("current", "delayed"):
             raise ValueError('mode: "current" or "delayed"')
         if not margin > 0:
             raise ValueError("margin must be positive")
-        self.mode, self.margin = mode, float(margin)
+        self.mode, self.margin, self.tiles = mode, float(margin), bool(tiles)
         self.v8 = self.shift = self.out = None
         self.calls = 0
 
     def _allocate(self, xv):
         B, S, H, D = xv.shape
         f32 = dict(dtype=torch.float32, device=xv.device)
-        self.v8 = torch.empty(xv.shape, dtype=torch.float8_e4m3fn, device=xv.device)
+        if self.tiles:
+            self.v8 = PreparedV(torch.empty(v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=xv.device), xv.shape)
+        else:
+            self.v8 = torch.empty(xv.shape, dtype=torch.float8_e4m3fn, device=xv.device)
         self.part = torch.empty((v_colstats_parts(S, H, D)[0], 3, B, H, D), **f32)
         self.shift, self.amax, self.dv = torch.empty((B, H, D), **f32), torch.empty((B, H), **f32), torch.empty((B, H), **f32)
         if self.mode == "delayed":                               # this step's statistics, for the next step
@@ -271,7 +418,10 @@ class SmoothedV:
             self.shift.copy_(self.next_mean)
             self.amax.copy_(self.next_amax)
         descale_from_amax(self.amax, self.margin, out=self.dv)
-        qk_prep_smooth(xv, norm=None, shift=self.shift, descale=self.dv, out=self.v8)
+        if self.tiles:
+            v_prep_tiles(xv, shift=self.shift, descale=self.dv, out=self.v8)
+        else:
+            qk_prep_smooth(xv, norm=None, shift=self.shift, descale=self.dv, out=self.v8)
         if self.mode == "delayed":
             v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax)
         self.calls += 1
@@ -296,13 +446,26 @@ class SmoothedV:
                             lse_out=lse if lse_dot is not None else None)
 
 
-# ---- op registration: torch.ops.lite_attention.v_colstats / attn_unshift, beside qk_prep_smooth ------------------------------------------
+# ---- op registration: torch.ops.lite_attention.v_colstats / attn_unshift / v_prep_tiles, beside qk_prep_smooth ------------------------------------------
 _V_COLSTATS_SCHEMA = ("v_colstats(Tensor x, Tensor(part!)? stat_part = None, Tensor(mean!)? mean_out = None, "
                       "Tensor(amax!)? amax_out = None) -> (Tensor(mean!), Tensor(amax!))")
 _ATTN_UNSHIFT_SCHEMA = ("attn_unshift(Tensor o, Tensor? shift = None, Tensor? lse = None, Tensor? lse_dot = None, "
                         "float? softmax_scale = None, Tensor(out!)? out = None, ScalarType? out_dtype = None, "
                         "Tensor(lse_out!)? lse_out = None) -> Tensor(out!)")
+_V_PREP_TILES_SCHEMA = ("v_prep_tiles(Tensor x, Tensor? descale = None, Tensor? shift = None, Tensor(amax!)? amax_out = None, "
+                        "Tensor(out!)? out = None) -> Tensor(out!)")
 _op_lib = None
+
+
+def _v_prep_tiles_op(x, descale=None, shift=None, amax_out=None, out=None):
+    """The op speaks tensors: ``out`` and the result are the uint8 workspace (``PreparedV(result, x.shape, descale)`` wraps it)."""
+    return v_prep_tiles(x, descale=descale, shift=shift, amax_out=amax_out, out=out).workspace
+
+
+def _v_prep_tiles_meta(x, descale=None, shift=None, amax_out=None, out=None):
+    """Shape and dtype only."""
+    B, S, H, D = x.shape
+    return out if out is not None else torch.empty(v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=x.device)
 
 
 def _v_colstats_op(x, stat_part=None, mean_out=None, amax_out=None):
@@ -341,6 +504,9 @@ def _register_op():
     lib.define(_ATTN_UNSHIFT_SCHEMA)
     lib.impl("attn_unshift", _attn_unshift_op, "CUDA")
     lib.impl("attn_unshift", _attn_unshift_meta, "Meta")
+    lib.define(_V_PREP_TILES_SCHEMA)
+    lib.impl("v_prep_tiles", _v_prep_tiles_op, "CUDA")
+    lib.impl("v_prep_tiles", _v_prep_tiles_meta, "Meta")
     _op_lib = lib
 
 
