@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes and la_v_tiles_workspace_bytes were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr and la_skip_list_stats_heads were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -255,6 +255,23 @@ int64_t la_fwd_workspace_bytes(const la_fwd_args* args);
 /* The forward pass. `stream` is a hipStream_t. */
 int la_fwd(const la_fwd_args* args, void* stream);
 
+/* la_fwd with one vote threshold per (batch, QUERY head) instead of the scalar args->thr (added under ABI 9: la_fwd_args is unchanged, a
+ * host detects the entry by symbol). Heads are independent in attention: o, lse and the written lists of head h depend on head h's
+ * threshold alone, and are bit for bit what la_fwd gives with that value as args->thr.
+ *   thr_head == NULL   la_fwd(args, stream) exactly; the strides are not looked at.
+ *   otherwise          the item of (b, h) votes with thr_head[b * thr_batch_stride + h * thr_head_stride] (log2 domain, as args->thr), and
+ *                      args->thr is not read. thr_head is a DEVICE fp32 array owned by the caller, read by the kernels while the launch
+ *                      runs (one load per work item): it may be rewritten between launches on the stream - or between replays of a
+ *                      captured graph - without another host call. Strides are in ELEMENTS; thr_batch_stride = 0 gives one row for all
+ *                      batches. h is the query head (the lists are per query head, also under GQA / MQA); b is the batch index, or the
+ *                      sequence index of a packed batch (cu_seqlens). Every route of la_fwd with lists takes it: all kernels and dtypes,
+ *                      both schedulers, q-tile windows, LA_FLAG_HALF_VOTE, LA_FLAG_LIST_INT16, LA_FLAG_V_PREPARED.
+ * Special values are the scalar's: -inf flags nothing (every walked tile stays listed); NaN is the caller's error and is NOT detected.
+ * Errors: every check of la_fwd, in its order and codes; then, still before any launch: a table on a dense launch (read_list == NULL)
+ * LA_ERR_LISTS; a negative stride or a thr_head off a 4-byte boundary LA_ERR_STRIDE. NOT detected: a table shorter than its strides
+ * and (batch, num_heads) address. */
+int la_fwd_head_thr(const la_fwd_args* args, const float* thr_head, int64_t thr_batch_stride, int64_t thr_head_stride, void* stream);
+
 /* Counts listed (= to be computed) tiles of a skip list on the device:
  *   out_counts[0] = sum over rows of sum over ranges (start - end + 1), rows = n_batch*H*Qt
  *   out_counts[1] = number of rows
@@ -266,6 +283,14 @@ int la_skip_list_stats(const int32_t* list, int32_t n_batch, int32_t num_heads, 
  * LA_FLAG_LIST_INT16). Other element sizes: LA_ERR_DTYPE; element size 2 with k_tiles + 1 > 32767: LA_ERR_SEQLEN. */
 int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles,
                           int32_t k_tiles, int64_t* out_counts, void* stream);
+
+/* The listed tiles per (batch, head): out_counts is a device int64 [n_batch, num_heads] contiguous, out_counts[b][h] = the sum over the
+ * q_tiles rows of that head of sum over ranges (start - end + 1), with the row rule of la_skip_list_stats_ex (a row length below 2
+ * counts as 2, one above k_tiles is clamped, a negative span counts 0). The rows per head are q_tiles for all of them. One workgroup per
+ * (b, h), a fixed-order reduction: no atomics, no memset, EVERY element is written and two launches agree bit for bit. The sum over
+ * (b, h) is la_skip_list_stats_ex's out_counts[0]. Errors: those of la_skip_list_stats_ex. */
+int la_skip_list_stats_heads(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles,
+                             int32_t k_tiles, int64_t* out_counts, void* stream);
 
 /* LSE-weighted merge of `num_splits` partial attention results (sequence-parallel K/V splits):
  *   o_partial   [num_splits, B, Sq, H, Dv] contiguous: fp32, or (partial_is_16bit != 0) the element type of o

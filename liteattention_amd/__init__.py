@@ -17,11 +17,12 @@ if not _BUILDING:
 
 if not _BUILDING:
     from .flash_attn_interface import (combine_partials, flash_attn_combine, flash_attn_func, get_tile_sizes,  # noqa: E402
-                                       skip_list_stats)
+                                       skip_list_stats, skip_list_stats_heads)
     from .lite_attention import LiteAttention, SeqParallelLiteAttention  # noqa: E402
     from .compat import (blockmask_to_skip_lists, fa2_flash_attn_func, flash_attn_varlen_func,  # noqa: E402
                          flash_blocksparse_attn_func, flash_blocksparse_attn_qkvpacked_func)
-    from .calibration import ErrorStats, calibrate_error_schedule, calibrate_threshold, output_error  # noqa: E402
+    from .calibration import (ErrorStats, calibrate_error_schedule, calibrate_head_thresholds, calibrate_threshold,  # noqa: E402
+                              output_error)
     from .qk_prep import RopeTables, qk_prep, qk_prep_reference, rope_tables, wan_rope_parts  # noqa: E402
     from .qk_prep import E4m3Scales, descale_from_amax, qk_prep_amax, qk_prep_fp8, qk_prep_fp8_reference  # noqa: E402
     from .qk_prep import (SmoothedQK, colsum_finish, lse_unshift, qk_prep_colmean, qk_prep_smooth, qk_prep_smooth_parts,  # noqa: E402
@@ -35,7 +36,7 @@ if not _BUILDING:
 __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flash_attn_combine", "combine_partials",
            "get_tile_sizes", "skip_list_stats", "fa2_flash_attn_func", "flash_attn_varlen_func",
            "flash_blocksparse_attn_func", "flash_blocksparse_attn_qkvpacked_func", "blockmask_to_skip_lists", "calibrate_threshold",
-           "calibrate_error_schedule", "output_error", "ErrorStats",
+           "calibrate_error_schedule", "output_error", "ErrorStats", "skip_list_stats_heads", "calibrate_head_thresholds",
            "qk_prep", "qk_prep_reference", "rope_tables", "wan_rope_parts", "RopeTables",
            "qk_prep_fp8", "qk_prep_amax", "descale_from_amax", "qk_prep_fp8_reference", "E4m3Scales",
            "qk_prep_smooth", "qk_prep_colmean", "colsum_finish", "qk_prep_smooth_parts", "qk_prep_smooth_reference", "lse_unshift", "SmoothedQK",

@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "la_skip_list_stats_ex", "la_blockmask_to_lists_ex", "la_output_error", "la_qk_prep", "la_qk_prep_fp8",
     "la_qk_prep_smooth", "la_qk_prep_smooth_parts", "la_qk_prep_smooth_part_rows", "la_colsum_finish",
     "la_v_colstats", "la_v_colstats_parts", "la_v_colstats_part_rows", "la_v_colstats_finish", "la_attn_unshift",
-    "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes",
+    "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes", "la_fwd_head_thr", "la_skip_list_stats_heads",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -227,6 +227,11 @@ def load() -> ctypes.CDLL:
     lib.la_get_tile_sizes_ex.restype = ctypes.c_int
     lib.la_fwd.argtypes = [ctypes.POINTER(LaFwdArgs), ctypes.c_void_p]
     lib.la_fwd.restype = ctypes.c_int
+    lib.la_fwd_head_thr.argtypes = [ctypes.POINTER(LaFwdArgs), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+    lib.la_fwd_head_thr.restype = ctypes.c_int
+    lib.la_skip_list_stats_heads.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.la_skip_list_stats_heads.restype = ctypes.c_int
     lib.la_fwd_workspace_bytes.argtypes = [ctypes.POINTER(LaFwdArgs)]
     lib.la_fwd_workspace_bytes.restype = ctypes.c_int64
     lib.la_skip_list_stats.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -131,7 +131,9 @@ class LiteAttentionBackend:
     """What ``calibrate_error_schedule`` drives: one ``LiteAttention`` on the inputs of ``qkv_at(t)``, errors from ``output_error``.
     A backend offers ``reset()``, ``snapshot()``, ``restore(snap)``, ``step(t, thr) -> out``, ``dense(t) -> out``,
     ``error(out, ref) -> float`` and ``skip_fraction()`` (of the list the next step reads); a CPU stand-in built on the oracle
-    offers the same seven."""
+    offers the same seven. ``calibrate_head_thresholds`` needs two more of its backend: ``step(t, thr)`` with an ``(H,)`` tensor of
+    thresholds, one per head, and ``error_heads(out, ref) -> (H,)`` tensor (the worst batch entry of every head);
+    ``skip_fraction_heads() -> (H,)`` is used for the trace when a backend has it."""
 
     def __init__(self, qkv_at: Callable[[int], Tuple[torch.Tensor, torch.Tensor, torch.Tensor]], metric: str = "rel_l1",
                  reduce: str = "max", max_batch_size: int = 1, list_dtype: Optional[torch.dtype] = None):
@@ -151,8 +153,11 @@ class LiteAttentionBackend:
     def restore(self, snap):
         self.att.restore(snap)
 
-    def step(self, t: int, thr: float) -> torch.Tensor:
-        self.att.set_threshold(thr)
+    def step(self, t: int, thr) -> torch.Tensor:
+        if isinstance(thr, torch.Tensor):          # (H,): one threshold per head (a device tensor is taken as it is: no sync)
+            self.att.set_head_thresholds(thr)
+        else:
+            self.att.set_threshold(thr)
         return self.att(*self.qkv_at(t))
 
     def dense(self, t: int) -> torch.Tensor:
@@ -163,8 +168,17 @@ class LiteAttentionBackend:
         per_head = getattr(output_error(out, ref), self.metric)
         return float(per_head.max() if self.reduce == "max" else per_head.mean())
 
+    def error_heads(self, out: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+        """``(H,)`` on the device: the metric per head, the worst entry of the batch. No synchronisation."""
+        return getattr(output_error(out, ref), self.metric).amax(dim=0)
+
     def skip_fraction(self) -> float:
         return self.att.get_skip_fraction()
+
+    def skip_fraction_heads(self) -> Optional[torch.Tensor]:
+        """``(H,)`` on the device: the skipped fraction of the list the next step reads, per head over the batch. No synchronisation."""
+        frac = self.att.get_skip_fraction_heads()
+        return None if frac is None else frac.mean(dim=0)
 
 
 def calibrate_error_schedule(qkv_at, n_steps: int, bounds: Sequence[float], metric: str = "rel_l1", reduce: str = "max",
@@ -226,3 +240,73 @@ def calibrate_error_schedule(qkv_at, n_steps: int, bounds: Sequence[float], metr
     thresholds.append(thresholds[-1])
     trace.append(dict(threshold=thresholds[-1], error=err_t, bound=float(bounds[t]), bound_met=err_t <= float(bounds[t]), skip_fraction=skip_t))
     return thresholds, trace
+
+
+def calibrate_head_thresholds(qkv_at, n_steps: int, bounds, metric: str = "rel_l1", lo: float = -20.0, hi: float = -1e-3,
+                              iters: int = 8, max_batch_size: int = 1, backend=None) -> Tuple[torch.Tensor, List[dict]]:
+    """``calibrate_error_schedule`` with one threshold per (step, head) instead of one per step: a table for
+    ``LiteAttention.set_head_thresholds``. Heads are independent in attention - output, LSE and lists of head h depend on head h's
+    threshold alone - so the greedy bisection of ``calibrate_error_schedule`` runs for all heads at once, at its launch count: for
+    step t, ``a``, ``b`` and ``best`` are ``(H,)`` tensors on the device, a probe restores the snapshot taken before step t, runs step
+    t with the vector of midpoints, runs step t + 1 and takes the error of every head against dense(t + 1) (``metric``: rel_l1, rel_l2
+    or max_abs; the worst entry of the batch); the three tensors move by ``torch.where``, so nothing inside the loop synchronises
+    with the host. Step t is committed, per head, at the HIGHEST PROBED value that met ``bounds[t + 1][h]`` - a point of the
+    depth-``iters`` dyadic grid of [lo, hi), kept in fp64 and rounded to fp32 once - else at ``lo``. ``bounds``: one value per
+    step, or ``(n_steps, H)``. The last row repeats the one before it (its list is never read).
+
+    Returns ``(table, trace)``: ``table`` fp32 ``(n_steps, H)`` on the device; ``trace[t]``: ``(H,)`` device tensors ``threshold``,
+    ``error`` (of the committed run of step t against dense(t)), ``bound``, ``bound_met`` (error <= bound) and ``skip_fraction`` (of
+    the list step t read). ``backend``: see ``LiteAttentionBackend`` (the default, built from ``qkv_at``)."""
+    if n_steps < 2:
+        raise ValueError("a table needs at least two steps (the thresholds of a step shape the lists the NEXT one reads)")
+    if not lo < hi:
+        raise ValueError("lo must be below hi")
+    be = LiteAttentionBackend(qkv_at, metric, "max", max_batch_size) if backend is None else backend
+    be.reset()
+    dense_t = be.dense(0)
+    H, dev = dense_t.shape[2], dense_t.device
+    bnd = torch.as_tensor(bounds, dtype=torch.float64, device=dev)
+    if bnd.dim() == 1:
+        bnd = bnd[:, None].expand(-1, H)
+    if tuple(bnd.shape) != (n_steps, H):
+        raise ValueError(f"bounds: one value per step or (n_steps, H) = ({n_steps}, {H}); got {tuple(bnd.shape)}")
+    skip_heads = getattr(be, "skip_fraction_heads", None)
+
+    def skipped():
+        frac = None if skip_heads is None else skip_heads()
+        return torch.zeros(H, dtype=torch.float32, device=dev) if frac is None else frac
+
+    def entry(thr32, out, dense, t, skip):
+        err = be.error_heads(out, dense).to(torch.float64)
+        return dict(threshold=thr32, error=err, bound=bnd[t], bound_met=err <= bnd[t], skip_fraction=skip)
+
+    rows: List[torch.Tensor] = []
+    trace: List[dict] = []
+    for t in range(n_steps - 1):
+        snap = be.snapshot()
+        skip_t = skipped()
+        dense_next = be.dense(t + 1)
+        a = torch.full((H,), float(lo), dtype=torch.float64, device=dev)
+        b = torch.full((H,), float(hi), dtype=torch.float64, device=dev)
+        best = a.clone()               # kept where no probe met the bound, whether lo meets it or not: the committed run measures it
+        for _ in range(iters):
+            mid = 0.5 * (a + b)
+            mid32 = mid.to(torch.float32)
+            be.restore(snap)
+            be.step(t, mid32)
+            ok = be.error_heads(be.step(t + 1, mid32), dense_next).to(torch.float64) <= bnd[t + 1]
+            best = torch.where(ok, mid, best)
+            a = torch.where(ok, mid, a)
+            b = torch.where(ok, b, mid)
+        row = best.to(torch.float32)
+        be.restore(snap)
+        out_t = be.step(t, row)
+        rows.append(row)
+        trace.append(entry(row, out_t, dense_t, t, skip_t))
+        dense_t = dense_next
+        del out_t
+    t = n_steps - 1
+    skip_t = skipped()
+    rows.append(rows[-1])
+    trace.append(entry(rows[-1], be.step(t, rows[-1]), dense_t, t, skip_t))
+    return torch.stack(rows), trace

@@ -171,9 +171,17 @@ int64_t la_fwd_workspace_bytes(const la_fwd_args* a) {
     return static_cast<int64_t>(la::fp8_workspace_bytes(a->batch, a->num_heads_k, k_tiles, a->head_dim) + kSchedWorkspaceBytes);
 }
 
-int la_fwd(const la_fwd_args* a, void* stream_) {
+// la_fwd (thr_head == nullptr) and la_fwd_head_thr: one body, so both make the same checks in the same order and fill the same block.
+// The table's own checks follow the last of la_fwd's on every path, before the first launch of that path.
+static int fwd_run(const la_fwd_args* a, const float* thr_head, int64_t thr_bs, int64_t thr_hs, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (a == nullptr) return LA_ERR_NULL_ARG;
+    const auto table_status = [&]() -> int {
+        if (thr_head == nullptr) return LA_OK;
+        if (a->read_list == nullptr) return LA_ERR_LISTS;                                // a dense launch votes on nothing
+        if (thr_bs < 0 || thr_hs < 0 || (reinterpret_cast<uintptr_t>(thr_head) & 3u) != 0) return LA_ERR_STRIDE;
+        return LA_OK;
+    };
     if (a->struct_size != sizeof(la_fwd_args)) return LA_ERR_STRUCT_SIZE;
     if (a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16 && a->dtype != LA_DTYPE_FP8_E4M3) return LA_ERR_DTYPE;   // flash_api.cpp:715
     const bool fp8 = a->dtype == LA_DTYPE_FP8_E4M3;
@@ -222,6 +230,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     if (a->seqlen_k == 0) {
         // flash_api.cpp:1241-1245: no keys -> out = 0, lse = +inf (the write list, if any, is left as it is: nothing was
         // walked). Varlen reaches here only when EVERY sequence is empty (seqlen_k is the maximum); rows then are total_q.
+        if (const int trc0 = table_status(); trc0 != LA_OK) return trc0;
         const hipError_t e0 = varlen
             ? la::launch_empty_k_fill(static_cast<uint16_t*>(a->o), nullptr, 0, a->o_row_stride, a->o_head_stride, 1,
                                       static_cast<int>(a->total_q), a->num_heads, a->head_dim_v, stream)
@@ -287,6 +296,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
     // each exp2 is exactly 1, while c = 0 makes NaN of the -inf of a masked key and of an empty running maximum (-inf * 0) and inf of tau / c
     if (p.scale_log2 == 0.0f) p.scale_log2 = 0x1p-100f;
     p.thr = a->thr;                                                                      // flash_api.cpp:930
+    if (thr_head != nullptr && a->read_list != nullptr) { p.thr_head = thr_head; p.thr_bs = thr_bs; p.thr_hs = thr_hs; }   // (the dense runs below never see a table)
     p.rescale_tau = (a->flags & LA_FLAG_EXACT_RESCALE) ? 0.0f : kRescaleTauBf16;
     p.cu_seqlens_q = a->cu_seqlens_q; p.cu_seqlens_k = a->cu_seqlens_k; p.total_q = a->total_q;
     p.read_list = a->read_list;
@@ -308,6 +318,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
             // lists keep the bound; a dense launch is cut into runs of tiles that fit, as for bf16 / fp16 below: per run the V^T prepare pass of
             // ITS keys into the one tile region (the runs follow each other on the stream), the forward on bf16 partial O / LSE, then the merge
             if (!f8_split || p.q_tile_count != p.q_tiles || (a->flags & LA_FLAG_V_PREPARED)) return LA_ERR_SEQLEN;
+            if (const int trc1 = table_status(); trc1 != LA_OK) return trc1;
             unsigned char* const ws = static_cast<unsigned char*>(a->workspace);
             uint16_t* const o_part = reinterpret_cast<uint16_t*>(ws + f8_tiles + kSchedWorkspaceBytes);
             float* const lse_part = reinterpret_cast<float*>(ws + f8_tiles + kSchedWorkspaceBytes + f8d.n * f8d.o_bytes);
@@ -333,6 +344,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
                                        p.o_batch_stride, p.o_row_stride, p.o_head_stride);
             return launch_status(e);
         }
+        if (const int trc2 = table_status(); trc2 != LA_OK) return trc2;
         // 1) V -> pre-transposed, pre-swizzled V^T tiles in the caller's workspace; 2) forward on (Q, K, V^T)
         hipError_t e8 = hipSuccess;
         if (!(a->flags & LA_FLAG_V_PREPARED))
@@ -359,6 +371,7 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
         const DenseSplit d = dense_split(p.k_tiles, a->head_dim, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v);
         if (a->workspace == nullptr || !aligned16(a->workspace) || a->workspace_bytes < kSchedWorkspaceBytes + d.n * (d.o_bytes + d.lse_bytes))
             return LA_ERR_SEQLEN;
+        if (const int trc3 = table_status(); trc3 != LA_OK) return trc3;
         unsigned char* const ws = static_cast<unsigned char*>(a->workspace);
         uint16_t* const o_part = reinterpret_cast<uint16_t*>(ws + kSchedWorkspaceBytes);
         float* const lse_part = reinterpret_cast<float*>(ws + kSchedWorkspaceBytes + d.n * d.o_bytes);
@@ -378,12 +391,17 @@ int la_fwd(const la_fwd_args* a, void* stream_) {
         }
         err = la::launch_combine(o_part, true, f16, lse_part, p.o, a->lse, d.n, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v, stream, false,
                                  p.o_batch_stride, p.o_row_stride, p.o_head_stride);
-    } else if (x64) {
-        err = la::launch_fwd_x64(p, a->head_dim, skipable, f16, stream);
     } else {
-        err = la::launch_fwd_bf16_v2(p, a->head_dim, skipable, f16, stream);
+        if (const int trc4 = table_status(); trc4 != LA_OK) return trc4;
+        err = x64 ? la::launch_fwd_x64(p, a->head_dim, skipable, f16, stream) : la::launch_fwd_bf16_v2(p, a->head_dim, skipable, f16, stream);
     }
     return launch_status(err);
+}
+
+int la_fwd(const la_fwd_args* a, void* stream_) { return fwd_run(a, nullptr, 0, 0, stream_); }
+
+int la_fwd_head_thr(const la_fwd_args* a, const float* thr_head, int64_t thr_batch_stride, int64_t thr_head_stride, void* stream_) {
+    return fwd_run(a, thr_head, thr_batch_stride, thr_head_stride, stream_);
 }
 
 int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
@@ -396,6 +414,18 @@ int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_ba
     if (rows > 0x7fffffffLL) return LA_ERR_SHAPE;
     const hipError_t err = la::launch_skip_list_stats(list, list_elem_size, static_cast<int>(rows), k_tiles, out_counts,
                                                       static_cast<hipStream_t>(stream_));
+    return launch_status(err);
+}
+
+int la_skip_list_stats_heads(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
+                             int64_t* out_counts, void* stream_) {
+    if (!list || !out_counts) return LA_ERR_NULL_ARG;
+    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
+    if (n_batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
+    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    if (static_cast<int64_t>(n_batch) * num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
+    const hipError_t err = la::launch_skip_list_stats_heads(list, list_elem_size, n_batch * num_heads, q_tiles, k_tiles, out_counts,
+                                                            static_cast<hipStream_t>(stream_));
     return launch_status(err);
 }
 

@@ -60,6 +60,43 @@ hipError_t launch_skip_list_stats(const void* list, int list_elem_size, int rows
     return hipGetLastError();
 }
 
+// la_skip_list_stats_heads: the same count per (batch, head). One workgroup per (b, h); its four waves stride over that head's q_tiles
+// rows with the row rule of skip_list_stats_kernel, lanes over the ranges of a row. Every partial is an integer, and the reduction is
+// a fixed shuffle tree per wave and four LDS words added in wave order: no atomics, no memset, out[bh] is written by every workgroup.
+template <typename ListT>
+__global__ void __launch_bounds__(256) skip_list_stats_heads_kernel(const ListT* __restrict__ list, int q_tiles, int k_tiles,
+                                                                     unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long part[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const ListT* const head = list + static_cast<int64_t>(blockIdx.x) * q_tiles * (k_tiles + 1);
+    unsigned long long acc = 0;
+    for (int r = wave; r < q_tiles; r += 4) {
+        const ListT* row = head + static_cast<int64_t>(r) * (k_tiles + 1);
+        int len = row[0];
+        if (len < 2) len = 2;
+        if (len > k_tiles) len = k_tiles;
+        for (int i = 1 + 2 * lane; i + 1 <= len; i += 128) {
+            const int d = row[i] - row[i + 1] + 1;
+            acc += d > 0 ? d : 0;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+hipError_t launch_skip_list_stats_heads(const void* list, int list_elem_size, int heads, int q_tiles, int k_tiles, int64_t* out, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (list_elem_size == 2)
+        hipLaunchKernelGGL(skip_list_stats_heads_kernel<int16_t>, dim3(heads), dim3(256), 0, stream, static_cast<const int16_t*>(list), q_tiles,
+                           k_tiles, reinterpret_cast<unsigned long long*>(out));
+    else
+        hipLaunchKernelGGL(skip_list_stats_heads_kernel<int32_t>, dim3(heads), dim3(256), 0, stream, static_cast<const int32_t*>(list), q_tiles,
+                           k_tiles, reinterpret_cast<unsigned long long*>(out));
+    return hipGetLastError();
+}
+
 // One wave per (batch, head, q-tile) row. Position j of the descending walk is tile kt-1-j; a kept run [start .. end] (start >= end)
 // becomes the pair (start, end) of the row, runs in descending order: row = [2 * runs, start0, end0, start1, end1, ..., 0 ...].
 // HBM-bound byte work: kt mask bytes in, kt+1 ints out. A lane's position starts a run when it is kept and position j-1 is not, ends

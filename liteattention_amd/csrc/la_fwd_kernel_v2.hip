@@ -242,7 +242,7 @@ la_fwd_v2_kernel(const FwdParams p) {                   // F16 selects fp16 inst
                    (((4 * db + 2 * ((lane >> 4) & 1) + ((a16 & 3) >> 1)) ^ v_swz<D>(v_key0)) << 4) + 8 * (a16 & 1);
 
     const float c = p.scale_log2;
-    const float thr = p.thr;
+    const float thr = SKIPABLE ? item_thr(p, b, h) : p.thr;
     const int tail_valid = seqlen_k - (k_tiles - 1) * BN;   // valid keys in tile k_tiles-1 (1..64)
     unsigned domask = 1u;                                     // wave-uniform "do" bits of 32 consecutive positions; position 0 is never flagged
     float l_run = 0.f;

@@ -48,9 +48,17 @@ struct FwdParams {
     // then the MAXIMA over the batch, lse is (H, total_q). nullptr = fixed length.
     const int* cu_seqlens_q;
     const int* cu_seqlens_k;
+    // la_fwd_head_thr: the vote threshold of the item of (batch or packed sequence b, QUERY head h) is thr_head[b * thr_bs + h * thr_hs] and thr
+    // above is not read; nullptr (la_fwd, and every dense launch) = thr for all. Device fp32, strides in elements.
+    const float* thr_head;
+    int64_t thr_bs, thr_hs;
     int64_t total_q;
     int list_int16;         // 1 = read_list / write_list hold int16_t (wave-uniform: the shells pick the element type of the list readers / writers by it)
 };
+// The threshold the item of (b, h) votes with: one wave-uniform load per item, taken before the item's parameter block is filled.
+__device__ __forceinline__ float item_thr(const FwdParams& p, int b, int h) {
+    return p.thr_head != nullptr ? p.thr_head[b * p.thr_bs + h * p.thr_hs] : p.thr;
+}
 
 // Varlen launches (la_fwd_args.cu_seqlens_*): sequence b's own rows and lengths.
 struct SeqView {
@@ -109,6 +117,7 @@ hipError_t launch_v_prep_tiles(const VPrepTilesParams& p, int in_dtype, hipStrea
 hipError_t launch_empty_k_fill(uint16_t* o, float* lse, int64_t o_batch_stride, int64_t o_row_stride, int64_t o_head_stride,
                                int batch, int seqlen_q, int num_heads, int head_dim_v, hipStream_t stream);
 hipError_t launch_skip_list_stats(const void* list, int list_elem_size, int rows, int k_tiles, int64_t* out, hipStream_t stream);
+hipError_t launch_skip_list_stats_heads(const void* list, int list_elem_size, int heads, int q_tiles, int k_tiles, int64_t* out, hipStream_t stream);   // out[heads]: heads = batch * num_heads
 hipError_t launch_blockmask_to_lists(const uint8_t* mask, int64_t mask_batch_stride, int64_t mask_head_stride, int batch,
                                      int num_heads, int q_tiles, int k_tiles, const int32_t* q_tiles_valid,
                                      const int32_t* k_tiles_valid, void* lists, int list_elem_size, int32_t* empty_rows, hipStream_t stream);

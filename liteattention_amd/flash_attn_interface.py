@@ -306,9 +306,28 @@ def _add_workspace(a, device, route):
     return workspace
 
 
-def _launch(lib, a, stream, route):
-    """``la_fwd`` on ``stream``; a return code becomes the route's exception."""
-    rc = lib.la_fwd(ctypes.byref(a), stream)
+def _check_thr_head(thr_head, q, batch, has_lists):
+    """``_thr_head`` of ``mha_fwd`` -> (tensor, batch stride, head stride) of ``la_fwd_head_thr``, in elements; None passes as None."""
+    if thr_head is None:
+        return None
+    H = q.shape[-2]
+    if not isinstance(thr_head, torch.Tensor) or thr_head.dtype != torch.float32 or thr_head.device != q.device:
+        raise ValueError("_thr_head must be a float32 tensor on the device of q")
+    if tuple(thr_head.shape) not in ((H,), (batch, H)):
+        raise ValueError(f"_thr_head must have shape (heads,) = ({H},) or (batch, heads) = ({batch}, {H}); got {tuple(thr_head.shape)}")
+    if not has_lists:
+        raise ValueError("_thr_head is the vote threshold per head of a call with skip lists: a dense call has no vote")
+    if thr_head.dim() == 1:
+        return thr_head, 0, thr_head.stride(0)
+    return thr_head, thr_head.stride(0), thr_head.stride(1)
+
+
+def _launch(lib, a, stream, route, thr_head=None):
+    """``la_fwd`` on ``stream`` (``la_fwd_head_thr`` with a table of ``_check_thr_head``); a return code becomes the route's exception."""
+    if thr_head is None:
+        rc = lib.la_fwd(ctypes.byref(a), stream)
+    else:
+        rc = lib.la_fwd_head_thr(ctypes.byref(a), ctypes.c_void_p(thr_head[0].data_ptr()), thr_head[1], thr_head[2], stream)
     if rc == _cabi.LA_OK:
         return
     msg = _cabi.status_string(rc)
@@ -327,7 +346,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
             is_rotary_interleaved=False, scheduler_metadata=None, num_splits=0, pack_gqa=None, sm_margin=0,
             attn_read_list=None, attn_must_do_list=None, attn_write_list=None, thr=-3.0,
             _must_do_is_1d: bool = False, _q_windows=None, _window_hook=None, _static_sched: bool = False, _flags: int = 0,
-            _v_prepared=None):
+            _v_prepared=None, _thr_head=None):
     """Host half of the op (flash_api.cpp:667-1249) for the non-causal, fixed-length subset (MHA / GQA / MQA) that
     ``LiteAttention.__call__`` reaches. Returns ``(out, softmax_lse, out_accum, softmax_lse_accum)``.
 
@@ -340,7 +359,11 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     (no collective is in flight beside window 0). ``_flags``: extra ``LA_FLAG_*`` bits ORed into ``la_fwd_args.flags`` (tests / A/B:
     LA_FLAG_EXACT_RESCALE, LA_FLAG_FP8_MFMA_ROWSUM, LA_FLAG_FP8_ENCODED_P); kernel-selection bits that change the tile geometry are not accepted here.
     ``_v_prepared``: the ``v_prep.PreparedV`` whose ``as_v()`` is given as ``v``: the launches run on ITS workspace (nothing is
-    allocated here) under LA_FLAG_V_PREPARED, every window of them; what it has no form for is refused before any launch."""
+    allocated here) under LA_FLAG_V_PREPARED, every window of them; what it has no form for is refused before any launch.
+    ``_thr_head``: a float32 DEVICE tensor ``(heads,)`` or ``(batch, heads)`` (packed batches: one row per sequence) of vote thresholds,
+    one per QUERY head, in place of the scalar ``thr`` (which is then not read): every launch of the call goes through
+    ``la_fwd_head_thr``. The last dimension may be strided; nothing is copied or synchronised, so the caller may rewrite the tensor in
+    place between calls or graph replays. A wrong shape, dtype or device, or a call without lists, is a ValueError before any launch."""
     if _v_prepared is not None:
         _v_prepared.check_call(q, k, cu_seqlens_q, cu_seqlens_k, num_splits)
     if _flags & ~_EXTRA_FLAGS:
@@ -376,7 +399,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     descales = (q_descale, k_descale, v_descale)
     if cu_seqlens_q is not None or cu_seqlens_k is not None:
         return _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales,
-                               softmax_scale, attn_read_list, attn_write_list, attn_must_do_list, thr, _must_do_is_1d)
+                               softmax_scale, attn_read_list, attn_write_list, attn_must_do_list, thr, _must_do_is_1d, _thr_head)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise RuntimeError("q, k, v must be 4D tensors (batch, seqlen, nheads, headdim)")
     B, Sq, H, D = q.shape
@@ -385,6 +408,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
     Sk = k.shape[1]
     if v.shape[-1] != D:
         raise NotImplementedError("head_dim_v != head_dim is outside the QK-Skip hot path in this build")
+    thr_table = _check_thr_head(_thr_head, q, B, attn_read_list is not None)
     if softmax_scale is None:
         softmax_scale = D ** -0.5
     host_flags = _cabi.default_flags()                       # the environment is read once per route
@@ -412,7 +436,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
                       q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
                       softmax_scale=softmax_scale, attn_read_list=attn_read_list, attn_must_do_list=attn_must_do_list,
                       attn_write_list=attn_write_list, thr=thr, _must_do_is_1d=_must_do_is_1d, _q_windows=_q_windows,
-                      _static_sched=_static_sched, _flags=_flags,
+                      _static_sched=_static_sched, _flags=_flags, _thr_head=_thr_head,
                       _window_hook=None if _window_hook is None else
                       (lambda i, o, r0, r1: _window_hook(i, o[..., :D], r0, r1)))
         return _unpadded(res, out, (B, Sq, H, D), out_dtype, q.device)
@@ -460,7 +484,7 @@ def mha_fwd(q, k, v, k_new=None, v_new=None, q_v=None, out=None, cu_seqlens_q=No
             a.flags = base_flags | (_cabi.LA_FLAG_V_PREPARED if (is_fp8 and (i > 0 or _v_prepared is not None)) else 0) | \
                       (_cabi.LA_FLAG_STATIC_SCHED if (_static_sched is True or (_static_sched == "after_first" and i > 0))
                        else 0)                                                   # V^T tiles prepared by window 0
-            _launch(lib, a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _FIXED)   # :1219
+            _launch(lib, a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _FIXED, thr_table)   # :1219
             if _window_hook is not None:
                 _window_hook(i, out, w_begin * block_m, min(Sq, (w_begin + w_count) * block_m) if w_count else Sq)
     return res
@@ -588,7 +612,8 @@ def _mha_fwd_split_kv(q, k, v, n, out, softmax_scale, descales, flags):
 
 
 def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales,
-                    softmax_scale, attn_read_list, attn_write_list, attn_must_do_list=None, thr=-3.0, _must_do_is_1d=False):
+                    softmax_scale, attn_read_list, attn_write_list, attn_must_do_list=None, thr=-3.0, _must_do_is_1d=False,
+                    _thr_head=None):
     """Packed variable-length batches (flash_api.cpp:672-674, 736-760): q (total_q, H, D), k/v (total_k, Hk, D), cu_seqlens_*
     int32 [B+1] on the device, max_seqlen_* size the grid. ONE launch, no host sync (fp8: plus the V^T prepare pass, which reads
     cu_seqlens_k itself). bf16 / fp16 / e4m3 at every head dim, e4m3 with ``descales`` = (q, k, v), each (B, Hk) or None. lse is
@@ -612,6 +637,7 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     Tq, H, D = q.shape
     B = cu_seqlens_q.numel() - 1
     _check_inputs(q, k, v, descales, B, "k/v shape mismatch: expected k, v (total_k, nheads_k, headdim)", True)
+    thr_table = _check_thr_head(_thr_head, q, B, attn_read_list is not None)
     if softmax_scale is None:
         softmax_scale = D ** -0.5
     is_fp8 = q.dtype == _FP8
@@ -621,7 +647,7 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     if D_kernel != D:
         res = _mha_fwd_varlen(_pad_head_dim(q, D_kernel), _pad_head_dim(k, D_kernel), _pad_head_dim(v, D_kernel), None, cu_seqlens_q,
                               cu_seqlens_k, max_seqlen_q, max_seqlen_k, descales, softmax_scale, attn_read_list, attn_write_list,
-                              attn_must_do_list, thr, _must_do_is_1d)
+                              attn_must_do_list, thr, _must_do_is_1d, _thr_head)
         return _unpadded(res, out, (Tq, H, D), out_dtype, q.device)
     if out is None:
         out = torch.empty((Tq, H, D), dtype=out_dtype, device=q.device)
@@ -655,7 +681,7 @@ def _mha_fwd_varlen(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     if attn_read_list is not None or is_fp8:      # ticket counters of the dynamic work distribution (as in the fixed-length path); fp8: + the V^T tiles
         workspace = _add_workspace(a, q.device, _PACKED)      # noqa: F841 - alive until the launch is enqueued
     with torch.cuda.device(q.device):
-        _launch(_cabi.load(), a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _PACKED)
+        _launch(_cabi.load(), a, ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream), _PACKED, thr_table)
     return res
 
 
@@ -956,4 +982,25 @@ def skip_list_stats(skip_list: torch.Tensor, batch: Optional[int] = None) -> tor
                                                 skip_list.shape[3] - 1, out.data_ptr(), ctypes.c_void_p(stream))
     if rc != _cabi.LA_OK:
         raise RuntimeError(f"la_skip_list_stats: {_cabi.status_string(rc)}")
+    return out
+
+
+def skip_list_stats_heads(skip_list: torch.Tensor, batch: Optional[int] = None) -> torch.Tensor:
+    """Device-side count of listed tiles per (batch, head): int64 ``(batch, heads)``, every element written by the one launch
+    (``la_skip_list_stats_heads``: no atomics, bit-equal across launches). No host sync. int32 or int16 lists. The rows behind each
+    number are ``skip_list.shape[2]``; the sum over the result is ``skip_list_stats(skip_list, batch)[0]``."""
+    if skip_list.dtype not in LIST_DTYPES or skip_list.dim() != 4 or not skip_list.is_contiguous():
+        raise RuntimeError("skip list must be a contiguous int32 or int16 tensor [batch, heads, q_blocks, k_blocks + 1]")
+    if not skip_list.is_cuda:
+        raise RuntimeError("skip_list_stats_heads has no CPU implementation")
+    nb = skip_list.shape[0] if batch is None else int(batch)
+    if nb < 1 or nb > skip_list.shape[0]:
+        raise RuntimeError(f"batch must lie in [1, {skip_list.shape[0]}]; got {nb}")
+    out = torch.empty((nb, skip_list.shape[1]), dtype=torch.int64, device=skip_list.device)
+    with torch.cuda.device(skip_list.device):
+        stream = torch.cuda.current_stream(skip_list.device).cuda_stream
+        rc = _cabi.load().la_skip_list_stats_heads(skip_list.data_ptr(), skip_list.element_size(), nb, skip_list.shape[1],
+                                                   skip_list.shape[2], skip_list.shape[3] - 1, out.data_ptr(), ctypes.c_void_p(stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_skip_list_stats_heads: {_cabi.status_string(rc)}")
     return out

@@ -51,6 +51,8 @@ class LiteAttention:
         self._last_percentage = 0.0
         self._threshold_schedule: Optional[Tuple[float, ...]] = None   # per-step thresholds (set_threshold_schedule); None = the constant
         self._step = 0                             # calls that used the lists since they were last (re)initialised
+        self._head_thresholds: Optional[Tensor] = None   # fp32 (H,) or (n_steps, H) (set_head_thresholds); None = the scalar threshold(s)
+        self._head_thresholds_dev = {}             # device -> copy of a table that was given on the host (made at the first call there)
         self.enable_skipping = enable_skipping
         self.max_batch_size = max_batch_size
         self.set_threshold(threshold)
@@ -144,6 +146,36 @@ class LiteAttention:
             self._step += 1
         return thr
 
+    def _head_table_on(self, device) -> Tensor:
+        """The table as the kernels read it: a device tensor is the caller's own (no copy, so an in-place rewrite is seen); a table
+        given on the host is copied to ``device`` once and kept."""
+        table = self._head_thresholds
+        if table.device == device:
+            return table
+        if table.device.type != "cpu":
+            raise ValueError(f"the head thresholds live on {table.device}, the call is on {device}")
+        dev = self._head_thresholds_dev.get(device)
+        if dev is None:
+            dev = self._head_thresholds_dev[device] = table.to(device)
+        return dev
+
+    def _check_head_table(self, query: Tensor):
+        """Before the lists of a call are handed out: a table for another number of heads is the caller's mistake, not a step."""
+        table = self._head_thresholds
+        if table is not None and table.shape[-1] != query.shape[2]:
+            raise ValueError(f"the head thresholds are for {table.shape[-1]} heads, the query has {query.shape[2]}")
+        if table is not None and table.device.type != "cpu" and table.device != query.device:
+            raise ValueError(f"the head thresholds live on {table.device}, the call is on {query.device}")
+
+    def _take_thresholds(self, query: Tensor, sparse: bool):
+        """``(thr, _thr_head)`` of the call whose lists were just handed out: the scalar of ``_take_threshold`` and, with a table set
+        and a call that uses the lists, the step's row of it on the query's device (``thr`` is then not read). One step is counted."""
+        row = None
+        if sparse and self._head_thresholds is not None:
+            table = self._head_table_on(query.device)
+            row = table if table.dim() == 1 else table[min(self._step, table.shape[0] - 1)]
+        return self._take_threshold(sparse), row
+
     def preallocate(self, query: Tensor, value: Tensor, batch: Optional[int] = None, must_skip_list: list = None):
         """Size the lists for ``batch`` sequences (default ``max_batch_size``) of this shape NOW, so that no later call has to grow them:
         what a caller does before capturing calls into a HIP graph (a graph keeps the list pointers of its capture; growth replaces the
@@ -203,6 +235,7 @@ class LiteAttention:
         restore = v_shift is not None or lse_shift is not None or out_dtype is not None
         if restore:
             self._check_restore(query, key, value, v_shift, lse_shift, out_dtype)
+        self._check_head_table(query)
         read_list, write_list = self._get_read_write_lists(query, key, must_skip_list)
         must_do = None
         if read_list is not None:
@@ -220,6 +253,15 @@ class LiteAttention:
         want_lse = return_softmax_lse or v_shift is not None or lse_shift is not None
         if tiles:
             output = self._fwd_prepared_v(query, key, value, scale, read_list, write_list, must_do, want_lse, **extra)
+        elif read_list is not None and self._head_thresholds is not None:
+            # a table of thresholds per head: flash_attn_func keeps the reference's signature, which has no such argument, so the
+            # call goes to mha_fwd directly - the call flash_attn_func makes for a 1-D must-do row, plus the step's row of the table
+            from .flash_attn_interface import mha_fwd
+            q, k, v = [x if x.stride(-1) == 1 else x.contiguous() for x in (query, key, value)]
+            thr, thr_head = self._take_thresholds(query, True)
+            out, lse, *_ = mha_fwd(q, k, v, softmax_scale=scale, attn_read_list=read_list, attn_must_do_list=must_do,
+                                   attn_write_list=write_list, thr=thr, _must_do_is_1d=True, _thr_head=thr_head, **extra)
+            output = (out, lse) if want_lse else out
         else:
             output = flash_attn_func(q=query, k=key, v=value, softmax_scale=scale, attn_read_list=read_list,
                                      attn_must_do_list=must_do, attn_write_list=write_list, thr=self._take_threshold(read_list is not None),
@@ -236,8 +278,11 @@ class LiteAttention:
         """The forward for a ``PreparedV``: ``mha_fwd`` directly, as ``call_windowed`` reaches it, on the PreparedV's workspace."""
         from .flash_attn_interface import mha_fwd
         q, k = [x if x.stride(-1) == 1 else x.contiguous() for x in (query, key)]
+        thr, thr_head = self._take_thresholds(query, read_list is not None)
+        if thr_head is not None:                   # only when a table is set: the host-logic tests record the exact call
+            descales = dict(descales, _thr_head=thr_head)
         out, lse, *_ = mha_fwd(q, k, value.as_v(), softmax_scale=scale, attn_read_list=read_list, attn_must_do_list=must_do,
-                               attn_write_list=write_list, thr=self._take_threshold(read_list is not None), _must_do_is_1d=True,
+                               attn_write_list=write_list, thr=thr, _must_do_is_1d=True,
                                _q_windows=q_windows, _window_hook=window_hook, _static_sched=static_sched, _v_prepared=value,
                                **descales)
         return (out, lse) if want_lse else out
@@ -280,6 +325,7 @@ class LiteAttention:
         tiles = not isinstance(value, Tensor)
         if tiles:
             value.check_call(query, key)
+        self._check_head_table(query)
         read_list, write_list = self._get_read_write_lists(query, key, must_skip_list)
         must_do = None
         if read_list is not None:
@@ -288,10 +334,12 @@ class LiteAttention:
             return self._fwd_prepared_v(query, key, value, scale, read_list, write_list, must_do, return_softmax_lse, q_windows,
                                         window_hook, static_sched, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale)
         q, k, v = [x if x.stride(-1) == 1 else x.contiguous() for x in (query, key, value)]
+        thr, thr_head = self._take_thresholds(query, read_list is not None)
+        extra = {} if thr_head is None else {"_thr_head": thr_head}      # only when a table is set
         out, lse, *_ = mha_fwd(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale,
                                softmax_scale=scale, attn_read_list=read_list, attn_must_do_list=must_do,
-                               attn_write_list=write_list, thr=self._take_threshold(read_list is not None), _must_do_is_1d=True,
-                               _q_windows=q_windows, _window_hook=window_hook, _static_sched=static_sched)
+                               attn_write_list=write_list, thr=thr, _must_do_is_1d=True,
+                               _q_windows=q_windows, _window_hook=window_hook, _static_sched=static_sched, **extra)
         return (out, lse) if return_softmax_lse else out
 
     # ---- state control ------------------------------------------------------------------------
@@ -310,6 +358,46 @@ class LiteAttention:
             raise ValueError("threshold must be negative when debug mode is not enabled")
         self.threshold = threshold
         self._threshold_schedule = None
+        self._set_head_table(None)
+
+    def _set_head_table(self, table: Optional[Tensor]):
+        self._head_thresholds = table
+        self._head_thresholds_dev = {}
+
+    def set_head_thresholds(self, thresholds):
+        """One vote threshold per QUERY head instead of one for all (extension: heads are independent in attention, so each can
+        skip what it can afford; ``calibration.calibrate_head_thresholds`` finds such a table). ``None`` removes the table. Shape
+        ``(H,)``: constant over the steps. Shape ``(n_steps, H)``: the i-th call that uses the skip lists takes row
+        ``min(i, n_steps - 1)`` - the counting of ``set_threshold_schedule`` (dense calls do not count; ``reset_skip_state`` or a shape
+        change restarts it). Values given on the HOST (a sequence, a CPU tensor) are checked like ``set_threshold``'s and copied to the
+        device of the first call. A DEVICE tensor (float32) is taken as it is - no check, no copy, no synchronisation: the kernels
+        read the caller's memory, which may be rewritten in place between calls or between replays of a captured graph. The last
+        setter wins: ``set_threshold`` and ``set_threshold_schedule`` remove the table, this removes neither of theirs but is what
+        a sparse call uses while it is set. A table whose H is not the query's is a ``ValueError`` at the call."""
+        if thresholds is None:
+            self._set_head_table(None)
+            return
+        on_device = isinstance(thresholds, Tensor) and thresholds.device.type != "cpu"
+        table = thresholds if on_device else torch.as_tensor(thresholds, dtype=torch.float32)
+        if table.dim() not in (1, 2) or table.numel() == 0:
+            raise ValueError(f"head thresholds must have shape (H,) or (n_steps, H); got {tuple(table.shape)}")
+        if on_device:
+            if table.dtype != torch.float32:
+                raise ValueError(f"a device table of head thresholds must be float32, got {table.dtype}")
+        else:
+            if bool((table >= 0).any()) and os.getenv("LITE_ATTENTION_DEBUG", "FALSE") == "FALSE":
+                raise ValueError("threshold must be negative when debug mode is not enabled")
+            if bool(torch.isnan(table).any()):
+                raise ValueError("a head threshold is NaN")
+            table = table.clone()
+        self._set_head_table(table)
+
+    def current_head_thresholds(self) -> Optional[Tensor]:
+        """The ``(H,)`` row the next call that uses the skip lists will pass (a view of the table as it was set), or None."""
+        table = self._head_thresholds
+        if table is None or table.dim() == 1:
+            return table
+        return table[min(self._step, table.shape[0] - 1)]
 
     def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
         """Per-step thresholds (extension; the reference's "error calibration" contribution, README.md:14, has no API there): the
@@ -319,6 +407,7 @@ class LiteAttention:
         schedule and the constant ``threshold`` applies again. ``calibration.calibrate_error_schedule`` finds such a schedule."""
         if thresholds is None:
             self._threshold_schedule = None
+            self._set_head_table(None)
             return
         sched = tuple(float(t) for t in thresholds)
         if not sched:
@@ -326,6 +415,7 @@ class LiteAttention:
         if any(t >= 0 for t in sched) and os.getenv("LITE_ATTENTION_DEBUG", "FALSE") == "FALSE":
             raise ValueError("threshold must be negative when debug mode is not enabled")
         self._threshold_schedule = sched
+        self._set_head_table(None)                 # the last setter wins
 
     def current_threshold(self) -> float:
         """The threshold the next call that uses the skip lists will pass."""
@@ -346,6 +436,16 @@ class LiteAttention:
         if rl is None:
             return 0.0
         return 1.0 - self.calc_percentage(rl[: (rl.shape[0] if batch is None else batch)])
+
+    def get_skip_fraction_heads(self, batch: Optional[int] = None) -> Optional[Tensor]:
+        """Fraction of tiles the next call skips, per (batch, head): a float32 DEVICE tensor ``(B, H)`` from one launch of
+        ``skip_list_stats_heads``, without synchronising (None before the lists exist)."""
+        from .flash_attn_interface import skip_list_stats_heads
+        rl = self.current_read_list()
+        if rl is None:
+            return None
+        listed = skip_list_stats_heads(rl, batch)
+        return 1.0 - listed.to(torch.float32) / float(rl.shape[2] * (rl.shape[3] - 1))
 
     def snapshot(self) -> dict:
         """Both ping-pong lists, the phase and the step counter, copied ON THE DEVICE (no host round trip, no sync: ``state_dict()``
@@ -370,7 +470,7 @@ class LiteAttention:
         """Everything a run needs to continue bit-identically: both ping-pong lists, the phase, the threshold and what the
         lists were built for (shape key incl. the DEVICE they live on). Tensors are returned on the CPU."""
         key = self._shape_key
-        return {
+        state = {
             "skip_list": None if self._skip_list is None else self._skip_list.detach().cpu().clone(),
             "phase": self._phase, "threshold": self.threshold, "enable_skipping": self.enable_skipping,
             "max_batch_size": self.max_batch_size,
@@ -381,6 +481,9 @@ class LiteAttention:
             "threshold_schedule": None if self._threshold_schedule is None else list(self._threshold_schedule),
             "step": self._step,                                            # both absent before threshold schedules existed: None, 0
         }
+        if self._head_thresholds is not None:      # only with a table set: without one the dict is what it was before tables existed
+            state["head_thresholds"] = self._head_thresholds.detach().cpu().tolist()      # (H,) or (n_steps, H) as nested lists
+        return state
 
     def load_state_dict(self, state: dict, device=None):
         """Restore ``state_dict()``. The lists are kept in THIS object's ``list_dtype``: a state saved with the other element type is
@@ -393,6 +496,8 @@ class LiteAttention:
         self.reset_skip_state()
         sched = state.get("threshold_schedule")
         self._threshold_schedule = None if sched is None else tuple(float(t) for t in sched)
+        table = state.get("head_thresholds")       # the values as they were saved, unchecked: a host table, copied to the device of the next call
+        self._set_head_table(None if table is None else torch.tensor(table, dtype=torch.float32))
         if state["skip_list"] is None:
             return
         if device is None:
@@ -464,6 +569,11 @@ class SeqParallelLiteAttention:
     def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
         for la in self.lite_attention:
             la.set_threshold_schedule(thresholds)
+
+    def set_head_thresholds(self, thresholds):
+        """``LiteAttention.set_head_thresholds`` on every node: each K/V split votes with the same table."""
+        for la in self.lite_attention:
+            la.set_head_thresholds(thresholds)
 
     def enable_skip_optimization(self, enable: bool = True):
         for la in self.lite_attention:

@@ -191,6 +191,18 @@ class HeadShardedLiteAttention:
     def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
         self.local.set_threshold_schedule(thresholds)
 
+    def set_head_thresholds(self, thresholds):
+        """``LiteAttention.set_head_thresholds`` with a table over ALL ``num_heads`` heads, ``(H,)`` or ``(n_steps, H)``: this rank's
+        ``LiteAttention`` gets its slice ``[..., h0:h1]`` - a view of a device tensor (the caller's memory is still what the kernels
+        read), the checked values of a host one. ``None`` removes the table."""
+        if thresholds is None:
+            self.local.set_head_thresholds(None)
+            return
+        table = thresholds if isinstance(thresholds, torch.Tensor) else torch.as_tensor(thresholds, dtype=torch.float32)
+        if table.dim() not in (1, 2) or table.shape[-1] != self.num_heads:
+            raise ValueError(f"head thresholds must have shape (H,) or (n_steps, H) with H = {self.num_heads}; got {tuple(table.shape)}")
+        self.local.set_head_thresholds(table[..., self.h0:self.h1])
+
 
 class UlyssesLiteAttention:
     """Sequence-sharded in, sequence-sharded out; heads sharded inside (the DeepSpeed-Ulysses scheme, which is what
