@@ -266,6 +266,11 @@ class UlyssesLiteAttention:
     def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
         self.inner.set_threshold_schedule(thresholds)
 
+    def set_head_thresholds(self, thresholds):
+        """``HeadShardedLiteAttention.set_head_thresholds``: a table over ALL ``num_heads`` heads; the attention of this rank runs on
+        heads ``[h0, h1)`` and gets that slice."""
+        self.inner.set_head_thresholds(thresholds)
+
 
 class RingSeqParallelLiteAttention:
     """Ring (context-parallel) attention over sequence shards with the reference's ``SeqParallelLiteAttention`` state
@@ -291,12 +296,30 @@ class RingSeqParallelLiteAttention:
         # test seams (CPU/gloo): attention_fn(q, k, v, split_idx, scale) -> (out, lse); combine_fn(outs, lses) -> out
         # e4m3 inputs: SeqParallelLiteAttention asks the library for the reference's row sums when the LSE is returned
         # (it clears the two fp8 fast-form flags): the partial results are merged by it
-        self._attention = attention_fn if attention_fn is not None else (
-            lambda q, k, v, j, scale, **kw: self.states(q, k, v, j, scale, return_softmax_lse=True, **kw))
+        self._attention = attention_fn if attention_fn is not None else self._partial
+        # bf16 / fp16 partials of a world > 1 run with the exact rescale (_partial says why; +27 % per partial). Set False for the forward's
+        # default lazy rescale: within an ulp of O per partial instead of half an ulp
+        self.exact_partials = True
         if combine_fn is None:
             from .flash_attn_interface import flash_attn_combine
             combine_fn = lambda outs, lses: flash_attn_combine(outs, lses, return_lse=False)   # noqa: E731
         self._combine = combine_fn
+
+    def _partial(self, q, k, v, j, scale, **kw):
+        """One (local Q x K/V shard j) partial on the kernels. bf16 / fp16 partials that are merged (G > 1) run with
+        LA_FLAG_EXACT_RESCALE: under the lazy rescale P is taken relative to an older row maximum, so the weight of the row's largest
+        key is no longer exactly 1 and carries a 16-bit rounding of its own (tests/test_gpu_fragmented.py: an ulp of O, half an ulp with
+        the flag). A partial is rounded to 16 bits once more before the merge, and with three shards the two roundings together
+        exceeded the reference's tolerance rule (1.02x in bf16, 1.20x in fp16; 0.50-0.52x with the flag: the figures are in
+        tests/test_gpu_parallel_ranks.py). The skip lists do not depend on the flag. It costs 27 % of a partial's
+        time (measured: 18 816 rows x 18 816 keys, 40 heads, bf16 head_dim 128 5.61 -> 7.11 ms, fp16 head_dim 64 3.78 -> 4.78 ms);
+        ``exact_partials = False`` keeps the lazy rescale."""
+        if self.exact_partials and self.world > 1 and q.dtype in (torch.bfloat16, torch.float16):
+            from ._cabi import LA_FLAG_EXACT_RESCALE
+            from .flash_attn_interface import fwd_flags
+            with fwd_flags(LA_FLAG_EXACT_RESCALE):
+                return self.states(q, k, v, j, scale, return_softmax_lse=True, **kw)
+        return self.states(q, k, v, j, scale, return_softmax_lse=True, **kw)
 
     def __call__(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None, *,
                  q_descale: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None,
@@ -344,3 +367,8 @@ class RingSeqParallelLiteAttention:
 
     def set_threshold_schedule(self, thresholds: Optional[Sequence[float]]):
         self.states.set_threshold_schedule(thresholds)
+
+    def set_head_thresholds(self, thresholds):
+        """``SeqParallelLiteAttention.set_head_thresholds``: every rank holds all heads, so every (local Q x K/V shard) state gets the
+        whole table."""
+        self.states.set_head_thresholds(thresholds)

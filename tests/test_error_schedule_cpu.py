@@ -204,6 +204,22 @@ def test_forwarders_hand_the_schedule_to_every_state(rec):
         assert all(la._threshold_schedule == tuple(SCHED) for la in states)
         obj.set_threshold_schedule(None)
         assert all(la._threshold_schedule is None for la in states)
+    # every driver forwards every setter of its states (the head table: sliced to the rank's heads where heads are sharded)
+    for obj in (sp, hs, ul, ring):
+        for name in ("reset_skip_state", "set_threshold", "set_threshold_schedule", "set_head_thresholds"):
+            assert callable(getattr(obj, name)), (type(obj).__name__, name)
+    for obj, states in ((ul, [ul.local]), (ring, ring.states.lite_attention)):
+        obj.set_head_thresholds([-1.0, -2.0])
+        assert all(la._head_thresholds.tolist() == [-1.0, -2.0] for la in states)
+        obj.set_threshold_schedule(SCHED)                  # the last setter wins, through the forwarders too
+        assert all(la._head_thresholds is None for la in states)
+    ul.inner.h0, ul.inner.h1 = 1, 2                        # the slice a second rank of two would own
+    ul.set_head_thresholds([[-1.0, -2.0], [-3.0, -4.0]])
+    assert ul.local._head_thresholds.tolist() == [[-2.0], [-4.0]]
+    with pytest.raises(ValueError):
+        ul.set_head_thresholds([-1.0, -2.0, -3.0])
+    ul.set_head_thresholds(None)
+    assert ul.local._head_thresholds is None
 
 
 def test_state_dict_round_trip_keeps_schedule_and_step_and_old_states_load(rec):
