@@ -36,6 +36,8 @@ bool rows_aligned(const void* ptr, int32_t dtype, int64_t bs, int64_t rs, int64_
     return rows_aligned(ptr, dtype == LA_DTYPE_FP8_E4M3 ? 8u : 16u, dtype == LA_DTYPE_FP32 ? 4 : 8, bs, rs, hs, batch, seqlen, heads);
 }
 
+bool is_input_dtype(int32_t d) { return d == LA_DTYPE_BF16 || d == LA_DTYPE_FP16 || d == LA_DTYPE_FP32; }   // what the passes around la_fwd read (and la_combine writes)
+
 // Kernel selection is a pure function of the arguments (no environment variables, no process-wide statics):
 //   bf16 / fp16 head_dim 128: the 256-row hand-scheduled kernel (x64) unless LA_FLAG_KERNEL_128ROW asks for the 128-row one (v2);
 //   head_dim 256: the hand-scheduled kernel in its 32-rows-per-wave form (q-tile 128) unless LA_FLAG_KERNEL_128ROW asks for the
@@ -70,20 +72,262 @@ int dense_tiles_per_launch(int head_dim, int element_size) {
     }
     return lo;
 }
-struct DenseSplit { int n, chunk_tiles; uint64_t o_bytes, lse_bytes; };
-// (the partial O of a run is 16-bit for every input type: bf16 / fp16 as the inputs, bf16 for e4m3)
-DenseSplit dense_split(int k_tiles, int head_dim, int64_t batch, int64_t seqlen_q, int64_t num_heads, int64_t head_dim_v, int element_size = 2) {
-    const int per = dense_tiles_per_launch(head_dim, element_size);
-    DenseSplit d{};
-    d.n = (k_tiles + per - 1) / per;
-    d.chunk_tiles = (k_tiles + d.n - 1) / d.n;
-    d.o_bytes = ((static_cast<uint64_t>(batch) * seqlen_q * num_heads * head_dim_v * 2) + 15) & ~15ull;
-    d.lse_bytes = static_cast<uint64_t>(batch) * num_heads * seqlen_q * 4;      // (exact: the merge reads run s at s * (elements of one partial); the O partials - always a
-                                                                                // multiple of 16 bytes, head_dim_v % 8 == 0 - come first, so every O partial is 16-byte aligned)
-    return d;
+// What la_skip_list_stats_ex, la_skip_list_stats_heads and la_blockmask_to_lists_ex check of a list's geometry [n_batch, num_heads, q_tiles,
+// k_tiles + 1] of list_elem_size-byte entries, in their order (strides_ok: the one check the mask entry point has between them).
+int list_geometry_status(int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles, bool strides_ok = true) {
+    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
+    if (n_batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
+    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    if (!strides_ok) return LA_ERR_STRIDE;
+    if (static_cast<int64_t>(n_batch) * num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;    // one wave or workgroup per row
+    return LA_OK;
+}
+// What la_combine and la_combine_list check alike, behind their NULL checks
+int combine_status(const void* o, int32_t o_dtype, int32_t partial_is_16bit, int32_t num_splits, int32_t max_splits, int32_t batch,
+                   int32_t seqlen_q, int32_t num_heads, int32_t head_dim_v) {
+    if (!is_input_dtype(o_dtype)) return LA_ERR_DTYPE;
+    if (o_dtype == LA_DTYPE_FP32 && partial_is_16bit) return LA_ERR_DTYPE;      // an fp32 result is the merge of fp32 partials
+    if (num_splits <= 0 || num_splits > max_splits || batch <= 0 || seqlen_q <= 0 || num_heads <= 0 || head_dim_v <= 0) return LA_ERR_SHAPE;
+    if (head_dim_v % 8 != 0) return LA_ERR_HEAD_DIM;
+    if (!aligned16(o)) return LA_ERR_STRIDE;
+    return LA_OK;
 }
 constexpr uint64_t kSchedWorkspaceBytes = 1024;   // 16 ticket / steal counters of 64 bytes, all of them zeroed by prepare_work_queue (no slack)
+
+// The caller's workspace of ONE la_fwd call, in the order it lies there: the prepared V^T tiles (e4m3 only; split: those of ONE run - the
+// runs follow each other on the stream), the ticket block, then - split only - the partial O and the partial LSE of the n runs. The one
+// description of it: la_fwd_workspace_bytes returns `total`, la_fwd checks workspace_bytes against it and takes every pointer from it.
+struct FwdWorkspace {
+    bool split;                                   // a dense key range longer than one launch's walk, cut into n equal runs of chunk_tiles
+    int n, chunk_tiles;                           // (not split: 1 run of all the key tiles)
+    uint64_t tickets, o_part, lse_part, total;    // byte offsets (the tiles are at 0) and the bytes in all
+    uint64_t o_bytes, lse_bytes;                  // one run's partial O (16-bit for every input type: bf16 / fp16 as the inputs, bf16 for e4m3) and LSE
+};
+// k_tiles: of the whole key range. may_split = false: one launch whatever the length. A launch that fits never reaches the bisection.
+FwdWorkspace fwd_workspace(const la_fwd_args* a, int esize, int k_tiles, bool may_split) {
+    const bool fp8 = esize == 1, skipable = a->read_list != nullptr, x64 = fp8 || !(a->flags & LA_FLAG_KERNEL_128ROW);
+    FwdWorkspace w;
+    w.split = may_split && x64 && !skipable && a->cu_seqlens_q == nullptr && la::fwd_lds_size_x64(esize, a->head_dim, k_tiles).bytes > la::X_LDS_LIMIT;
+    w.n = 1; w.chunk_tiles = k_tiles; w.o_bytes = w.lse_bytes = 0;
+    if (w.split) {
+        const int per = dense_tiles_per_launch(a->head_dim, esize);
+        w.n = (k_tiles + per - 1) / per;
+        w.chunk_tiles = (k_tiles + w.n - 1) / w.n;
+        w.o_bytes = ((static_cast<uint64_t>(a->batch) * a->seqlen_q * a->num_heads * a->head_dim_v * 2) + 15) & ~15ull;
+        w.lse_bytes = static_cast<uint64_t>(a->batch) * a->num_heads * a->seqlen_q * 4;   // (exact: the merge reads run s at s * one partial; the O partials come first, so each is 16-byte aligned)
+    }
+    // ticket counters: e4m3 and split launches always have room for them; else launches with lists and dense launches of the hand-scheduled
+    // kernels (the 128-row template keeps the static map for dense), unless LA_FLAG_STATIC_SCHED
+    const bool tickets = fp8 || w.split || ((skipable || x64) && !(a->flags & LA_FLAG_STATIC_SCHED));
+    w.tickets = fp8 ? la::fp8_workspace_bytes(a->batch, a->num_heads_k, w.chunk_tiles, a->head_dim) : 0;
+    w.o_part = w.tickets + (tickets ? kSchedWorkspaceBytes : 0);
+    w.lse_part = w.o_part + w.n * w.o_bytes;
+    w.total = w.lse_part + w.n * w.lse_bytes;
+    return w;
+}
 constexpr float kRescaleTauBf16 = 8.0f;           // lazy-rescale slack of the x64 kernel, log2 units (HISTORY.md section 3.1)
+
+// ---- la_fwd / la_fwd_head_thr: check, then fill, then dispatch. What the checks compute on their way and the later steps need:
+struct FwdChecked {
+    bool fp8, f16, varlen, half_vote, ws_ok;       // f16: same kernels as bf16 with the fp16 MFMA and conversions; ws_ok: the workspace holds `ws`
+    int esize, bm, bn, k_tiles;
+    int q_tiles, list_q_tiles, q_tile_begin, q_tile_count;      // the window in the KERNEL's items (half-vote: pairs of list rows)
+    FwdWorkspace ws;
+};
+// Every check of la_fwd, in the order that decides the first error code. With no keys (seqlen_k == 0) nothing is walked: the checks stop
+// behind the varlen ones and c holds nothing from `ws_ok` on.
+int fwd_check(const la_fwd_args* a, FwdChecked& c) {
+    if (a == nullptr) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_fwd_args)) return LA_ERR_STRUCT_SIZE;
+    if (a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16 && a->dtype != LA_DTYPE_FP8_E4M3) return LA_ERR_DTYPE;   // flash_api.cpp:715
+    const bool fp8 = c.fp8 = a->dtype == LA_DTYPE_FP8_E4M3;
+    c.f16 = a->dtype == LA_DTYPE_FP16;
+    const int esize = c.esize = fp8 ? 1 : 2;
+    if (!a->q || !a->o || ((!a->k || !a->v) && a->seqlen_k != 0)) return LA_ERR_NULL_ARG;   // empty K/V tensors may be NULL
+    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k < 0 || a->num_heads <= 0 || a->num_heads_k <= 0 ||
+        a->head_dim <= 0 || a->head_dim_v <= 0)
+        return LA_ERR_SHAPE;                                                             // flash_api.cpp:776-778
+    if (a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;                          // flash_api.cpp:777
+    if (a->head_dim % (fp8 ? 16 : 8) != 0) return LA_ERR_HEAD_DIM;                         // flash_api.cpp:854-856
+    if (a->head_dim_v != a->head_dim) return LA_ERR_UNSUPPORTED;
+    if (a->reserved0 != 0 || (a->flags & ~kKnownFlags) != 0) return LA_ERR_UNSUPPORTED;
+    const bool skipable = a->read_list != nullptr;                                       // is_skipable, flash_api.cpp:931
+    if ((a->flags & LA_FLAG_LIST_INT16) && !skipable && a->write_list == nullptr)
+        return LA_ERR_UNSUPPORTED;                     // the flag types the list pointers: a launch without lists has nothing it could mean
+    const int trc = la_get_tile_sizes_ex(a->head_dim, esize, a->flags, &c.bm, &c.bn);
+    if (trc != LA_OK) return trc;
+    if (a->block_m != c.bm || a->block_n != c.bn) return LA_ERR_TILE_MISMATCH;
+    if (skipable != (a->write_list != nullptr)) return LA_ERR_LISTS;
+    // 16-byte vector access on every row: row/head/batch strides multiples of 8 elements, base aligned
+    const int64_t strides[] = {a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->k_batch_stride,
+                               a->k_row_stride,   a->k_head_stride, a->v_batch_stride, a->v_row_stride,
+                               a->v_head_stride,  a->o_batch_stride, a->o_row_stride,  a->o_head_stride};
+    for (int i = 0; i < 12; ++i) {                                                       // flash_api.cpp:726-728 (+alignment)
+        const int64_t s = strides[i];
+        const int gran = (fp8 && i < 9) ? 16 : 8;                                        // 16-byte rows: 16 fp8 / 8 bf16 elements
+        if (s % gran != 0 || s < 0) return LA_ERR_STRIDE;
+    }
+    if (a->o_row_stride > 0x3fffffff || a->q_row_stride > 0x3fffffff)
+        return LA_ERR_STRIDE;                                                             // byte strides kept in 32 bits (the row offset itself is 64-bit)
+    // K / V: a lane's DMA offset inside a key tile, row_in_tile * row_stride_bytes + chunk + bias, is an UNSIGNED 32-bit register of the
+    // load (hand-scheduled bodies: rows 0 .. 63, chunk < 512, bias <= 3072) or an int (128-row template: rows 0 .. 14 and 0 .. 7 of a wave's
+    // slice): 63 * 2^26 + 3584 < 2^32 and 14 * 2^26 < 2^31. LA_MAX_KV_ROW_STRIDE_BYTES is the largest power of two inside both.
+    if (a->k_row_stride > LA_MAX_KV_ROW_STRIDE_BYTES / esize || a->v_row_stride > LA_MAX_KV_ROW_STRIDE_BYTES / esize)
+        return LA_ERR_STRIDE;
+    if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || !aligned16(a->o)) return LA_ERR_STRIDE;
+
+    const bool varlen = c.varlen = a->cu_seqlens_q != nullptr || a->cu_seqlens_k != nullptr;
+    if (varlen) {                                                                        // flash_api.cpp:736-760
+        if (a->cu_seqlens_q == nullptr || a->cu_seqlens_k == nullptr) return LA_ERR_NULL_ARG;
+        if (skipable && ((a->flags & LA_FLAG_KERNEL_128ROW) || (a->head_dim > 128 && !fp8)))
+            return LA_ERR_UNSUPPORTED;                                                    // lists + cu_seqlens: the hand-scheduled kernels, head_dim <= 128 (e4m3: every head dim)
+        if (a->total_q < 0 || a->q_tile_count != 0) return LA_ERR_SHAPE;
+    }
+    if (a->seqlen_k == 0) return LA_OK;
+
+    c.k_tiles = (a->seqlen_k + c.bn - 1) / c.bn;
+    c.ws = fwd_workspace(a, esize, c.k_tiles, true);
+    c.ws_ok = a->workspace != nullptr && aligned16(a->workspace) && a->workspace_bytes >= c.ws.total;
+    if (fp8 && !c.ws_ok) return LA_ERR_WORKSPACE;                                         // e4m3 cannot run without it; for bf16 / fp16 only a split needs it (below)
+    if ((a->flags & LA_FLAG_LIST_INT16) && c.k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    c.list_q_tiles = c.q_tiles = (a->seqlen_q + c.bm - 1) / c.bm;
+    c.half_vote = uses_half_vote(a->head_dim, esize, a->flags);
+    c.q_tile_begin = a->q_tile_begin; c.q_tile_count = a->q_tile_count != 0 ? a->q_tile_count : c.q_tiles;      // count 0: all (begin must then be 0)
+    if (a->q_tile_count == 0 ? a->q_tile_begin != 0 : (a->q_tile_begin < 0 || a->q_tile_count < 0 || a->q_tile_begin > c.q_tiles - a->q_tile_count))
+        return LA_ERR_Q_WINDOW;
+    // half-vote: q-tiles (list rows) are 128-row halves, the kernel's items are pairs of them: a window starts on an even q-tile
+    // and holds an even number of them unless it reaches the last one
+    if (c.half_vote && a->q_tile_count != 0 && ((a->q_tile_begin & 1) || ((a->q_tile_count & 1) && a->q_tile_begin + a->q_tile_count != c.q_tiles)))
+        return LA_ERR_Q_WINDOW;
+    if (c.half_vote) {                                 // the kernel's geometry: items of 2 * bm rows; the lists keep bm-row rows
+        c.q_tiles = (c.list_q_tiles + 1) / 2;
+        c.q_tile_count = (c.q_tile_begin + c.q_tile_count + 1) / 2 - c.q_tile_begin / 2;
+        c.q_tile_begin = c.q_tile_begin / 2;
+    }
+    const bool x64 = fp8 || !(a->flags & LA_FLAG_KERNEL_128ROW);
+    if (!x64 && la::fwd_lds_bytes_v2(a->head_dim <= 128 ? a->head_dim : 256, c.k_tiles, nullptr) > la::X_LDS_LIMIT) return LA_ERR_SEQLEN;
+    if (static_cast<int64_t>(a->batch) * a->num_heads * c.q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
+    // Keys too long for the walk of ONE launch of the hand-scheduled kernels. Lists name their tiles over the whole key range and keep the bound,
+    // a varlen launch too; a dense launch is cut into runs (ws.split) - of every q-tile, of a V la_fwd prepares run by run (the flag means
+    // nothing to bf16 / fp16), and with the workspace for the runs' partials, which bf16 / fp16 callers may have left out.
+    const bool too_long = c.ws.split || (x64 && (skipable || varlen) &&
+                                         la::fwd_lds_size_x64(esize, a->head_dim, c.k_tiles, c.half_vote && skipable).bytes > la::X_LDS_LIMIT);
+    if (too_long && (!c.ws.split || c.q_tile_count != c.q_tiles || (fp8 && (a->flags & LA_FLAG_V_PREPARED)) || !c.ws_ok)) return LA_ERR_SEQLEN;
+    return LA_OK;
+}
+
+la::FwdParams fwd_fill(const la_fwd_args* a, const FwdChecked& c, const float* thr_head, int64_t thr_bs, int64_t thr_hs) {
+    la::FwdParams p{};
+    p.q = static_cast<const uint16_t*>(a->q);
+    p.k = static_cast<const uint16_t*>(a->k);
+    p.v = static_cast<const uint16_t*>(a->v);
+    p.o = static_cast<uint16_t*>(a->o);
+    p.lse = a->lse;
+    p.q_batch_stride = a->q_batch_stride; p.q_row_stride = a->q_row_stride; p.q_head_stride = a->q_head_stride;
+    p.k_batch_stride = a->k_batch_stride; p.k_row_stride = a->k_row_stride; p.k_head_stride = a->k_head_stride;
+    p.v_batch_stride = a->v_batch_stride; p.v_row_stride = a->v_row_stride; p.v_head_stride = a->v_head_stride;
+    p.o_batch_stride = a->o_batch_stride; p.o_row_stride = a->o_row_stride; p.o_head_stride = a->o_head_stride;
+    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
+    p.h_ratio = a->num_heads / a->num_heads_k;
+    p.q_tiles = c.q_tiles; p.list_q_tiles = c.list_q_tiles; p.k_tiles = c.k_tiles;
+    p.q_tile_begin = c.q_tile_begin; p.q_tile_count = c.q_tile_count;
+    p.half_vote = c.half_vote ? 1 : 0;
+    p.list_int16 = (a->flags & LA_FLAG_LIST_INT16) ? 1 : 0;
+    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);  // flash_api.cpp:125-126
+    // softmax_scale = 0 (uniform attention: O = mean of V, LSE = ln seqlen_k) runs at c = 2^-100: every |score * c| stays far below 2^-24, so
+    // each exp2 is exactly 1, while c = 0 makes NaN of the -inf of a masked key and of an empty running maximum (-inf * 0) and inf of tau / c
+    if (p.scale_log2 == 0.0f) p.scale_log2 = 0x1p-100f;
+    p.thr = a->thr;                                                                      // flash_api.cpp:930
+    if (thr_head != nullptr && a->read_list != nullptr) { p.thr_head = thr_head; p.thr_bs = thr_bs; p.thr_hs = thr_hs; }   // (dense runs never see a table)
+    p.rescale_tau = (a->flags & LA_FLAG_EXACT_RESCALE) ? 0.0f : kRescaleTauBf16;
+    // the ticket block, when the workspace has it (bf16 / fp16: optional): persistent workgroups and ticket queues; without it, or under
+    // LA_FLAG_STATIC_SCHED, the static one-workgroup-per-item map (same results either way)
+    if (c.ws_ok && c.ws.o_part != c.ws.tickets && !(a->flags & LA_FLAG_STATIC_SCHED))
+        p.work_counter = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(a->workspace) + c.ws.tickets);
+    p.cu_seqlens_q = a->cu_seqlens_q; p.cu_seqlens_k = a->cu_seqlens_k; p.total_q = a->total_q;
+    p.read_list = a->read_list;
+    p.write_list = a->write_list;
+    p.must_do_list = a->must_do_list;
+    p.must_do_is_1d = a->must_do_is_1d;
+    p.q_descale = a->q_descale; p.k_descale = a->k_descale; p.v_descale = a->v_descale;
+    p.q_descale_batch_stride = a->q_descale_batch_stride; p.q_descale_head_stride = a->q_descale_head_stride;
+    p.k_descale_batch_stride = a->k_descale_batch_stride; p.k_descale_head_stride = a->k_descale_head_stride;
+    p.v_descale_batch_stride = a->v_descale_batch_stride; p.v_descale_head_stride = a->v_descale_head_stride;
+    return p;
+}
+
+// The runs of a split (FwdWorkspace): run s walks key rows [s, s + 1) * chunk_tiles * bn into its own contiguous partial O / LSE in the
+// workspace - launch_run(ps) launches one run - then the merge by LSE writes the caller's o / lse by the caller's strides. The first error
+// ends it. (The reference has no such bound: its producer reads the list from global memory, mainloop...:47-115.)
+template <class LaunchRun>
+hipError_t fwd_dense_runs(const la_fwd_args* a, const la::FwdParams& p, const FwdChecked& c, hipStream_t stream, LaunchRun&& launch_run) {
+    const FwdWorkspace& w = c.ws;
+    unsigned char* const ws = static_cast<unsigned char*>(a->workspace);
+    uint16_t* const o_part = reinterpret_cast<uint16_t*>(ws + w.o_part);
+    float* const lse_part = reinterpret_cast<float*>(ws + w.lse_part);
+    const int64_t run_rows = static_cast<int64_t>(w.chunk_tiles) * c.bn;
+    for (int s = 0; s < w.n; ++s) {
+        la::FwdParams ps = p;
+        const int64_t row0 = s * run_rows, left = a->seqlen_k - row0;
+        ps.seqlen_k = static_cast<int>(left < run_rows ? left : run_rows);                // the last run may be shorter
+        ps.k_tiles = (ps.seqlen_k + c.bn - 1) / c.bn;
+        ps.k = reinterpret_cast<const uint16_t*>(static_cast<const unsigned char*>(a->k) + row0 * a->k_row_stride * c.esize);   // strides are elements
+        ps.v = reinterpret_cast<const uint16_t*>(static_cast<const unsigned char*>(a->v) + row0 * a->v_row_stride * c.esize);
+        ps.o = o_part + s * (w.o_bytes / 2);
+        ps.o_head_stride = a->head_dim_v; ps.o_row_stride = static_cast<int64_t>(p.num_heads) * a->head_dim_v;
+        ps.o_batch_stride = static_cast<int64_t>(p.seqlen_q) * ps.o_row_stride;
+        ps.lse = lse_part + s * (w.lse_bytes / 4);
+        const hipError_t e = launch_run(ps);
+        if (e != hipSuccess) return e;
+    }
+    return la::launch_combine(o_part, true, c.f16, lse_part, p.o, a->lse, w.n, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v, stream, false,
+                              p.o_batch_stride, p.o_row_stride, p.o_head_stride);
+}
+
+// la_fwd (thr_head == nullptr) and la_fwd_head_thr: one body, so both make the same checks in the same order and fill the same block.
+int fwd_run(const la_fwd_args* a, const float* thr_head, int64_t thr_bs, int64_t thr_hs, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    FwdChecked c;
+    if (const int rc = fwd_check(a, c); rc != LA_OK) return rc;
+    if (thr_head != nullptr) {                         // la_fwd_head_thr's own checks: behind the last of la_fwd's on every path, before the first launch
+        if (a->read_list == nullptr) return LA_ERR_LISTS;                                // a dense launch votes on nothing
+        if (thr_bs < 0 || thr_hs < 0 || (reinterpret_cast<uintptr_t>(thr_head) & 3u) != 0) return LA_ERR_STRIDE;
+    }
+    if (a->seqlen_k == 0) {
+        // flash_api.cpp:1241-1245: no keys -> out = 0, lse = +inf (the write list, if any, is left as it is: nothing was walked). Varlen
+        // reaches here only when EVERY sequence is empty (seqlen_k is the maximum); rows then are total_q.
+        hipError_t e = c.varlen
+            ? la::launch_empty_k_fill(static_cast<uint16_t*>(a->o), nullptr, 0, a->o_row_stride, a->o_head_stride, 1,
+                                      static_cast<int>(a->total_q), a->num_heads, a->head_dim_v, stream)
+            : la::launch_empty_k_fill(static_cast<uint16_t*>(a->o), a->lse, a->o_batch_stride, a->o_row_stride, a->o_head_stride,
+                                      a->batch, a->seqlen_q, a->num_heads, a->head_dim_v, stream);
+        if (e == hipSuccess && c.varlen && a->lse != nullptr && a->total_q > 0)            // +inf = 0x7f800000 is not a memset byte pattern
+            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->lse), 0x7f800000, static_cast<size_t>(a->total_q) * a->num_heads, stream);
+        return launch_status(e);
+    }
+    la::FwdParams p = fwd_fill(a, c, thr_head, thr_bs, thr_hs);
+    const bool skipable = a->read_list != nullptr;
+    if (c.fp8) {
+        // 1) V -> pre-transposed, pre-swizzled V^T tiles at the front of the workspace (split: per run ITS keys); 2) forward on (Q, K, V^T)
+        const int p_mode = (a->flags & LA_FLAG_FP8_ENCODED_P) ? 0 : (a->flags & LA_FLAG_FP8_MFMA_ROWSUM) ? 1 : 2;   // default: the reference's arithmetic
+        const auto launch = [&](la::FwdParams& ps, const int* cu_seqlens_k) {
+            hipError_t e = hipSuccess;
+            if (!(a->flags & LA_FLAG_V_PREPARED))
+                e = la::launch_prep_v_fp8(ps.v, a->v_batch_stride, a->v_row_stride, a->v_head_stride, a->workspace, a->batch, ps.seqlen_k,
+                                          a->num_heads_k, ps.k_tiles, a->head_dim, stream, cu_seqlens_k);
+            if (e != hipSuccess) return e;
+            ps.v = static_cast<const uint16_t*>(a->workspace);
+            return la::launch_fwd_x64_fp8(ps, skipable, p_mode, a->head_dim, stream);
+        };
+        if (c.ws.split) return launch_status(fwd_dense_runs(a, p, c, stream, [&](la::FwdParams& ps) { return launch(ps, nullptr); }));
+        return launch_status(launch(p, a->cu_seqlens_k));
+    }
+    // every instantiated head_dim: the hand-scheduled x64 kernel unless LA_FLAG_KERNEL_128ROW (the hipcc-scheduled template: 64 / 128 / 256)
+    if (c.ws.split)
+        return launch_status(fwd_dense_runs(a, p, c, stream, [&](la::FwdParams& ps) { return la::launch_fwd_x64(ps, a->head_dim, false, c.f16, stream); }));
+    if (a->flags & LA_FLAG_KERNEL_128ROW) return launch_status(la::launch_fwd_bf16_v2(p, a->head_dim, skipable, c.f16, stream));
+    return launch_status(la::launch_fwd_x64(p, a->head_dim, skipable, c.f16, stream));
+}
 }  // namespace
 
 extern "C" {
@@ -139,263 +383,19 @@ int la_get_tile_sizes(int head_dim, int element_size, int* block_m, int* block_n
 int64_t la_fwd_workspace_bytes(const la_fwd_args* a) {
     if (a == nullptr) return LA_ERR_NULL_ARG;
     if (a->struct_size != sizeof(la_fwd_args)) return LA_ERR_STRUCT_SIZE;
-    if (a->dtype == LA_DTYPE_BF16 || a->dtype == LA_DTYPE_FP16) {    // ticket counters of the dynamic work distribution: launches with lists, and
-        // (round 5) dense launches of the hand-scheduled kernels; the 128-row template keeps the static map for dense
-        int64_t need = ((a->read_list != nullptr || !(a->flags & LA_FLAG_KERNEL_128ROW)) && !(a->flags & LA_FLAG_STATIC_SCHED))
-                           ? static_cast<int64_t>(kSchedWorkspaceBytes) : 0;
-        // (round 6) a dense key range longer than one launch's walk: + the partial O / LSE of its runs (see dense_split)
-        if (a->read_list == nullptr && !(a->flags & LA_FLAG_KERNEL_128ROW) && a->cu_seqlens_q == nullptr && a->seqlen_k > 0 && a->batch > 0 &&
-            a->seqlen_q > 0 && a->num_heads > 0 && la::tile_shape(a->head_dim, 2).block_m != 0) {
-            const int k_tiles = (a->seqlen_k + 63) / 64;
-            if (la::fwd_lds_size_x64(2, a->head_dim, k_tiles).bytes > la::X_LDS_LIMIT) {
-                const DenseSplit d = dense_split(k_tiles, a->head_dim, a->batch, a->seqlen_q, a->num_heads, a->head_dim_v);
-                need = static_cast<int64_t>(kSchedWorkspaceBytes + d.n * (d.o_bytes + d.lse_bytes));
-            }
-        }
-        return need;
-    }
-    if (a->dtype != LA_DTYPE_FP8_E4M3) return LA_ERR_DTYPE;
-    int bm = 0, bn = 0;
-    const int trc = la_get_tile_sizes_ex(a->head_dim, 1, a->flags, &bm, &bn);
-    if (trc != LA_OK) return trc;
-    if (a->batch <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->seqlen_k < 0) return LA_ERR_SHAPE;
-    const int k_tiles = (a->seqlen_k + bn - 1) / bn;
-    if (a->read_list == nullptr && a->cu_seqlens_q == nullptr && a->seqlen_q > 0 && la::fwd_lds_size_x64(1, a->head_dim, k_tiles).bytes > la::X_LDS_LIMIT) {
-        // a dense key range longer than one launch's walk (see dense_split): the V^T tiles of ONE run (the runs follow each other on the
-        // stream), the ticket counters, the partial O / LSE of the runs
-        const DenseSplit d = dense_split(k_tiles, a->head_dim, a->batch, a->seqlen_q, a->num_heads, a->head_dim_v, 1);
-        return static_cast<int64_t>(la::fp8_workspace_bytes(a->batch, a->num_heads_k, d.chunk_tiles, a->head_dim) + kSchedWorkspaceBytes +
-                                    d.n * (d.o_bytes + d.lse_bytes));
-    }
-    // V^T tiles, then the ticket counter of the dynamic work distribution
-    return static_cast<int64_t>(la::fp8_workspace_bytes(a->batch, a->num_heads_k, k_tiles, a->head_dim) + kSchedWorkspaceBytes);
-}
-
-// la_fwd (thr_head == nullptr) and la_fwd_head_thr: one body, so both make the same checks in the same order and fill the same block.
-// The table's own checks follow the last of la_fwd's on every path, before the first launch of that path.
-static int fwd_run(const la_fwd_args* a, const float* thr_head, int64_t thr_bs, int64_t thr_hs, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (a == nullptr) return LA_ERR_NULL_ARG;
-    const auto table_status = [&]() -> int {
-        if (thr_head == nullptr) return LA_OK;
-        if (a->read_list == nullptr) return LA_ERR_LISTS;                                // a dense launch votes on nothing
-        if (thr_bs < 0 || thr_hs < 0 || (reinterpret_cast<uintptr_t>(thr_head) & 3u) != 0) return LA_ERR_STRIDE;
-        return LA_OK;
-    };
-    if (a->struct_size != sizeof(la_fwd_args)) return LA_ERR_STRUCT_SIZE;
-    if (a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16 && a->dtype != LA_DTYPE_FP8_E4M3) return LA_ERR_DTYPE;   // flash_api.cpp:715
     const bool fp8 = a->dtype == LA_DTYPE_FP8_E4M3;
-    const bool f16 = a->dtype == LA_DTYPE_FP16;      // same kernels as bf16 with the fp16 MFMA and conversions
-    const int esize = fp8 ? 1 : 2;
-    if (!a->q || !a->o || ((!a->k || !a->v) && a->seqlen_k != 0)) return LA_ERR_NULL_ARG;   // empty K/V tensors may be NULL
-    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k < 0 || a->num_heads <= 0 || a->num_heads_k <= 0 ||
-        a->head_dim <= 0 || a->head_dim_v <= 0)
-        return LA_ERR_SHAPE;                                                             // flash_api.cpp:776-778
-    if (a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;                          // flash_api.cpp:777
-    if (a->head_dim % (fp8 ? 16 : 8) != 0) return LA_ERR_HEAD_DIM;                         // flash_api.cpp:854-856
-    if (a->head_dim_v != a->head_dim) return LA_ERR_UNSUPPORTED;
-    if (a->reserved0 != 0 || (a->flags & ~kKnownFlags) != 0) return LA_ERR_UNSUPPORTED;
-    if ((a->flags & LA_FLAG_LIST_INT16) && a->read_list == nullptr && a->write_list == nullptr)
-        return LA_ERR_UNSUPPORTED;                     // the flag types the list pointers: a launch without lists has nothing it could mean
+    if (!fp8 && a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
     int bm = 0, bn = 0;
-    const int trc = la_get_tile_sizes_ex(a->head_dim, esize, a->flags, &bm, &bn);
-    if (trc != LA_OK) return trc;
-    if (a->block_m != bm || a->block_n != bn) return LA_ERR_TILE_MISMATCH;
-    if ((a->read_list == nullptr) != (a->write_list == nullptr)) return LA_ERR_LISTS;
-    // 16-byte vector access on every row: row/head/batch strides multiples of 8 elements, base aligned
-    const int64_t strides[] = {a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->k_batch_stride,
-                               a->k_row_stride,   a->k_head_stride, a->v_batch_stride, a->v_row_stride,
-                               a->v_head_stride,  a->o_batch_stride, a->o_row_stride,  a->o_head_stride};
-    for (int i = 0; i < 12; ++i) {                                                       // flash_api.cpp:726-728 (+alignment)
-        const int64_t s = strides[i];
-        const int gran = (fp8 && i < 9) ? 16 : 8;                                        // 16-byte rows: 16 fp8 / 8 bf16 elements
-        if (s % gran != 0 || s < 0) return LA_ERR_STRIDE;
-    }
-    if (a->o_row_stride > 0x3fffffff || a->q_row_stride > 0x3fffffff)
-        return LA_ERR_STRIDE;                                                             // byte strides kept in 32 bits (the row offset itself is 64-bit)
-    // K / V: a lane's DMA offset inside a key tile, row_in_tile * row_stride_bytes + chunk + bias, is an UNSIGNED 32-bit register of the
-    // load (hand-scheduled bodies: rows 0 .. 63, chunk < 512, bias <= 3072) or an int (128-row template: rows 0 .. 14 and 0 .. 7 of a wave's
-    // slice): 63 * 2^26 + 3584 < 2^32 and 14 * 2^26 < 2^31. LA_MAX_KV_ROW_STRIDE_BYTES is the largest power of two inside both.
-    if (a->k_row_stride > LA_MAX_KV_ROW_STRIDE_BYTES / esize || a->v_row_stride > LA_MAX_KV_ROW_STRIDE_BYTES / esize)
-        return LA_ERR_STRIDE;
-    if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v) || !aligned16(a->o)) return LA_ERR_STRIDE;
-
-    const bool varlen = a->cu_seqlens_q != nullptr || a->cu_seqlens_k != nullptr;
-    if (varlen) {                                                                        // flash_api.cpp:736-760
-        if (a->cu_seqlens_q == nullptr || a->cu_seqlens_k == nullptr) return LA_ERR_NULL_ARG;
-        if (a->read_list != nullptr && ((a->flags & LA_FLAG_KERNEL_128ROW) || (a->head_dim > 128 && !fp8)))
-            return LA_ERR_UNSUPPORTED;                                                    // lists + cu_seqlens: the hand-scheduled kernels, head_dim <= 128 (e4m3: every head dim)
-        if (a->total_q < 0 || a->q_tile_count != 0) return LA_ERR_SHAPE;
-    }
-    if (a->seqlen_k == 0) {
-        // flash_api.cpp:1241-1245: no keys -> out = 0, lse = +inf (the write list, if any, is left as it is: nothing was
-        // walked). Varlen reaches here only when EVERY sequence is empty (seqlen_k is the maximum); rows then are total_q.
-        if (const int trc0 = table_status(); trc0 != LA_OK) return trc0;
-        const hipError_t e0 = varlen
-            ? la::launch_empty_k_fill(static_cast<uint16_t*>(a->o), nullptr, 0, a->o_row_stride, a->o_head_stride, 1,
-                                      static_cast<int>(a->total_q), a->num_heads, a->head_dim_v, stream)
-            : la::launch_empty_k_fill(static_cast<uint16_t*>(a->o), a->lse, a->o_batch_stride, a->o_row_stride, a->o_head_stride,
-                                      a->batch, a->seqlen_q, a->num_heads, a->head_dim_v, stream);
-        hipError_t e1 = hipSuccess;
-        if (e0 == hipSuccess && varlen && a->lse != nullptr && a->total_q > 0)            // +inf = 0x7f800000 is not a memset byte pattern
-            e1 = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->lse), 0x7f800000, static_cast<size_t>(a->total_q) * a->num_heads, stream);
-        return launch_status(e0 != hipSuccess ? e0 : e1);
-    }
-
-    la::FwdParams p{};
-    size_t f8_tiles = 0;                               // fp8: bytes of prepared V^T tiles at the front of the workspace
-    bool f8_split = false;                             // fp8: a dense key range longer than one launch's walk, cut into runs (dense_split)
-    DenseSplit f8d{};
+    const int trc = la_get_tile_sizes_ex(a->head_dim, fp8 ? 1 : 2, fp8 ? a->flags : a->flags & kKnownFlags, &bm, &bn);
+    // The two dtypes answer a block la_fwd refuses differently, and callers have seen both: e4m3 returns the code of a head dim, flag or size
+    // it cannot size tiles for; bf16 / fp16 check nothing and size such a block (one without kernels or without rows; unknown flags are
+    // not looked at) as ONE launch: the ticket block or nothing.
     if (fp8) {
-        const int kt = (a->seqlen_k + bn - 1) / bn;
-        f8_split = a->read_list == nullptr && !varlen && la::fwd_lds_size_x64(1, a->head_dim, kt).bytes > la::X_LDS_LIMIT;
-        if (f8_split) f8d = dense_split(kt, a->head_dim, a->batch, a->seqlen_q, a->num_heads, a->head_dim_v, 1);
-        f8_tiles = la::fp8_workspace_bytes(a->batch, a->num_heads_k, f8_split ? f8d.chunk_tiles : kt, a->head_dim);   // split: the tiles of ONE run
-        const uint64_t need = f8_tiles + kSchedWorkspaceBytes + (f8_split ? f8d.n * (f8d.o_bytes + f8d.lse_bytes) : 0);
-        if (a->workspace == nullptr || a->workspace_bytes < need || !aligned16(a->workspace))
-            return LA_ERR_WORKSPACE;
-        if (!(a->flags & LA_FLAG_STATIC_SCHED))        // lists or dense: persistent workgroups + ticket queues
-            p.work_counter = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(a->workspace) + f8_tiles);
+        if (trc != LA_OK) return trc;
+        if (a->batch <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->seqlen_k < 0) return LA_ERR_SHAPE;
     }
-    p.q = static_cast<const uint16_t*>(a->q);
-    p.k = static_cast<const uint16_t*>(a->k);
-    p.v = static_cast<const uint16_t*>(a->v);
-    p.o = static_cast<uint16_t*>(a->o);
-    p.lse = a->lse;
-    p.q_batch_stride = a->q_batch_stride; p.q_row_stride = a->q_row_stride; p.q_head_stride = a->q_head_stride;
-    p.k_batch_stride = a->k_batch_stride; p.k_row_stride = a->k_row_stride; p.k_head_stride = a->k_head_stride;
-    p.v_batch_stride = a->v_batch_stride; p.v_row_stride = a->v_row_stride; p.v_head_stride = a->v_head_stride;
-    p.o_batch_stride = a->o_batch_stride; p.o_row_stride = a->o_row_stride; p.o_head_stride = a->o_head_stride;
-    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
-    p.h_ratio = a->num_heads / a->num_heads_k;
-    p.q_tiles = (a->seqlen_q + bm - 1) / bm;
-    p.list_q_tiles = p.q_tiles;
-    p.k_tiles = (a->seqlen_k + bn - 1) / bn;
-    if ((a->flags & LA_FLAG_LIST_INT16) && p.k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;    // before any launch
-    p.list_int16 = (a->flags & LA_FLAG_LIST_INT16) ? 1 : 0;
-    const bool half_vote = uses_half_vote(a->head_dim, esize, a->flags);
-    if (a->q_tile_count == 0) {
-        if (a->q_tile_begin != 0) return LA_ERR_Q_WINDOW;
-        p.q_tile_begin = 0; p.q_tile_count = p.q_tiles;
-    } else {
-        if (a->q_tile_begin < 0 || a->q_tile_count < 0 || a->q_tile_begin > p.q_tiles - a->q_tile_count) return LA_ERR_Q_WINDOW;
-        // half-vote: q-tiles (list rows) are 128-row halves, the kernel's items are pairs of them: a window starts on an even q-tile
-        // and holds an even number of them unless it reaches the last one
-        if (half_vote && ((a->q_tile_begin & 1) || ((a->q_tile_count & 1) && a->q_tile_begin + a->q_tile_count != p.q_tiles)))
-            return LA_ERR_Q_WINDOW;
-        p.q_tile_begin = a->q_tile_begin; p.q_tile_count = a->q_tile_count;
-    }
-    if (half_vote) {                                   // the kernel's geometry: items of 2 * bm rows; the lists keep bm-row rows
-        p.half_vote = 1;
-        p.q_tiles = (p.list_q_tiles + 1) / 2;
-        p.q_tile_count = (p.q_tile_begin + p.q_tile_count + 1) / 2 - p.q_tile_begin / 2;
-        p.q_tile_begin = p.q_tile_begin / 2;
-    }
-    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);  // flash_api.cpp:125-126
-    // softmax_scale = 0 (uniform attention: O = mean of V, LSE = ln seqlen_k) runs at c = 2^-100: every |score * c| stays far below 2^-24, so
-    // each exp2 is exactly 1, while c = 0 makes NaN of the -inf of a masked key and of an empty running maximum (-inf * 0) and inf of tau / c
-    if (p.scale_log2 == 0.0f) p.scale_log2 = 0x1p-100f;
-    p.thr = a->thr;                                                                      // flash_api.cpp:930
-    if (thr_head != nullptr && a->read_list != nullptr) { p.thr_head = thr_head; p.thr_bs = thr_bs; p.thr_hs = thr_hs; }   // (the dense runs below never see a table)
-    p.rescale_tau = (a->flags & LA_FLAG_EXACT_RESCALE) ? 0.0f : kRescaleTauBf16;
-    p.cu_seqlens_q = a->cu_seqlens_q; p.cu_seqlens_k = a->cu_seqlens_k; p.total_q = a->total_q;
-    p.read_list = a->read_list;
-    p.write_list = a->write_list;
-    p.must_do_list = a->must_do_list;
-    p.must_do_is_1d = a->must_do_is_1d;
-    p.q_descale = a->q_descale; p.k_descale = a->k_descale; p.v_descale = a->v_descale;
-    p.q_descale_batch_stride = a->q_descale_batch_stride; p.q_descale_head_stride = a->q_descale_head_stride;
-    p.k_descale_batch_stride = a->k_descale_batch_stride; p.k_descale_head_stride = a->k_descale_head_stride;
-    p.v_descale_batch_stride = a->v_descale_batch_stride; p.v_descale_head_stride = a->v_descale_head_stride;
-
-    if (!fp8 && (a->flags & LA_FLAG_KERNEL_128ROW) &&
-        la::fwd_lds_bytes_v2(a->head_dim <= 128 ? a->head_dim : 256, p.k_tiles, nullptr) > la::X_LDS_LIMIT) return LA_ERR_SEQLEN;
-    if (static_cast<int64_t>(p.batch) * p.num_heads * p.q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
-
-    if (fp8) {
-        const int p_mode = (a->flags & LA_FLAG_FP8_ENCODED_P) ? 0 : (a->flags & LA_FLAG_FP8_MFMA_ROWSUM) ? 1 : 2;   // default: the reference's arithmetic
-        if (la::fwd_lds_size_x64(1, a->head_dim, p.k_tiles).bytes > la::X_LDS_LIMIT) {
-            // lists keep the bound; a dense launch is cut into runs of tiles that fit, as for bf16 / fp16 below: per run the V^T prepare pass of
-            // ITS keys into the one tile region (the runs follow each other on the stream), the forward on bf16 partial O / LSE, then the merge
-            if (!f8_split || p.q_tile_count != p.q_tiles || (a->flags & LA_FLAG_V_PREPARED)) return LA_ERR_SEQLEN;
-            if (const int trc1 = table_status(); trc1 != LA_OK) return trc1;
-            unsigned char* const ws = static_cast<unsigned char*>(a->workspace);
-            uint16_t* const o_part = reinterpret_cast<uint16_t*>(ws + f8_tiles + kSchedWorkspaceBytes);
-            float* const lse_part = reinterpret_cast<float*>(ws + f8_tiles + kSchedWorkspaceBytes + f8d.n * f8d.o_bytes);
-            hipError_t e = hipSuccess;
-            for (int s = 0; s < f8d.n && e == hipSuccess; ++s) {
-                la::FwdParams ps = p;
-                const int64_t row0 = static_cast<int64_t>(s) * f8d.chunk_tiles * bn;
-                const int64_t left = a->seqlen_k - row0, full = static_cast<int64_t>(f8d.chunk_tiles) * bn;
-                ps.seqlen_k = static_cast<int>(left < full ? left : full);
-                ps.k_tiles = (ps.seqlen_k + bn - 1) / bn;
-                ps.k = reinterpret_cast<const uint16_t*>(static_cast<const unsigned char*>(a->k) + row0 * a->k_row_stride);     // 1-byte elements: strides are bytes
-                ps.v = static_cast<const uint16_t*>(a->workspace);
-                ps.o = o_part + s * (f8d.o_bytes / 2);
-                ps.o_head_stride = a->head_dim_v; ps.o_row_stride = static_cast<int64_t>(p.num_heads) * a->head_dim_v;
-                ps.o_batch_stride = static_cast<int64_t>(p.seqlen_q) * ps.o_row_stride;
-                ps.lse = lse_part + s * (f8d.lse_bytes / 4);
-                e = la::launch_prep_v_fp8(static_cast<const unsigned char*>(a->v) + row0 * a->v_row_stride, a->v_batch_stride, a->v_row_stride, a->v_head_stride,
-                                          a->workspace, a->batch, ps.seqlen_k, a->num_heads_k, ps.k_tiles, a->head_dim, stream, nullptr);
-                if (e == hipSuccess) e = la::launch_fwd_x64_fp8(ps, false, p_mode, a->head_dim, stream);
-            }
-            if (e == hipSuccess)
-                e = la::launch_combine(o_part, true, false, lse_part, p.o, a->lse, f8d.n, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v, stream, false,
-                                       p.o_batch_stride, p.o_row_stride, p.o_head_stride);
-            return launch_status(e);
-        }
-        if (const int trc2 = table_status(); trc2 != LA_OK) return trc2;
-        // 1) V -> pre-transposed, pre-swizzled V^T tiles in the caller's workspace; 2) forward on (Q, K, V^T)
-        hipError_t e8 = hipSuccess;
-        if (!(a->flags & LA_FLAG_V_PREPARED))
-            e8 = la::launch_prep_v_fp8(a->v, a->v_batch_stride, a->v_row_stride, a->v_head_stride, a->workspace,
-                                       a->batch, a->seqlen_k, a->num_heads_k, p.k_tiles, a->head_dim, stream, a->cu_seqlens_k);
-        if (e8 == hipSuccess) {
-            p.v = static_cast<const uint16_t*>(a->workspace);
-            e8 = la::launch_fwd_x64_fp8(p, a->read_list != nullptr, p_mode, a->head_dim, stream);
-        }
-        return launch_status(e8);
-    }
-    // every instantiated head_dim: the hand-scheduled x64 kernel unless LA_FLAG_KERNEL_128ROW (the hipcc-scheduled template: 64 / 128 / 256)
-    const bool skipable = a->read_list != nullptr;                                      // is_skipable, flash_api.cpp:931
-    const bool x64 = !(a->flags & LA_FLAG_KERNEL_128ROW);
-    hipError_t err;
-    // optional workspace (la_fwd_workspace_bytes): with it, the launch uses persistent workgroups and the ticket queues (lists:
-    // every kernel; dense: the hand-scheduled ones); without it, the static one-workgroup-per-item map (same results either way)
-    if ((skipable || x64) && a->workspace != nullptr && a->workspace_bytes >= kSchedWorkspaceBytes && aligned16(a->workspace) &&
-        !(a->flags & LA_FLAG_STATIC_SCHED))
-        p.work_counter = static_cast<unsigned*>(a->workspace);
-    if (x64 && la::fwd_lds_size_x64(2, a->head_dim, p.k_tiles, half_vote && skipable).bytes > la::X_LDS_LIMIT) {
-        // lists keep the bound; a dense launch is cut into runs of tiles that fit (dense_split) when the caller gave the workspace for it
-        if (skipable || varlen || p.q_tile_count != p.q_tiles) return LA_ERR_SEQLEN;
-        const DenseSplit d = dense_split(p.k_tiles, a->head_dim, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v);
-        if (a->workspace == nullptr || !aligned16(a->workspace) || a->workspace_bytes < kSchedWorkspaceBytes + d.n * (d.o_bytes + d.lse_bytes))
-            return LA_ERR_SEQLEN;
-        if (const int trc3 = table_status(); trc3 != LA_OK) return trc3;
-        unsigned char* const ws = static_cast<unsigned char*>(a->workspace);
-        uint16_t* const o_part = reinterpret_cast<uint16_t*>(ws + kSchedWorkspaceBytes);
-        float* const lse_part = reinterpret_cast<float*>(ws + kSchedWorkspaceBytes + d.n * d.o_bytes);
-        for (int s = 0; s < d.n; ++s) {
-            la::FwdParams ps = p;
-            const int64_t row0 = static_cast<int64_t>(s) * d.chunk_tiles * bn;
-            ps.k = p.k + row0 * p.k_row_stride;
-            ps.v = p.v + row0 * p.v_row_stride;
-            ps.seqlen_k = static_cast<int>(a->seqlen_k - row0 < static_cast<int64_t>(d.chunk_tiles) * bn ? a->seqlen_k - row0 : static_cast<int64_t>(d.chunk_tiles) * bn);
-            ps.k_tiles = (ps.seqlen_k + bn - 1) / bn;
-            ps.o = o_part + s * (d.o_bytes / 2);
-            ps.o_head_stride = a->head_dim_v; ps.o_row_stride = static_cast<int64_t>(p.num_heads) * a->head_dim_v;
-            ps.o_batch_stride = static_cast<int64_t>(p.seqlen_q) * ps.o_row_stride;
-            ps.lse = lse_part + s * (d.lse_bytes / 4);
-            err = la::launch_fwd_x64(ps, a->head_dim, false, f16, stream);
-            if (err != hipSuccess) return launch_status(err);
-        }
-        err = la::launch_combine(o_part, true, f16, lse_part, p.o, a->lse, d.n, p.batch, p.seqlen_q, p.num_heads, a->head_dim_v, stream, false,
-                                 p.o_batch_stride, p.o_row_stride, p.o_head_stride);
-    } else {
-        if (const int trc4 = table_status(); trc4 != LA_OK) return trc4;
-        err = x64 ? la::launch_fwd_x64(p, a->head_dim, skipable, f16, stream) : la::launch_fwd_bf16_v2(p, a->head_dim, skipable, f16, stream);
-    }
-    return launch_status(err);
+    const bool may_split = fp8 ? a->seqlen_q > 0 : trc == LA_OK && a->seqlen_k > 0 && a->batch > 0 && a->seqlen_q > 0 && a->num_heads > 0;
+    return static_cast<int64_t>(fwd_workspace(a, fp8 ? 1 : 2, trc == LA_OK ? (a->seqlen_k + bn - 1) / bn : 0, may_split).total);
 }
 
 int la_fwd(const la_fwd_args* a, void* stream_) { return fwd_run(a, nullptr, 0, 0, stream_); }
@@ -407,12 +407,8 @@ int la_fwd_head_thr(const la_fwd_args* a, const float* thr_head, int64_t thr_bat
 int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
                           int64_t* out_counts, void* stream_) {
     if (!list || !out_counts) return LA_ERR_NULL_ARG;
-    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
-    if (n_batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
-    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
-    const int64_t rows = static_cast<int64_t>(n_batch) * num_heads * q_tiles;
-    if (rows > 0x7fffffffLL) return LA_ERR_SHAPE;
-    const hipError_t err = la::launch_skip_list_stats(list, list_elem_size, static_cast<int>(rows), k_tiles, out_counts,
+    if (const int rc = list_geometry_status(list_elem_size, n_batch, num_heads, q_tiles, k_tiles); rc != LA_OK) return rc;
+    const hipError_t err = la::launch_skip_list_stats(list, list_elem_size, n_batch * num_heads * q_tiles, k_tiles, out_counts,
                                                       static_cast<hipStream_t>(stream_));
     return launch_status(err);
 }
@@ -420,10 +416,7 @@ int la_skip_list_stats_ex(const void* list, int32_t list_elem_size, int32_t n_ba
 int la_skip_list_stats_heads(const void* list, int32_t list_elem_size, int32_t n_batch, int32_t num_heads, int32_t q_tiles, int32_t k_tiles,
                              int64_t* out_counts, void* stream_) {
     if (!list || !out_counts) return LA_ERR_NULL_ARG;
-    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
-    if (n_batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
-    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
-    if (static_cast<int64_t>(n_batch) * num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
+    if (const int rc = list_geometry_status(list_elem_size, n_batch, num_heads, q_tiles, k_tiles); rc != LA_OK) return rc;
     const hipError_t err = la::launch_skip_list_stats_heads(list, list_elem_size, n_batch * num_heads, q_tiles, k_tiles, out_counts,
                                                             static_cast<hipStream_t>(stream_));
     return launch_status(err);
@@ -438,11 +431,8 @@ int la_blockmask_to_lists_ex(const uint8_t* blockmask, int64_t mask_batch_stride
                              int32_t num_heads, int32_t q_tiles, int32_t k_tiles, const int32_t* q_tiles_valid,
                              const int32_t* k_tiles_valid, void* lists, int32_t list_elem_size, int32_t* empty_rows, void* stream_) {
     if (!blockmask || !lists) return LA_ERR_NULL_ARG;
-    if (list_elem_size != 2 && list_elem_size != 4) return LA_ERR_DTYPE;
-    if (batch <= 0 || num_heads <= 0 || q_tiles <= 0 || k_tiles <= 0) return LA_ERR_SHAPE;
-    if (list_elem_size == 2 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
-    if (mask_batch_stride < 0 || mask_head_stride < 0) return LA_ERR_STRIDE;
-    if (static_cast<int64_t>(batch) * num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;
+    if (const int rc = list_geometry_status(list_elem_size, batch, num_heads, q_tiles, k_tiles, mask_batch_stride >= 0 && mask_head_stride >= 0); rc != LA_OK)
+        return rc;
     const hipError_t err = la::launch_blockmask_to_lists(blockmask, mask_batch_stride, mask_head_stride, batch, num_heads, q_tiles,
                                                          k_tiles, q_tiles_valid, k_tiles_valid, lists, list_elem_size, empty_rows,
                                                          static_cast<hipStream_t>(stream_));
@@ -472,11 +462,8 @@ int la_combine(const void* o_partial, int32_t partial_is_16bit, const float* lse
                int32_t num_splits, int32_t batch, int32_t seqlen_q, int32_t num_heads, int32_t head_dim_v,
                void* stream_) {
     if (!o_partial || !lse_partial || !o) return LA_ERR_NULL_ARG;
-    if (o_dtype != LA_DTYPE_BF16 && o_dtype != LA_DTYPE_FP16 && o_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
-    if (o_dtype == LA_DTYPE_FP32 && partial_is_16bit) return LA_ERR_DTYPE;      // an fp32 result is the merge of fp32 partials
-    if (num_splits <= 0 || batch <= 0 || seqlen_q <= 0 || num_heads <= 0 || head_dim_v <= 0) return LA_ERR_SHAPE;
-    if (head_dim_v % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!aligned16(o_partial) || !aligned16(o)) return LA_ERR_STRIDE;
+    if (const int rc = combine_status(o, o_dtype, partial_is_16bit, num_splits, 0x7fffffff, batch, seqlen_q, num_heads, head_dim_v); rc != LA_OK) return rc;
+    if (!aligned16(o_partial)) return LA_ERR_STRIDE;
     const hipError_t err = la::launch_combine(o_partial, partial_is_16bit != 0, o_dtype == LA_DTYPE_FP16, lse_partial, static_cast<uint16_t*>(o), lse,
                                               num_splits, batch, seqlen_q, num_heads, head_dim_v,
                                               static_cast<hipStream_t>(stream_), o_dtype == LA_DTYPE_FP32);
@@ -486,11 +473,8 @@ int la_combine(const void* o_partial, int32_t partial_is_16bit, const float* lse
 int la_combine_list(const void* const* o_partials, int32_t partial_is_16bit, const float* const* lse_partials, void* o, int32_t o_dtype,
                     float* lse, int32_t num_splits, int32_t batch, int32_t seqlen_q, int32_t num_heads, int32_t head_dim_v, void* stream_) {
     if (!o_partials || !lse_partials || !o) return LA_ERR_NULL_ARG;
-    if (o_dtype != LA_DTYPE_BF16 && o_dtype != LA_DTYPE_FP16 && o_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
-    if (o_dtype == LA_DTYPE_FP32 && partial_is_16bit) return LA_ERR_DTYPE;
-    if (num_splits <= 0 || num_splits > LA_COMBINE_LIST_MAX || batch <= 0 || seqlen_q <= 0 || num_heads <= 0 || head_dim_v <= 0) return LA_ERR_SHAPE;
-    if (head_dim_v % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!aligned16(o)) return LA_ERR_STRIDE;
+    if (const int rc = combine_status(o, o_dtype, partial_is_16bit, num_splits, LA_COMBINE_LIST_MAX, batch, seqlen_q, num_heads, head_dim_v); rc != LA_OK)
+        return rc;
     for (int i = 0; i < num_splits; ++i) {
         if (!o_partials[i] || !lse_partials[i]) return LA_ERR_NULL_ARG;
         if (!aligned16(o_partials[i])) return LA_ERR_STRIDE;
@@ -505,17 +489,13 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
                     const void* ref, int32_t ref_dtype, int64_t ref_batch_stride, int64_t ref_row_stride, int64_t ref_head_stride,
                     int32_t batch, int32_t seqlen, int32_t num_heads, int32_t head_dim, int32_t rows_per_bin, double* stats, void* stream_) {
     if (!out || !ref || !stats) return LA_ERR_NULL_ARG;
-    const auto dtype_ok = [](int32_t d) { return d == LA_DTYPE_BF16 || d == LA_DTYPE_FP16 || d == LA_DTYPE_FP32; };
-    if (!dtype_ok(out_dtype) || !dtype_ok(ref_dtype)) return LA_ERR_DTYPE;
+    if (!is_input_dtype(out_dtype) || !is_input_dtype(ref_dtype)) return LA_ERR_DTYPE;
     if (batch <= 0 || seqlen <= 0 || num_heads <= 0 || head_dim <= 0 || rows_per_bin <= 0) return LA_ERR_SHAPE;
     if (head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
-    // every row start is a 16-byte boundary: the pointer, and every stride that is used, in units of 16 / element size
-    const auto strides_ok = [&](const void* p, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
-        const int64_t unit = d == LA_DTYPE_FP32 ? 4 : 8;
-        return bs >= 0 && rs >= 0 && hs >= 0 && aligned16(p) && rs % unit == 0 && hs % unit == 0 && (batch == 1 || bs % unit == 0);
-    };
-    if (!strides_ok(out, out_dtype, out_batch_stride, out_row_stride, out_head_stride) ||
-        !strides_ok(ref, ref_dtype, ref_batch_stride, ref_row_stride, ref_head_stride)) return LA_ERR_STRIDE;
+    // every row start is a 16-byte boundary (rows_aligned). This entry point holds the row and the head stride to it also where seqlen or
+    // num_heads is 1 and the stride goes unused - only the batch stride of batch 1 is exempt, as its header says: hence the 2s
+    if (!rows_aligned(out, out_dtype, out_batch_stride, out_row_stride, out_head_stride, batch, 2, 2) ||
+        !rows_aligned(ref, ref_dtype, ref_batch_stride, ref_row_stride, ref_head_stride, batch, 2, 2)) return LA_ERR_STRIDE;
     const int64_t nbins = (static_cast<int64_t>(seqlen) + rows_per_bin - 1) / rows_per_bin;
     if (static_cast<int64_t>(batch) * num_heads * nbins > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per stats row
     const hipError_t err = la::launch_output_error(out, out_dtype, out_batch_stride, out_row_stride, out_head_stride, ref, ref_dtype,
@@ -607,8 +587,7 @@ int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
     if (!a) return LA_ERR_NULL_ARG;
     if (a->struct_size != sizeof(la_qk_prep_args)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || !a->out) return LA_ERR_NULL_ARG;
-    const bool in_ok = a->in_dtype == LA_DTYPE_BF16 || a->in_dtype == LA_DTYPE_FP16 || a->in_dtype == LA_DTYPE_FP32;
-    if (!in_ok || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
+    if (!is_input_dtype(a->in_dtype) || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
     la::QkPrepParams p;
     const int rc = qk_prep_check_and_fill(a, a->out_dtype, p);
     if (rc != LA_OK) return rc;
@@ -619,7 +598,7 @@ int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream_) {
     if (!a) return LA_ERR_NULL_ARG;
     if (a->struct_size != sizeof(la_qk_prep_fp8_args)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax)) return LA_ERR_NULL_ARG;
-    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
     if (!qk_prep_scale_strides_ok(a)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
@@ -643,7 +622,7 @@ int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream_) {
     if (a->struct_size != sizeof(la_qk_prep_smooth_args)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax && !a->colsum_part && !a->dot_out)) return LA_ERR_NULL_ARG;
     if ((a->dot_out != nullptr) != (a->dot_vec != nullptr)) return LA_ERR_NULL_ARG;
-    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
     if (a->dot_vec && (a->heads_per_dot < 1 || a->num_heads % a->heads_per_dot != 0)) return LA_ERR_SHAPE;
     if (!qk_prep_scale_strides_ok(a) || (reinterpret_cast<uintptr_t>(a->dot_out) & 3u)) return LA_ERR_STRIDE;
@@ -697,7 +676,7 @@ int la_v_colstats(const la_v_colstats_args* a, void* stream_) {
     if (!a) return LA_ERR_NULL_ARG;
     if (a->struct_size != sizeof(la_v_colstats_args)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || !a->stat_part) return LA_ERR_NULL_ARG;
-    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
     if (!rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
@@ -736,7 +715,7 @@ int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
     if (!a->o || !a->out) return LA_ERR_NULL_ARG;
     if ((a->lse_dot != nullptr) != (a->lse_out != nullptr) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
     if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
-    if (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16 && a->out_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (!is_input_dtype(a->out_dtype)) return LA_ERR_DTYPE;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
@@ -768,14 +747,14 @@ int64_t la_v_tiles_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, i
 
 int64_t la_v_tiles_workspace_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim) {
     const int64_t tiles = la_v_tiles_bytes(batch, num_heads_k, seqlen_k, head_dim);
-    return tiles < 0 ? tiles : tiles + static_cast<int64_t>(kSchedWorkspaceBytes);      // what la_fwd asks for when it does not cut the keys into runs
+    return tiles < 0 ? tiles : tiles + static_cast<int64_t>(kSchedWorkspaceBytes);      // FwdWorkspace's first two terms: an e4m3 la_fwd that is one launch
 }
 
 int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream_) {
     if (!a) return LA_ERR_NULL_ARG;
     if (a->struct_size != sizeof(la_v_prep_tiles_args)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || !a->tiles) return LA_ERR_NULL_ARG;
-    if (a->in_dtype != LA_DTYPE_BF16 && a->in_dtype != LA_DTYPE_FP16 && a->in_dtype != LA_DTYPE_FP32) return LA_ERR_DTYPE;
+    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     if (la::tile_shape(a->head_dim, 1).block_m == 0) return LA_ERR_HEAD_DIM;     // the head dims the e4m3 forward has
     if (a->reserved0 != 0) return LA_ERR_UNSUPPORTED;
