@@ -16,6 +16,11 @@ the attention output by the restoring pass, which also replaces the block's `.fl
 attention call as a `PreparedV`: the same codes, no e4m3 V tensor. (The block with skipping disabled is then never split over the
 keys; with a tensor V it is above 704 keys, so its rows agree with those of the tensor route to rounding there, bit for bit below.)
 
+`--brick-order [BT,BH,BW ...]` (with the fused prologue; default bricks 1,16,16 1,8,8): the block runs on the tokens in brick order
+(`brick_order`) - the hidden states are gathered ONCE on entry, q and k are rotated as the positions the rows have
+(`qk_prep(positions=order)`), v and the output need nothing, and the result is restored at the exit. Prints the largest difference of
+the attention output to the raster run, beside the reference's tolerance rule for it.
+
 Prints, per denoising step, the fraction of tiles skipped and the error against the same block with skipping disabled.
 """
 import argparse
@@ -31,6 +36,7 @@ from lite_attention import qk_prep, rope_tables  # noqa: E402  (the fused q / k 
 from lite_attention import E4m3Scales  # noqa: E402  (its e4m3 form with per-head scales: fp8=True)
 from lite_attention import SmoothedQK  # noqa: E402  (... with the keys mean-shifted before they are quantized: smooth_k=True)
 from lite_attention import SmoothedV  # noqa: E402  (... and V: smooth_v=True; the attention call adds the mean back to its output)
+from lite_attention import brick_order  # noqa: E402  (token orders: the block on 3-D bricks of the latent grid instead of raster stripes)
 
 
 class RMSNorm(nn.Module):
@@ -86,9 +92,13 @@ class WanLikeSelfAttention(nn.Module):
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
         # the recipe: ONE LiteAttention per attention layer (its skip lists are that layer's state)
         self.lite_attention = LiteAttention(enable_skipping=enable_skipping, threshold=threshold, max_batch_size=max_batch_size)
+        self.keep_last, self.last = False, None                     # keep_last: (q, k, v, o) of the fused-prep path stay for inspection
 
-    def forward(self, x, grid):
+    def forward(self, x, grid, order=None):
+        """order: a TokenOrder the rows of x are ALREADY in (gathered at the model boundary): q and k are rotated as the positions
+        the rows have; v, the attention call and the output projection are per row and need nothing (fused_prep only)."""
         b, s, n, d = *x.shape[:2], self.num_heads, self.head_dim
+        assert order is None or (self.fused_prep and not self.fp8), "a token order runs through the fused prologue"
         if self.fp8:                                                # norm + rope + scale + e4m3 cast of q and k, scale + cast of v
             tables = rope_tables(grid, d, device=x.device)
             if self.smoothed is not None:
@@ -105,9 +115,13 @@ class WanLikeSelfAttention(nn.Module):
             return self.o(self.lite_attention(q, k, v, q_descale=dq, k_descale=dk, v_descale=dv).float().flatten(2))
         if self.fused_prep:                                         # norm + rope + cast of q and of k: one pass each
             tables = rope_tables(grid, d, device=x.device)
-            q = qk_prep(self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables, out_dtype=torch.bfloat16)
-            k = qk_prep(self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables, out_dtype=torch.bfloat16)
-            return self.o(self.lite_attention(q, k, self.v(x).view(b, s, n, d).bfloat16()).float().flatten(2))
+            q = qk_prep(self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables, out_dtype=torch.bfloat16, positions=order)
+            k = qk_prep(self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables, out_dtype=torch.bfloat16, positions=order)
+            v = self.v(x).view(b, s, n, d).bfloat16()
+            o = self.lite_attention(q, k, v)
+            if self.keep_last:
+                self.last = (q, k, v, o)
+            return self.o(o.float().flatten(2))
         q = self.norm_q(self.q(x)).view(b, s, n, d)
         k = self.norm_k(self.k(x)).view(b, s, n, d)
         v = self.v(x).view(b, s, n, d)
@@ -158,10 +172,16 @@ class WanLikeCrossAttention(nn.Module):
 
 
 def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False, *,
-        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False):
+        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, bricks=None):
+    """bricks: None (raster order), or the brick levels of `brick_order` - the blocks then run in that order (fused prologue) and the
+    rows gain a fourth entry, the largest difference of the dense block's attention output to its raster run."""
     torch.manual_seed(seed)
     dim, grid = heads * 128, (frames, height, width)
     S = frames * height * width
+    order = None
+    if bricks is not None:
+        assert not fp8, "--brick-order runs the bf16 block"
+        fused_prep, order = True, brick_order(grid, bricks, device=device)
     kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v, v_tiles=v_tiles)
     sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep, **kw).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
@@ -169,6 +189,7 @@ def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0,
     sparse.k.load_state_dict(sparse.q.state_dict())
     dense = WanLikeSelfAttention(dim, heads, enable_skipping=False, fused_prep=fused_prep, **kw).to(device)
     dense.load_state_dict(sparse.state_dict())
+    dense.keep_last = order is not None
     # a latent with frame-to-frame structure, denoised over `steps` steps (noise level 0.5 -> 0.05)
     base = torch.randn(1, frames, 1, dim, device=device).expand(1, frames, height * width, dim).reshape(1, S, dim) * 2.0
     base = base + 0.5 * torch.randn(1, S, dim, device=device)
@@ -177,13 +198,34 @@ def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0,
         for t in range(steps):
             sigma = 0.5 + (0.05 - 0.5) * t / max(1, steps - 1)
             x = (1 - sigma ** 2) ** 0.5 * base + sigma * torch.randn(1, S, dim, device=device)
-            y, y_ref = sparse(x, grid), dense(x, grid)
+            if order is not None:
+                # the model boundary: the hidden states (bf16 here, so that the gather is an exact copy) go into the order ONCE ...
+                x = x.bfloat16()
+                xo = order.gather(x.view(1, S, heads, 128)).view(1, S, dim).float()
+                y, y_ref = sparse(xo, grid, order), dense(xo, grid, order)
+                o_bricks = order.restore(dense.last[3])             # ... and come back at the exit (here: the attention output)
+                dense(x.float(), grid)                              # the same block on the same tokens in raster order
+                q, k, v, o_raster = dense.last
+                diff, tol = (o_bricks.float() - o_raster.float()).abs().max().item(), attention_tolerance(q, k, v)
+            else:
+                y, y_ref = sparse(x, grid), dense(x, grid)
             skipped = sparse.lite_attention.get_skip_fraction(batch=1)
             err = (y - y_ref).abs().max().item() / y_ref.abs().max().item()
-            rows.append((t, skipped, err))
+            rows.append((t, skipped, err) if order is None else (t, skipped, err, diff))
             if verbose:
                 print(f"step {t}: tiles skipped by the NEXT step {skipped:6.1%}   max rel. error vs dense block {err:.2e}")
+                if order is not None:
+                    print(f"step {t}: brick order {order.bricks}: max abs difference to the raster run {diff:.3e} (tolerance {tol:.3e})")
     return rows
+
+
+def attention_tolerance(q, k, v):
+    """The reference's acceptance rule for an attention output (its tests/test_flash_attn.py): twice the error of the same attention in
+    torch bf16 against torch fp32, plus twice the fp32 roundoff at the magnitude of the output."""
+    scale = q.shape[-1] ** -0.5
+    ref = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale, -1), v.float())
+    low = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(torch.einsum("bqhd,bkhd->bhqk", q, k).float() * scale, -1).to(v.dtype), v)
+    return 2 * (low.float() - ref).abs().max().item() + 2 * (ref + 0.3 - 0.3 - ref).abs().max().item()
 
 
 if __name__ == "__main__":
@@ -200,8 +242,16 @@ if __name__ == "__main__":
                     "the attention call adds it back and returns fp32")
     ap.add_argument("--v-tiles", action="store_true", help="with --fp8: quantize V straight into the V^T tiles the e4m3 forward stages "
                     "(v_prep_tiles through E4m3Scales / SmoothedV with tiles=True): no e4m3 V tensor, no prepare pass in the call")
+    ap.add_argument("--brick-order", nargs="*", metavar="BT,BH,BW", default=None, help="run the block on the tokens in brick order "
+                    "(brick levels, outermost first; none given: 1,16,16 1,8,8): gather once on entry, positions= in the fused prologue, "
+                    "restore at the exit; prints the difference to the raster run")
     a = ap.parse_args()
+    bricks = None
+    if a.brick_order is not None:
+        if a.fp8:
+            ap.error("--brick-order runs the bf16 block (the e4m3 forms take positions= alike: INTEGRATION.md 1h)")
+        bricks = tuple(tuple(int(v) for v in level.split(",")) for level in a.brick_order) or ((1, 16, 16), (1, 8, 8))
     if (a.smooth_k or a.smooth_v or a.v_tiles) and not a.fp8:
         ap.error("--smooth-k, --smooth-v and --v-tiles need --fp8")
     run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep, fp8=a.fp8, fp8_mode=a.fp8_mode,
-        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v, v_tiles=a.v_tiles)
+        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v, v_tiles=a.v_tiles, bricks=bricks)

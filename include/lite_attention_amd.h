@@ -29,6 +29,9 @@
  *   la_qk_prep_smooth     <- nothing: la_qk_prep_fp8 that can subtract a per-head vector from k before quantizing ("smooth K"), with
  *                            the deterministic column sums that vector is made from (la_colsum_finish) and the q . c row dots that
  *                            undo its shift of the LSE
+ *   la_qk_prep_rows       <- nothing: the three passes above with a row map (la_qk_prep_fp8_rows, la_qk_prep_smooth_rows): out row s is
+ *                            made from a row of x and rotated as a position that two int32 tables name - the token orders of
+ *                            sliding-tile, radial and permuted attention, and the plain row gather that brings V and O into them
  *   la_v_colstats         <- nothing: mean and exact amax of V - mean in one read of V (with la_v_colstats_finish), for a V that is
  *                            quantized mean-shifted ("smooth V")
  *   la_attn_unshift       <- nothing: adds that mean back to the attention output (exact: the rows of P sum to 1), restores the LSE
@@ -55,7 +58,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr and la_skip_list_stats_heads were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads and la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -514,6 +517,40 @@ int la_qk_prep_smooth_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_
 /* Errors: NULL part / mean_out LA_ERR_NULL_ARG; a non-positive size LA_ERR_SHAPE; a negative stride or a pointer off 4 bytes LA_ERR_STRIDE. */
 int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
                      float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride, void* stream);
+
+/* Token orders: la_qk_prep, la_qk_prep_fp8 and la_qk_prep_smooth with a ROW MAP (added under ABI 9: the three argument structs are
+ * unchanged, a host detects the entry points by symbol). Non-causal attention is permutation-equivariant over tokens, so a caller may
+ * run it in any token order - bricks of the (frame, height, width) grid, zig-zag ring shards, a pruned sequence, several clips - when
+ * every row is still rotated as the position it HAS. out has args->seqlen rows, x has src_seqlen rows; for out row s of batch b, with
+ * i = b * batch_stride + s:
+ *   src = src_rows ? src_rows[i] : s                      the row of x that is read; the result is stored to row s of out
+ *   p   = pos_offset + (positions ? positions[i] : src)   the rope position of the row (la_qk_prep: p = pos_offset + s)
+ * Everything behind the load is la_qk_prep's / la_qk_prep_fp8's / la_qk_prep_smooth's own arithmetic in its own order: a row's bits
+ * depend on the row it is made from and on its position alone. amax is order-free; colsum_part sums the rows of each part in the order
+ * of the OUT rows (the parts are cut from args->seqlen); dot_out is indexed by the out row. The wave that owns a token reads its two
+ * table entries in front of the token: no extra pass, no workspace, no atomics beyond those of the unmapped forms.
+ * The kernels CLAMP what they read from the tables, src into [0, src_seqlen) and p into [0, e0*e1*e2), before use: an entry outside
+ * its range reads the nearest row of x or of the rope tables, never memory outside them. This is the definition of such an entry, not
+ * an error path; a host that wants it reported checks its table once, when it builds it.
+ * LA_NORM_NONE without rope tables and with src_rows is a plain row gather (16-bit to the same 16-bit type: an exact copy of finite
+ * values), which is how V, hidden states and O are brought into and out of an order.
+ * A map with both tables NULL and src_seqlen == args->seqlen IS the unmapped entry point: the same kernels, the same bits.
+ * Errors (all before any HIP call): the checks of the unmapped entry point in its order and codes, and with them: NULL map
+ * LA_ERR_NULL_ARG (with NULL args); map->struct_size LA_ERR_STRUCT_SIZE (behind args->struct_size); src_seqlen < 1, or src_rows NULL
+ * and src_seqlen < seqlen, LA_ERR_SHAPE (with the sizes); x's row stride is a used stride when src_seqlen > 1; src_rows or positions
+ * off a 4-byte boundary or a negative batch_stride LA_ERR_STRIDE (behind the strides of x and out); src_rows with out == x
+ * LA_ERR_UNSUPPORTED (a gather in place is not defined); when rotating, positions == NULL holds pos_offset + src_seqlen to e0*e1*e2
+ * (LA_ERR_SHAPE) and positions != NULL holds nothing (the clamp). NOT detected: a table shorter than [B or 1][seqlen]. */
+typedef struct la_row_map {
+    uint32_t struct_size;        /* = sizeof(la_row_map)                                          */
+    int32_t  src_seqlen;         /* rows of x (out has args->seqlen rows)                         */
+    const int32_t* src_rows;     /* [B or 1][seqlen]; NULL: s                                     */
+    const int32_t* positions;    /* [B or 1][seqlen]; NULL: the source row index                  */
+    int64_t  batch_stride;       /* elements; 0: one map for all batches                          */
+} la_row_map;
+int la_qk_prep_rows(const la_qk_prep_args* args, const la_row_map* map, void* stream);
+int la_qk_prep_fp8_rows(const la_qk_prep_fp8_args* args, const la_row_map* map, void* stream);
+int la_qk_prep_smooth_rows(const la_qk_prep_smooth_args* args, const la_row_map* map, void* stream);
 
 /* V smoothing: the twin of K smoothing for the one operand that is quantized as it leaves its projection. la_fwd divides by its own
  * row sum, so the rows of P sum to 1 over whatever keys a row visits - with skip lists, with split keys and after an LSE merge - and

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "la_qk_prep_smooth", "la_qk_prep_smooth_parts", "la_qk_prep_smooth_part_rows", "la_colsum_finish",
     "la_v_colstats", "la_v_colstats_parts", "la_v_colstats_part_rows", "la_v_colstats_finish", "la_attn_unshift",
     "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes", "la_fwd_head_thr", "la_skip_list_stats_heads",
+    "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -99,6 +100,14 @@ class LaQkPrepSmoothArgs(ctypes.Structure):
         ("colsum_part", ctypes.c_void_p),
         ("dot_vec", ctypes.c_void_p), ("dot_vec_batch_stride", ctypes.c_int64), ("dot_vec_head_stride", ctypes.c_int64),
         ("dot_out", ctypes.c_void_p), ("heads_per_dot", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+    ]
+
+
+class LaRowMap(ctypes.Structure):
+    """Mirror of ``la_row_map`` (field order and types must match the header)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("src_seqlen", ctypes.c_int32),
+        ("src_rows", ctypes.c_void_p), ("positions", ctypes.c_void_p), ("batch_stride", ctypes.c_int64),
     ]
 
 
@@ -264,6 +273,10 @@ def load() -> ctypes.CDLL:
     lib.la_qk_prep_fp8.restype = ctypes.c_int
     lib.la_qk_prep_smooth.argtypes = [ctypes.POINTER(LaQkPrepSmoothArgs), ctypes.c_void_p]
     lib.la_qk_prep_smooth.restype = ctypes.c_int
+    for fn, struct in ((lib.la_qk_prep_rows, LaQkPrepArgs), (lib.la_qk_prep_fp8_rows, LaQkPrepFp8Args),
+                       (lib.la_qk_prep_smooth_rows, LaQkPrepSmoothArgs)):
+        fn.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(LaRowMap), ctypes.c_void_p]
+        fn.restype = ctypes.c_int
     for fn in (lib.la_qk_prep_smooth_parts, lib.la_qk_prep_smooth_part_rows):
         fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
         fn.restype = ctypes.c_int

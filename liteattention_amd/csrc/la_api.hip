@@ -508,20 +508,28 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
 
 // What la_qk_prep, la_qk_prep_fp8 and la_qk_prep_smooth check alike, from the norm mode on, and the kernel parameters they share. A: any
 // of the three argument structs (the same field names). out_dtype: la_dtype of out (LA_DTYPE_FP8_E4M3: 8 elements = 8 bytes, row starts on 8-byte boundaries).
+// map: the la_row_map of a _rows entry point (its struct_size already checked), NULL for the unmapped ones: x then has seqlen rows, and
+// each rule of the map sits with the unmapped rules of its kind.
 template <class A>
-static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParams& p) {
+static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, const la_row_map* map, la::QkPrepParams& p) {
+    const int32_t src_seqlen = map ? map->src_seqlen : a->seqlen;
     if (a->norm_mode != LA_NORM_NONE && a->norm_mode != LA_NORM_TOKEN && a->norm_mode != LA_NORM_HEAD) return LA_ERR_UNSUPPORTED;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    // without src_rows out row s is made from row s of x: x has at least seqlen rows
+    if (map && (src_seqlen < 1 || (!map->src_rows && src_seqlen < a->seqlen))) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
     // LA_NORM_TOKEN: the token stays in registers from the load to the store - of one wave up to 5120 elements, of the four waves of a
     // workgroup up to 8 chunks of 8 elements per lane
     if (a->norm_mode == LA_NORM_TOKEN && static_cast<int64_t>(a->num_heads) * a->head_dim > 16384) return LA_ERR_UNSUPPORTED;
     // every row start is aligned (rows_aligned), and the kernels keep a chunk's offset from its token's start in 32 bits
-    const auto strides_ok = [&](const void* ptr, int32_t d, int64_t bs, int64_t rs, int64_t hs) {
-        return rows_aligned(ptr, d, bs, rs, hs, a->batch, a->seqlen, a->num_heads) && hs <= (0x7fffffffLL - a->head_dim) / a->num_heads;
+    const auto strides_ok = [&](const void* ptr, int32_t d, int64_t bs, int64_t rs, int64_t hs, int32_t rows) {
+        return rows_aligned(ptr, d, bs, rs, hs, a->batch, rows, a->num_heads) && hs <= (0x7fffffffLL - a->head_dim) / a->num_heads;
     };
-    if (!strides_ok(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride) ||
-        (a->out && !strides_ok(a->out, out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride))) return LA_ERR_STRIDE;
+    if (!strides_ok(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, src_seqlen) ||
+        (a->out && !strides_ok(a->out, out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->seqlen))) return LA_ERR_STRIDE;
+    if (map && (map->batch_stride < 0 ||
+                ((reinterpret_cast<uintptr_t>(map->src_rows) | reinterpret_cast<uintptr_t>(map->positions)) & 3u))) return LA_ERR_STRIDE;
+    if (map && map->src_rows && a->out == a->x) return LA_ERR_UNSUPPORTED;        // a gather in place: rows would be read after they were overwritten
     if (a->weight && !aligned16(a->weight)) return LA_ERR_STRIDE;                 // read 16 bytes at a time
     for (int i = 0; i < 3; ++i)
         if (reinterpret_cast<uintptr_t>(a->rope_table[i]) & 7u) return LA_ERR_STRIDE;      // (cos, sin) is one 8-byte load
@@ -533,6 +541,7 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParam
     if (pairs > a->head_dim / 2) return LA_ERR_SHAPE;
     const bool rotate = a->rope_table[0] || a->rope_table[1] || a->rope_table[2];      // all three NULL: norm and cast only
     if (a->pos_offset < 0) return LA_ERR_SHAPE;
+    int64_t pos_limit = 1;
     if (rotate) {
         for (int i = 0; i < 3; ++i)
             if (!a->rope_table[i] && a->axis_pairs[i] > 0) return LA_ERR_NULL_ARG;
@@ -542,7 +551,10 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParam
             positions *= a->axis_extent[i];                       // three factors below 2^31: the product of the first two fits, the third is checked
             if (i == 1 && positions > 0x7fffffffLL) return LA_ERR_SHAPE;
         }
-        if (positions > 0x7fffffffLL || static_cast<int64_t>(a->pos_offset) + a->seqlen > positions) return LA_ERR_SHAPE;
+        // the positions of a table are clamped by the kernel; without one the last position is that of x's last row
+        if (positions > 0x7fffffffLL || (!(map && map->positions) && static_cast<int64_t>(a->pos_offset) + src_seqlen > positions))
+            return LA_ERR_SHAPE;
+        pos_limit = positions;
     }
     p = {};
     p.x = a->x; p.out = a->out; p.weight = a->norm_mode == LA_NORM_NONE ? nullptr : a->weight;
@@ -554,6 +566,8 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, la::QkPrepParam
     p.ext1 = rotate ? a->axis_extent[1] : 1; p.ext2 = rotate ? a->axis_extent[2] : 1;
     for (int i = 0; i < 3; ++i) { p.table[i] = a->rope_table[i]; p.pairs[i] = rotate ? a->axis_pairs[i] : 0; }
     p.pos_offset = a->pos_offset; p.eps = a->eps;
+    p.src_seqlen = src_seqlen; p.pos_limit = static_cast<int>(pos_limit);
+    if (map) { p.src_rows = map->src_rows; p.positions = map->positions; p.map_bs = map->batch_stride; }
     return LA_OK;
 }
 
@@ -570,8 +584,8 @@ static bool qk_prep_scale_strides_ok(const A* a) {
 }
 // ... and behind them the limit of heads and the fill, with everything shared with la_qk_prep
 template <class A>
-static int qk_prep_e4m3_check_and_fill(const A* a, la::QkPrepParams& p) {
-    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, p);
+static int qk_prep_e4m3_check_and_fill(const A* a, const la_row_map* map, la::QkPrepParams& p) {
+    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, map, p);
     if (rc != LA_OK) return rc;
     if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;      // a workgroup keeps every head's scale and maximum in LDS
     p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
@@ -581,45 +595,37 @@ static int qk_prep_e4m3_check_and_fill(const A* a, la::QkPrepParams& p) {
     return LA_OK;
 }
 
-extern "C" {
+// The three passes, each behind its unmapped entry point (mapped false, map NULL) and its _rows one (mapped true: a map is required; it is
+// checked for presence with the arguments and for its size behind theirs, its fields inside the shared checker).
+static bool row_map_size_ok(bool mapped, const la_row_map* map) { return !mapped || map->struct_size == sizeof(la_row_map); }
 
-int la_qk_prep(const la_qk_prep_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_args)) return LA_ERR_STRUCT_SIZE;
+static int qk_prep_run(const la_qk_prep_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || !a->out) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype) || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
     la::QkPrepParams p;
-    const int rc = qk_prep_check_and_fill(a, a->out_dtype, p);
+    const int rc = qk_prep_check_and_fill(a, a->out_dtype, map, p);
     if (rc != LA_OK) return rc;
     return launch_status(la::launch_qk_prep(p, a->in_dtype, a->out_dtype, 0, static_cast<hipStream_t>(stream_)));
 }
 
-int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_fp8_args)) return LA_ERR_STRUCT_SIZE;
+static int qk_prep_fp8_run(const la_qk_prep_fp8_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_fp8_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
     if (!qk_prep_scale_strides_ok(a)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
-    const int rc = qk_prep_e4m3_check_and_fill(a, p);
+    const int rc = qk_prep_e4m3_check_and_fill(a, map, p);
     if (rc != LA_OK) return rc;
     return launch_status(la::launch_qk_prep(p, a->in_dtype, LA_DTYPE_FP8_E4M3, a->out ? 1 : 2, static_cast<hipStream_t>(stream_)));
 }
 
-int la_qk_prep_smooth_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
-    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
-    return 4 * la::qk_prep_part_blocks(seqlen);                   // today a function of seqlen alone
-}
-
-int la_qk_prep_smooth_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
-    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
-    return la::qk_prep_part_rows(seqlen);
-}
-
-int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_smooth_args)) return LA_ERR_STRUCT_SIZE;
+static int qk_prep_smooth_run(const la_qk_prep_smooth_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_smooth_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax && !a->colsum_part && !a->dot_out)) return LA_ERR_NULL_ARG;
     if ((a->dot_out != nullptr) != (a->dot_vec != nullptr)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
@@ -632,7 +638,7 @@ int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream_) {
                                      a->num_heads / a->heads_per_dot)) ||
         !aligned16(a->colsum_part)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
-    const int rc = qk_prep_e4m3_check_and_fill(a, p);
+    const int rc = qk_prep_e4m3_check_and_fill(a, map, p);
     if (rc != LA_OK) return rc;
     // a thread keeps the running sums of its columns in LDS: at most 16 chunks of 8
     if (a->colsum_part && la::qk_prep_sum_slots(p) > la::kQkPrepSumSlots) return LA_ERR_UNSUPPORTED;
@@ -647,6 +653,27 @@ int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream_) {
         p.part_rows = la::qk_prep_part_rows(a->seqlen); p.part_blocks = la::qk_prep_part_blocks(a->seqlen);
     }
     return launch_status(la::launch_qk_prep(p, a->in_dtype, LA_DTYPE_FP8_E4M3, mode, static_cast<hipStream_t>(stream_)));
+}
+
+extern "C" {
+
+int la_qk_prep(const la_qk_prep_args* a, void* stream) { return qk_prep_run(a, false, nullptr, stream); }
+int la_qk_prep_rows(const la_qk_prep_args* a, const la_row_map* map, void* stream) { return qk_prep_run(a, true, map, stream); }
+int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream) { return qk_prep_fp8_run(a, false, nullptr, stream); }
+int la_qk_prep_fp8_rows(const la_qk_prep_fp8_args* a, const la_row_map* map, void* stream) { return qk_prep_fp8_run(a, true, map, stream); }
+int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream) { return qk_prep_smooth_run(a, false, nullptr, stream); }
+int la_qk_prep_smooth_rows(const la_qk_prep_smooth_args* a, const la_row_map* map, void* stream) {
+    return qk_prep_smooth_run(a, true, map, stream);
+}
+
+int la_qk_prep_smooth_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
+    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
+    return 4 * la::qk_prep_part_blocks(seqlen);                   // today a function of seqlen alone
+}
+
+int la_qk_prep_smooth_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
+    if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
+    return la::qk_prep_part_rows(seqlen);
 }
 
 int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,

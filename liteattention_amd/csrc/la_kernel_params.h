@@ -162,6 +162,13 @@ struct QkPrepParams {
     int heads_per_dot;
     int batch;
     int part_rows, part_blocks;  // rows of a part; part p = rows [p part_rows, (p + 1) part_rows) of a batch; 4 parts per block
+    // the _rows entry points only (the others leave the pointers NULL): out row s of batch b is made from row src_rows[b map_bs + s] of x
+    // (NULL: s) and rotated as position pos_offset + positions[b map_bs + s] (NULL: the source row). Entries are clamped, never trusted.
+    const int32_t* src_rows;     // [batch or 1][seqlen]
+    const int32_t* positions;    // [batch or 1][seqlen]
+    int64_t map_bs;              // elements between the tables of two batches; 0: one table for every batch
+    int src_seqlen;              // rows of x: a source row is clamped into [0, src_seqlen)
+    int pos_limit;               // e0 * e1 * e2 (1 when nothing rotates): a position is clamped into [0, pos_limit)
 };
 constexpr int kQkPrepScaleSlots = 1024;      // heads whose scale and running amax a workgroup keeps in LDS (la_qk_prep_fp8)
 constexpr int kQkPrepSumSlots = 16;          // chunks of 8 columns a thread keeps running column sums for in LDS (la_qk_prep_smooth): 128 KiB

@@ -57,6 +57,11 @@
 //    the bits depend on (S, H, D) alone. la_colsum_finish_kernel adds the parts in index order and divides by S.
 //  * row dots: a chunk's share (a fixed tree of its 8 products) goes to LDS by chunk index; one thread per head adds the D / 8 shares
 //    in column order (token kernel), or the head's G lanes run the xor butterfly (head kernel). One 4-byte vector store per (head, row).
+//
+// Row maps (the _rows entry points; every form of both templates): out row s is made from row src_rows[s] of x and rotated as position
+// pos_offset + positions[s] (map_row; NULL tables: s and the source row). The wave that owns a token reads its two table entries, one
+// 4-byte load each, in front of the token's loads; everything behind the load - sums, rotation, maxima, column parts, row dots, the
+// store - is indexed by the OUT row and unchanged. Without tables the two values are s and pos_offset + s: the bits of an unmapped launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -160,6 +165,23 @@ struct RotStage {
         }
     }
 };
+
+// The row of x that out row s of batch b is made from and the position it is rotated as (s: wave-uniform and inside the sequence).
+// Without a table: (s, pos_offset + s), what a launch without a map computes. With one (the _rows entry points) the source row is
+// clamped into [0, src_seqlen) and the position into [0, pos_limit): no entry of a table can take a load outside x or the rope tables.
+__device__ __forceinline__ void map_row(const QkPrepParams& p, int64_t b, int s, int& src, int& pos) {
+    src = s;
+    pos = p.pos_offset + s;
+    if (p.src_rows || p.positions) {
+        const int64_t at = b * p.map_bs + s;
+        if (p.src_rows) {
+            const int r = __builtin_amdgcn_readfirstlane(p.src_rows[at]);
+            src = r < 0 ? 0 : (r < p.src_seqlen ? r : p.src_seqlen - 1);
+        }
+        const int64_t q = static_cast<int64_t>(p.pos_offset) + (p.positions ? __builtin_amdgcn_readfirstlane(p.positions[at]) : src);
+        pos = static_cast<int>(q < 0 ? 0 : (q < p.pos_limit ? q : p.pos_limit - 1));
+    }
+}
 
 // y (8 elements starting at element e of a head) *= scale * w, then the pairs below `rot_pairs` are rotated by the staged row
 template <bool ROT>
@@ -269,11 +291,13 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
             b = t / p.seqlen;
             s = static_cast<int>(t - b * p.seqlen);
         }
-        const int64_t x_tok = b * p.x_bs + s * p.x_rs, o_tok = b * p.o_bs + s * p.o_rs;
+        int src, pos;                                              // x is read at row src, everything else speaks of the out row s
+        map_row(p, b, live ? s : 0, src, pos);
+        const int64_t x_tok = b * p.x_bs + src * p.x_rs, o_tok = b * p.o_bs + s * p.o_rs;
         raw_t v[NCH];                                              // the token: it stays in registers until it is stored
 #pragma unroll
         for (int i = 0; i < NCH; ++i) v[i] = col[i] >= 0 && live ? PrepLoad<DT_IN>::load(p.x, x_tok + x_off[i]) : PrepLoad<DT_IN>::zero();
-        if (rotate && live) rs.stage(p, p.pos_offset + s, lane, row);
+        if (rotate && live) rs.stage(p, pos, lane, row);
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -413,9 +437,11 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
             b = t / p.seqlen;
             s = static_cast<int>(t - b * p.seqlen);
         }
-        const int64_t x_tok = b * p.x_bs + s * p.x_rs + e, o_tok = b * p.o_bs + s * p.o_rs + e;
+        int src, pos;                                              // x is read at row src, everything else speaks of the out row s
+        map_row(p, b, live ? s : 0, src, pos);
+        const int64_t x_tok = b * p.x_bs + src * p.x_rs + e, o_tok = b * p.o_bs + s * p.o_rs + e;
         if (rotate) {
-            if (live) rs.stage(p, p.pos_offset + s, lane, row);
+            if (live) rs.stage(p, pos, lane, row);
             wave_lds_fence();
         }
         for (int h0 = 0; h0 < H; h0 += heads_per_pass * kHeadUnroll) {

@@ -13,7 +13,11 @@ the buffers of one tensor and returns ``(x8, descale)``; the descales then go in
 
 K smoothing (``la_qk_prep_smooth``): ``qk_prep_smooth`` subtracts a per-head vector from the keys before it quantizes them and collects
 the column sums that vector is made from (``qk_prep_colmean``) and the ``q . c`` row dots that undo its shift of the LSE
-(``lse_unshift``); ``SmoothedQK`` keeps the buffers of one layer's q and k."""
+(``lse_unshift``); ``SmoothedQK`` keeps the buffers of one layer's q and k.
+
+Row maps (``la_qk_prep_rows`` and its e4m3 and smoothing forms): every call above takes ``rows=`` (out row s is made from row
+``rows[s]`` of x) and ``positions=`` (row s is rotated as position ``positions[s]``), so that the attention can run in another token
+order than the raster order of the grid; ``token_order.py`` builds the orders."""
 from __future__ import annotations
 
 import ctypes
@@ -135,19 +139,69 @@ def _check_scales(x, heads_per_scale, descale, amax):
     return hps
 
 
-def _e4m3_out(x, out):
-    """``out`` of a quantizing pass (allocated when None), checked against ``x``."""
+def _e4m3_out(x, out, seqlen=None):
+    """``out`` of a quantizing pass (allocated when None), checked against ``x`` (``seqlen``: its rows under a row map)."""
+    shape = _out_shape(x, x.shape[1] if seqlen is None else seqlen)
     if out is None:
-        out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+        out = torch.empty(shape, dtype=torch.float8_e4m3fn, device=x.device)
     if out.dtype != torch.float8_e4m3fn:
         raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
-    if out.shape != x.shape or out.device != x.device:
-        raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    if tuple(out.shape) != shape or out.device != x.device:
+        raise ValueError(f"out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
     return out
 
 
-def _prep_args(struct, x, out, mode, weight, eps, pos_offset, tables, axis_pairs):
-    """A ``struct`` (one of the three argument structs) with the fields all three share filled in; ``out`` None: nothing is stored."""
+def _map_table(name, t, x, seqlen=None):
+    """An int32 table ``[S]`` or ``[B, S]`` on ``x.device`` (or a ``TokenOrder``: its ``src_rows``) -> (table, S, batch stride).
+    Metadata only: the entries were checked when the table was built (``TokenOrder.from_rows``), or are the caller's, and the kernel
+    clamps them."""
+    t = getattr(t, "src_rows", t)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{name}: a TokenOrder or an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != x.shape[0]):
+        raise ValueError(f"{name} must be [S] or [{x.shape[0]}, S], got {tuple(t.shape)}")
+    if t.device != x.device:
+        raise ValueError(f"{name} lives on {t.device}, x on {x.device}")
+    if t.stride(-1) != 1:
+        raise ValueError(f"the last dimension of {name} must be contiguous")
+    if seqlen is not None and t.shape[-1] != seqlen:
+        raise ValueError(f"{name} has {t.shape[-1]} entries, the result has {seqlen} rows")
+    return t, t.shape[-1], (t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else 0)
+
+
+def _row_map(x, rows, positions):
+    """``(la_row_map or None, rows of the result)`` for the ``rows=`` / ``positions=`` of a prologue call on ``x`` (B, S_x, H, D):
+    ``rows`` names the row of x each out row is made from (the result has as many rows as the table), ``positions`` the rope position
+    of each out row (default: the source row). Checks shapes, dtypes and devices - before anything launches."""
+    if rows is None and positions is None:
+        return None, x.shape[1]
+    m = _cabi.LaRowMap()
+    m.struct_size, m.src_seqlen = ctypes.sizeof(_cabi.LaRowMap), x.shape[1]
+    seqlen, strides, keep = None, set(), []
+    if rows is not None:
+        t, seqlen, bs = _map_table("rows", rows, x)
+        m.src_rows = t.data_ptr()
+        strides.add(bs)
+        keep.append(t)
+    if positions is not None:
+        t, seqlen, bs = _map_table("positions", positions, x, seqlen if rows is not None else x.shape[1])
+        m.positions = t.data_ptr()
+        strides.add(bs)
+        keep.append(t)
+    if len(strides) > 1:
+        raise ValueError("rows and positions must both be [S] or both be [B, S] with one batch stride")
+    m.batch_stride = strides.pop()
+    m._keep = keep                                               # the tables live as long as the struct that points at them
+    return m, seqlen
+
+
+def _out_shape(x, seqlen):
+    return (x.shape[0], seqlen, x.shape[2], x.shape[3])
+
+
+def _prep_args(struct, x, out, mode, weight, eps, pos_offset, tables, axis_pairs, seqlen=None):
+    """A ``struct`` (one of the three argument structs) with the fields all three share filled in; ``out`` None: nothing is stored.
+    ``seqlen``: rows of the result under a row map (default: those of x)."""
     a = struct()
     a.struct_size = ctypes.sizeof(struct)
     a.in_dtype, a.norm_mode = _IN_DTYPES[x.dtype], mode
@@ -157,6 +211,8 @@ def _prep_args(struct, x, out, mode, weight, eps, pos_offset, tables, axis_pairs
         a.out = out.data_ptr()
         a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
     a.batch, a.seqlen, a.num_heads, a.head_dim = x.shape
+    if seqlen is not None:
+        a.seqlen = seqlen
     a.weight = None if weight is None or mode == _cabi.LA_NORM_NONE else weight.data_ptr()
     a.eps, a.pos_offset = float(eps), int(pos_offset)
     if tables is not None:
@@ -185,38 +241,48 @@ def _call(entry, x, detail, *args):
         raise RuntimeError(f"{entry}: {_cabi.status_string(rc)} ({detail()})")
 
 
-def _call_prep(entry, a, x, pos_offset, detail):
-    """``_call`` of one of the three prologue entry points; ``detail()``: what the form adds between the strides of x and the grid."""
-    _call(entry, x, lambda: f"x {tuple(x.shape)} strides {x.stride()}, {detail()}, pos_offset {pos_offset}, {x.shape[1]} rows on a grid "
-                            f"of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]}", ctypes.byref(a))
+def _call_prep(entry, a, x, pos_offset, detail, row_map=None):
+    """``_call`` of one of the three prologue entry points - its ``_rows`` form when the call has a ``row_map``; ``detail()``: what the
+    form adds between the strides of x and the grid."""
+    mapped = () if row_map is None else (ctypes.byref(row_map),)
+    _call(entry + ("_rows" if mapped else ""), x,
+          lambda: f"x {tuple(x.shape)} strides {x.stride()}, {detail()}, pos_offset {pos_offset}, {a.seqlen} rows on a grid "
+                  f"of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]}"
+                  + ("" if row_map is None else f", row map: rows {bool(row_map.src_rows)}, positions {bool(row_map.positions)}, "
+                                                f"batch stride {row_map.batch_stride}"), ctypes.byref(a), *mapped)
 
 
-def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None):
+def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None,
+                  rows=None, positions=None):
     mode = _check_x_norm(x, norm, "qk_prep_reference")
+    row_map, seqlen = _row_map(x, rows, positions)
+    shape = _out_shape(x, seqlen)
     if out is None:
         if out_dtype is None:
             out_dtype = x.dtype if x.dtype in _OUT_DTYPES else torch.bfloat16
-        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        out = torch.empty(shape, dtype=out_dtype, device=x.device)
     elif out_dtype is not None and out.dtype != out_dtype:
         raise TypeError(f"out is {out.dtype}, out_dtype says {out_dtype}")
     if out.dtype not in _OUT_DTYPES:
         raise TypeError(f"out: bf16 or fp16, got {out.dtype}")
-    if out.shape != x.shape or out.device != x.device:
-        raise ValueError(f"out must be {tuple(x.shape)} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    if tuple(out.shape) != shape or out.device != x.device:
+        raise ValueError(f"out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
     if x.stride(-1) != 1 or out.stride(-1) != 1:
         raise ValueError("the last dimension of x and out must be contiguous")
-    if x.shape[0] * x.shape[1] == 0:
+    if rows is not None and out.data_ptr() == x.data_ptr():
+        raise ValueError("rows= gathers: out must not be x (no in-place form)")
+    if x.shape[0] * x.shape[1] * seqlen == 0:
         return out
     _check_weight(x, weight, mode)
-    a = _prep_args(_cabi.LaQkPrepArgs, x, out, mode, weight, eps, pos_offset, tables, axis_pairs)
+    a = _prep_args(_cabi.LaQkPrepArgs, x, out, mode, weight, eps, pos_offset, tables, axis_pairs, seqlen)
     a.out_dtype = _OUT_DTYPES[out.dtype]
-    _call_prep("la_qk_prep", a, x, pos_offset, lambda: f"out strides {out.stride()}, norm {norm!r}")
+    _call_prep("la_qk_prep", a, x, pos_offset, lambda: f"out strides {out.stride()}, norm {norm!r}", row_map)
     return out
 
 
 def qk_prep(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
             norm: Optional[str] = "token", pos_offset: int = 0, out: Optional[torch.Tensor] = None,
-            out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+            out_dtype: Optional[torch.dtype] = None, *, rows=None, positions=None) -> torch.Tensor:
     """``out = cast(rope(rmsnorm(x) * weight))`` for ``x`` (B, S, H, D) bf16 / fp16 / fp32 on the GPU, in one pass (``la_qk_prep``):
     fp32 arithmetic, one rounding at the store. ``x`` may be any view whose last dimension is contiguous and whose rows start on
     16-byte boundaries - e.g. the q or k slice of a fused (B, S, 3, H, D) projection.
@@ -227,22 +293,51 @@ def qk_prep(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float =
               tables' grid (a chunk of a longer sequence passes its first position).
     out       bf16 or fp16, same shape; default: a new contiguous tensor of ``out_dtype`` (default: ``x.dtype``, bf16 for fp32 input).
               ``out`` may BE ``x`` (same dtype, same strides: in place); any other overlap of the two is an error nobody detects.
+    rows      a ``TokenOrder`` or an int32 table ``[S']`` / ``[B, S']`` on ``x.device``: out row s is made from row ``rows[s]`` of x
+              and rotated as position ``pos_offset + rows[s]`` - the gather into a token order, fused (``la_qk_prep_rows``). The result
+              has S' rows; ``out`` must not be ``x``.
+    positions a ``TokenOrder`` or an int32 table ``[S]`` / ``[B, S]``: row s is rotated as position ``pos_offset + positions[s]`` - for
+              an ``x`` that already is in another order (gathered once at the model boundary), and with ``rows`` to override the
+              position of each gathered row. The kernel clamps what it reads from either table (rows into x, positions into the
+              tables' grid); ``TokenOrder.from_rows`` is where a table is checked, once.
     No host sync, no allocation besides ``out``; asynchronous on the current stream. It captures into a HIP graph when the tables
     were built before the capture (building them copies from the host)."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
-    return _qk_prep_impl(x, weight, eps, tabs, pairs, norm, pos_offset, out, out_dtype)
+    return _qk_prep_impl(x, weight, eps, tabs, pairs, norm, pos_offset, out, out_dtype, rows, positions)
+
+
+def _reference_table(name, t, x):
+    """``rows`` / ``positions`` of a reference function as an int64 ``(1 or B, S)`` tensor on ``x.device`` (None stays None)."""
+    if t is None:
+        return None
+    t = getattr(t, "src_rows", t)
+    t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] not in (1, x.shape[0])):
+        raise ValueError(f"{name} must be an integer table [S] or [{x.shape[0]}, S], got {t.dtype} {tuple(t.shape)}")
+    return (t if t.dim() == 2 else t[None]).to(device=x.device, dtype=torch.int64)
 
 
 def qk_prep_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
-                      norm: Optional[str] = "token", pos_offset: int = 0, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+                      norm: Optional[str] = "token", pos_offset: int = 0, out_dtype: Optional[torch.dtype] = None, *, rows=None,
+                      positions=None) -> torch.Tensor:
     """The formula of ``qk_prep`` in torch fp64 on whatever device ``x`` lives on, from the same fp32 weight and tables. Returns fp64
-    (the unrounded value), or ``out_dtype`` when given."""
+    (the unrounded value), or ``out_dtype`` when given. ``rows`` / ``positions``: integer tables ``[S]`` or ``[B, S]`` (or a
+    ``TokenOrder``) as in ``qk_prep``; here an entry outside its range raises (the kernel clamps it)."""
     if x.dim() != 4:
         raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
     if norm not in _NORM_MODES:
         raise ValueError('norm: "token", "head" or None')
     mode = _NORM_MODES[norm]
+    rows, positions = _reference_table("rows", rows, x), _reference_table("positions", positions, x)
+    if rows is not None:
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= x.shape[1]):
+            raise ValueError(f"rows has an entry outside [0, {x.shape[1]})")
+        x = torch.stack([x[b, rows[b if rows.shape[0] > 1 else 0]] for b in range(x.shape[0])])
+        if positions is None:
+            positions = rows
     B, S, H, D = x.shape
+    if positions is not None and positions.shape[1] != S:
+        raise ValueError(f"positions has {positions.shape[1]} entries, the result has {S} rows")
     y = x.double()
     if mode != _cabi.LA_NORM_NONE:
         eps64 = float(torch.tensor(eps, dtype=torch.float32))                 # the kernel is handed eps as fp32
@@ -253,13 +348,14 @@ def qk_prep_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, ep
     tabs, pairs = _unpack_tables(tables, D)
     if tabs is not None and sum(pairs) > 0:
         e1, e2 = tabs[1].shape[0], tabs[2].shape[0]
-        pos = pos_offset + torch.arange(S, device=x.device)
-        if pos_offset < 0 or pos_offset + S > tabs[0].shape[0] * e1 * e2:
-            raise ValueError("pos_offset + S exceeds the grid of the tables")
+        pos = pos_offset + (torch.arange(S, device=x.device)[None] if positions is None else positions)      # (1 or B, S)
+        if pos_offset < 0 or (pos.numel() and (int(pos.min()) < 0 or int(pos.max()) >= tabs[0].shape[0] * e1 * e2)):
+            raise ValueError("pos_offset + S exceeds the grid of the tables" if positions is None else
+                             "pos_offset + positions leaves the grid of the tables")
         coords = (pos // (e1 * e2), (pos // e2) % e1, pos % e2)
-        cs = torch.cat([t.to(x.device)[c].double() for t, c in zip(tabs, coords)], dim=1)      # (S, rotated pairs, 2)
-        n = cs.shape[1]
-        cos, sin = cs[None, :, None, :, 0], cs[None, :, None, :, 1]
+        cs = torch.cat([t.to(x.device)[c].double() for t, c in zip(tabs, coords)], dim=2)      # (1 or B, S, rotated pairs, 2)
+        n = cs.shape[2]
+        cos, sin = cs[:, :, None, :, 0], cs[:, :, None, :, 1]
         pair = y[..., :2 * n].reshape(B, S, H, n, 2)
         a, b = pair[..., 0], pair[..., 1]
         rot = torch.stack((a * cos - b * sin, a * sin + b * cos), dim=-1).reshape(B, S, H, 2 * n)
@@ -272,29 +368,32 @@ E4M3_MAX = 448.0
 _TINY = 2.0 ** -100        # the smallest amax a descale is made from: its reciprocal, 448 / tiny / margin, stays finite in fp32 (0 * it = 0)
 
 
-def _qk_prep_fp8_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, descale, amax, heads_per_scale, out, store):
+def _qk_prep_fp8_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, descale, amax, heads_per_scale, out, store, rows=None,
+                      positions=None):
     """One ``la_qk_prep_fp8`` call. ``store``: quantize into ``out`` (allocated when None); otherwise the amax pass alone."""
     mode = _check_x_norm(x, norm, "qk_prep_fp8_reference")
     hps = _check_scales(x, heads_per_scale, descale, amax)
+    row_map, seqlen = _row_map(x, rows, positions)
     if store:
-        out = _e4m3_out(x, out)
+        out = _e4m3_out(x, out, seqlen)
     elif amax is None:
         raise ValueError("the amax pass needs amax_out")
     if x.stride(-1) != 1 or (store and out.stride(-1) != 1):
         raise ValueError("the last dimension of x and out must be contiguous")
-    if x.shape[0] * x.shape[1] == 0:
+    if x.shape[0] * x.shape[1] * seqlen == 0:
         return out
     _check_weight(x, weight, mode)
-    a = _prep_args(_cabi.LaQkPrepFp8Args, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs)
+    a = _prep_args(_cabi.LaQkPrepFp8Args, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs, seqlen)
     _fill_scales(a, hps, descale, amax, store)
     _call_prep("la_qk_prep_fp8", a, x, pos_offset,
-               lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}")
+               lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}", row_map)
     return out
 
 
 def qk_prep_fp8(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                 norm: Optional[str] = "token", pos_offset: int = 0, *, descale: Optional[torch.Tensor] = None,
-                amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1, out: Optional[torch.Tensor] = None,
+                rows=None, positions=None) -> torch.Tensor:
     """``qk_prep`` with a ``float8_e4m3fn`` result (``la_qk_prep_fp8``): with y the fp32 value ``qk_prep`` would round,
     ``out = e4m3(clamp(y / descale[b, h // heads_per_scale], -448, 448))``, round to nearest even, a NaN stays a NaN.
 
@@ -305,20 +404,23 @@ def qk_prep_fp8(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: flo
                      one; a NaN in the group makes it NaN). None: not computed.
     norm / tables    as ``qk_prep``; ``norm=None`` without tables is the V form (scale, clamp, cast, amax).
     out              float8_e4m3fn, same shape, rows / heads / batches on 8-byte boundaries; it must not overlap ``x``.
+    rows / positions as ``qk_prep`` (``la_qk_prep_fp8_rows``): a row's bytes depend on its source row and its position alone, the amax
+                     on no order at all.
     No host sync, no allocation besides ``out``; asynchronous on the current stream; captures into a HIP graph like ``qk_prep``."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
-    return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True)
+    return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True, rows, positions)
 
 
 def qk_prep_amax(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                  norm: Optional[str] = "token", pos_offset: int = 0, *, amax_out: Optional[torch.Tensor] = None,
-                 heads_per_scale: int = 1) -> torch.Tensor:
+                 heads_per_scale: int = 1, rows=None, positions=None) -> torch.Tensor:
     """The amax pass of ``qk_prep_fp8`` alone: x is read once, nothing else is written. Returns ``amax_out`` (B, H // heads_per_scale)
-    fp32 raised to the largest ``|y|`` of each group - the bits the quantizing call reports; None: a new zeroed tensor."""
+    fp32 raised to the largest ``|y|`` of each group - the bits the quantizing call reports; None: a new zeroed tensor.
+    ``rows`` / ``positions``: as ``qk_prep_fp8`` (the maximum is taken over the rows the map names)."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
     if amax_out is None and x.dim() == 4:
         amax_out = torch.zeros((x.shape[0], x.shape[2] // max(1, int(heads_per_scale))), dtype=torch.float32, device=x.device)
-    _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, None, amax_out, heads_per_scale, None, False)
+    _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, None, amax_out, heads_per_scale, None, False, rows, positions)
     return amax_out
 
 
@@ -331,10 +433,10 @@ def descale_from_amax(amax: torch.Tensor, margin: float = 1.0, out: Optional[tor
 
 def qk_prep_fp8_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                           norm: Optional[str] = "token", pos_offset: int = 0, *, descale: Optional[torch.Tensor] = None,
-                          heads_per_scale: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+                          heads_per_scale: int = 1, rows=None, positions=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The formula of ``qk_prep_fp8`` in torch fp64: ``(clamp(y / descale, -448, 448)`` UNROUNDED, ``amax`` (B, H // heads_per_scale)
-    of the unscaled ``|y|)``, both fp64, with ``y = qk_prep_reference(...)``."""
-    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset)
+    of the unscaled ``|y|)``, both fp64, with ``y = qk_prep_reference(...)`` (``rows`` / ``positions`` included)."""
+    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset, rows=rows, positions=positions)
     B, S, H, D = y.shape
     hps = int(heads_per_scale)
     if hps < 1 or H % hps:
@@ -372,14 +474,21 @@ class E4m3Scales:
         self.amax = self.descale = self.out = None
         self.calls = 0
 
-    def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0):
+    def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None):
+        """``rows`` / ``positions``: as ``qk_prep_fp8``, for both passes. ``tiles=True`` takes no map: gather V first
+        (``TokenOrder.gather``)."""
         B, S, H, D = x.shape
         hps = self.heads_per_scale
+        mapped = dict(rows=rows, positions=positions) if rows is not None or positions is not None else {}
+        if mapped:
+            S = _row_map(x, rows, positions)[1]
         if self.tiles:
             from . import v_prep                                     # (v_prep imports this module)
             if norm is not None or weight is not None or tables is not None:
                 raise ValueError("tiles=True quantizes V as its projection wrote it: norm=None, no weight, no tables")
-        first = self.amax is None or self.out.shape != x.shape or self.out.device != x.device
+            if mapped:
+                raise ValueError("tiles=True (v_prep_tiles) takes no row map: bring V into the order first with TokenOrder.gather")
+        first = self.amax is None or tuple(self.out.shape) != (B, S, H, D) or self.out.device != x.device
         if first:
             self.amax = torch.zeros((B, H // hps), dtype=torch.float32, device=x.device)
             self.descale = torch.empty_like(self.amax)
@@ -390,7 +499,7 @@ class E4m3Scales:
                 self.out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
         if first or self.mode == "current":
             self.amax.zero_()
-            self._amax_pass(x, weight, eps, tables, norm, pos_offset, amax_out=self.amax, heads_per_scale=hps)
+            self._amax_pass(x, weight, eps, tables, norm, pos_offset, amax_out=self.amax, heads_per_scale=hps, **mapped)
         descale_from_amax(self.amax, self.margin, out=self.descale)
         collect = None
         if self.mode == "delayed":                               # this step's amax, for the next step's descale
@@ -400,7 +509,7 @@ class E4m3Scales:
             v_prep.v_prep_tiles(x, descale=self.descale, amax_out=collect, out=self.out)
         else:
             self._quant_pass(x, weight, eps, tables, norm, pos_offset, descale=self.descale, amax_out=collect, heads_per_scale=hps,
-                             out=self.out)
+                             out=self.out, **mapped)
         self.calls += 1
         return self.out, self.descale
 
@@ -418,10 +527,11 @@ def qk_prep_smooth_parts(seqlen: int, num_heads: int, head_dim: int) -> Tuple[in
 
 
 def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, shift, descale, amax, heads_per_scale, colsum_part,
-                         dot_vec, heads_per_dot, dot_out, out, store):
+                         dot_vec, heads_per_dot, dot_out, out, store, rows=None, positions=None):
     """One ``la_qk_prep_smooth`` call. ``store``: quantize into ``out`` (allocated when None)."""
     mode = _check_x_norm(x, norm, "qk_prep_smooth_reference")
-    B, S, H, D = x.shape
+    B, _, H, D = x.shape
+    row_map, S = _row_map(x, rows, positions)                    # S: rows of the result - of out, of dot_out and of the parts
     hps, hpd = _check_scales(x, heads_per_scale, descale, amax), int(heads_per_dot)
     if shift is not None:
         _f32("shift", shift, (B, H, D), x.device)
@@ -440,7 +550,7 @@ def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, s
             raise ValueError("dot_out must be contiguous")
     elif dot_out is not None:
         raise ValueError("dot_out needs dot_vec")
-    if B * S == 0:
+    if B * S * x.shape[1] == 0:
         return out
     if colsum_part is not None:
         n_parts, _ = qk_prep_smooth_parts(S, H, D)
@@ -448,13 +558,13 @@ def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, s
         if not colsum_part.is_contiguous():
             raise ValueError("colsum_part must be contiguous")
     if store:
-        out = _e4m3_out(x, out)
+        out = _e4m3_out(x, out, S)
     elif amax is None and colsum_part is None and dot_out is None:
         raise ValueError("a pass that stores nothing needs amax_out, colsum_part or dot_vec")
     if x.stride(-1) != 1 or (store and out.stride(-1) != 1):
         raise ValueError("the last dimension of x and out must be contiguous")
     _check_weight(x, weight, mode)
-    a = _prep_args(_cabi.LaQkPrepSmoothArgs, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs)
+    a = _prep_args(_cabi.LaQkPrepSmoothArgs, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs, S)
     _fill_scales(a, hps, descale, amax, store)
     a.heads_per_dot = hpd
     if shift is not None:
@@ -466,7 +576,7 @@ def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, s
         a.dot_out = dot_out.data_ptr()
     _call_prep("la_qk_prep_smooth", a, x, pos_offset,
                lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, heads_per_dot {hpd}, shift "
-                       f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}")
+                       f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}", row_map)
     return out
 
 
@@ -475,7 +585,7 @@ def qk_prep_smooth(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: 
                    descale: Optional[torch.Tensor] = None, amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1,
                    colsum_part: Optional[torch.Tensor] = None, dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1,
                    dot_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                   quantize: bool = True) -> Optional[torch.Tensor]:
+                   quantize: bool = True, rows=None, positions=None) -> Optional[torch.Tensor]:
     """``qk_prep_fp8`` with K smoothing (``la_qk_prep_smooth``). With y the fp32 value ``qk_prep`` would round:
 
     shift         fp32 (B, H, D): ``out`` and ``amax_out`` are taken from ``y - shift[b, h]``. Subtracting one vector from every key
@@ -487,12 +597,15 @@ def qk_prep_smooth(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: 
                   ``heads_per_dot`` = H_q // H_kv; ``lse_unshift`` then restores the LSE. ``dot_out`` None: allocated; read it from
                   the ``dot_out`` you pass.
     quantize      False: nothing is stored (a sums-only, dots-only or amax-only pass), returns None.
+    rows / positions   as ``qk_prep`` (``la_qk_prep_smooth_rows``): ``out`` and ``dot_out`` are indexed by the row of the RESULT, and the
+                  parts of ``colsum_part`` are cut from the rows of the result - the same S terms per column as the unmapped call, added
+                  in another order.
     Everything else as ``qk_prep_fp8``; with ``shift``, ``colsum_part`` and ``dot_vec`` all None it is ``qk_prep_fp8``, bit for bit."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
     if not quantize and out is not None:
         raise ValueError("quantize=False stores nothing: out must be None")
     return _qk_prep_smooth_impl(x, weight, eps, tabs, pairs, norm, pos_offset, shift, descale, amax_out, heads_per_scale, colsum_part,
-                                dot_vec, heads_per_dot, dot_out, out, bool(quantize))
+                                dot_vec, heads_per_dot, dot_out, out, bool(quantize), rows, positions)
 
 
 def colsum_finish(colsum_part: torch.Tensor, seqlen: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -512,24 +625,27 @@ def colsum_finish(colsum_part: torch.Tensor, seqlen: int, out: Optional[torch.Te
 
 def qk_prep_colmean(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                     norm: Optional[str] = "token", pos_offset: int = 0, *, colsum_part: Optional[torch.Tensor] = None,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, rows=None, positions=None) -> torch.Tensor:
     """The mean of y over the rows, fp32 (B, H, D): the sums-only pass of ``qk_prep_smooth`` plus ``colsum_finish``. x is read once and
-    nothing of its size is written. ``colsum_part`` / ``out``: buffers to reuse (None: allocated)."""
-    B, S, H, D = x.shape
+    nothing of its size is written. ``colsum_part`` / ``out``: buffers to reuse (None: allocated). ``rows`` / ``positions``: as
+    ``qk_prep_smooth`` (the mean over the rows the map names)."""
+    _check_x(x, "qk_prep_smooth_reference")
+    B, _, H, D = x.shape
+    S = _row_map(x, rows, positions)[1]
     if colsum_part is None:
         colsum_part = torch.empty((qk_prep_smooth_parts(S, H, D)[0], B, H, D), dtype=torch.float32, device=x.device)
-    qk_prep_smooth(x, weight, eps, tables, norm, pos_offset, colsum_part=colsum_part, quantize=False)
+    qk_prep_smooth(x, weight, eps, tables, norm, pos_offset, colsum_part=colsum_part, quantize=False, rows=rows, positions=positions)
     return colsum_finish(colsum_part, S, out=out)
 
 
 def qk_prep_smooth_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6,
                              tables: Optional[RopeTables] = None, norm: Optional[str] = "token", pos_offset: int = 0, *,
                              shift: Optional[torch.Tensor] = None, descale: Optional[torch.Tensor] = None, heads_per_scale: int = 1,
-                             dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1):
+                             dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1, rows=None, positions=None):
     """The formula of ``qk_prep_smooth`` in torch fp64, with ``y = qk_prep_reference(...)``: ``(clamp((y - shift) / descale, -448, 448)``
     UNROUNDED, the amax (B, H // heads_per_scale) of ``|y - shift|``, the mean (B, H, D) of y over the rows, the row dots (B, H, S) of y
-    with ``dot_vec`` or None``)``, all fp64."""
-    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset)
+    with ``dot_vec`` or None``)``, all fp64. ``rows`` / ``positions``: as ``qk_prep_reference``; S is the number of rows of the result."""
+    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset, rows=rows, positions=positions)
     B, S, H, D = y.shape
     hps, hpd = int(heads_per_scale), int(heads_per_dot)
     if hps < 1 or H % hps:
@@ -578,50 +694,54 @@ class SmoothedQK:
         self.q8 = self.k8 = None
         self.calls = 0
 
-    def _allocate(self, xq, xk, hps):
+    def _allocate(self, xq, xk, hps, sq, sk):
         dev = xk.device
-        B, S, Hk, D = xk.shape
-        Hq = xq.shape[2]
+        B, _, Hk, D = xk.shape
+        S, Hq = sk, xq.shape[2]
         f32 = dict(dtype=torch.float32, device=dev)
-        self.q8 = torch.empty(xq.shape, dtype=torch.float8_e4m3fn, device=dev)
-        self.k8 = torch.empty(xk.shape, dtype=torch.float8_e4m3fn, device=dev)
+        self.q8 = torch.empty(_out_shape(xq, sq), dtype=torch.float8_e4m3fn, device=dev)
+        self.k8 = torch.empty(_out_shape(xk, sk), dtype=torch.float8_e4m3fn, device=dev)
         self.amax_q, self.amax_k = torch.zeros((B, Hq // hps), **f32), torch.zeros((B, Hk), **f32)
         self.dq, self.dk = torch.empty_like(self.amax_q), torch.empty_like(self.amax_k)
         self.part = torch.empty((qk_prep_smooth_parts(S, Hk, D)[0], B, Hk, D), **f32)
         self.mean = torch.empty((B, Hk, D), **f32)
-        self.lse_shift = torch.empty((B, Hq, xq.shape[1]), **f32)
+        self.lse_shift = torch.empty((B, Hq, sq), **f32)
 
-    def pair(self, xq, xk, wq=None, wk=None, eps=1e-6, tables=None, norm="token", pos_offset=0):
+    def pair(self, xq, xk, wq=None, wk=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None):
+        """``rows`` / ``positions``: one map for q and k (self-attention: both in the same order), as ``qk_prep_smooth``."""
         Hq, Hk = xq.shape[2], xk.shape[2]
         if Hq % Hk:
             raise ValueError(f"{Hq} query heads are no multiple of {Hk} key heads")
         hps = Hq // Hk if self.heads_per_scale is None else int(self.heads_per_scale)
         if hps != Hq // Hk:
             raise ValueError(f"heads_per_scale of q must be H_q // H_kv = {Hq // Hk} (the attention call takes descales per kv head)")
-        first = self.q8 is None or self.q8.shape != xq.shape or self.k8.shape != xk.shape or self.k8.device != xk.device
+        m = dict(rows=rows, positions=positions)
+        sq, sk = _row_map(xq, rows, positions)[1], _row_map(xk, rows, positions)[1]
+        first = (self.q8 is None or tuple(self.q8.shape) != _out_shape(xq, sq) or tuple(self.k8.shape) != _out_shape(xk, sk)
+                 or self.k8.device != xk.device)
         if first:
-            self._allocate(xq, xk, hps)
+            self._allocate(xq, xk, hps, sq, sk)
         args_q, args_k = (xq, wq, eps, tables, norm, pos_offset), (xk, wk, eps, tables, norm, pos_offset)
         if first or self.mode == "current":
-            qk_prep_colmean(*args_k, colsum_part=self.part, out=self.mean)
+            qk_prep_colmean(*args_k, colsum_part=self.part, out=self.mean, **m)
             self.amax_k.zero_()
-            qk_prep_smooth(*args_k, shift=self.mean, amax_out=self.amax_k, quantize=False)
+            qk_prep_smooth(*args_k, shift=self.mean, amax_out=self.amax_k, quantize=False, **m)
             descale_from_amax(self.amax_k, self.margin, out=self.dk)
-            qk_prep_smooth(*args_k, shift=self.mean, descale=self.dk, out=self.k8)
+            qk_prep_smooth(*args_k, shift=self.mean, descale=self.dk, out=self.k8, **m)
             self.amax_q.zero_()
-            qk_prep_amax(*args_q, amax_out=self.amax_q, heads_per_scale=hps)
+            qk_prep_amax(*args_q, amax_out=self.amax_q, heads_per_scale=hps, **m)
             descale_from_amax(self.amax_q, self.margin, out=self.dq)
             qk_prep_smooth(*args_q, descale=self.dq, heads_per_scale=hps, dot_vec=self.mean, heads_per_dot=hps, dot_out=self.lse_shift,
-                           out=self.q8)
+                           out=self.q8, **m)
         else:
             descale_from_amax(self.amax_k, self.margin, out=self.dk)
             descale_from_amax(self.amax_q, self.margin, out=self.dq)
             self.amax_k.zero_()
             self.amax_q.zero_()
-            qk_prep_smooth(*args_k, shift=self.mean, descale=self.dk, amax_out=self.amax_k, colsum_part=self.part, out=self.k8)
+            qk_prep_smooth(*args_k, shift=self.mean, descale=self.dk, amax_out=self.amax_k, colsum_part=self.part, out=self.k8, **m)
             qk_prep_smooth(*args_q, descale=self.dq, amax_out=self.amax_q, heads_per_scale=hps, dot_vec=self.mean, heads_per_dot=hps,
-                           dot_out=self.lse_shift, out=self.q8)
-            colsum_finish(self.part, xk.shape[1], out=self.mean)          # behind q's read of the mean this step used
+                           dot_out=self.lse_shift, out=self.q8, **m)
+            colsum_finish(self.part, sk, out=self.mean)                   # behind q's read of the mean this step used
         self.calls += 1
         return self.q8, self.k8, self.dq, self.dk, self.lse_shift
 
