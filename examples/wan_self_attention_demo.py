@@ -36,6 +36,7 @@ from lite_attention import qk_prep, rope_tables  # noqa: E402  (the fused q / k 
 from lite_attention import E4m3Scales  # noqa: E402  (its e4m3 form with per-head scales: fp8=True)
 from lite_attention import SmoothedQK  # noqa: E402  (... with the keys mean-shifted before they are quantized: smooth_k=True)
 from lite_attention import SmoothedV  # noqa: E402  (... and V: smooth_v=True; the attention call adds the mean back to its output)
+from lite_attention import attn_out_fp8, attn_unshift  # noqa: E402  (O restored as row-scaled e4m3 for an fp8 output projection: fp8_oproj=True)
 from lite_attention import brick_order  # noqa: E402  (token orders: the block on 3-D bricks of the latent grid instead of raster stripes)
 
 
@@ -71,9 +72,28 @@ def rope_3d(x, grid, theta=10000.0):
     return torch.cat(out, dim=-1).type_as(x)
 
 
+def fp8_linear(r, linear):
+    """`linear` on a RowScaledE4m3 activation (one scale per token), its weight quantized per OUTPUT channel in torch:
+    `torch._scaled_mm` with row-wise scales where this torch / ROCm accepts the call, else the two operands dequantised and a
+    matmul. Returns (y fp32, which of the two ran)."""
+    a, sa = r.as_matrix()                                           # (B * S, H * D) e4m3, (B * S, 1) fp32
+    w = linear.weight.float()                                       # (out, in)
+    sw = w.abs().amax(dim=1, keepdim=True).clamp_min(2.0 ** -100) / 448.0
+    w8 = (w / sw).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    try:
+        y = torch._scaled_mm(a, w8.t(), scale_a=sa, scale_b=sw.t().contiguous(), out_dtype=torch.bfloat16).float()
+        how = "torch._scaled_mm with row-wise scales"
+    except Exception as e:                                          # this build has no row-wise form: the same product, dequantised
+        y = (a.float() * sa) @ (w8.float() * sw).t()
+        how = f"dequantise + matmul (torch._scaled_mm refused: {type(e).__name__})"
+    if linear.bias is not None:
+        y = y + linear.bias.float()
+    return y.view(*r.data.shape[:2], -1), how
+
+
 class WanLikeSelfAttention(nn.Module):
     def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1, fused_prep=False, *, fp8=False,
-                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False):
+                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, fp8_oproj=False):
         super().__init__()
         assert dim % num_heads == 0
         self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
@@ -88,6 +108,9 @@ class WanLikeSelfAttention(nn.Module):
         # smooth_v: v goes through a SmoothedV; the attention call restores O (v_shift) and hands it on in fp32 (out_dtype)
         assert fp8 or not smooth_v, "smooth_v is a form of the fp8 path"
         self.smoothed_v = SmoothedV(mode=fp8_mode, margin=fp8_margin, tiles=v_tiles) if smooth_v else None
+        # fp8_oproj: the restoring pass writes row-scaled e4m3 (attn_out_fp8) and the output projection runs on it (fp8_linear)
+        assert fp8 or not fp8_oproj, "fp8_oproj is a form of the fp8 path"
+        self.fp8_oproj, self.oproj_how, self.oproj_error = fp8_oproj, None, None
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim), RMSNorm(dim)
         # the recipe: ONE LiteAttention per attention layer (its skip lists are that layer's state)
@@ -107,6 +130,17 @@ class WanLikeSelfAttention(nn.Module):
             else:
                 q, dq = self.scales[0](self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables)
                 k, dk = self.scales[1](self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables)
+            if self.fp8_oproj:
+                v_shift = None
+                if self.smoothed_v is not None:
+                    v, dv, v_shift = self.smoothed_v(self.v(x).view(b, s, n, d))
+                else:
+                    v, dv = self.scales[2](self.v(x).view(b, s, n, d), norm=None)
+                o, lse = self.lite_attention(q, k, v, q_descale=dq, k_descale=dk, v_descale=dv, return_softmax_lse=True)
+                y, self.oproj_how = fp8_linear(attn_out_fp8(o, v_shift, lse=lse), self.o)       # one scale per token
+                y16 = self.o(attn_unshift(o, v_shift, lse=lse).float().flatten(2))             # the bf16 path, for the comparison
+                self.oproj_error = ((y - y16).abs().max() / y16.abs().max()).item()
+                return y
             if self.smoothed_v is not None:                         # the block's .float() becomes the restoring pass' out_dtype
                 v, dv, v_shift = self.smoothed_v(self.v(x).view(b, s, n, d))
                 return self.o(self.lite_attention(q, k, v, q_descale=dq, k_descale=dk, v_descale=dv, v_shift=v_shift,
@@ -172,7 +206,7 @@ class WanLikeCrossAttention(nn.Module):
 
 
 def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False, *,
-        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, bricks=None):
+        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, bricks=None, fp8_oproj=False):
     """bricks: None (raster order), or the brick levels of `brick_order` - the blocks then run in that order (fused prologue) and the
     rows gain a fourth entry, the largest difference of the dense block's attention output to its raster run."""
     torch.manual_seed(seed)
@@ -182,7 +216,8 @@ def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0,
     if bricks is not None:
         assert not fp8, "--brick-order runs the bf16 block"
         fused_prep, order = True, brick_order(grid, bricks, device=device)
-    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v, v_tiles=v_tiles)
+    kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v, v_tiles=v_tiles,
+              fp8_oproj=fp8_oproj)
     sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep, **kw).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
     # under which tokens of the same frame attend to each other
@@ -214,6 +249,8 @@ def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0,
             rows.append((t, skipped, err) if order is None else (t, skipped, err, diff))
             if verbose:
                 print(f"step {t}: tiles skipped by the NEXT step {skipped:6.1%}   max rel. error vs dense block {err:.2e}")
+                if fp8_oproj:
+                    print(f"step {t}: fp8 output projection ({dense.oproj_how}): max rel. error vs the bf16 path {dense.oproj_error:.2e}")
                 if order is not None:
                     print(f"step {t}: brick order {order.bricks}: max abs difference to the raster run {diff:.3e} (tolerance {tol:.3e})")
     return rows
@@ -242,6 +279,8 @@ if __name__ == "__main__":
                     "the attention call adds it back and returns fp32")
     ap.add_argument("--v-tiles", action="store_true", help="with --fp8: quantize V straight into the V^T tiles the e4m3 forward stages "
                     "(v_prep_tiles through E4m3Scales / SmoothedV with tiles=True): no e4m3 V tensor, no prepare pass in the call")
+    ap.add_argument("--fp8-oproj", action="store_true", help="with --fp8: the attention output restored and row-scaled to e4m3 in one "
+                    "pass (attn_out_fp8) and the output projection on it, its weight quantized per output channel in torch")
     ap.add_argument("--brick-order", nargs="*", metavar="BT,BH,BW", default=None, help="run the block on the tokens in brick order "
                     "(brick levels, outermost first; none given: 1,16,16 1,8,8): gather once on entry, positions= in the fused prologue, "
                     "restore at the exit; prints the difference to the raster run")
@@ -251,7 +290,8 @@ if __name__ == "__main__":
         if a.fp8:
             ap.error("--brick-order runs the bf16 block (the e4m3 forms take positions= alike: INTEGRATION.md 1h)")
         bricks = tuple(tuple(int(v) for v in level.split(",")) for level in a.brick_order) or ((1, 16, 16), (1, 8, 8))
-    if (a.smooth_k or a.smooth_v or a.v_tiles) and not a.fp8:
-        ap.error("--smooth-k, --smooth-v and --v-tiles need --fp8")
+    if (a.smooth_k or a.smooth_v or a.v_tiles or a.fp8_oproj) and not a.fp8:
+        ap.error("--smooth-k, --smooth-v, --v-tiles and --fp8-oproj need --fp8")
     run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep, fp8=a.fp8, fp8_mode=a.fp8_mode,
-        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v, v_tiles=a.v_tiles, bricks=bricks)
+        fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v, v_tiles=a.v_tiles, bricks=bricks,
+        fp8_oproj=a.fp8_oproj)

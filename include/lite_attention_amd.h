@@ -630,6 +630,65 @@ typedef struct la_attn_unshift_args {
 } la_attn_unshift_args;
 int la_attn_unshift(const la_attn_unshift_args* args, void* stream);
 
+/* la_attn_unshift_fp8 (added under ABI 9: a host detects it by symbol): la_attn_unshift with a row-scaled e4m3 result - the activation
+ * of an fp8 output projection in one read of O and one 1-byte write. Everything la_attn_unshift does comes first, in its order and in
+ * fp32, and nothing is rounded before the e4m3 conversion:
+ *   y[h][:]          = float(o[b][s][h][:]) + shift[b][h / heads_per_vec][:]      one fp32 addition; shift NULL: nothing is added
+ *   y[h][:]          = 0 when lse is given and lse[b][h][s] is +inf or -inf          the empty-row rule, per head; a NaN lse: the normal path
+ *   lse_out[b][h][s] = fmaf(softmax_scale, lse_dot[b][h][s], lse[b][h][s])          only when lse_dot is given; an empty row keeps its lse
+ * Heads share scales in groups of heads_per_scale (a divisor of num_heads), g = h / heads_per_scale.
+ * DYNAMIC mode (descale_in NULL):
+ *   amax             = max |y| over the heads_per_scale * head_dim elements of (b, s, g), as the unsigned maximum of the bit patterns:
+ *                      order free, and any NaN wins
+ *   row_descale[b][s][g] = max(amax, 2^-100) / 448       one IEEE division; fp32, by its own batch / row / group strides (elements)
+ *   out              = e4m3fn_rne(clamp(y * (1 / row_descale[b][s][g]), -448, +448))     one IEEE division per (b, s, g); a NaN stays
+ *   a NaN among the elements of a group makes that group's descale and its bytes NaN - no other group's, no other token's. No atomics;
+ *   the order of the reduction is a function of the shape: two launches agree bit for bit. heads_per_scale == num_heads gives one
+ *   scale per token, the row-wise scale of a scaled GEMM over H * D. amax is not read.
+ * STATIC mode (descale_in given: fp32 [B] by descale_in_batch_stride, 0 = one element for every batch):
+ *   out              = e4m3fn_rne(clamp(y * (1 / descale_in[b]), -448, +448)); row_descale is neither read nor written.
+ *   amax             optional fp32 [B] by amax_batch_stride: amax[b] = max(amax[b], max |y| of the batch) as the unsigned maximum of the
+ *                    bit patterns, la_qk_prep_fp8's semantics (zero it first for this call's maximum; any NaN wins; one integer
+ *                    atomicMax per workgroup, no float atomics).
+ * o bf16 / fp16 (B, S, H, D) and out e4m3 (B, S, H, D), each by its own strides (elements), last dimension contiguous; rows, heads and
+ * batches of o start on 16-byte boundaries, those of out on 8-byte boundaries. There is NO in-place form. A scale group stays in the
+ * registers of one wave between the reduction and the store: heads_per_scale * head_dim <= 16384 (LA_NORM_TOKEN's limit in la_qk_prep).
+ * Errors (all before any HIP call), in this order: NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; NULL o or out, row_descale
+ * and descale_in both NULL, exactly one of lse_dot / lse_out, or the two without lse, LA_ERR_NULL_ARG; o_dtype not bf16 / fp16
+ * LA_ERR_DTYPE; a non-positive size, (with shift) heads_per_vec below 1 or not a divisor of num_heads, or heads_per_scale below 1 or
+ * not a divisor of num_heads, LA_ERR_SHAPE; head_dim % 8 != 0 LA_ERR_HEAD_DIM; a negative stride of o, out or shift, o or shift off a
+ * 16-byte boundary, out off an 8-byte one, a used stride of them that takes a row, head or batch start off one, LA_ERR_STRIDE; lse,
+ * lse_dot, lse_out, row_descale, descale_in or amax off a 4-byte boundary, or a negative stride of the last three, LA_ERR_STRIDE;
+ * out == o LA_ERR_UNSUPPORTED; heads_per_scale * head_dim above 16384, or more than 1024 heads (a workgroup keeps the empty-row flags
+ * of every head of its 32 rows in LDS), LA_ERR_UNSUPPORTED; more than 2^31 - 1 tiles (B * ceil(S / 32), one workgroup each)
+ * LA_ERR_SHAPE. NOT detected: any other overlap of out and o, a row_descale shorter than its strides say, a descale_in that is zero,
+ * negative or not finite. */
+typedef struct la_attn_unshift_fp8_args {
+    uint32_t struct_size;        /* = sizeof(la_attn_unshift_fp8_args)                            */
+    int32_t  o_dtype;            /* la_dtype of o: LA_DTYPE_BF16 or LA_DTYPE_FP16                 */
+    int32_t  heads_per_vec;      /* query heads that share one shift row: H_q / H_kv              */
+    int32_t  heads_per_scale;    /* heads that share one scale; divides num_heads                 */
+    const void* o;               /* (B, S, H, D), last dimension contiguous                       */
+    void*       out;             /* e4m3 (B, S, H, D) by its own strides; never o                 */
+    int64_t o_batch_stride, o_row_stride, o_head_stride;          /* in elements                  */
+    int64_t out_batch_stride, out_row_stride, out_head_stride;
+    int32_t batch, seqlen, num_heads, head_dim;
+    const float* shift;          /* fp32 [B, H / heads_per_vec, D] by the strides below; NULL = no shift */
+    int64_t shift_batch_stride, shift_head_stride;
+    const float* lse;            /* fp32 [B, H, S] contiguous; NULL = no empty-row rule           */
+    const float* lse_dot;        /* fp32 [B, H, S] contiguous; given exactly when lse_out is      */
+    float*       lse_out;        /* fp32 [B, H, S] contiguous; may be lse                         */
+    float   softmax_scale;       /* the one given to la_fwd                                       */
+    int32_t reserved0;           /* 0                                                              */
+    float*  row_descale;         /* fp32 [B, S, H / heads_per_scale] by the strides below: written in the dynamic mode */
+    int64_t row_descale_batch_stride, row_descale_row_stride, row_descale_group_stride;
+    const float* descale_in;     /* fp32 [B] by the stride below (0: one element); given = the static mode */
+    int64_t descale_in_batch_stride;
+    float*  amax;                /* fp32 [B] by the stride below, accumulated, static mode only; NULL = not wanted */
+    int64_t amax_batch_stride;
+} la_attn_unshift_fp8_args;
+int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* args, void* stream);
+
 /* fp8 V in one pass. la_fwd's e4m3 kernels do not read V (B, Sk, Hk, D): they stage pre-transposed, pre-swizzled V^T tiles
  * [B, Hk, ceil(Sk / 64)][head_dim (96: 128 rows, the last 32 zeros)][64 keys] from the front of the workspace, which la_fwd's prepare pass
  * writes from the e4m3 V unless LA_FLAG_V_PREPARED says they are there. la_v_prep_tiles writes the same bytes from V as its projection

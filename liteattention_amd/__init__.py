@@ -30,6 +30,7 @@ if not _BUILDING:
     from .v_prep import (SmoothedV, attn_unshift, attn_unshift_reference, v_colstats, v_colstats_parts,  # noqa: E402
                          v_colstats_reference, v_shift_as_bias)
     from .v_prep import PreparedV, v_prep_tiles, v_prep_tiles_reference, v_tiles_bytes  # noqa: E402
+    from .v_prep import RowScaledE4m3, attn_out_fp8, attn_out_fp8_reference  # noqa: E402
     from .token_order import TokenOrder, brick_order  # noqa: E402
     from .parallel import (HeadShardedLiteAttention, RingSeqParallelLiteAttention,  # noqa: E402
                            UlyssesLiteAttention)
@@ -43,5 +44,6 @@ __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flas
            "qk_prep_smooth", "qk_prep_colmean", "colsum_finish", "qk_prep_smooth_parts", "qk_prep_smooth_reference", "lse_unshift", "SmoothedQK",
            "v_colstats", "v_colstats_parts", "v_colstats_reference", "attn_unshift", "attn_unshift_reference", "v_shift_as_bias", "SmoothedV",
            "v_prep_tiles", "v_prep_tiles_reference", "v_tiles_bytes", "PreparedV",
+           "attn_out_fp8", "attn_out_fp8_reference", "RowScaledE4m3",
            "TokenOrder", "brick_order",
            "HeadShardedLiteAttention", "UlyssesLiteAttention", "RingSeqParallelLiteAttention", "__version__"]

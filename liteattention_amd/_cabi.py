@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "la_qk_prep_smooth", "la_qk_prep_smooth_parts", "la_qk_prep_smooth_part_rows", "la_colsum_finish",
     "la_v_colstats", "la_v_colstats_parts", "la_v_colstats_part_rows", "la_v_colstats_finish", "la_attn_unshift",
     "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes", "la_fwd_head_thr", "la_skip_list_stats_heads",
-    "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows",
+    "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows", "la_attn_unshift_fp8",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -132,6 +132,18 @@ class LaAttnUnshiftArgs(ctypes.Structure):
         ("shift", ctypes.c_void_p), ("shift_batch_stride", ctypes.c_int64), ("shift_head_stride", ctypes.c_int64),
         ("lse", ctypes.c_void_p), ("lse_dot", ctypes.c_void_p), ("lse_out", ctypes.c_void_p),
         ("softmax_scale", ctypes.c_float), ("reserved0", ctypes.c_int32),
+    ]
+
+
+class LaAttnUnshiftFp8Args(ctypes.Structure):
+    """Mirror of ``la_attn_unshift_fp8_args``: ``la_attn_unshift_args`` with ``heads_per_scale`` for ``out_dtype``, then the scales."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("o_dtype", ctypes.c_int32), ("heads_per_vec", ctypes.c_int32), ("heads_per_scale", ctypes.c_int32),
+    ] + LaAttnUnshiftArgs._fields_[4:] + [
+        ("row_descale", ctypes.c_void_p), ("row_descale_batch_stride", ctypes.c_int64), ("row_descale_row_stride", ctypes.c_int64),
+        ("row_descale_group_stride", ctypes.c_int64),
+        ("descale_in", ctypes.c_void_p), ("descale_in_batch_stride", ctypes.c_int64),
+        ("amax", ctypes.c_void_p), ("amax_batch_stride", ctypes.c_int64),
     ]
 
 
@@ -294,6 +306,8 @@ def load() -> ctypes.CDLL:
     lib.la_v_colstats_finish.restype = ctypes.c_int
     lib.la_attn_unshift.argtypes = [ctypes.POINTER(LaAttnUnshiftArgs), ctypes.c_void_p]
     lib.la_attn_unshift.restype = ctypes.c_int
+    lib.la_attn_unshift_fp8.argtypes = [ctypes.POINTER(LaAttnUnshiftFp8Args), ctypes.c_void_p]
+    lib.la_attn_unshift_fp8.restype = ctypes.c_int
     lib.la_v_prep_tiles.argtypes = [ctypes.POINTER(LaVPrepTilesArgs), ctypes.c_void_p]
     lib.la_v_prep_tiles.restype = ctypes.c_int
     for fn in (lib.la_v_tiles_bytes, lib.la_v_tiles_workspace_bytes):

@@ -765,6 +765,52 @@ int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
     return launch_status(err);
 }
 
+int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_attn_unshift_fp8_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->o || !a->out || (!a->descale_in && !a->row_descale)) return LA_ERR_NULL_ARG;
+    if ((a->lse_dot != nullptr) != (a->lse_out != nullptr) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
+    if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
+    if (a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
+    if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
+    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, a->seqlen, a->num_heads) ||
+        !rows_aligned(a->out, LA_DTYPE_FP8_E4M3, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen,
+                      a->num_heads)) return LA_ERR_STRIDE;
+    if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
+                            a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
+    if ((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out) |
+         reinterpret_cast<uintptr_t>(a->row_descale) | reinterpret_cast<uintptr_t>(a->descale_in) | reinterpret_cast<uintptr_t>(a->amax)) & 3u)
+        return LA_ERR_STRIDE;
+    if (a->row_descale_batch_stride < 0 || a->row_descale_row_stride < 0 || a->row_descale_group_stride < 0 ||
+        a->descale_in_batch_stride < 0 || a->amax_batch_stride < 0) return LA_ERR_STRIDE;
+    if (a->out == a->o) return LA_ERR_UNSUPPORTED;                   // one byte for two: a chunk's bytes lie over another chunk's elements
+    // a wave keeps a scale group in registers; a workgroup the empty-row flags of every head of its rows in LDS
+    if (static_cast<int64_t>(a->heads_per_scale) * a->head_dim > la::kAttnOutFp8MaxGroup || a->num_heads > la::kAttnOutFp8MaxHeads)
+        return LA_ERR_UNSUPPORTED;
+    // one workgroup per tile of rows of a batch
+    if (static_cast<int64_t>(a->batch) * ((static_cast<int64_t>(a->seqlen) + la::kAttnOutFp8Rows - 1) / la::kAttnOutFp8Rows) > 0x7fffffffLL)
+        return LA_ERR_SHAPE;
+    la::AttnUnshiftParams p = {};
+    p.o = a->o; p.out = a->out; p.shift = a->shift; p.lse = a->lse; p.lse_dot = a->lse_dot; p.lse_out = a->lse_out;
+    p.o_bs = a->o_batch_stride; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
+    p.out_bs = a->out_batch_stride; p.out_rs = a->out_row_stride; p.out_hs = a->out_head_stride;
+    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
+    p.softmax_scale = a->softmax_scale;
+    p.heads_per_scale = a->heads_per_scale;
+    if (a->descale_in) {                                             // static: the batch's scale, an optional running maximum
+        p.descale_in = a->descale_in; p.di_bs = a->descale_in_batch_stride;
+        p.amax = a->amax; p.am_bs = a->amax_batch_stride;
+    } else {                                                         // dynamic: a scale per (token, group), written
+        p.row_descale = a->row_descale;
+        p.rd_bs = a->row_descale_batch_stride; p.rd_rs = a->row_descale_row_stride; p.rd_gs = a->row_descale_group_stride;
+    }
+    return launch_status(la::launch_attn_unshift(p, a->o_dtype, LA_DTYPE_FP8_E4M3, static_cast<hipStream_t>(stream_)));
+}
+
 // ---- fp8 V in one pass (la_prep_fp8.hip) -------------------------------------------------------------------------------------------
 int64_t la_v_tiles_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim) {
     if (batch <= 0 || num_heads_k <= 0 || seqlen_k < 0) return LA_ERR_SHAPE;

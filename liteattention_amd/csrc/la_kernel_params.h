@@ -218,7 +218,17 @@ struct AttnUnshiftParams {
     int64_t o_bs, o_rs, o_hs, out_bs, out_rs, out_hs, sh_bs, sh_hs;
     int batch, seqlen, num_heads, head_dim, heads_per_vec;
     float softmax_scale;
+    // la_attn_unshift_fp8 only (la_attn_unshift leaves them zero): out is e4m3. Scale group of head h = h / heads_per_scale.
+    float* row_descale;          // [B, S, H / heads_per_scale] by rd_bs / rd_rs / rd_gs: written in the dynamic mode (descale_in NULL)
+    const float* descale_in;     // [B] by di_bs (0: one element for every batch); given = the static mode, row_descale is not written
+    float* amax;                 // [B] by am_bs, static mode: running maximum of |y| as the unsigned maximum of its bit pattern; NULL = not wanted
+    int64_t rd_bs, rd_rs, rd_gs, di_bs, am_bs;
+    int heads_per_scale;         // >= 1, divides num_heads; heads_per_scale * head_dim <= kAttnOutFp8MaxGroup
 };
-hipError_t launch_attn_unshift(const AttnUnshiftParams& p, int o_dtype, int out_dtype, hipStream_t stream);   // 0 bf16, 1 fp16, 3 fp32 (out only)
+constexpr int kAttnOutFp8MaxGroup = 16384;   // elements of a scale group (la_attn_unshift_fp8): a wave keeps them in registers, 32 chunks of 8 a lane
+constexpr int kAttnOutFp8MaxHeads = 1024;    // heads whose empty-row flags of 32 rows a workgroup keeps in LDS
+constexpr int kAttnOutFp8Rows = 32;          // rows of a workgroup's tile: one 128-byte line of lse per head
+// out_dtype: 0 bf16, 1 fp16, 3 fp32 (la_attn_unshift), 2 e4m3 (la_attn_unshift_fp8: one workgroup per tile of kAttnOutFp8Rows rows of a batch)
+hipError_t launch_attn_unshift(const AttnUnshiftParams& p, int o_dtype, int out_dtype, hipStream_t stream);
 
 }  // namespace la

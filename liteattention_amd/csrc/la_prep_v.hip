@@ -210,10 +210,169 @@ void launch_unshift_typed(const AttnUnshiftParams& p, hipStream_t stream) {
     }
 }
 
+// la_attn_unshift_fp8: the same restoring arithmetic, then a row-scaled e4m3 store. A UNIT is one (token, scale group): n = heads_per_scale
+// * head_dim / 8 chunks, contiguous along the row when the heads are. A TEAM of `team` lanes (a power of two, at most a wave, fixed by
+// the shape: unit_team) owns a unit: lane l takes chunks l, l + team, ... - C slots, C the template's bound -, loads them all
+// before it converts the first, keeps them in registers as loaded (4 registers a chunk), reduces max |y| over the team by the xor
+// butterfly of the bit patterns (order free), makes descale and its reciprocal once, makes y again and stores 8 bytes a chunk. No LDS
+// in the reduction, no barrier, no atomics.
+// A workgroup takes kAttnOutFp8Rows consecutive rows of one batch and every head: the empty-row flags of the tile come from lse in
+// whole 128-byte lines along s (a byte per (head, row) in LDS; lse_out written on the way, as la_attn_unshift_lse_kernel does), then
+// its teams walk the tile's units in memory order. Static mode (descale_in): no reduction, the reciprocal of the batch; the running
+// maximum of the workgroup goes through four words of LDS into ONE atomicMax on the bit pattern.
+// STAGE: the batch's shift rows lie in LDS behind the flags (the launcher decides: a shift that fits). A unit reads its shift twice,
+// 32 bytes for every 16 of o, chunk after chunk: from LDS that is a short wait each, from the L2 a trip each.
+template <int DT_O, int C, bool STAGE>
+__global__ void __launch_bounds__(256) la_attn_out_fp8_kernel(const AttnUnshiftParams p, const int team) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char empty_tile[];     // [num_heads][kAttnOutFp8Rows] flags (read only with lse)
+    __shared__ unsigned wave_max[4];
+    float* const shift_tile = reinterpret_cast<float*>(empty_tile + p.num_heads * kAttnOutFp8Rows);     // [H / heads_per_vec][D]
+    const int cph = p.head_dim / 8, n = p.heads_per_scale * cph, groups = p.num_heads / p.heads_per_scale;
+    const int s_tiles = (p.seqlen + kAttnOutFp8Rows - 1) / kAttnOutFp8Rows;
+    const int b = static_cast<int>(blockIdx.x / s_tiles), s0 = static_cast<int>(blockIdx.x % s_tiles) * kAttnOutFp8Rows;
+    const int ns = p.seqlen - s0 < kAttnOutFp8Rows ? p.seqlen - s0 : kAttnOutFp8Rows;
+    if (p.lse != nullptr) {
+        for (int i = threadIdx.x; i < p.num_heads * kAttnOutFp8Rows; i += 256) {
+            const int hh = i / kAttnOutFp8Rows, ss = i % kAttnOutFp8Rows;
+            if (ss < ns) {
+                const int64_t idx = (static_cast<int64_t>(b) * p.num_heads + hh) * p.seqlen + s0 + ss;
+                const float l = p.lse[idx];
+                const bool empty = l == INFINITY || l == -INFINITY;    // a NaN takes the normal path
+                empty_tile[i] = empty;
+                if (p.lse_out != nullptr) p.lse_out[idx] = empty ? l : fmaf(p.softmax_scale, p.lse_dot[idx], l);
+            }
+        }
+    }
+    if constexpr (STAGE) {
+        const int per_head = p.head_dim / 4;
+        for (int i = threadIdx.x; i < (p.num_heads / p.heads_per_vec) * per_head; i += 256) {
+            const int hv = i / per_head, d4 = i - hv * per_head;
+            reinterpret_cast<pq_f32x4*>(shift_tile)[i] = *reinterpret_cast<const pq_f32x4*>(p.shift + b * p.sh_bs + hv * p.sh_hs + d4 * 4);
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & (team - 1), teams = 256 / team;
+    // (head of the group, chunk of the head) of the lane's first chunk, and the step from one of its chunks to the next
+    const int hh0 = lane / cph, ch0 = lane - hh0 * cph, dh = team / cph, dc = team - dh * cph;
+    const float inv_static = p.descale_in != nullptr ? __fdiv_rn(1.f, p.descale_in[b * p.di_bs]) : 0.f;
+    unsigned run_max = 0;
+    for (int u = threadIdx.x / team; u < ns * groups; u += teams) {
+        const int ss = u / groups, g = u - ss * groups, s = s0 + ss;
+        const int64_t o_row = b * p.o_bs + s * p.o_rs, out_row = b * p.out_bs + s * p.out_rs;
+        typename PrepLoad<DT_O>::raw w[C];
+        {
+            int hh = hh0, ch = ch0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                w[c] = lane + c * team < n ? PrepLoad<DT_O>::load(p.o, o_row + (g * p.heads_per_scale + hh) * p.o_hs + ch * 8)
+                                           : PrepLoad<DT_O>::zero();
+                hh += dh; ch += dc;
+                if (ch >= cph) { ch -= cph; ++hh; }
+            }
+        }
+        // y of the lane's chunk c: the restoring arithmetic of unshift_chunk. Made twice - for the maximum, then for the store - from
+        // the same registers, shift and flags by the same operations (the same bits): a lane keeps 4 registers a chunk, not 8
+        const auto restore = [&](int c, int hh, int ch, float (&y)[8]) {
+            const int h = g * p.heads_per_scale + hh;
+            PrepLoad<DT_O>::to_float(w[c], y);
+            if (STAGE || p.shift != nullptr) {
+                float sh[8];
+                if constexpr (STAGE) load_f32x8(shift_tile + (h / p.heads_per_vec) * p.head_dim + ch * 8, sh);
+                else load_f32x8(p.shift + b * p.sh_bs + (h / p.heads_per_vec) * p.sh_hs + ch * 8, sh);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y[j] += sh[j];
+            }
+            if (p.lse != nullptr && empty_tile[h * kAttnOutFp8Rows + ss]) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y[j] = 0.f;
+            }
+        };
+        float inv = inv_static;
+        if (p.descale_in == nullptr || p.amax != nullptr) {
+            unsigned m = 0;
+            int hh = hh0, ch = ch0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                if (lane + c * team < n) {
+                    float y[8];
+                    restore(c, hh, ch, y);
+                    m = umax(m, absmax8(y));
+                }
+                hh += dh; ch += dc;
+                if (ch >= cph) { ch -= cph; ++hh; }
+            }
+            if (p.descale_in == nullptr) {
+#pragma unroll
+                for (int sft = 32; sft >= 1; sft >>= 1)
+                    if (sft < team) m = umax(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), sft, 64)));
+                const float amax = __uint_as_float(m);                 // a NaN fails the compare and stays
+                const float descale = __fdiv_rn(amax < 0x1p-100f ? 0x1p-100f : amax, 448.f);
+                inv = __fdiv_rn(1.f, descale);
+                if (lane == 0) p.row_descale[b * p.rd_bs + s * p.rd_rs + g * p.rd_gs] = descale;
+            } else {
+                run_max = umax(run_max, m);
+            }
+        }
+        {
+            int hh = hh0, ch = ch0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                if (lane + c * team < n) {
+                    float y[8];
+                    restore(c, hh, ch, y);
+                    scale_clamp8(y, inv);
+                    PrepStore<2>::store8(p.out, out_row + (g * p.heads_per_scale + hh) * p.out_hs + ch * 8, y);
+                }
+                hh += dh; ch += dc;
+                if (ch >= cph) { ch -= cph; ++hh; }
+            }
+        }
+    }
+    if (p.descale_in != nullptr && p.amax != nullptr) {
+#pragma unroll
+        for (int sft = 32; sft >= 1; sft >>= 1) run_max = umax(run_max, static_cast<unsigned>(__shfl_xor(static_cast<int>(run_max), sft, 64)));
+        if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = run_max;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned wg = umax(umax(wave_max[0], wave_max[1]), umax(wave_max[2], wave_max[3]));
+            if (wg) atomicMax(reinterpret_cast<unsigned*>(p.amax + b * p.am_bs), wg);
+        }
+    }
+}
+
+// lanes of a team for n chunks a unit: the next power of two, at most a wave. A function of the shape alone.
+inline int unit_team(int n) {
+    int t = 1;
+    while (t < n && t < 64) t <<= 1;
+    return t;
+}
+
+constexpr size_t kAttnOutFp8MaxLds = 64 * 1024;      // dynamic LDS a launch may ask for without opting in to more
+
+template <int DT_O, bool STAGE>
+void launch_out_fp8_staged(const AttnUnshiftParams& p, size_t lds, hipStream_t stream) {
+    const int n = p.heads_per_scale * (p.head_dim / 8), team = unit_team(n), per_lane = (n + team - 1) / team;      // <= 32: la_api.hip
+    const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(p.batch) * ((p.seqlen + kAttnOutFp8Rows - 1) / kAttnOutFp8Rows)));
+    if (per_lane <= 1) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 1, STAGE>), grid, dim3(256), lds, stream, p, team);
+    else if (per_lane <= 4) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 4, STAGE>), grid, dim3(256), lds, stream, p, team);
+    else if (per_lane <= 10) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 10, STAGE>), grid, dim3(256), lds, stream, p, team);
+    else if (per_lane <= 16) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 16, STAGE>), grid, dim3(256), lds, stream, p, team);
+    else hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 32, STAGE>), grid, dim3(256), lds, stream, p, team);
+}
+
+template <int DT_O>
+void launch_out_fp8(const AttnUnshiftParams& p, hipStream_t stream) {
+    const size_t flags = static_cast<size_t>(p.num_heads) * kAttnOutFp8Rows;      // a multiple of 16 bytes: the shift rows behind it are aligned
+    const size_t rows = p.shift != nullptr ? static_cast<size_t>(p.num_heads / p.heads_per_vec) * p.head_dim * sizeof(float) : 0;
+    if (rows != 0 && flags + rows <= kAttnOutFp8MaxLds) launch_out_fp8_staged<DT_O, true>(p, flags + rows, stream);
+    else launch_out_fp8_staged<DT_O, false>(p, flags, stream);
+}
+
 template <int DT_O>
 void launch_unshift_o(const AttnUnshiftParams& p, int out_dtype, hipStream_t stream) {
     if (out_dtype == 0) launch_unshift_typed<DT_O, 0>(p, stream);
     else if (out_dtype == 1) launch_unshift_typed<DT_O, 1>(p, stream);
+    else if (out_dtype == 2) launch_out_fp8<DT_O>(p, stream);
     else launch_unshift_typed<DT_O, 3>(p, stream);
 }
 

@@ -213,7 +213,7 @@ class LiteAttention:
                  return_softmax_lse: bool = False, must_do_list: list = None, must_skip_list: list = None, *,
                  q_descale: Optional[Tensor] = None, k_descale: Optional[Tensor] = None,
                  v_descale: Optional[Tensor] = None, v_shift: Optional[Tensor] = None, lse_shift: Optional[Tensor] = None,
-                 out_dtype: Optional[torch.dtype] = None) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+                 out_dtype: Optional[torch.dtype] = None, out_fp8=False) -> Union[Tensor, Tuple[Tensor, Tensor]]:
         """One attention call of a denoising step (:244-291).
 
         query (B, S, H, D) bf16; key/value (B, Sk, H, D). Returns out (B, S, H, D) — the reference
@@ -227,14 +227,17 @@ class LiteAttention:
         (batch, nheads_k, D): the vector subtracted from V (``SmoothedV``), added back to O; rows without keys stay 0.
         ``lse_shift`` fp32 (batch, nheads, S): ``q . c`` of ``SmoothedQK``, folded into the returned LSE. ``out_dtype``:
         bf16 / fp16 / fp32 of the returned O (fp32: what an output projection reads).
+        ``out_fp8`` (keyword-only extension): True, or ``dict(heads_per_scale=..., descale=...)``: the restoring pass is
+        ``attn_out_fp8`` and a ``v_prep.RowScaledE4m3`` (e4m3 data, its descale: the activation of an fp8 output projection) is
+        returned in the place of O. Not together with ``out_dtype``.
         ``value`` may be a ``v_prep.PreparedV`` (``v_prep_tiles``, ``SmoothedV(tiles=True)``): e4m3 query / key, the launch runs on
         its workspace and a dense call is never split over the keys."""
         tiles = not isinstance(value, Tensor)
         if tiles:
             value.check_call(query, key)
-        restore = v_shift is not None or lse_shift is not None or out_dtype is not None
+        restore = v_shift is not None or lse_shift is not None or out_dtype is not None or out_fp8 is not False
         if restore:
-            self._check_restore(query, key, value, v_shift, lse_shift, out_dtype)
+            out_fp8 = self._check_restore(query, key, value, v_shift, lse_shift, out_dtype, out_fp8)
         self._check_head_table(query)
         read_list, write_list = self._get_read_write_lists(query, key, must_skip_list)
         must_do = None
@@ -270,7 +273,7 @@ class LiteAttention:
             self._last_percentage = self.calc_percentage(read_list[: query.shape[0]])
             print(f"[Info]: Percentage of tiles skipped: {1.0 - self._last_percentage:.2%}")
         if restore:
-            output = self._restore(output, want_lse, return_softmax_lse, scale, v_shift, lse_shift, out_dtype)
+            output = self._restore(output, want_lse, return_softmax_lse, scale, v_shift, lse_shift, out_dtype, out_fp8)
         return output
 
     def _fwd_prepared_v(self, query, key, value, scale, read_list, write_list, must_do, want_lse, q_windows=None, window_hook=None,
@@ -288,9 +291,21 @@ class LiteAttention:
         return (out, lse) if want_lse else out
 
     @staticmethod
-    def _check_restore(query, key, value, v_shift, lse_shift, out_dtype):
-        """The arguments of the restoring pass, before anything is launched."""
+    def _check_restore(query, key, value, v_shift, lse_shift, out_dtype, out_fp8=False):
+        """The arguments of the restoring pass, before anything is launched. Returns ``out_fp8`` as None (off) or the keyword
+        arguments of ``attn_out_fp8``."""
         B, S, H = query.shape[0], query.shape[1], query.shape[2]
+        if out_fp8 is False or out_fp8 is None:
+            out_fp8 = None
+        else:
+            if out_dtype is not None:
+                raise ValueError(f"out_fp8 returns e4m3: out_dtype must be None, got {out_dtype}")
+            out_fp8 = {} if out_fp8 is True else out_fp8
+            if not isinstance(out_fp8, dict) or set(out_fp8) - {"heads_per_scale", "descale"}:
+                raise ValueError(f"out_fp8: True, False or dict(heads_per_scale=..., descale=...), got {out_fp8!r}")
+            from .v_prep import _check_out_fp8
+            _check_out_fp8(torch.empty((B, S, H, value.shape[3]), device="meta"), out_fp8.get("heads_per_scale"), out_fp8.get("descale"),
+                           None)
         if v_shift is not None and (v_shift.dtype != torch.float32 or tuple(v_shift.shape) != (B, key.shape[2], value.shape[3])):
             raise ValueError(f"v_shift must be fp32 (batch, nheads_k, D) = {(B, key.shape[2], value.shape[3])}, got {v_shift.dtype} "
                              f"{tuple(v_shift.shape)}")
@@ -298,13 +313,19 @@ class LiteAttention:
             raise ValueError(f"lse_shift must be fp32 (batch, nheads, S) = {(B, H, S)}, got {lse_shift.dtype} {tuple(lse_shift.shape)}")
         if out_dtype not in (None, torch.bfloat16, torch.float16, torch.float32):
             raise ValueError(f"out_dtype: bf16, fp16 or fp32, got {out_dtype}")
+        return out_fp8
 
     @staticmethod
-    def _restore(output, have_lse, return_lse, scale, v_shift, lse_shift, out_dtype):
-        from .v_prep import attn_unshift
+    def _restore(output, have_lse, return_lse, scale, v_shift, lse_shift, out_dtype, out_fp8=None):
+        from .v_prep import attn_out_fp8, attn_unshift
         o, lse = output if have_lse else (output, None)
         in_place = out_dtype is None or out_dtype == o.dtype
         fix_lse = lse_shift is not None and return_lse
+        if out_fp8 is not None:
+            res = attn_out_fp8(o, v_shift, lse=lse, lse_dot=lse_shift if fix_lse else None, softmax_scale=scale,
+                               lse_out=lse if fix_lse else None, **out_fp8)
+            out = res[0] if fix_lse else res
+            return (out, lse) if return_lse else out
         if v_shift is None and in_place and not fix_lse:        # an LSE shift nobody asked the LSE of: nothing to do
             return (o, lse) if return_lse else o
         res = attn_unshift(o, v_shift, lse=lse, lse_dot=lse_shift if fix_lse else None, softmax_scale=scale, out=o if in_place else None,
@@ -541,14 +562,17 @@ class SeqParallelLiteAttention:
     def __call__(self, query: Tensor, key: Tensor, value: Tensor, split_idx: int, scale: Optional[float] = None,
                  return_softmax_lse: bool = False, *, q_descale: Optional[Tensor] = None, k_descale: Optional[Tensor] = None,
                  v_descale: Optional[Tensor] = None, v_shift: Optional[Tensor] = None, lse_shift: Optional[Tensor] = None,
-                 out_dtype: Optional[torch.dtype] = None) -> Union[Tensor, Tuple[Tensor, Tensor]]:
-        """``v_shift`` / ``lse_shift`` / ``out_dtype`` as ``LiteAttention.__call__``: this shard's output and LSE are restored HERE, before
-        the caller merges the shards by LSE - the shards' V means differ, and a merge would weight them."""
+                 out_dtype: Optional[torch.dtype] = None, out_fp8=False) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+        """``v_shift`` / ``lse_shift`` / ``out_dtype`` / ``out_fp8`` as ``LiteAttention.__call__``: this shard's output and LSE are
+        restored HERE, before the caller merges the shards by LSE - the shards' V means differ, and a merge would weight them.
+        (``out_fp8`` is for a shard whose output is final: e4m3 partials are not merged.)"""
         assert split_idx < self.num_nodes, "split_idx must be less than num_nodes"
         kw = {}
         for name, val in (("v_shift", v_shift), ("lse_shift", lse_shift), ("out_dtype", out_dtype)):      # only when given
             if val is not None:
                 kw[name] = val
+        if out_fp8 is not False:
+            kw["out_fp8"] = out_fp8
         if q_descale is not None or k_descale is not None or v_descale is not None:       # keyword-only extension, as LiteAttention.__call__
             kw.update(q_descale=q_descale, k_descale=k_descale, v_descale=v_descale)
         if return_softmax_lse and self.exact_fp8_lse and query.dtype == torch.float8_e4m3fn:

@@ -198,6 +198,159 @@ def attn_unshift_reference(o: torch.Tensor, shift: Optional[torch.Tensor] = None
     return out, torch.where(l64.isinf(), l64, l64 + scale * lse_dot.double())
 
 
+# ---- O restored and row-scaled to e4m3 in one pass: la_attn_unshift_fp8 ----------------------------------------------------------------
+ATTN_OUT_FP8_MAX_GROUP = 16384      # elements of a scale group (heads_per_scale * head_dim): a wave keeps them in registers
+ATTN_OUT_FP8_MAX_HEADS = 1024
+
+
+class RowScaledE4m3:
+    """What ``attn_out_fp8`` returns: ``data`` float8_e4m3fn (B, S, H, D) and ``descale`` fp32 - (B, S, H / heads_per_scale) in the
+    dynamic mode, the tensor that was given in the static one - with ``data.float() * descale`` (broadcast over a group) the restored
+    O. ``data, descale = r`` unpacks."""
+
+    __slots__ = ("data", "descale")
+
+    def __init__(self, data: torch.Tensor, descale: torch.Tensor):
+        self.data, self.descale = data, descale
+
+    def __iter__(self):
+        return iter((self.data, self.descale))
+
+    def as_matrix(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(data.view(B * S, H * D), descale.view(B * S, 1))``: the activation and the row-wise scale a scaled GEMM over H * D takes.
+        One scale per token (``heads_per_scale == H``) and contiguous tensors only; views, nothing is copied."""
+        B, S, H, D = self.data.shape
+        if tuple(self.descale.shape) != (B, S, 1):
+            raise ValueError(f"as_matrix() needs one scale per token: descale (B, S, 1) = {(B, S, 1)}, got {tuple(self.descale.shape)}")
+        if not self.data.is_contiguous() or not self.descale.is_contiguous():
+            raise ValueError("as_matrix() needs contiguous data and descale")
+        return self.data.view(B * S, H * D), self.descale.view(B * S, 1)
+
+
+def _check_out_fp8(o, heads_per_scale, descale, amax_out):
+    """Shapes and dtypes of the scale arguments of ``attn_out_fp8`` (device-free: the attention classes check with it before the
+    forward). Returns heads_per_scale (None: H, one scale per token)."""
+    B, S, H, D = o.shape
+    hps = H if heads_per_scale is None else int(heads_per_scale)
+    if hps < 1 or H % hps:
+        raise ValueError(f"heads_per_scale must divide the {H} heads, got {heads_per_scale}")
+    if hps * D > ATTN_OUT_FP8_MAX_GROUP:
+        raise NotImplementedError(f"a scale group holds at most {ATTN_OUT_FP8_MAX_GROUP} elements, got heads_per_scale * head_dim = "
+                                  f"{hps} * {D}")
+    if H > ATTN_OUT_FP8_MAX_HEADS:
+        raise NotImplementedError(f"at most {ATTN_OUT_FP8_MAX_HEADS} heads, got {H}")
+    if D % 8:
+        raise ValueError(f"head_dim must be a multiple of 8, got {D}")
+    if descale is not None:
+        if descale.dtype != torch.float32 or descale.numel() not in (1, B) or descale.dim() > 1:
+            raise ValueError(f"descale must be fp32 of {B} elements (one per batch) or of one, got {descale.dtype} {tuple(descale.shape)}")
+    if amax_out is not None:
+        if descale is None:
+            raise ValueError("amax_out is the running maximum of the static mode: it needs descale")
+        if amax_out.dtype != torch.float32 or tuple(amax_out.shape) != (B,):
+            raise ValueError(f"amax_out must be fp32 ({B},), got {amax_out.dtype} {tuple(amax_out.shape)}")
+    return hps
+
+
+def attn_out_fp8(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
+                 lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, heads_per_scale: Optional[int] = None,
+                 descale: Optional[torch.Tensor] = None, amax_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                 descale_out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None):
+    """``attn_unshift`` with a row-scaled e4m3 result: the activation of an fp8 output projection in one read of O and one 1-byte
+    write (``la_attn_unshift_fp8``). ``o``, ``shift``, ``lse``, ``lse_dot``, ``softmax_scale`` and ``lse_out`` are ``attn_unshift``'s;
+    with y the fp32 value that pass would round:
+
+        dynamic (``descale`` None)   descale[b, s, g] = max(max |y| over the group, 2^-100) / 448      g = h // heads_per_scale
+        static  (``descale`` given)  fp32 of B elements or of one: a tensor-wise, delayed scale; ``amax_out`` fp32 (B,), ACCUMULATED as
+                                     in ``qk_prep_fp8``, collects max |y| for the next step's scale (zero it for this call's)
+        data = e4m3(clamp(y * (1 / descale), -448, 448))
+
+    heads_per_scale   heads that share a scale; None: all H - ONE scale per token, what a row-wise scaled GEMM over H * D takes (not
+                      one per head). ``heads_per_scale * head_dim <= 16384``.
+    out               float8_e4m3fn (B, S, H, D) by its own strides, e.g. a view of a (B, S, H * D) buffer; never ``o`` (there is no
+                      in-place form); None: allocated.
+    descale_out       fp32 (B, S, H / heads_per_scale) by its own strides (dynamic mode); None: allocated.
+    A NaN in a group makes that group's descale and bytes NaN and no other's. Returns ``RowScaledE4m3(data, descale)``, or
+    ``(that, lse_out)`` with ``lse_dot``. No host sync; no allocation when the outputs are given; captures into a HIP graph."""
+    hpv = _check_unshift(o, shift, lse, lse_dot)
+    hps = _check_out_fp8(o, heads_per_scale, descale, amax_out)
+    _check_x(o, "attn_out_fp8_reference", "o", _UNSHIFT_IN_DTYPES, "bf16 or fp16")
+    B, S, H, D = o.shape
+    G = H // hps
+    if out is None:
+        out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=o.device)
+    if out.dtype != torch.float8_e4m3fn:
+        raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
+    if out.shape != o.shape or out.device != o.device:
+        raise ValueError(f"out must be {tuple(o.shape)} on {o.device}, got {tuple(out.shape)} on {out.device}")
+    if o.stride(-1) != 1 or out.stride(-1) != 1:
+        raise ValueError("the last dimension of o and out must be contiguous")
+    if descale is None:
+        if descale_out is None:
+            descale_out = torch.empty((B, S, G), dtype=torch.float32, device=o.device)
+        _f32("descale_out", descale_out, (B, S, G), o.device)
+    elif descale_out is not None:
+        raise ValueError("descale_out is written in the dynamic mode only: descale was given")
+    for name, t in (("shift", shift), ("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out), ("descale", descale), ("amax_out", amax_out)):
+        if t is not None and t.device != o.device:
+            raise ValueError(f"{name} lives on {t.device}, o on {o.device}")
+    if lse_dot is not None:
+        if lse_out is None:
+            lse_out = torch.empty((B, H, S), dtype=torch.float32, device=o.device)
+        _f32("lse_out", lse_out, (B, H, S), o.device)
+    elif lse_out is not None:
+        raise ValueError("lse_out needs lse_dot")
+    for name, t in (("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    res = RowScaledE4m3(out, descale_out if descale is None else descale)
+    if B * S * H * D == 0:
+        return res if lse_dot is None else (res, lse_out.copy_(lse))
+    a = _cabi.LaAttnUnshiftFp8Args()
+    a.struct_size = ctypes.sizeof(_cabi.LaAttnUnshiftFp8Args)
+    a.o_dtype, a.heads_per_vec, a.heads_per_scale = _UNSHIFT_IN_DTYPES[o.dtype], hpv, hps
+    a.o, a.out = o.data_ptr(), out.data_ptr()
+    a.o_batch_stride, a.o_row_stride, a.o_head_stride = o.stride(0), o.stride(1), o.stride(2)
+    a.out_batch_stride, a.out_row_stride, a.out_head_stride = out.stride(0), out.stride(1), out.stride(2)
+    a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
+    if shift is not None:
+        a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
+    if lse is not None:
+        a.lse = lse.data_ptr()
+    if lse_dot is not None:
+        a.lse_dot, a.lse_out = lse_dot.data_ptr(), lse_out.data_ptr()
+        a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
+    if descale is None:
+        a.row_descale = descale_out.data_ptr()
+        a.row_descale_batch_stride, a.row_descale_row_stride, a.row_descale_group_stride = descale_out.stride()
+    else:
+        a.descale_in = descale.data_ptr()
+        a.descale_in_batch_stride = descale.stride(0) if descale.numel() > 1 else 0
+        if amax_out is not None:
+            a.amax, a.amax_batch_stride = amax_out.data_ptr(), amax_out.stride(0)
+    _call("la_attn_unshift_fp8", o, lambda: f"o {tuple(o.shape)} strides {o.stride()}, out strides {out.stride()}, heads_per_scale {hps}, "
+                                            f"shift {None if shift is None else (tuple(shift.shape), shift.stride())}", ctypes.byref(a))
+    return res if lse_dot is None else (res, lse_out)
+
+
+def attn_out_fp8_reference(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
+                           lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None,
+                           heads_per_scale: Optional[int] = None, descale: Optional[torch.Tensor] = None):
+    """The formula of ``attn_out_fp8`` in torch fp64, UNROUNDED, on whatever device ``o`` lives on: ``(z, descale)`` with ``z = clamp(y /
+    descale, -448, 448)`` fp64 (B, S, H, D) - the values the kernel rounds to e4m3 - and ``descale`` fp64 (B, S, H / heads_per_scale)
+    = ``max(max |y|, 2^-100) / 448``, or the given one as fp64 (B, 1, 1); with ``lse_dot``, ``((z, descale), lse_out)``."""
+    res = attn_unshift_reference(o, shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale)
+    y, lse_new = res if lse_dot is not None else (res, None)
+    hps = _check_out_fp8(o, heads_per_scale, descale, None)
+    B, S, H, D = y.shape
+    if descale is None:
+        d = y.reshape(B, S, H // hps, hps * D).abs().amax(dim=-1).clamp_min(2.0 ** -100) / 448.0
+    else:
+        d = descale.double().to(y.device).reshape(-1, 1, 1).expand(B, 1, 1)
+    z = (y.reshape(B, S, -1, hps * D) / d[..., None]).clamp(-448.0, 448.0).reshape(B, S, H, D)
+    return (z, d) if lse_dot is None else ((z, d), lse_new)
+
+
 def v_shift_as_bias(weight: torch.Tensor, bias: Optional[torch.Tensor], shift: torch.Tensor,
                     dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """The zero-pass alternative to ``attn_unshift`` when nothing between the attention and its output projection needs the true O:
@@ -388,7 +541,7 @@ class SmoothedV:
         if not margin > 0:
             raise ValueError("margin must be positive")
         self.mode, self.margin, self.tiles = mode, float(margin), bool(tiles)
-        self.v8 = self.shift = self.out = None
+        self.v8 = self.shift = self.out = self.out8 = self.out_descale = None
         self.calls = 0
 
     def _allocate(self, xv):
@@ -428,13 +581,33 @@ class SmoothedV:
         return self.v8, self.dv, self.shift
 
     def finish(self, o: torch.Tensor, lse: Optional[torch.Tensor] = None, lse_dot: Optional[torch.Tensor] = None,
-               softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None):
+               softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+               *, fp8: bool = False, heads_per_scale: Optional[int] = None, descale: Optional[torch.Tensor] = None):
         """``attn_unshift(o, shift, ...)`` with the shift of the last call. ``out`` None: ``o`` itself when ``out_dtype`` is None or
         ``o.dtype`` (in place: the attention call's result is overwritten), else a buffer of ``out_dtype`` this object keeps. With
         ``lse_dot`` (K smoothed too) the LSE is restored in place and ``(out, lse)`` is returned. Pass ``lse`` whenever the call may
-        have had no keys."""
+        have had no keys.
+        ``fp8=True``: ``attn_out_fp8(o, shift, ..., heads_per_scale=, descale=)`` instead - a ``RowScaledE4m3`` whose buffers this
+        object keeps (``out``: the e4m3 tensor to write; ``out_dtype`` must be None)."""
         if self.shift is None:
             raise RuntimeError("finish() before the first call: there is no shift yet")
+        if fp8:
+            if out_dtype is not None:
+                raise ValueError("fp8=True writes e4m3: out_dtype must be None")
+            _check_unshift(o, self.shift, lse, lse_dot)
+            hps = _check_out_fp8(o, heads_per_scale, descale, None)
+            if out is None:
+                if self.out8 is None or self.out8.shape != o.shape or self.out8.device != o.device:
+                    self.out8 = torch.empty(o.shape, dtype=torch.float8_e4m3fn, device=o.device)
+                out = self.out8
+            want = (o.shape[0], o.shape[1], o.shape[2] // hps)
+            if descale is None and (self.out_descale is None or tuple(self.out_descale.shape) != want or self.out_descale.device != o.device):
+                self.out_descale = torch.empty(want, dtype=torch.float32, device=o.device)
+            return attn_out_fp8(o, self.shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, heads_per_scale=hps, descale=descale,
+                                out=out, descale_out=self.out_descale if descale is None else None,
+                                lse_out=lse if lse_dot is not None else None)
+        if heads_per_scale is not None or descale is not None:
+            raise ValueError("heads_per_scale and descale belong to fp8=True")
         if out is None:
             if out_dtype is None or out_dtype == o.dtype:
                 out = o
@@ -492,6 +665,33 @@ def _attn_unshift_meta(o, shift=None, lse=None, lse_dot=None, softmax_scale=None
     return out if out is not None else torch.empty(o.shape, dtype=o.dtype if out_dtype is None else out_dtype, device=o.device)
 
 
+_ATTN_OUT_FP8_SCHEMA = ("attn_out_fp8(Tensor o, Tensor? shift = None, Tensor? lse = None, Tensor? lse_dot = None, "
+                        "float? softmax_scale = None, int? heads_per_scale = None, Tensor? descale = None, "
+                        "Tensor(amax!)? amax_out = None, Tensor(out!)? out = None, Tensor(ds!)? descale_out = None, "
+                        "Tensor(lse_out!)? lse_out = None) -> (Tensor, Tensor)")
+
+
+def _attn_out_fp8_op(o, shift=None, lse=None, lse_dot=None, softmax_scale=None, heads_per_scale=None, descale=None, amax_out=None,
+                     out=None, descale_out=None, lse_out=None):
+    """The op returns ``(data, descale)``; with ``lse_dot`` it wants ``lse_out`` too and writes the LSE there. What it returns are new
+    tensors on the given storage (an op may not return its arguments)."""
+    if lse_dot is not None and lse_out is None:
+        raise ValueError("the op writes the LSE into lse_out: give it")
+    res = attn_out_fp8(o, shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, heads_per_scale=heads_per_scale, descale=descale,
+                       amax_out=amax_out, out=out, descale_out=descale_out, lse_out=lse_out)
+    res = res if lse_dot is None else res[0]
+    return res.data.view(res.data.shape), res.descale.view(res.descale.shape)
+
+
+def _attn_out_fp8_meta(o, shift=None, lse=None, lse_dot=None, softmax_scale=None, heads_per_scale=None, descale=None, amax_out=None,
+                       out=None, descale_out=None, lse_out=None):
+    """Shapes and dtypes only."""
+    B, S, H, _ = o.shape
+    hps = H if heads_per_scale is None else heads_per_scale
+    return (torch.empty(o.shape, dtype=torch.float8_e4m3fn, device=o.device),
+            torch.empty((B, S, H // hps) if descale is None else descale.shape, dtype=torch.float32, device=o.device))
+
+
 def _register_op():
     global _op_lib
     if _op_lib is not None:
@@ -504,6 +704,9 @@ def _register_op():
     lib.define(_ATTN_UNSHIFT_SCHEMA)
     lib.impl("attn_unshift", _attn_unshift_op, "CUDA")
     lib.impl("attn_unshift", _attn_unshift_meta, "Meta")
+    lib.define(_ATTN_OUT_FP8_SCHEMA)
+    lib.impl("attn_out_fp8", _attn_out_fp8_op, "CUDA")
+    lib.impl("attn_out_fp8", _attn_out_fp8_meta, "Meta")
     lib.define(_V_PREP_TILES_SCHEMA)
     lib.impl("v_prep_tiles", _v_prep_tiles_op, "CUDA")
     lib.impl("v_prep_tiles", _v_prep_tiles_meta, "Meta")
