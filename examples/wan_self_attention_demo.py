@@ -10,7 +10,8 @@ per layer, the skip state carried across denoising steps.
 
 `--fused-prep` (`fused_prep=True` on the modules): RMSNorm, RoPE and the bf16 cast of q and k run as ONE pass each (`qk_prep`) instead of
 the eager lines below. `--fp8 --smooth-k`: each key head's mean over the tokens is subtracted before the e4m3 cast (`SmoothedQK`); the
-output needs no correction. `--fp8 --smooth-v` (combinable with `--smooth-k`): the same for V (`SmoothedV`); the mean is added back to
+output needs no correction. `--fp8 [--smooth-k] --rotate`: every head of q and k is multiplied by one signed Hadamard matrix before
+the cast (`head_rotation`; the same object for both, so the scores stand). `--fp8 --smooth-v` (combinable with `--smooth-k`): the same for V (`SmoothedV`); the mean is added back to
 the attention output by the restoring pass, which also replaces the block's `.float()` (`out_dtype=torch.float32`).
 `--fp8 [--smooth-v] --v-tiles`: V is quantized straight into the V^T tiles the e4m3 forward stages (`v_prep_tiles`) and handed to the
 attention call as a `PreparedV`: the same codes, no e4m3 V tensor. (The block with skipping disabled is then never split over the
@@ -35,6 +36,7 @@ from lite_attention import LiteAttention  # noqa: E402  (same import line as the
 from lite_attention import qk_prep, rope_tables  # noqa: E402  (the fused q / k prologue: fused_prep=True)
 from lite_attention import E4m3Scales  # noqa: E402  (its e4m3 form with per-head scales: fp8=True)
 from lite_attention import SmoothedQK  # noqa: E402  (... with the keys mean-shifted before they are quantized: smooth_k=True)
+from lite_attention import head_rotation  # noqa: E402  (... every head of q and k rotated by one signed Hadamard matrix first: rotate=True)
 from lite_attention import SmoothedV  # noqa: E402  (... and V: smooth_v=True; the attention call adds the mean back to its output)
 from lite_attention import attn_out_fp8, attn_unshift  # noqa: E402  (O restored as row-scaled e4m3 for an fp8 output projection: fp8_oproj=True)
 from lite_attention import brick_order  # noqa: E402  (token orders: the block on 3-D bricks of the latent grid instead of raster stripes)
@@ -93,7 +95,7 @@ def fp8_linear(r, linear):
 
 class WanLikeSelfAttention(nn.Module):
     def __init__(self, dim, num_heads, threshold=-10.0, enable_skipping=True, max_batch_size=1, fused_prep=False, *, fp8=False,
-                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, fp8_oproj=False):
+                 fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, fp8_oproj=False, rotate=False):
         super().__init__()
         assert dim % num_heads == 0
         self.num_heads, self.head_dim, self.fused_prep = num_heads, dim // num_heads, fused_prep
@@ -105,6 +107,9 @@ class WanLikeSelfAttention(nn.Module):
         # smooth_k: q and k go through one SmoothedQK instead (k first, q with the dots that would restore the LSE); v as before
         assert fp8 or not smooth_k, "smooth_k is a form of the fp8 path"
         self.smoothed = SmoothedQK(mode=fp8_mode, margin=fp8_margin) if smooth_k else None
+        # rotate: every head of q and k times ONE signed Hadamard matrix before the cast (the same object for both: the scores stand)
+        assert fp8 or not rotate, "rotate is a form of the fp8 path"
+        self.rotate = rotate
         # smooth_v: v goes through a SmoothedV; the attention call restores O (v_shift) and hands it on in fp32 (out_dtype)
         assert fp8 or not smooth_v, "smooth_v is a form of the fp8 path"
         self.smoothed_v = SmoothedV(mode=fp8_mode, margin=fp8_margin, tiles=v_tiles) if smooth_v else None
@@ -124,12 +129,13 @@ class WanLikeSelfAttention(nn.Module):
         assert order is None or (self.fused_prep and not self.fp8), "a token order runs through the fused prologue"
         if self.fp8:                                                # norm + rope + scale + e4m3 cast of q and k, scale + cast of v
             tables = rope_tables(grid, d, device=x.device)
+            rot = head_rotation(d, device=x.device) if self.rotate else None
             if self.smoothed is not None:
                 q, k, dq, dk, _ = self.smoothed.pair(self.q(x).view(b, s, n, d), self.k(x).view(b, s, n, d), self.norm_q.weight,
-                                                     self.norm_k.weight, self.norm_q.eps, tables)
+                                                     self.norm_k.weight, self.norm_q.eps, tables, rotate=rot)
             else:
-                q, dq = self.scales[0](self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables)
-                k, dk = self.scales[1](self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables)
+                q, dq = self.scales[0](self.q(x).view(b, s, n, d), self.norm_q.weight, self.norm_q.eps, tables, rotate=rot)
+                k, dk = self.scales[1](self.k(x).view(b, s, n, d), self.norm_k.weight, self.norm_k.eps, tables, rotate=rot)
             if self.fp8_oproj:
                 v_shift = None
                 if self.smoothed_v is not None:
@@ -206,7 +212,8 @@ class WanLikeCrossAttention(nn.Module):
 
 
 def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0, device="cuda", verbose=True, fused_prep=False, *,
-        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, bricks=None, fp8_oproj=False):
+        fp8=False, fp8_mode="current", fp8_margin=1.0, smooth_k=False, smooth_v=False, v_tiles=False, bricks=None, fp8_oproj=False,
+        rotate=False):
     """bricks: None (raster order), or the brick levels of `brick_order` - the blocks then run in that order (fused prologue) and the
     rows gain a fourth entry, the largest difference of the dense block's attention output to its raster run."""
     torch.manual_seed(seed)
@@ -217,7 +224,7 @@ def run(frames=5, height=16, width=16, heads=4, steps=6, threshold=-6.0, seed=0,
         assert not fp8, "--brick-order runs the bf16 block"
         fused_prep, order = True, brick_order(grid, bricks, device=device)
     kw = dict(fp8=fp8, fp8_mode=fp8_mode, fp8_margin=fp8_margin, smooth_k=smooth_k, smooth_v=smooth_v, v_tiles=v_tiles,
-              fp8_oproj=fp8_oproj)
+              fp8_oproj=fp8_oproj, rotate=rotate)
     sparse = WanLikeSelfAttention(dim, heads, threshold=threshold, fused_prep=fused_prep, **kw).to(device)
     # random q and k projections give unstructured scores (nothing to skip); tie them, as a stand-in for trained weights
     # under which tokens of the same frame attend to each other
@@ -275,6 +282,8 @@ if __name__ == "__main__":
     ap.add_argument("--fp8-mode", choices=("current", "delayed"), default="current")
     ap.add_argument("--fp8-margin", type=float, default=1.0)
     ap.add_argument("--smooth-k", action="store_true", help="with --fp8: subtract each key head's mean before the e4m3 cast (SmoothedQK)")
+    ap.add_argument("--rotate", action="store_true", help="with --fp8 (and with --fp8 --smooth-k): every head of q and k times one signed "
+                    "Hadamard matrix before the e4m3 cast (head_rotation; head_dim 64, 128 or 256)")
     ap.add_argument("--smooth-v", action="store_true", help="with --fp8: subtract each V head's mean before the e4m3 cast (SmoothedV); "
                     "the attention call adds it back and returns fp32")
     ap.add_argument("--v-tiles", action="store_true", help="with --fp8: quantize V straight into the V^T tiles the e4m3 forward stages "
@@ -290,8 +299,8 @@ if __name__ == "__main__":
         if a.fp8:
             ap.error("--brick-order runs the bf16 block (the e4m3 forms take positions= alike: INTEGRATION.md 1h)")
         bricks = tuple(tuple(int(v) for v in level.split(",")) for level in a.brick_order) or ((1, 16, 16), (1, 8, 8))
-    if (a.smooth_k or a.smooth_v or a.v_tiles or a.fp8_oproj) and not a.fp8:
-        ap.error("--smooth-k, --smooth-v, --v-tiles and --fp8-oproj need --fp8")
+    if (a.smooth_k or a.smooth_v or a.v_tiles or a.fp8_oproj or a.rotate) and not a.fp8:
+        ap.error("--smooth-k, --smooth-v, --v-tiles, --fp8-oproj and --rotate need --fp8")
     run(a.frames, a.height, a.width, a.heads, a.steps, a.threshold, fused_prep=a.fused_prep, fp8=a.fp8, fp8_mode=a.fp8_mode,
         fp8_margin=a.fp8_margin, smooth_k=a.smooth_k, smooth_v=a.smooth_v, v_tiles=a.v_tiles, bricks=bricks,
-        fp8_oproj=a.fp8_oproj)
+        fp8_oproj=a.fp8_oproj, rotate=a.rotate)

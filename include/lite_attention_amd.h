@@ -32,6 +32,9 @@
  *   la_qk_prep_rows       <- nothing: the three passes above with a row map (la_qk_prep_fp8_rows, la_qk_prep_smooth_rows): out row s is
  *                            made from a row of x and rotated as a position that two int32 tables name - the token orders of
  *                            sliding-tile, radial and permuted attention, and the plain row gather that brings V and O into them
+ *   la_qk_prep_rot        <- nothing in the reference; FlashAttention-3's "incoherent processing": the three passes (la_qk_prep_fp8_rot,
+ *                            la_qk_prep_smooth_rot) with every head of q and k multiplied by one signed Hadamard matrix before the cast,
+ *                            in registers - the scores stand, the e4m3 rounding error of concentrated heads falls
  *   la_v_colstats         <- nothing: mean and exact amax of V - mean in one read of V (with la_v_colstats_finish), for a V that is
  *                            quantized mean-shifted ("smooth V")
  *   la_attn_unshift       <- nothing: adds that mean back to the attention output (exact: the rows of P sum to 1), restores the LSE
@@ -58,7 +61,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads and la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads, la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows and la_qk_prep_rot / la_qk_prep_fp8_rot / la_qk_prep_smooth_rot were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -551,6 +554,32 @@ typedef struct la_row_map {
 int la_qk_prep_rows(const la_qk_prep_args* args, const la_row_map* map, void* stream);
 int la_qk_prep_fp8_rows(const la_qk_prep_fp8_args* args, const la_row_map* map, void* stream);
 int la_qk_prep_smooth_rows(const la_qk_prep_smooth_args* args, const la_row_map* map, void* stream);
+
+/* Head rotation ("incoherent processing"): the three passes with every head of y multiplied by ONE orthogonal matrix before anything
+ * consumes it (added under ABI 9: no struct changes, a host detects the entry points by symbol). With y the fp32 value behind norm,
+ * weight and rope,
+ *   y <- (y o signs) H_D / sqrt(D),     H_D[i][j] = (-1)^popcount(i & j)   (the Sylvester Hadamard matrix in natural order)
+ * for every head of every row, and all that follows - the 16-bit store, amax, descale and the e4m3 cast, and for la_qk_prep_smooth the
+ * shift, colsum_part (so the mean la_colsum_finish makes) and the row dots with dot_vec - is a quantity of the ROTATED y, computed as
+ * the unrotated entry point computes it. (qM)(kM)^T = q k^T for orthogonal M: scores, P, O, the LSE and the skip vote of an attention
+ * call whose q AND k went through the same rotation are unchanged in exact arithmetic, while a head whose energy sits in a few channels
+ * is spread over all D before it is rounded to e4m3. The rotation is linear, so K smoothing composes with it exactly: the column mean
+ * of kM is (mean k) M, and the q . c dots are those of the rotated q with the rotated mean. V is not rotated.
+ * head_dim must be 64, 128 or 256 (a head then sits on aligned lanes of a wave; the exchanges never leave it). `map` may be NULL (no
+ * row map) or a la_row_map as for the _rows entry points. signs: device fp32 [head_dim] of +1 / -1 (only the sign bit is read), shared
+ * by every head and batch; NULL = all +1.
+ * Errors (all before any HIP call): the checks of la_qk_prep(_fp8, _smooth)_rows in their order and codes, and with them: NULL rot
+ * LA_ERR_NULL_ARG (with NULL args / map); rot->struct_size LA_ERR_STRUCT_SIZE (behind args' and map's); head_dim not 64 / 128 / 256
+ * LA_ERR_HEAD_DIM (with the head_dim check); signs off a 4-byte boundary LA_ERR_STRIDE (with the weight). NOT detected: q and k of
+ * one attention call prepared with different rotations - the scores are then those of other operands. */
+typedef struct la_head_rotation {
+    uint32_t struct_size;        /* = sizeof(la_head_rotation)                                    */
+    int32_t  reserved;           /* 0                                                             */
+    const float* signs;          /* [head_dim] of +-1; NULL: all +1 (plain H_D / sqrt(D))          */
+} la_head_rotation;
+int la_qk_prep_rot(const la_qk_prep_args* args, const la_row_map* map, const la_head_rotation* rot, void* stream);
+int la_qk_prep_fp8_rot(const la_qk_prep_fp8_args* args, const la_row_map* map, const la_head_rotation* rot, void* stream);
+int la_qk_prep_smooth_rot(const la_qk_prep_smooth_args* args, const la_row_map* map, const la_head_rotation* rot, void* stream);
 
 /* V smoothing: the twin of K smoothing for the one operand that is quantized as it leaves its projection. la_fwd divides by its own
  * row sum, so the rows of P sum to 1 over whatever keys a row visits - with skip lists, with split keys and after an LSE merge - and

@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "la_v_colstats", "la_v_colstats_parts", "la_v_colstats_part_rows", "la_v_colstats_finish", "la_attn_unshift",
     "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes", "la_fwd_head_thr", "la_skip_list_stats_heads",
     "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows", "la_attn_unshift_fp8",
+    "la_qk_prep_rot", "la_qk_prep_fp8_rot", "la_qk_prep_smooth_rot",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -109,6 +110,11 @@ class LaRowMap(ctypes.Structure):
         ("struct_size", ctypes.c_uint32), ("src_seqlen", ctypes.c_int32),
         ("src_rows", ctypes.c_void_p), ("positions", ctypes.c_void_p), ("batch_stride", ctypes.c_int64),
     ]
+
+
+class LaHeadRotation(ctypes.Structure):
+    """Mirror of ``la_head_rotation`` (field order and types must match the header)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("signs", ctypes.c_void_p)]
 
 
 class LaVColstatsArgs(ctypes.Structure):
@@ -288,6 +294,10 @@ def load() -> ctypes.CDLL:
     for fn, struct in ((lib.la_qk_prep_rows, LaQkPrepArgs), (lib.la_qk_prep_fp8_rows, LaQkPrepFp8Args),
                        (lib.la_qk_prep_smooth_rows, LaQkPrepSmoothArgs)):
         fn.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(LaRowMap), ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+    for fn, struct in ((lib.la_qk_prep_rot, LaQkPrepArgs), (lib.la_qk_prep_fp8_rot, LaQkPrepFp8Args),
+                       (lib.la_qk_prep_smooth_rot, LaQkPrepSmoothArgs)):
+        fn.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(LaRowMap), ctypes.POINTER(LaHeadRotation), ctypes.c_void_p]
         fn.restype = ctypes.c_int
     for fn in (lib.la_qk_prep_smooth_parts, lib.la_qk_prep_smooth_part_rows):
         fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]

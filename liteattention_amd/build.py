@@ -157,7 +157,10 @@ def _compile_into(lib_path: str, obj_dir: str, tmp: str, common, defines, verbos
 
     def compile_one(src):
         obj = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
-        cmd = common + ["-c", os.path.join(CSRC, src), "-o", obj, "-Rpass-analysis=kernel-resource-usage"]
+        flags = _buildinfo.SOURCE_FLAGS.get(src, [])
+        if src == "la_prep_qk.hip" and "LA_QK_PREP_SAME_FLAGS=1" in defines:       # A/B variant: the unrotated prologue under the rotated unit's flags
+            flags = _buildinfo.SOURCE_FLAGS["la_prep_qk_rot.hip"]
+        cmd = common + flags + ["-c", os.path.join(CSRC, src), "-o", obj, "-Rpass-analysis=kernel-resource-usage"]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         return obj, subprocess.run(cmd, check=False, stderr=subprocess.PIPE, text=True)

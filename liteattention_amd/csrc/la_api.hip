@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "../../include/lite_attention_amd.h"
 #include "la_fwd_shell.h"      // fwd_lds_size_x64, X_LDS_LIMIT: the LDS a launch of the hand-scheduled kernels needs
 #include "la_kernel_params.h"
@@ -509,15 +511,19 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
 // What la_qk_prep, la_qk_prep_fp8 and la_qk_prep_smooth check alike, from the norm mode on, and the kernel parameters they share. A: any
 // of the three argument structs (the same field names). out_dtype: la_dtype of out (LA_DTYPE_FP8_E4M3: 8 elements = 8 bytes, row starts on 8-byte boundaries).
 // map: the la_row_map of a _rows entry point (its struct_size already checked), NULL for the unmapped ones: x then has seqlen rows, and
-// each rule of the map sits with the unmapped rules of its kind.
+// each rule of the map sits with the unmapped rules of its kind. rot: the la_head_rotation of a _rot entry point (its struct_size
+// already checked), NULL for the others; its rules sit the same way.
 template <class A>
-static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, const la_row_map* map, la::QkPrepParams& p) {
+static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, const la_row_map* map, const la_head_rotation* rot, la::QkPrepParams& p,
+                                  la::QkPrepRot& pr) {
     const int32_t src_seqlen = map ? map->src_seqlen : a->seqlen;
     if (a->norm_mode != LA_NORM_NONE && a->norm_mode != LA_NORM_TOKEN && a->norm_mode != LA_NORM_HEAD) return LA_ERR_UNSUPPORTED;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
     // without src_rows out row s is made from row s of x: x has at least seqlen rows
     if (map && (src_seqlen < 1 || (!map->src_rows && src_seqlen < a->seqlen))) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
+    // a rotated head sits on 8 / 16 / 32 aligned lanes of a wave
+    if (rot && a->head_dim != 64 && a->head_dim != 128 && a->head_dim != 256) return LA_ERR_HEAD_DIM;
     // LA_NORM_TOKEN: the token stays in registers from the load to the store - of one wave up to 5120 elements, of the four waves of a
     // workgroup up to 8 chunks of 8 elements per lane
     if (a->norm_mode == LA_NORM_TOKEN && static_cast<int64_t>(a->num_heads) * a->head_dim > 16384) return LA_ERR_UNSUPPORTED;
@@ -531,6 +537,7 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, const la_row_ma
                 ((reinterpret_cast<uintptr_t>(map->src_rows) | reinterpret_cast<uintptr_t>(map->positions)) & 3u))) return LA_ERR_STRIDE;
     if (map && map->src_rows && a->out == a->x) return LA_ERR_UNSUPPORTED;        // a gather in place: rows would be read after they were overwritten
     if (a->weight && !aligned16(a->weight)) return LA_ERR_STRIDE;                 // read 16 bytes at a time
+    if (rot && (reinterpret_cast<uintptr_t>(rot->signs) & 3u)) return LA_ERR_STRIDE;
     for (int i = 0; i < 3; ++i)
         if (reinterpret_cast<uintptr_t>(a->rope_table[i]) & 7u) return LA_ERR_STRIDE;      // (cos, sin) is one 8-byte load
     int64_t pairs = 0;
@@ -568,6 +575,12 @@ static int qk_prep_check_and_fill(const A* a, int32_t out_dtype, const la_row_ma
     p.pos_offset = a->pos_offset; p.eps = a->eps;
     p.src_seqlen = src_seqlen; p.pos_limit = static_cast<int>(pos_limit);
     if (map) { p.src_rows = map->src_rows; p.positions = map->positions; p.map_bs = map->batch_stride; }
+    pr = {};
+    if (rot) {
+        pr.signs = rot->signs;
+        pr.log2_lanes = a->head_dim == 64 ? 3 : (a->head_dim == 128 ? 4 : 5);
+        pr.scale = static_cast<float>(1.0 / std::sqrt(static_cast<double>(a->head_dim)));
+    }
     return LA_OK;
 }
 
@@ -584,8 +597,9 @@ static bool qk_prep_scale_strides_ok(const A* a) {
 }
 // ... and behind them the limit of heads and the fill, with everything shared with la_qk_prep
 template <class A>
-static int qk_prep_e4m3_check_and_fill(const A* a, const la_row_map* map, la::QkPrepParams& p) {
-    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, map, p);
+static int qk_prep_e4m3_check_and_fill(const A* a, const la_row_map* map, const la_head_rotation* rot, la::QkPrepParams& p,
+                                       la::QkPrepRot& pr) {
+    const int rc = qk_prep_check_and_fill(a, LA_DTYPE_FP8_E4M3, map, rot, p, pr);
     if (rc != LA_OK) return rc;
     if (a->num_heads > la::kQkPrepScaleSlots) return LA_ERR_UNSUPPORTED;      // a workgroup keeps every head's scale and maximum in LDS
     p.descale = a->out ? a->descale : nullptr; p.amax = a->amax;
@@ -595,37 +609,52 @@ static int qk_prep_e4m3_check_and_fill(const A* a, const la_row_map* map, la::Qk
     return LA_OK;
 }
 
-// The three passes, each behind its unmapped entry point (mapped false, map NULL) and its _rows one (mapped true: a map is required; it is
-// checked for presence with the arguments and for its size behind theirs, its fields inside the shared checker).
+// The three passes, each behind its unmapped entry point (mapped false, map NULL), its _rows one (mapped true: a map is required; it is
+// checked for presence with the arguments and for its size behind theirs, its fields inside the shared checker) and its _rot one
+// (rotated true: a la_head_rotation is required and checked the same way, behind the map; the map is there when it is given).
+// The rotating launcher is a weak reference HERE only: a host-only link of this file against stand-ins for the older launchers
+// (tests/cabi_launches) stays complete without one for it; a link that lacks la_prep_qk_rot.hip answers LA_ERR_UNSUPPORTED.
+namespace la {
+hipError_t launch_qk_prep_rot(const QkPrepParams& p, const QkPrepRot& rot, int in_dtype, int out_dtype, int mode, hipStream_t stream)
+    __attribute__((weak));
+}
+static int launch_prep(const la::QkPrepParams& p, const la::QkPrepRot& pr, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
+    if (pr.log2_lanes == 0) return launch_status(la::launch_qk_prep(p, in_dtype, out_dtype, mode, stream));
+    if (!la::launch_qk_prep_rot) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_qk_prep_rot(p, pr, in_dtype, out_dtype, mode, stream));
+}
 static bool row_map_size_ok(bool mapped, const la_row_map* map) { return !mapped || map->struct_size == sizeof(la_row_map); }
+static bool head_rot_size_ok(bool rotated, const la_head_rotation* rot) { return !rotated || rot->struct_size == sizeof(la_head_rotation); }
 
-static int qk_prep_run(const la_qk_prep_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+static int qk_prep_run(const la_qk_prep_args* a, bool mapped, const la_row_map* map, bool rotated, const la_head_rotation* rot, void* stream_) {
+    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_args) || !row_map_size_ok(mapped, map) || !head_rot_size_ok(rotated, rot)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || !a->out) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype) || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
     la::QkPrepParams p;
-    const int rc = qk_prep_check_and_fill(a, a->out_dtype, map, p);
+    la::QkPrepRot pr;
+    const int rc = qk_prep_check_and_fill(a, a->out_dtype, map, rot, p, pr);
     if (rc != LA_OK) return rc;
-    return launch_status(la::launch_qk_prep(p, a->in_dtype, a->out_dtype, 0, static_cast<hipStream_t>(stream_)));
+    return launch_prep(p, pr, a->in_dtype, a->out_dtype, 0, static_cast<hipStream_t>(stream_));
 }
 
-static int qk_prep_fp8_run(const la_qk_prep_fp8_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_fp8_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+static int qk_prep_fp8_run(const la_qk_prep_fp8_args* a, bool mapped, const la_row_map* map, bool rotated, const la_head_rotation* rot, void* stream_) {
+    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_fp8_args) || !row_map_size_ok(mapped, map) || !head_rot_size_ok(rotated, rot)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
     if (!qk_prep_scale_strides_ok(a)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
-    const int rc = qk_prep_e4m3_check_and_fill(a, map, p);
+    la::QkPrepRot pr;
+    const int rc = qk_prep_e4m3_check_and_fill(a, map, rot, p, pr);
     if (rc != LA_OK) return rc;
-    return launch_status(la::launch_qk_prep(p, a->in_dtype, LA_DTYPE_FP8_E4M3, a->out ? 1 : 2, static_cast<hipStream_t>(stream_)));
+    return launch_prep(p, pr, a->in_dtype, LA_DTYPE_FP8_E4M3, a->out ? 1 : 2, static_cast<hipStream_t>(stream_));
 }
 
-static int qk_prep_smooth_run(const la_qk_prep_smooth_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_smooth_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+static int qk_prep_smooth_run(const la_qk_prep_smooth_args* a, bool mapped, const la_row_map* map, bool rotated, const la_head_rotation* rot, void* stream_) {
+    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_qk_prep_smooth_args) || !row_map_size_ok(mapped, map) || !head_rot_size_ok(rotated, rot)) return LA_ERR_STRUCT_SIZE;
     if (!a->x || (!a->out && !a->amax && !a->colsum_part && !a->dot_out)) return LA_ERR_NULL_ARG;
     if ((a->dot_out != nullptr) != (a->dot_vec != nullptr)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
@@ -638,7 +667,8 @@ static int qk_prep_smooth_run(const la_qk_prep_smooth_args* a, bool mapped, cons
                                      a->num_heads / a->heads_per_dot)) ||
         !aligned16(a->colsum_part)) return LA_ERR_STRIDE;
     la::QkPrepParams p;
-    const int rc = qk_prep_e4m3_check_and_fill(a, map, p);
+    la::QkPrepRot pr;
+    const int rc = qk_prep_e4m3_check_and_fill(a, map, rot, p, pr);
     if (rc != LA_OK) return rc;
     // a thread keeps the running sums of its columns in LDS: at most 16 chunks of 8
     if (a->colsum_part && la::qk_prep_sum_slots(p) > la::kQkPrepSumSlots) return LA_ERR_UNSUPPORTED;
@@ -652,18 +682,29 @@ static int qk_prep_smooth_run(const la_qk_prep_smooth_args* a, bool mapped, cons
         p.heads_per_dot = a->dot_vec ? a->heads_per_dot : 1; p.dot_out = a->dot_out;
         p.part_rows = la::qk_prep_part_rows(a->seqlen); p.part_blocks = la::qk_prep_part_blocks(a->seqlen);
     }
-    return launch_status(la::launch_qk_prep(p, a->in_dtype, LA_DTYPE_FP8_E4M3, mode, static_cast<hipStream_t>(stream_)));
+    return launch_prep(p, pr, a->in_dtype, LA_DTYPE_FP8_E4M3, mode, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" {
 
-int la_qk_prep(const la_qk_prep_args* a, void* stream) { return qk_prep_run(a, false, nullptr, stream); }
-int la_qk_prep_rows(const la_qk_prep_args* a, const la_row_map* map, void* stream) { return qk_prep_run(a, true, map, stream); }
-int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream) { return qk_prep_fp8_run(a, false, nullptr, stream); }
-int la_qk_prep_fp8_rows(const la_qk_prep_fp8_args* a, const la_row_map* map, void* stream) { return qk_prep_fp8_run(a, true, map, stream); }
-int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream) { return qk_prep_smooth_run(a, false, nullptr, stream); }
+int la_qk_prep(const la_qk_prep_args* a, void* stream) { return qk_prep_run(a, false, nullptr, false, nullptr, stream); }
+int la_qk_prep_rows(const la_qk_prep_args* a, const la_row_map* map, void* stream) { return qk_prep_run(a, true, map, false, nullptr, stream); }
+int la_qk_prep_rot(const la_qk_prep_args* a, const la_row_map* map, const la_head_rotation* rot, void* stream) {
+    return qk_prep_run(a, map != nullptr, map, true, rot, stream);
+}
+int la_qk_prep_fp8(const la_qk_prep_fp8_args* a, void* stream) { return qk_prep_fp8_run(a, false, nullptr, false, nullptr, stream); }
+int la_qk_prep_fp8_rows(const la_qk_prep_fp8_args* a, const la_row_map* map, void* stream) {
+    return qk_prep_fp8_run(a, true, map, false, nullptr, stream);
+}
+int la_qk_prep_fp8_rot(const la_qk_prep_fp8_args* a, const la_row_map* map, const la_head_rotation* rot, void* stream) {
+    return qk_prep_fp8_run(a, map != nullptr, map, true, rot, stream);
+}
+int la_qk_prep_smooth(const la_qk_prep_smooth_args* a, void* stream) { return qk_prep_smooth_run(a, false, nullptr, false, nullptr, stream); }
 int la_qk_prep_smooth_rows(const la_qk_prep_smooth_args* a, const la_row_map* map, void* stream) {
-    return qk_prep_smooth_run(a, true, map, stream);
+    return qk_prep_smooth_run(a, true, map, false, nullptr, stream);
+}
+int la_qk_prep_smooth_rot(const la_qk_prep_smooth_args* a, const la_row_map* map, const la_head_rotation* rot, void* stream) {
+    return qk_prep_smooth_run(a, map != nullptr, map, true, rot, stream);
 }
 
 int la_qk_prep_smooth_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {

@@ -170,11 +170,20 @@ struct QkPrepParams {
     int src_seqlen;              // rows of x: a source row is clamped into [0, src_seqlen)
     int pos_limit;               // e0 * e1 * e2 (1 when nothing rotates): a position is clamped into [0, pos_limit)
 };
+// The _rot entry points: every head of y is multiplied by diag(signs) H_D / sqrt(D) right behind the rope. A kernel argument of its own
+// BEHIND the others (QkPrepParams keeps its size, the unrotated kernels the offsets of everything they read - their code is unchanged).
+struct QkPrepRot {
+    const float* signs;          // fp32 [head_dim] of +-1; NULL = all +1
+    int log2_lanes;              // log2(head_dim / 8) = 3, 4 or 5; 0: no head rotation
+    float scale;                 // 1 / sqrt(head_dim), rounded once on the host
+};
 constexpr int kQkPrepScaleSlots = 1024;      // heads whose scale and running amax a workgroup keeps in LDS (la_qk_prep_fp8)
 constexpr int kQkPrepSumSlots = 16;          // chunks of 8 columns a thread keeps running column sums for in LDS (la_qk_prep_smooth): 128 KiB
 // dtypes: 0 bf16, 1 fp16, 3 fp32 (in only), 2 e4m3 (out only). mode: 0 la_qk_prep (16-bit out); la_qk_prep_fp8: 1 quantize, 2 the amax pass
 // alone (p.out == NULL); la_qk_prep_smooth with a shift, column sums or row dots: 3 with out, 4 without
 hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, int mode, hipStream_t stream);
+// ... and with a head rotation (rot.log2_lanes != 0; la_prep_qk_rot.hip)
+hipError_t launch_qk_prep_rot(const QkPrepParams& p, const QkPrepRot& rot, int in_dtype, int out_dtype, int mode, hipStream_t stream);
 // la_qk_prep_smooth: rows of a part and blocks of 4 parts for a sequence length - the one place the row -> part map is decided
 inline int qk_prep_part_rows(int seqlen) { const int r = static_cast<int>((static_cast<int64_t>(seqlen) + 1023) / 1024); return r < 16 ? 16 : r; }
 inline int qk_prep_part_blocks(int seqlen) {

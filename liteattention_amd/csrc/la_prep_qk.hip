@@ -62,6 +62,22 @@
 // pos_offset + positions[s] (map_row; NULL tables: s and the source row). The wave that owns a token reads its two table entries, one
 // 4-byte load each, in front of the token's loads; everything behind the load - sums, rotation, maxima, column parts, row dots, the
 // store - is indexed by the OUT row and unchanged. Without tables the two values are s and pos_offset + s: the bits of an unmapped launch.
+//
+// Head rotation (the _rot entry points; template parameter HAD of both templates, every form, with and without a row map): right behind
+// scale_rotate8 every head of y is multiplied by the orthogonal M = diag(s) H_D / sqrt(D), H_D the Sylvester Hadamard matrix in natural
+// order, s the +-1 signs of la_head_rotation - (qM)(kM)^T = q k^T, so the scores stand and the e4m3 cast sees a head whose energy is
+// spread over all D channels. EVERYTHING behind that point is a quantity of yM, computed by the unrotated code: the colsum parts, the
+// row dots (dot_vec is a vector in the rotated basis), shift, amax, the clamp and the conversion, the 16-bit store.
+//  * data movement (HeadRot): a head of D = 64 / 128 / 256 sits on D / 8 = 8 / 16 / 32 ALIGNED neighbouring lanes, 8 elements a lane, in
+//    both templates (token kernel: chunks l + 64 j or tid + 256 j and 64 % (D / 8) == 0, so a lane's place in its head is the same for
+//    all of its chunks; head kernel: G = D / 8). Element index = 8 (lane in head) + e: the three low index bits are 24 additions on the
+//    lane's own registers, the other 3 / 4 / 5 bits are exchanges with lanes ^1, ^2 (DPP quad_perm on the addition itself), ^4, ^8, ^16
+//    (ds_swizzle in bit mode: the LDS crossbar, no LDS memory). The lane whose bit is set takes partner - own, the other own + partner;
+//    that sign and the eight signs of s are lane masks resolved before the token loop. 1 / sqrt(D) is one multiplication per element.
+//  * the xor masks stay below D / 8: no lane reads a partner outside its head, and a head's lanes are live or idle together (spare waves
+//    of a round, chunks past the token's end and heads past H never enter the exchanges). The order of every addition is fixed by D.
+//  * the rotated forms are this file compiled once more (la_prep_qk_rot.hip: LA_QK_PREP_HADAMARD 1, a code object of their own); with
+//    HAD false nothing here adds an instruction to the unrotated kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -70,9 +86,17 @@
 #include "la_kernel_params.h"
 #include "la_prep_common.h"
 
+#ifndef LA_QK_ROT_LDS
+#define LA_QK_ROT_LDS 0                    // 1: the A/B form of the low cross-lane stages (HeadRot::apply); never the product
+#endif
+#ifndef LA_QK_PREP_HADAMARD
+#define LA_QK_PREP_HADAMARD 0              // 1: la_prep_qk_rot.hip compiles this file into the head-rotating forms (launch_qk_prep_rot)
+#endif
+
 namespace la {
 namespace {
 
+constexpr bool kHadamard = LA_QK_PREP_HADAMARD != 0;
 constexpr int kMaxGrid = 2048;             // workgroups: 8 per compute unit; the rest of the tokens by grid stride
 constexpr int kRotRow = 128;               // pairs of one token's rotation row (head_dim <= 256)
 constexpr int kHeadUnroll = 4;             // passes of the head kernel whose loads are issued together
@@ -201,10 +225,91 @@ __device__ __forceinline__ void scale_rotate8(float (&y)[8], float r, const floa
     }
 }
 
+// y <- (y o s) H_D / sqrt(D) for the head whose D / 8 = 1 << glog chunks sit on aligned neighbouring lanes, this lane holding elements
+// [8 (lane % (D / 8)), + 8). Token independent: the signs of the lane's elements and of "own" in each exchange are lane masks.
+struct HeadRot {
+    bool neg[8];                           // s < 0 at this lane's elements
+    bool hi[5];                            // bit k of the lane: it takes partner - own in the exchange with lane ^ (1 << k)
+    int glog;                              // log2(D / 8): 3, 4 or 5 (wave-uniform)
+    float scale;                           // 1 / sqrt(D)
+    __device__ __forceinline__ void init(const QkPrepRot& rot, int lane) {
+        glog = rot.log2_lanes;
+        scale = rot.scale;
+        const int e = (lane & ((1 << glog) - 1)) * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) neg[j] = rot.signs != nullptr && (__float_as_uint(rot.signs[e + j]) >> 31) != 0;     // the sign bit alone
+#pragma unroll
+        for (int k = 0; k < 5; ++k) hi[k] = ((lane >> k) & 1) != 0;
+    }
+    // y of lane ^ (1 << K): quad_perm [1 0 3 2] / [2 3 0 1] (folded into the addition that takes it), ds_swizzle and = 0x1f, xor = 4 / 8 / 16
+    template <int K>
+    static __device__ __forceinline__ float partner(float v) {
+        const int i = __float_as_int(v);
+        if (K == 0) return __int_as_float(__builtin_amdgcn_mov_dpp(i, 0xB1, 0xf, 0xf, true));
+        if (K == 1) return __int_as_float(__builtin_amdgcn_mov_dpp(i, 0x4E, 0xf, 0xf, true));
+        return __int_as_float(__builtin_amdgcn_ds_swizzle(i, 0x1f | (1 << (K + 10))));
+    }
+    template <int K>
+    __device__ __forceinline__ void exchange(float (&y)[8]) const {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) y[j] = partner<K>(y[j]) + (hi[K] ? -y[j] : y[j]);
+    }
+    __device__ __forceinline__ void apply(float (&y)[8]) const {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) y[j] = neg[j] ? -y[j] : y[j];
+#pragma unroll
+        for (int bit = 1; bit < 8; bit <<= 1)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (!(j & bit)) {
+                    const float a = y[j], c = y[j | bit];
+                    y[j] = a + c;
+                    y[j | bit] = a - c;
+                }
+#if LA_QK_ROT_LDS
+        // A/B build (-DLA_QK_ROT_LDS=1; tools/qk_rotate_bench.py times it beside the product): the three low lane bits are
+        // transposed against the three register bits through the wave's own LDS tile, so that their stages run on the lane's own
+        // registers, and transposed back - the same additions, the same bits. Lane l holds row l of an 8 x 8 tile per group of 8 lanes
+        // (8 words of padding a group: its column reads hit 64 different banks); only the 8 lanes of a group touch its tile, a
+        // wavefront fence orders them, no workgroup barrier.
+        __shared__ __attribute__((aligned(16))) float had_tile[4][64 * 8 + 64];
+        const int l = threadIdx.x & 63;
+        float* tile = had_tile[threadIdx.x >> 6] + (l >> 3) * 72;
+        for (int pass = 0; pass < 2; ++pass) {
+            wave_lds_fence();
+            *reinterpret_cast<pq_f32x4*>(tile + (l & 7) * 8) = pq_f32x4{y[0], y[1], y[2], y[3]};
+            *reinterpret_cast<pq_f32x4*>(tile + (l & 7) * 8 + 4) = pq_f32x4{y[4], y[5], y[6], y[7]};
+            wave_lds_fence();
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y[j] = tile[j * 8 + (l & 7)];
+            if (pass == 0) {
+#pragma unroll
+                for (int bit = 1; bit < 8; bit <<= 1)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (!(j & bit)) {
+                            const float a = y[j], c = y[j | bit];
+                            y[j] = a + c;
+                            y[j | bit] = a - c;
+                        }
+            }
+        }
+#else
+        exchange<0>(y);
+        exchange<1>(y);
+        exchange<2>(y);
+#endif
+        if (glog >= 4) exchange<3>(y);
+        if (glog >= 5) exchange<4>(y);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) y[j] *= scale;
+    }
+};
+
 // WG false: one wave per token. WG true (H * D > 5120): the four waves of the workgroup share one token, so that a lane still keeps
 // at most 10 chunks; the four partial sums meet in LDS and are added in a fixed order.
-template <int DT_IN, int DT_OUT, int NCH, bool WG, int MODE>
-__global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParams p) {
+template <int DT_IN, int DT_OUT, int NCH, bool WG, bool HAD, int MODE>
+__global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParams p, const QkPrepRot rot) {
     typedef PrepPolicy<MODE> POL;
     __shared__ __attribute__((aligned(16))) float rot_lds[4][2 * kRotRow];
     __shared__ float part[4];
@@ -243,6 +348,8 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
     }
     RotStage rs;
     rs.init(p, lane);
+    HeadRot hr;
+    if constexpr (HAD) hr.init(rot, lane);
 
     const int64_t t0 = WG ? static_cast<int64_t>(blockIdx.x) : static_cast<int64_t>(blockIdx.x) * 4 + wave;
     const int64_t t_step = WG ? static_cast<int64_t>(gridDim.x) : static_cast<int64_t>(gridDim.x) * 4;
@@ -325,6 +432,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
                 if (weight) load_f32x8(weight + (first + kLanes * i) * 8, w);       // 4 H D bytes every token rereads: they stay in L1 / L2
                 if (rotate) scale_rotate8<true>(y, r, w, col[i], rot_pairs, row);
                 else scale_rotate8<false>(y, r, w, col[i], rot_pairs, row);
+                if constexpr (HAD) hr.apply(y);
                 if constexpr (POL::kSmooth) {                      // sums and dots see y, the maximum and the store y - shift
                     if (p.colsum_part) colsum_add8(i, y);
                     if (p.dot_vec) {
@@ -375,8 +483,8 @@ __global__ void __launch_bounds__(256) la_qk_prep_token_kernel(const QkPrepParam
     }
 }
 
-template <int DT_IN, int DT_OUT, int MODE>
-__global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams p, int group_log2) {
+template <int DT_IN, int DT_OUT, bool HAD, int MODE>
+__global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams p, int group_log2, const QkPrepRot rot) {
     typedef PrepPolicy<MODE> POL;
     __shared__ __attribute__((aligned(16))) float rot_lds[4][2 * kRotRow];
     __shared__ unsigned am_tab[POL::kScaled ? kQkPrepScaleSlots : 1];
@@ -397,6 +505,8 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
     if (norm && p.weight && col_ok) load_f32x8(p.weight + e, w);
     RotStage rs;
     rs.init(p, lane);
+    HeadRot hr;
+    if constexpr (HAD) hr.init(rot, lane);
 
     // e4m3 forms: t counts rounds (4 consecutive tokens of one batch), the same trips for every thread
     const int64_t rpb = (p.seqlen + 3) / 4;
@@ -466,6 +576,7 @@ __global__ void __launch_bounds__(256) la_qk_prep_head_kernel(const QkPrepParams
                 if (col_ok && h < H && live) {
                     if (rotate) scale_rotate8<true>(y, r, w, e, rot_pairs, row);
                     else scale_rotate8<false>(y, r, w, e, rot_pairs, row);
+                    if constexpr (HAD) hr.apply(y);
                     if constexpr (POL::kSmooth) {                  // sums and dots see y, the maximum and the store y - shift
                         if (p.colsum_part) colsum_add8(h0 / heads_per_pass + u, y);
                         if (p.dot_vec) {
@@ -548,11 +659,11 @@ void launch_kernel(K kfn, const QkPrepParams& p, int per_wg, hipStream_t stream,
 }
 
 template <int DT_IN, int DT_OUT, int MODE>
-void launch_typed(const QkPrepParams& p, hipStream_t stream) {
+void launch_typed(const QkPrepParams& p, const QkPrepRot& rot, hipStream_t stream) {
     if (p.norm_mode == 1) {
         const TokenShape ts = token_shape(p.num_heads * p.head_dim / 8);
 #define LA_QK_PREP_TOKEN(NCH, WG) \
-        if (ts.nch == NCH && ts.wg == WG) launch_kernel<MODE>(la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, MODE>, p, WG ? 1 : 4, stream)
+        if (ts.nch == NCH && ts.wg == WG) launch_kernel<MODE>(la_qk_prep_token_kernel<DT_IN, DT_OUT, NCH, WG, kHadamard, MODE>, p, WG ? 1 : 4, stream, rot)
         LA_QK_PREP_TOKEN(1, false);
         LA_QK_PREP_TOKEN(2, false);
         LA_QK_PREP_TOKEN(4, false);
@@ -562,7 +673,7 @@ void launch_typed(const QkPrepParams& p, hipStream_t stream) {
         LA_QK_PREP_TOKEN(8, true);
 #undef LA_QK_PREP_TOKEN
     } else {
-        launch_kernel<MODE>(la_qk_prep_head_kernel<DT_IN, DT_OUT, MODE>, p, 4, stream, head_group_log2(p.head_dim));
+        launch_kernel<MODE>(la_qk_prep_head_kernel<DT_IN, DT_OUT, kHadamard, MODE>, p, 4, stream, head_group_log2(p.head_dim), rot);
     }
 }
 
@@ -574,6 +685,7 @@ void with_in_dtype(int in_dtype, F f) {
     else f(std::integral_constant<int, 3>());
 }
 
+#if !LA_QK_PREP_HADAMARD
 // mean[b][h][d] = (part[0][b][h][d] + part[1][b][h][d] + ...) / seqlen, added in index order: one thread per column
 __global__ void __launch_bounds__(256) la_colsum_finish_kernel(const float* __restrict__ part, int n_parts, int64_t cols, int head_dim,
                                                                  int num_heads, float seqlen, float* __restrict__ mean, int64_t m_bs,
@@ -585,8 +697,11 @@ __global__ void __launch_bounds__(256) la_colsum_finish_kernel(const float* __re
     const int64_t bh = c / head_dim, b = bh / num_heads;
     mean[b * m_bs + (bh - b * num_heads) * m_hs + (c - bh * head_dim)] = acc / seqlen;
 }
+#endif
 
 }  // namespace
+
+#if !LA_QK_PREP_HADAMARD
 
 // chunk slots of 8 columns per thread whose running sums live in LDS: the token kernel's NCH; the head kernel's passes of 64 / G heads,
 // in whole batches of kHeadUnroll
@@ -596,25 +711,33 @@ int qk_prep_sum_slots(const QkPrepParams& p) {
     return (p.num_heads + per_batch - 1) / per_batch * kHeadUnroll;
 }
 
+#endif
+
 // Templates are instantiated in the order they are named, and that is the order of the kernels in the code object: the cases below keep
 // the order the kernels have had since each form was added, so that an assembly diff against an earlier build shows code changes only.
+#if LA_QK_PREP_HADAMARD
+hipError_t launch_qk_prep_rot(const QkPrepParams& p, const QkPrepRot& rot, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
+#else
 hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
+    const QkPrepRot rot = {};
+#endif
     (void)hipGetLastError();
-    if (mode == 3) with_in_dtype(in_dtype, [&](auto dt) { launch_typed<decltype(dt)::value, 2, 3>(p, stream); });
-    else if (mode == 4) with_in_dtype(in_dtype, [&](auto dt) { launch_typed<decltype(dt)::value, 2, 4>(p, stream); });
+    if (mode == 3) with_in_dtype(in_dtype, [&](auto dt) { launch_typed<decltype(dt)::value, 2, 3>(p, rot, stream); });
+    else if (mode == 4) with_in_dtype(in_dtype, [&](auto dt) { launch_typed<decltype(dt)::value, 2, 4>(p, rot, stream); });
     else if (mode == 0)
         with_in_dtype(in_dtype, [&](auto dt) {
-            if (out_dtype == 0) launch_typed<decltype(dt)::value, 0, 0>(p, stream);
-            else launch_typed<decltype(dt)::value, 1, 0>(p, stream);
+            if (out_dtype == 0) launch_typed<decltype(dt)::value, 0, 0>(p, rot, stream);
+            else launch_typed<decltype(dt)::value, 1, 0>(p, rot, stream);
         });
     else
         with_in_dtype(in_dtype, [&](auto dt) {
-            if (mode == 1) launch_typed<decltype(dt)::value, 2, 1>(p, stream);
-            else launch_typed<decltype(dt)::value, 2, 2>(p, stream);
+            if (mode == 1) launch_typed<decltype(dt)::value, 2, 1>(p, rot, stream);
+            else launch_typed<decltype(dt)::value, 2, 2>(p, rot, stream);
         });
     return hipGetLastError();
 }
 
+#if !LA_QK_PREP_HADAMARD
 hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean,
                                 int64_t m_bs, int64_t m_hs, hipStream_t stream) {
     (void)hipGetLastError();
@@ -623,5 +746,6 @@ hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int n
                        head_dim, num_heads, static_cast<float>(seqlen), mean, m_bs, m_hs);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace la

@@ -17,7 +17,11 @@ the column sums that vector is made from (``qk_prep_colmean``) and the ``q . c``
 
 Row maps (``la_qk_prep_rows`` and its e4m3 and smoothing forms): every call above takes ``rows=`` (out row s is made from row
 ``rows[s]`` of x) and ``positions=`` (row s is rotated as position ``positions[s]``), so that the attention can run in another token
-order than the raster order of the grid; ``token_order.py`` builds the orders."""
+order than the raster order of the grid; ``token_order.py`` builds the orders.
+
+Head rotation (``la_qk_prep_rot`` and its e4m3 and smoothing forms): every call above takes ``rotate=head_rotation(head_dim)``, which
+multiplies every head by one signed Hadamard matrix before anything else sees it. Scores are unchanged when q and k use the SAME
+rotation; the e4m3 rounding error of heads whose energy sits in a few channels falls."""
 from __future__ import annotations
 
 import ctypes
@@ -80,6 +84,71 @@ def rope_tables(grid: Sequence[int], head_dim: int, theta: float = 10000.0, part
         _TABLES.pop(next(iter(_TABLES)))
     res = _TABLES[key] = RopeTables(tuple(tables), tuple(p // 2 for p in parts))
     return res
+
+
+class HeadRotation(NamedTuple):
+    """``signs``: fp32 ``[head_dim]`` of +-1 on the device; the rotation is ``M = diag(signs) H / sqrt(head_dim)``, H the Sylvester
+    Hadamard matrix in natural order, ``H[i][j] = (-1) ** popcount(i & j)``."""
+    signs: torch.Tensor
+
+
+ROTATE_HEAD_DIMS = (64, 128, 256)      # a rotated head sits on 8 / 16 / 32 aligned lanes of a wave
+_ROTATIONS = {}                         # (head_dim, seed, signs, device) -> HeadRotation
+
+
+def head_rotation(head_dim: int, seed: int = 0, device=None, signs: bool = True) -> HeadRotation:
+    """The rotation ``rotate=`` takes, for heads of ``head_dim`` (64, 128 or 256). ``signs=True``: random +-1 from a
+    ``torch.Generator`` seeded with ``seed`` (what makes the rotation "incoherent" with any fixed channel pattern); False: plain
+    ``H / sqrt(head_dim)``. Built on the host, cached per (head_dim, seed, signs, device): q and k of one attention call must be
+    prepared with the SAME object - the one way to misuse this: two different rotations give the scores of other operands and nothing
+    detects it. V is never rotated."""
+    head_dim = int(head_dim)
+    if head_dim not in ROTATE_HEAD_DIMS:
+        raise ValueError(f"head rotation is built for head_dim 64, 128 or 256, got {head_dim}")
+    device = torch.device("cpu" if device is None else device)
+    key = (head_dim, int(seed), bool(signs), str(device))
+    hit = _ROTATIONS.get(key)
+    if hit is not None:
+        return hit
+    s = torch.ones(head_dim, dtype=torch.float32)
+    if signs:
+        s = torch.randint(0, 2, (head_dim,), generator=torch.Generator().manual_seed(int(seed))).float() * 2 - 1
+    while len(_ROTATIONS) >= 16:
+        _ROTATIONS.pop(next(iter(_ROTATIONS)))
+    res = _ROTATIONS[key] = HeadRotation(s.to(device))
+    return res
+
+
+def _head_rot(x, rotate):
+    """The ``la_head_rotation`` of a call's ``rotate=`` (None stays None), checked against ``x`` (B, S, H, D) before anything launches."""
+    if rotate is None:
+        return None
+    signs = getattr(rotate, "signs", None)
+    if not isinstance(signs, torch.Tensor):
+        raise TypeError(f"rotate: what head_rotation returns, got {type(rotate).__name__}")
+    D = x.shape[-1]
+    if D not in ROTATE_HEAD_DIMS:
+        raise ValueError(f"rotate= needs head_dim 64, 128 or 256, got {D}")
+    if signs.dtype != torch.float32 or tuple(signs.shape) != (D,) or not signs.is_contiguous():
+        raise ValueError(f"rotate.signs must be contiguous fp32 [{D}] (head_rotation({D})), got {signs.dtype} {tuple(signs.shape)}")
+    if signs.device != x.device:
+        raise ValueError(f"rotate.signs lives on {signs.device}, x on {x.device}: build it with head_rotation({D}, device=x.device)")
+    r = _cabi.LaHeadRotation()
+    r.struct_size, r.signs = ctypes.sizeof(_cabi.LaHeadRotation), signs.data_ptr()
+    r._keep = signs
+    return r
+
+
+def rotation_matrix(rotate: HeadRotation) -> torch.Tensor:
+    """``M = diag(signs) H / sqrt(D)`` as a dense fp64 ``[D, D]`` matrix on the device of the signs (what the references multiply by)."""
+    s = rotate.signs.double()
+    i = torch.arange(s.numel(), device=s.device)
+    bits = i[:, None] & i[None]
+    parity = torch.zeros_like(bits)
+    while bool(bits.any()):
+        parity ^= bits & 1
+        bits = bits >> 1
+    return s[:, None] * (1.0 - 2.0 * parity.double()) / float(s.numel()) ** 0.5
 
 
 def _unpack_tables(tables, head_dim):
@@ -241,21 +310,27 @@ def _call(entry, x, detail, *args):
         raise RuntimeError(f"{entry}: {_cabi.status_string(rc)} ({detail()})")
 
 
-def _call_prep(entry, a, x, pos_offset, detail, row_map=None):
-    """``_call`` of one of the three prologue entry points - its ``_rows`` form when the call has a ``row_map``; ``detail()``: what the
-    form adds between the strides of x and the grid."""
+def _call_prep(entry, a, x, pos_offset, detail, row_map=None, rot=None):
+    """``_call`` of one of the three prologue entry points - its ``_rows`` form when the call has a ``row_map``, its ``_rot`` form (map
+    or NULL, then the rotation) when it has a ``rot``; ``detail()``: what the form adds between the strides of x and the grid."""
     mapped = () if row_map is None else (ctypes.byref(row_map),)
-    _call(entry + ("_rows" if mapped else ""), x,
+    if rot is not None:
+        entry, mapped = entry + "_rot", (mapped[0] if mapped else None, ctypes.byref(rot))
+    elif mapped:
+        entry += "_rows"
+    _call(entry, x,
           lambda: f"x {tuple(x.shape)} strides {x.stride()}, {detail()}, pos_offset {pos_offset}, {a.seqlen} rows on a grid "
                   f"of {[int(v) for v in a.axis_extent]}, pairs {[int(v) for v in a.axis_pairs]}"
                   + ("" if row_map is None else f", row map: rows {bool(row_map.src_rows)}, positions {bool(row_map.positions)}, "
-                                                f"batch stride {row_map.batch_stride}"), ctypes.byref(a), *mapped)
+                                                f"batch stride {row_map.batch_stride}")
+                  + ("" if rot is None else ", head rotation"), ctypes.byref(a), *mapped)
 
 
 def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="token", pos_offset=0, out=None, out_dtype=None,
-                  rows=None, positions=None):
+                  rows=None, positions=None, rotate=None):
     mode = _check_x_norm(x, norm, "qk_prep_reference")
     row_map, seqlen = _row_map(x, rows, positions)
+    rot = _head_rot(x, rotate)
     shape = _out_shape(x, seqlen)
     if out is None:
         if out_dtype is None:
@@ -276,13 +351,13 @@ def _qk_prep_impl(x, weight=None, eps=1e-6, tables=None, axis_pairs=None, norm="
     _check_weight(x, weight, mode)
     a = _prep_args(_cabi.LaQkPrepArgs, x, out, mode, weight, eps, pos_offset, tables, axis_pairs, seqlen)
     a.out_dtype = _OUT_DTYPES[out.dtype]
-    _call_prep("la_qk_prep", a, x, pos_offset, lambda: f"out strides {out.stride()}, norm {norm!r}", row_map)
+    _call_prep("la_qk_prep", a, x, pos_offset, lambda: f"out strides {out.stride()}, norm {norm!r}", row_map, rot)
     return out
 
 
 def qk_prep(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
             norm: Optional[str] = "token", pos_offset: int = 0, out: Optional[torch.Tensor] = None,
-            out_dtype: Optional[torch.dtype] = None, *, rows=None, positions=None) -> torch.Tensor:
+            out_dtype: Optional[torch.dtype] = None, *, rows=None, positions=None, rotate: Optional[HeadRotation] = None) -> torch.Tensor:
     """``out = cast(rope(rmsnorm(x) * weight))`` for ``x`` (B, S, H, D) bf16 / fp16 / fp32 on the GPU, in one pass (``la_qk_prep``):
     fp32 arithmetic, one rounding at the store. ``x`` may be any view whose last dimension is contiguous and whose rows start on
     16-byte boundaries - e.g. the q or k slice of a fused (B, S, 3, H, D) projection.
@@ -300,10 +375,13 @@ def qk_prep(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float =
               an ``x`` that already is in another order (gathered once at the model boundary), and with ``rows`` to override the
               position of each gathered row. The kernel clamps what it reads from either table (rows into x, positions into the
               tables' grid); ``TokenOrder.from_rows`` is where a table is checked, once.
+    rotate    what ``head_rotation(D)`` returns, on ``x.device`` (``la_qk_prep_rot``; D = 64, 128 or 256): every head of the fp32 value
+              is multiplied by ``M = diag(signs) H / sqrt(D)`` behind the rope, in registers, and ``out`` is the rounded ``y M``.
+              ``(q M)(k M)^T = q k^T``: give q and k the same object.
     No host sync, no allocation besides ``out``; asynchronous on the current stream. It captures into a HIP graph when the tables
     were built before the capture (building them copies from the host)."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
-    return _qk_prep_impl(x, weight, eps, tabs, pairs, norm, pos_offset, out, out_dtype, rows, positions)
+    return _qk_prep_impl(x, weight, eps, tabs, pairs, norm, pos_offset, out, out_dtype, rows, positions, rotate)
 
 
 def _reference_table(name, t, x):
@@ -319,10 +397,11 @@ def _reference_table(name, t, x):
 
 def qk_prep_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                       norm: Optional[str] = "token", pos_offset: int = 0, out_dtype: Optional[torch.dtype] = None, *, rows=None,
-                      positions=None) -> torch.Tensor:
+                      positions=None, rotate: Optional[HeadRotation] = None) -> torch.Tensor:
     """The formula of ``qk_prep`` in torch fp64 on whatever device ``x`` lives on, from the same fp32 weight and tables. Returns fp64
     (the unrounded value), or ``out_dtype`` when given. ``rows`` / ``positions``: integer tables ``[S]`` or ``[B, S]`` (or a
-    ``TokenOrder``) as in ``qk_prep``; here an entry outside its range raises (the kernel clamps it)."""
+    ``TokenOrder``) as in ``qk_prep``; here an entry outside its range raises (the kernel clamps it). ``rotate``: every head times the
+    dense fp64 ``rotation_matrix(rotate)``, last."""
     if x.dim() != 4:
         raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
     if norm not in _NORM_MODES:
@@ -360,6 +439,10 @@ def qk_prep_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, ep
         a, b = pair[..., 0], pair[..., 1]
         rot = torch.stack((a * cos - b * sin, a * sin + b * cos), dim=-1).reshape(B, S, H, 2 * n)
         y = torch.cat((rot, y[..., 2 * n:]), dim=-1)
+    if rotate is not None:
+        if rotate.signs.numel() != D:
+            raise ValueError(f"rotate.signs has {rotate.signs.numel()} entries, a head has {D}")
+        y = y @ rotation_matrix(rotate).to(y.device)
     return y if out_dtype is None else y.to(out_dtype)
 
 
@@ -369,11 +452,12 @@ _TINY = 2.0 ** -100        # the smallest amax a descale is made from: its recip
 
 
 def _qk_prep_fp8_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, descale, amax, heads_per_scale, out, store, rows=None,
-                      positions=None):
+                      positions=None, rotate=None):
     """One ``la_qk_prep_fp8`` call. ``store``: quantize into ``out`` (allocated when None); otherwise the amax pass alone."""
     mode = _check_x_norm(x, norm, "qk_prep_fp8_reference")
     hps = _check_scales(x, heads_per_scale, descale, amax)
     row_map, seqlen = _row_map(x, rows, positions)
+    rot = _head_rot(x, rotate)
     if store:
         out = _e4m3_out(x, out, seqlen)
     elif amax is None:
@@ -386,14 +470,14 @@ def _qk_prep_fp8_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, desc
     a = _prep_args(_cabi.LaQkPrepFp8Args, x, out if store else None, mode, weight, eps, pos_offset, tables, axis_pairs, seqlen)
     _fill_scales(a, hps, descale, amax, store)
     _call_prep("la_qk_prep_fp8", a, x, pos_offset,
-               lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}", row_map)
+               lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}", row_map, rot)
     return out
 
 
 def qk_prep_fp8(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                 norm: Optional[str] = "token", pos_offset: int = 0, *, descale: Optional[torch.Tensor] = None,
                 amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1, out: Optional[torch.Tensor] = None,
-                rows=None, positions=None) -> torch.Tensor:
+                rows=None, positions=None, rotate: Optional[HeadRotation] = None) -> torch.Tensor:
     """``qk_prep`` with a ``float8_e4m3fn`` result (``la_qk_prep_fp8``): with y the fp32 value ``qk_prep`` would round,
     ``out = e4m3(clamp(y / descale[b, h // heads_per_scale], -448, 448))``, round to nearest even, a NaN stays a NaN.
 
@@ -406,21 +490,24 @@ def qk_prep_fp8(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: flo
     out              float8_e4m3fn, same shape, rows / heads / batches on 8-byte boundaries; it must not overlap ``x``.
     rows / positions as ``qk_prep`` (``la_qk_prep_fp8_rows``): a row's bytes depend on its source row and its position alone, the amax
                      on no order at all.
+    rotate           as ``qk_prep`` (``la_qk_prep_fp8_rot``): y is the ROTATED value - ``amax_out`` and ``descale`` speak of ``y M``.
     No host sync, no allocation besides ``out``; asynchronous on the current stream; captures into a HIP graph like ``qk_prep``."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
-    return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True, rows, positions)
+    return _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, descale, amax_out, heads_per_scale, out, True, rows, positions,
+                             rotate)
 
 
 def qk_prep_amax(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                  norm: Optional[str] = "token", pos_offset: int = 0, *, amax_out: Optional[torch.Tensor] = None,
-                 heads_per_scale: int = 1, rows=None, positions=None) -> torch.Tensor:
+                 heads_per_scale: int = 1, rows=None, positions=None, rotate: Optional[HeadRotation] = None) -> torch.Tensor:
     """The amax pass of ``qk_prep_fp8`` alone: x is read once, nothing else is written. Returns ``amax_out`` (B, H // heads_per_scale)
     fp32 raised to the largest ``|y|`` of each group - the bits the quantizing call reports; None: a new zeroed tensor.
-    ``rows`` / ``positions``: as ``qk_prep_fp8`` (the maximum is taken over the rows the map names)."""
+    ``rows`` / ``positions``: as ``qk_prep_fp8`` (the maximum is taken over the rows the map names); ``rotate``: as ``qk_prep_fp8`` -
+    it must be the one the quantizing call gets."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
     if amax_out is None and x.dim() == 4:
         amax_out = torch.zeros((x.shape[0], x.shape[2] // max(1, int(heads_per_scale))), dtype=torch.float32, device=x.device)
-    _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, None, amax_out, heads_per_scale, None, False, rows, positions)
+    _qk_prep_fp8_impl(x, weight, eps, tabs, pairs, norm, pos_offset, None, amax_out, heads_per_scale, None, False, rows, positions, rotate)
     return amax_out
 
 
@@ -433,10 +520,11 @@ def descale_from_amax(amax: torch.Tensor, margin: float = 1.0, out: Optional[tor
 
 def qk_prep_fp8_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                           norm: Optional[str] = "token", pos_offset: int = 0, *, descale: Optional[torch.Tensor] = None,
-                          heads_per_scale: int = 1, rows=None, positions=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                          heads_per_scale: int = 1, rows=None, positions=None,
+                          rotate: Optional[HeadRotation] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The formula of ``qk_prep_fp8`` in torch fp64: ``(clamp(y / descale, -448, 448)`` UNROUNDED, ``amax`` (B, H // heads_per_scale)
-    of the unscaled ``|y|)``, both fp64, with ``y = qk_prep_reference(...)`` (``rows`` / ``positions`` included)."""
-    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset, rows=rows, positions=positions)
+    of the unscaled ``|y|)``, both fp64, with ``y = qk_prep_reference(...)`` (``rows`` / ``positions`` / ``rotate`` included)."""
+    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset, rows=rows, positions=positions, rotate=rotate)
     B, S, H, D = y.shape
     hps = int(heads_per_scale)
     if hps < 1 or H % hps:
@@ -474,14 +562,19 @@ class E4m3Scales:
         self.amax = self.descale = self.out = None
         self.calls = 0
 
-    def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None):
-        """``rows`` / ``positions``: as ``qk_prep_fp8``, for both passes. ``tiles=True`` takes no map: gather V first
-        (``TokenOrder.gather``)."""
+    def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None, rotate=None):
+        """``rows`` / ``positions`` / ``rotate``: as ``qk_prep_fp8``, for both passes. ``tiles=True`` takes no map: gather V first
+        (``TokenOrder.gather``) - and no rotation: V is not rotated."""
         B, S, H, D = x.shape
         hps = self.heads_per_scale
-        mapped = dict(rows=rows, positions=positions) if rows is not None or positions is not None else {}
+        mapped = rows is not None or positions is not None
+        extra = dict(rows=rows, positions=positions) if mapped else {}       # what both passes take beside the shared arguments
         if mapped:
             S = _row_map(x, rows, positions)[1]
+        if rotate is not None:
+            if self.tiles:
+                raise ValueError("tiles=True quantizes V, which is never rotated")
+            extra["rotate"] = rotate
         if self.tiles:
             from . import v_prep                                     # (v_prep imports this module)
             if norm is not None or weight is not None or tables is not None:
@@ -499,7 +592,7 @@ class E4m3Scales:
                 self.out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
         if first or self.mode == "current":
             self.amax.zero_()
-            self._amax_pass(x, weight, eps, tables, norm, pos_offset, amax_out=self.amax, heads_per_scale=hps, **mapped)
+            self._amax_pass(x, weight, eps, tables, norm, pos_offset, amax_out=self.amax, heads_per_scale=hps, **extra)
         descale_from_amax(self.amax, self.margin, out=self.descale)
         collect = None
         if self.mode == "delayed":                               # this step's amax, for the next step's descale
@@ -509,7 +602,7 @@ class E4m3Scales:
             v_prep.v_prep_tiles(x, descale=self.descale, amax_out=collect, out=self.out)
         else:
             self._quant_pass(x, weight, eps, tables, norm, pos_offset, descale=self.descale, amax_out=collect, heads_per_scale=hps,
-                             out=self.out, **mapped)
+                             out=self.out, **extra)
         self.calls += 1
         return self.out, self.descale
 
@@ -527,11 +620,12 @@ def qk_prep_smooth_parts(seqlen: int, num_heads: int, head_dim: int) -> Tuple[in
 
 
 def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, shift, descale, amax, heads_per_scale, colsum_part,
-                         dot_vec, heads_per_dot, dot_out, out, store, rows=None, positions=None):
+                         dot_vec, heads_per_dot, dot_out, out, store, rows=None, positions=None, rotate=None):
     """One ``la_qk_prep_smooth`` call. ``store``: quantize into ``out`` (allocated when None)."""
     mode = _check_x_norm(x, norm, "qk_prep_smooth_reference")
     B, _, H, D = x.shape
     row_map, S = _row_map(x, rows, positions)                    # S: rows of the result - of out, of dot_out and of the parts
+    rot = _head_rot(x, rotate)
     hps, hpd = _check_scales(x, heads_per_scale, descale, amax), int(heads_per_dot)
     if shift is not None:
         _f32("shift", shift, (B, H, D), x.device)
@@ -576,7 +670,7 @@ def _qk_prep_smooth_impl(x, weight, eps, tables, axis_pairs, norm, pos_offset, s
         a.dot_out = dot_out.data_ptr()
     _call_prep("la_qk_prep_smooth", a, x, pos_offset,
                lambda: f"out strides {out.stride() if store else None}, norm {norm!r}, heads_per_scale {hps}, heads_per_dot {hpd}, shift "
-                       f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}", row_map)
+                       f"{None if shift is None else shift.stride()}, part sums {colsum_part is not None}", row_map, rot)
     return out
 
 
@@ -585,7 +679,7 @@ def qk_prep_smooth(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: 
                    descale: Optional[torch.Tensor] = None, amax_out: Optional[torch.Tensor] = None, heads_per_scale: int = 1,
                    colsum_part: Optional[torch.Tensor] = None, dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1,
                    dot_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                   quantize: bool = True, rows=None, positions=None) -> Optional[torch.Tensor]:
+                   quantize: bool = True, rows=None, positions=None, rotate: Optional[HeadRotation] = None) -> Optional[torch.Tensor]:
     """``qk_prep_fp8`` with K smoothing (``la_qk_prep_smooth``). With y the fp32 value ``qk_prep`` would round:
 
     shift         fp32 (B, H, D): ``out`` and ``amax_out`` are taken from ``y - shift[b, h]``. Subtracting one vector from every key
@@ -600,12 +694,15 @@ def qk_prep_smooth(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: 
     rows / positions   as ``qk_prep`` (``la_qk_prep_smooth_rows``): ``out`` and ``dot_out`` are indexed by the row of the RESULT, and the
                   parts of ``colsum_part`` are cut from the rows of the result - the same S terms per column as the unmapped call, added
                   in another order.
+    rotate        as ``qk_prep`` (``la_qk_prep_smooth_rot``): y is the ROTATED value, so ``colsum_part`` (and the mean made of it),
+                  ``shift`` and ``dot_vec`` are vectors in the rotated basis - the mean of ``k M`` is ``(mean k) M``, and the dots of
+                  ``q M`` with it are ``q . mean k``: what the numbers mean changes, what ``lse_unshift`` restores does not.
     Everything else as ``qk_prep_fp8``; with ``shift``, ``colsum_part`` and ``dot_vec`` all None it is ``qk_prep_fp8``, bit for bit."""
     tabs, pairs = _unpack_tables(tables, x.shape[-1] if x.dim() else 0)
     if not quantize and out is not None:
         raise ValueError("quantize=False stores nothing: out must be None")
     return _qk_prep_smooth_impl(x, weight, eps, tabs, pairs, norm, pos_offset, shift, descale, amax_out, heads_per_scale, colsum_part,
-                                dot_vec, heads_per_dot, dot_out, out, bool(quantize), rows, positions)
+                                dot_vec, heads_per_dot, dot_out, out, bool(quantize), rows, positions, rotate)
 
 
 def colsum_finish(colsum_part: torch.Tensor, seqlen: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -625,27 +722,30 @@ def colsum_finish(colsum_part: torch.Tensor, seqlen: int, out: Optional[torch.Te
 
 def qk_prep_colmean(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6, tables: Optional[RopeTables] = None,
                     norm: Optional[str] = "token", pos_offset: int = 0, *, colsum_part: Optional[torch.Tensor] = None,
-                    out: Optional[torch.Tensor] = None, rows=None, positions=None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, rows=None, positions=None, rotate: Optional[HeadRotation] = None) -> torch.Tensor:
     """The mean of y over the rows, fp32 (B, H, D): the sums-only pass of ``qk_prep_smooth`` plus ``colsum_finish``. x is read once and
     nothing of its size is written. ``colsum_part`` / ``out``: buffers to reuse (None: allocated). ``rows`` / ``positions``: as
-    ``qk_prep_smooth`` (the mean over the rows the map names)."""
+    ``qk_prep_smooth`` (the mean over the rows the map names); ``rotate``: the mean of the rotated y."""
     _check_x(x, "qk_prep_smooth_reference")
     B, _, H, D = x.shape
     S = _row_map(x, rows, positions)[1]
     if colsum_part is None:
         colsum_part = torch.empty((qk_prep_smooth_parts(S, H, D)[0], B, H, D), dtype=torch.float32, device=x.device)
-    qk_prep_smooth(x, weight, eps, tables, norm, pos_offset, colsum_part=colsum_part, quantize=False, rows=rows, positions=positions)
+    qk_prep_smooth(x, weight, eps, tables, norm, pos_offset, colsum_part=colsum_part, quantize=False, rows=rows, positions=positions,
+                   rotate=rotate)
     return colsum_finish(colsum_part, S, out=out)
 
 
 def qk_prep_smooth_reference(x: torch.Tensor, weight: Optional[torch.Tensor] = None, eps: float = 1e-6,
                              tables: Optional[RopeTables] = None, norm: Optional[str] = "token", pos_offset: int = 0, *,
                              shift: Optional[torch.Tensor] = None, descale: Optional[torch.Tensor] = None, heads_per_scale: int = 1,
-                             dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1, rows=None, positions=None):
+                             dot_vec: Optional[torch.Tensor] = None, heads_per_dot: int = 1, rows=None, positions=None,
+                             rotate: Optional[HeadRotation] = None):
     """The formula of ``qk_prep_smooth`` in torch fp64, with ``y = qk_prep_reference(...)``: ``(clamp((y - shift) / descale, -448, 448)``
     UNROUNDED, the amax (B, H // heads_per_scale) of ``|y - shift|``, the mean (B, H, D) of y over the rows, the row dots (B, H, S) of y
-    with ``dot_vec`` or None``)``, all fp64. ``rows`` / ``positions``: as ``qk_prep_reference``; S is the number of rows of the result."""
-    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset, rows=rows, positions=positions)
+    with ``dot_vec`` or None``)``, all fp64. ``rows`` / ``positions`` / ``rotate``: as ``qk_prep_reference``; S is the number of rows of
+    the result."""
+    y = qk_prep_reference(x, weight, eps, tables, norm, pos_offset, rows=rows, positions=positions, rotate=rotate)
     B, S, H, D = y.shape
     hps, hpd = int(heads_per_scale), int(heads_per_dot)
     if hps < 1 or H % hps:
@@ -707,15 +807,17 @@ class SmoothedQK:
         self.mean = torch.empty((B, Hk, D), **f32)
         self.lse_shift = torch.empty((B, Hq, sq), **f32)
 
-    def pair(self, xq, xk, wq=None, wk=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None):
-        """``rows`` / ``positions``: one map for q and k (self-attention: both in the same order), as ``qk_prep_smooth``."""
+    def pair(self, xq, xk, wq=None, wk=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None,
+             rotate=None):
+        """``rows`` / ``positions``: one map for q and k (self-attention: both in the same order), as ``qk_prep_smooth``. ``rotate``: one
+        ``head_rotation`` for every pass over q and k; the mean is then that of the rotated keys."""
         Hq, Hk = xq.shape[2], xk.shape[2]
         if Hq % Hk:
             raise ValueError(f"{Hq} query heads are no multiple of {Hk} key heads")
         hps = Hq // Hk if self.heads_per_scale is None else int(self.heads_per_scale)
         if hps != Hq // Hk:
             raise ValueError(f"heads_per_scale of q must be H_q // H_kv = {Hq // Hk} (the attention call takes descales per kv head)")
-        m = dict(rows=rows, positions=positions)
+        m = dict(rows=rows, positions=positions, rotate=rotate)
         sq, sk = _row_map(xq, rows, positions)[1], _row_map(xk, rows, positions)[1]
         first = (self.q8 is None or tuple(self.q8.shape) != _out_shape(xq, sq) or tuple(self.k8.shape) != _out_shape(xk, sk)
                  or self.k8.device != xk.device)
