@@ -761,6 +761,39 @@ int la_v_prep_tiles(const la_v_prep_tiles_args* args, void* stream);
 int64_t la_v_tiles_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim);
 int64_t la_v_tiles_workspace_bytes(int32_t batch, int32_t num_heads_k, int32_t seqlen_k, int32_t head_dim);
 
+/* Token orders through V and O: la_v_colstats, la_v_prep_tiles, la_attn_unshift and la_attn_unshift_fp8 with a ROW MAP (added under ABI 9:
+ * the four argument structs are unchanged, a host detects the entry points by symbol). A layer that cannot permute its hidden states
+ * gathers V into the order of the call and restores O and the LSE out of it; these passes read V and O once anyway, so the gather
+ * and the restore are taken into their loads and cost no pass of their own. The map is the la_row_map of la_qk_prep_rows: src_rows is
+ * REQUIRED, positions must be NULL (nothing here has a position), and with i = b * batch_stride + s
+ *   row s of what the pass works on = row clamp(src_rows[i], 0, src_seqlen - 1) of the tensor it reads.
+ * args->seqlen counts the ENTRIES of the table - a permutation, a pruned selection, one with repeats - src_seqlen the rows of x / o.
+ * Each pass does per element what the row gather la_qk_prep_rows (LA_NORM_NONE, 16-bit to the same type) followed by its unmapped
+ * form does, bit for bit:
+ *   la_v_colstats_rows        stat_part is that of the gathered tensor: parts cut from args->seqlen (la_v_colstats_parts(args->seqlen, ..)),
+ *                             each part's rows added in TABLE order. la_v_colstats_finish follows unchanged, with seqlen = args->seqlen.
+ *   la_v_prep_tiles_rows      key n * 64 + r of tile n is made from row src_rows[n * 64 + r] of x; ceil(args->seqlen / 64) tiles, zeros past
+ *                             the end, the same codes, padding and amax. tiles: la_v_tiles_bytes(B, Hk, args->seqlen, D) bytes.
+ *   la_attn_unshift_rows      out[b][s] and lse_out[b][h][s] are made from o[b][src], lse[b][h][src] and lse_dot[b][h][src], the empty-row
+ *   la_attn_unshift_fp8_rows  rule included; row_descale is indexed by the out row s. o is (B, src_seqlen, H, D), lse and lse_dot
+ *                             [B, H, src_seqlen], out (B, seqlen, H, D), lse_out [B, H, seqlen]. To RESTORE the result of a call that ran
+ *                             in the order `order`, the table is its inverse (order's dst_rows). With neither shift nor lse_dot this is
+ *                             the restoring copy of O alone (give lse for the empty-row rule). Here lse_out may be given WITHOUT
+ *                             lse_dot: lse_out[b][h][s] = lse[b][h][src], the LSE restored with O (lse_dot without lse_out stays an error).
+ * The kernels clamp what they read from the table, as la_qk_prep_rows does: an entry outside [0, src_seqlen) reads the nearest row,
+ * never memory outside the tensor. The 64 (la_v_prep_tiles_rows) or 32 (the output passes with lse) indices of a workgroup's tile are
+ * read once and kept in LDS; source rows are read whole, and the writes keep their memory order.
+ * Errors (all before any HIP call): the checks of the unmapped entry point in its order and codes, and with them: NULL map
+ * LA_ERR_NULL_ARG (with NULL args); map->struct_size LA_ERR_STRUCT_SIZE (with args->struct_size); NULL src_rows LA_ERR_NULL_ARG (with
+ * the other pointers); src_seqlen < 1 LA_ERR_SHAPE (with the sizes); positions != NULL LA_ERR_UNSUPPORTED; the row stride of x / o
+ * is a used stride when src_seqlen > 1; src_rows off a 4-byte boundary or a negative batch_stride LA_ERR_STRIDE (with the strides);
+ * for the output passes out == o or lse_out == lse LA_ERR_UNSUPPORTED (a gather in place is not defined).
+ * NOT detected: a table shorter than [B or 1][seqlen], an lse or lse_dot shorter than [B, H, src_seqlen]. */
+int la_v_colstats_rows(const la_v_colstats_args* args, const la_row_map* map, void* stream);
+int la_v_prep_tiles_rows(const la_v_prep_tiles_args* args, const la_row_map* map, void* stream);
+int la_attn_unshift_rows(const la_attn_unshift_args* args, const la_row_map* map, void* stream);
+int la_attn_unshift_fp8_rows(const la_attn_unshift_fp8_args* args, const la_row_map* map, void* stream);
+
 /* How many workgroups of the kernel la_fwd runs for (head_dim, element size, flags) are resident at once on the current device:
  * compute units x workgroups per compute unit. A host that splits one attention into q-tile windows (la_fwd_args.q_tile_begin)
  * sizes them in whole rounds of this number. No counterpart in the reference (one launch per call). */

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "la_v_prep_tiles", "la_v_tiles_bytes", "la_v_tiles_workspace_bytes", "la_fwd_head_thr", "la_skip_list_stats_heads",
     "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows", "la_attn_unshift_fp8",
     "la_qk_prep_rot", "la_qk_prep_fp8_rot", "la_qk_prep_smooth_rot",
+    "la_v_colstats_rows", "la_v_prep_tiles_rows", "la_attn_unshift_rows", "la_attn_unshift_fp8_rows",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -292,7 +293,9 @@ def load() -> ctypes.CDLL:
     lib.la_qk_prep_smooth.argtypes = [ctypes.POINTER(LaQkPrepSmoothArgs), ctypes.c_void_p]
     lib.la_qk_prep_smooth.restype = ctypes.c_int
     for fn, struct in ((lib.la_qk_prep_rows, LaQkPrepArgs), (lib.la_qk_prep_fp8_rows, LaQkPrepFp8Args),
-                       (lib.la_qk_prep_smooth_rows, LaQkPrepSmoothArgs)):
+                       (lib.la_qk_prep_smooth_rows, LaQkPrepSmoothArgs), (lib.la_v_colstats_rows, LaVColstatsArgs),
+                       (lib.la_v_prep_tiles_rows, LaVPrepTilesArgs), (lib.la_attn_unshift_rows, LaAttnUnshiftArgs),
+                       (lib.la_attn_unshift_fp8_rows, LaAttnUnshiftFp8Args)):
         fn.argtypes = [ctypes.POINTER(struct), ctypes.POINTER(LaRowMap), ctypes.c_void_p]
         fn.restype = ctypes.c_int
     for fn, struct in ((lib.la_qk_prep_rot, LaQkPrepArgs), (lib.la_qk_prep_fp8_rot, LaQkPrepFp8Args),

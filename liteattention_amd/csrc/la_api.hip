@@ -729,6 +729,50 @@ int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t 
     return launch_status(err);
 }
 
+}  // extern "C"
+
+// The la_row_map of the V and O passes' _rows entry points (la_v_colstats_rows, la_v_prep_tiles_rows, la_attn_unshift_rows,
+// la_attn_unshift_fp8_rows), in the three places their order of checks has, each beside the unmapped rules of its kind: presence (with the
+// pointers), src_seqlen (with the sizes), the table's alignment and batch stride (behind the strides of the tensors). args->seqlen
+// counts the table's entries, src_seqlen the rows of the tensor that is read: its row stride is a used stride when src_seqlen > 1.
+// The launchers of the mapped kernels are weak references, as the rotating prologue's above and for its reason.
+namespace la {
+hipError_t launch_v_prep_tiles_rows(const VPrepTilesParams& p, const RowGather& g, int in_dtype, hipStream_t stream) __attribute__((weak));
+hipError_t launch_v_colstats_rows(const VColstatsParams& p, const RowGather& g, int in_dtype, hipStream_t stream) __attribute__((weak));
+hipError_t launch_attn_unshift_rows(const AttnUnshiftParams& p, const RowGather& g, int o_dtype, int out_dtype, hipStream_t stream)
+    __attribute__((weak));
+}
+static bool vo_map_present(bool mapped, const la_row_map* map) { return !mapped || (map->src_rows != nullptr); }
+static bool vo_map_strides_ok(const la_row_map* map) {
+    return !map || (map->batch_stride >= 0 && (reinterpret_cast<uintptr_t>(map->src_rows) & 3u) == 0);
+}
+static la::RowGather vo_gather(const la_row_map* map) { return la::RowGather{map->src_rows, map->batch_stride, map->src_seqlen}; }
+
+static int v_colstats_run(const la_v_colstats_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_v_colstats_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || !a->stat_part || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
+    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
+    if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
+    if (map && map->positions) return LA_ERR_UNSUPPORTED;                 // nothing here has a position
+    if (!rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
+                      a->num_heads) || !aligned16(a->stat_part) || !vo_map_strides_ok(map)) return LA_ERR_STRIDE;
+    la::VColstatsParams p = {};
+    p.x = a->x; p.stat_part = a->stat_part;
+    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    p.n_parts = la::v_colstats_parts(a->seqlen, a->num_heads, a->head_dim);
+    p.part_rows = la::v_colstats_part_rows(a->seqlen, a->num_heads, a->head_dim);
+    // one thread per (part, batch, head, chunk of 8 columns), 256 per workgroup
+    if (static_cast<int64_t>(p.n_parts) * a->batch * a->num_heads * (a->head_dim / 8) > 0x7fffffffLL * 256) return LA_ERR_SHAPE;
+    if (!map) return launch_status(la::launch_v_colstats(p, a->in_dtype, static_cast<hipStream_t>(stream_)));
+    if (!la::launch_v_colstats_rows) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_v_colstats_rows(p, vo_gather(map), a->in_dtype, static_cast<hipStream_t>(stream_)));
+}
+
+extern "C" {
+
 // ---- V smoothing (la_prep_v.hip) ---------------------------------------------------------------------------------------------------
 int la_v_colstats_parts(int32_t seqlen, int32_t num_heads, int32_t head_dim) {
     if (seqlen <= 0 || num_heads <= 0 || head_dim <= 0) return LA_ERR_SHAPE;
@@ -740,26 +784,8 @@ int la_v_colstats_part_rows(int32_t seqlen, int32_t num_heads, int32_t head_dim)
     return la::v_colstats_part_rows(seqlen, num_heads, head_dim);
 }
 
-int la_v_colstats(const la_v_colstats_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_v_colstats_args)) return LA_ERR_STRUCT_SIZE;
-    if (!a->x || !a->stat_part) return LA_ERR_NULL_ARG;
-    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
-    if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
-    if (!rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
-        !aligned16(a->stat_part)) return LA_ERR_STRIDE;
-    la::VColstatsParams p = {};
-    p.x = a->x; p.stat_part = a->stat_part;
-    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
-    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
-    p.n_parts = la::v_colstats_parts(a->seqlen, a->num_heads, a->head_dim);
-    p.part_rows = la::v_colstats_part_rows(a->seqlen, a->num_heads, a->head_dim);
-    // one thread per (part, batch, head, chunk of 8 columns), 256 per workgroup
-    if (static_cast<int64_t>(p.n_parts) * a->batch * a->num_heads * (a->head_dim / 8) > 0x7fffffffLL * 256) return LA_ERR_SHAPE;
-    const hipError_t err = la::launch_v_colstats(p, a->in_dtype, static_cast<hipStream_t>(stream_));
-    return launch_status(err);
-}
+int la_v_colstats(const la_v_colstats_args* a, void* stream) { return v_colstats_run(a, false, nullptr, stream); }
+int la_v_colstats_rows(const la_v_colstats_args* a, const la_row_map* map, void* stream) { return v_colstats_run(a, true, map, stream); }
 
 int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int32_t num_heads, int32_t head_dim, int32_t seqlen,
                          float* mean_out, int64_t mean_batch_stride, int64_t mean_head_stride, float* amax_out, int64_t amax_batch_stride,
@@ -777,23 +803,30 @@ int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int3
     return launch_status(err);
 }
 
-int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_attn_unshift_args)) return LA_ERR_STRUCT_SIZE;
-    if (!a->o || !a->out) return LA_ERR_NULL_ARG;
-    if ((a->lse_dot != nullptr) != (a->lse_out != nullptr) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
+// la_attn_unshift and la_attn_unshift_fp8 behind their unmapped entry points (mapped false, map NULL) and their _rows ones: o, lse and
+// lse_dot then have map->src_seqlen rows, out, lse_out and row_descale args->seqlen, and nothing may be written over what is read
+static int attn_unshift_run(const la_attn_unshift_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_attn_unshift_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+    if (!a->o || !a->out || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
+    // (under a map lse_out may come without lse_dot: the LSE at the rows)
+    if ((a->lse_dot && !a->lse_out) || (a->lse_out && !a->lse_dot && !map) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
     if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
     if (!is_input_dtype(a->out_dtype)) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
     if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, a->seqlen, a->num_heads) ||
+    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
+                      a->num_heads) ||
         !rows_aligned(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen, a->num_heads))
         return LA_ERR_STRIDE;
     if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
                             a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
     if ((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out)) & 3u)
         return LA_ERR_STRIDE;
+    if (!vo_map_strides_ok(map)) return LA_ERR_STRIDE;
+    // a gather in place is not defined (rows would be read after they were overwritten), and nothing here has a position
+    if (map && (a->out == a->o || (a->lse_out && a->lse_out == a->lse) || map->positions)) return LA_ERR_UNSUPPORTED;
     la::AttnUnshiftParams p = {};
     p.o = a->o; p.out = a->out; p.shift = a->shift; p.lse = a->lse; p.lse_dot = a->lse_dot; p.lse_out = a->lse_out;
     p.o_bs = a->o_batch_stride; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
@@ -802,21 +835,26 @@ int la_attn_unshift(const la_attn_unshift_args* a, void* stream_) {
     p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
     p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
     p.softmax_scale = a->softmax_scale;
-    const hipError_t err = la::launch_attn_unshift(p, a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
-    return launch_status(err);
+    if (!map) return launch_status(la::launch_attn_unshift(p, a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_)));
+    if (!la::launch_attn_unshift_rows) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_attn_unshift_rows(p, vo_gather(map), a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_)));
 }
+int la_attn_unshift(const la_attn_unshift_args* a, void* stream) { return attn_unshift_run(a, false, nullptr, stream); }
+int la_attn_unshift_rows(const la_attn_unshift_args* a, const la_row_map* map, void* stream) { return attn_unshift_run(a, true, map, stream); }
 
-int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_attn_unshift_fp8_args)) return LA_ERR_STRUCT_SIZE;
-    if (!a->o || !a->out || (!a->descale_in && !a->row_descale)) return LA_ERR_NULL_ARG;
-    if ((a->lse_dot != nullptr) != (a->lse_out != nullptr) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
+static int attn_unshift_fp8_run(const la_attn_unshift_fp8_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_attn_unshift_fp8_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+    if (!a->o || !a->out || (!a->descale_in && !a->row_descale) || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
+    // (under a map lse_out may come without lse_dot: the LSE at the rows)
+    if ((a->lse_dot && !a->lse_out) || (a->lse_out && !a->lse_dot && !map) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
     if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
     if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
     if (a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, a->seqlen, a->num_heads) ||
+    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
+                      a->num_heads) ||
         !rows_aligned(a->out, LA_DTYPE_FP8_E4M3, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen,
                       a->num_heads)) return LA_ERR_STRIDE;
     if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
@@ -825,8 +863,9 @@ int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* a, void* stream_) {
          reinterpret_cast<uintptr_t>(a->row_descale) | reinterpret_cast<uintptr_t>(a->descale_in) | reinterpret_cast<uintptr_t>(a->amax)) & 3u)
         return LA_ERR_STRIDE;
     if (a->row_descale_batch_stride < 0 || a->row_descale_row_stride < 0 || a->row_descale_group_stride < 0 ||
-        a->descale_in_batch_stride < 0 || a->amax_batch_stride < 0) return LA_ERR_STRIDE;
+        a->descale_in_batch_stride < 0 || a->amax_batch_stride < 0 || !vo_map_strides_ok(map)) return LA_ERR_STRIDE;
     if (a->out == a->o) return LA_ERR_UNSUPPORTED;                   // one byte for two: a chunk's bytes lie over another chunk's elements
+    if (map && ((a->lse_out && a->lse_out == a->lse) || map->positions)) return LA_ERR_UNSUPPORTED;      // as la_attn_unshift_rows
     // a wave keeps a scale group in registers; a workgroup the empty-row flags of every head of its rows in LDS
     if (static_cast<int64_t>(a->heads_per_scale) * a->head_dim > la::kAttnOutFp8MaxGroup || a->num_heads > la::kAttnOutFp8MaxHeads)
         return LA_ERR_UNSUPPORTED;
@@ -849,7 +888,13 @@ int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* a, void* stream_) {
         p.row_descale = a->row_descale;
         p.rd_bs = a->row_descale_batch_stride; p.rd_rs = a->row_descale_row_stride; p.rd_gs = a->row_descale_group_stride;
     }
-    return launch_status(la::launch_attn_unshift(p, a->o_dtype, LA_DTYPE_FP8_E4M3, static_cast<hipStream_t>(stream_)));
+    if (!map) return launch_status(la::launch_attn_unshift(p, a->o_dtype, LA_DTYPE_FP8_E4M3, static_cast<hipStream_t>(stream_)));
+    if (!la::launch_attn_unshift_rows) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_attn_unshift_rows(p, vo_gather(map), a->o_dtype, LA_DTYPE_FP8_E4M3, static_cast<hipStream_t>(stream_)));
+}
+int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* a, void* stream) { return attn_unshift_fp8_run(a, false, nullptr, stream); }
+int la_attn_unshift_fp8_rows(const la_attn_unshift_fp8_args* a, const la_row_map* map, void* stream) {
+    return attn_unshift_fp8_run(a, true, map, stream);
 }
 
 // ---- fp8 V in one pass (la_prep_fp8.hip) -------------------------------------------------------------------------------------------
@@ -864,15 +909,18 @@ int64_t la_v_tiles_workspace_bytes(int32_t batch, int32_t num_heads_k, int32_t s
     return tiles < 0 ? tiles : tiles + static_cast<int64_t>(kSchedWorkspaceBytes);      // FwdWorkspace's first two terms: an e4m3 la_fwd that is one launch
 }
 
-int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_v_prep_tiles_args)) return LA_ERR_STRUCT_SIZE;
-    if (!a->x || !a->tiles) return LA_ERR_NULL_ARG;
+// behind la_v_prep_tiles (mapped false, map NULL) and la_v_prep_tiles_rows: x then has map->src_seqlen rows, the tiles args->seqlen keys
+static int v_prep_tiles_run(const la_v_prep_tiles_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_v_prep_tiles_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
+    if (!a->x || !a->tiles || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0) return LA_ERR_SHAPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
     if (la::tile_shape(a->head_dim, 1).block_m == 0) return LA_ERR_HEAD_DIM;     // the head dims the e4m3 forward has
-    if (a->reserved0 != 0) return LA_ERR_UNSUPPORTED;
-    if (!rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, a->seqlen, a->num_heads) ||
+    if (a->reserved0 != 0 || (map && map->positions)) return LA_ERR_UNSUPPORTED;
+    if (!vo_map_strides_ok(map) ||
+        !rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
+                      a->num_heads) ||
         (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1, a->num_heads)) ||
         !aligned16(a->tiles) || a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 ||
         a->amax_head_stride < 0 || ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u))
@@ -886,7 +934,11 @@ int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream_) {
     p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
     p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
     p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
-    return launch_status(la::launch_v_prep_tiles(p, a->in_dtype, static_cast<hipStream_t>(stream_)));
+    if (!map) return launch_status(la::launch_v_prep_tiles(p, a->in_dtype, static_cast<hipStream_t>(stream_)));
+    if (!la::launch_v_prep_tiles_rows) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_v_prep_tiles_rows(p, vo_gather(map), a->in_dtype, static_cast<hipStream_t>(stream_)));
 }
+int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream) { return v_prep_tiles_run(a, false, nullptr, stream); }
+int la_v_prep_tiles_rows(const la_v_prep_tiles_args* a, const la_row_map* map, void* stream) { return v_prep_tiles_run(a, true, map, stream); }
 
 }  // extern "C"

@@ -240,4 +240,23 @@ constexpr int kAttnOutFp8Rows = 32;          // rows of a workgroup's tile: one 
 // out_dtype: 0 bf16, 1 fp16, 3 fp32 (la_attn_unshift), 2 e4m3 (la_attn_unshift_fp8: one workgroup per tile of kAttnOutFp8Rows rows of a batch)
 hipError_t launch_attn_unshift(const AttnUnshiftParams& p, int o_dtype, int out_dtype, hipStream_t stream);
 
+// The _rows entry points of the V and O passes (la_v_prep_tiles_rows, la_v_colstats_rows, la_attn_unshift_rows, la_attn_unshift_fp8_rows):
+// row s of batch b of what the pass works on is row rows[b map_bs + s] of the tensor it reads, clamped into [0, src_seqlen). A kernel
+// argument of its own BEHIND the pass's parameter block, which keeps its size and means what it meant - `seqlen` there counts the
+// rows of the table (the keys of the tiles, the rows of the statistics, the rows of out and lse_out), src_seqlen the rows of x / o and of
+// lse / lse_dot. Kernels of their own, instantiated from the bodies the unmapped kernels are instantiated from (ROWS false: every line
+// that names the map is compiled out, and the unmapped kernels keep their arguments).
+struct RowGather {
+    const int32_t* rows;         // [batch or 1][seqlen], never NULL
+    int64_t map_bs;              // elements between the tables of two batches; 0: one table for every batch
+    int src_seqlen;              // rows of the tensor that is read
+};
+__device__ __forceinline__ int gather_row(const RowGather& g, int b, int64_t s) {
+    const int r = g.rows[b * g.map_bs + s];
+    return r < 0 ? 0 : (r >= g.src_seqlen ? g.src_seqlen - 1 : r);
+}
+hipError_t launch_v_prep_tiles_rows(const VPrepTilesParams& p, const RowGather& g, int in_dtype, hipStream_t stream);
+hipError_t launch_v_colstats_rows(const VColstatsParams& p, const RowGather& g, int in_dtype, hipStream_t stream);
+hipError_t launch_attn_unshift_rows(const AttnUnshiftParams& p, const RowGather& g, int o_dtype, int out_dtype, hipStream_t stream);
+
 }  // namespace la

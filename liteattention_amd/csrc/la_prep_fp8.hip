@@ -10,7 +10,8 @@
 //
 // la_v_prep_tiles is the same tile writer behind a quantizing front end: it reads V as the projection wrote it (bf16 / fp16 / fp32),
 // quantizes it as la_qk_prep_smooth does for LA_NORM_NONE and stores the tiles, so that la_fwd runs under LA_FLAG_V_PREPARED and the
-// e4m3 (B, S, Hk, D) tensor between the two passes is never written.
+// e4m3 (B, S, Hk, D) tensor between the two passes is never written. la_v_prep_tiles_rows is that pass with a token order's gather of V
+// taken into its loads (v_prep_tiles_body, ROWS).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -107,8 +108,19 @@ __global__ void __launch_bounds__(256) la_prep_v_fp8_kernel(const uint8_t* __res
 // seqlen are zeros. amax: the unsigned maximum of the bit patterns of |y'| (order-free, a NaN wins) per wave by shuffles, per
 // workgroup over four LDS words, ONE global atomicMax per workgroup. No float atomics: two launches write the same bytes.
 // ------------------------------------------------------------------------------------------------
-template <int D, int DT>
-__global__ void __launch_bounds__(256) la_v_prep_tiles_kernel(const VPrepTilesParams p) {
+// ROWS (la_v_prep_tiles_rows): key n 64 + r of tile n is made from row g.rows[b][n 64 + r] of x - the gather that stood in front of this
+// pass, fused into its loads. p.seqlen counts the table's entries (a permutation, a pruned selection, one with repeats), g.src_seqlen
+// the rows of x. What is settled here:
+//  * the 64 row indices of the tile are read ONCE per workgroup - its first wave, one coalesced 256-byte read -, clamped into
+//    [0, src_seqlen) and kept in LDS; a thread then takes the row of each of its D / 32 chunks from there (a thread's chunks lie in D / 32
+//    different rows, and 8 to 32 threads share a row: per chunk that would be up to 2048 index loads a tile for 64 words);
+//  * behind the one barrier that costs, all row loads of a thread are issued before the first conversion, as without a map;
+//  * a source row of a head is still one contiguous D x elsize run that neighbouring threads read in neighbouring 16-byte pieces: the
+//    loads stay 16-byte and whole-line, only the lines of different keys no longer follow each other in memory;
+//  * everything behind the loads - canonicalize, shift, amax, descale, clamp, the e4m3 cast, zeros past the end, the transposing second
+//    phase f8_store_vt_tile - is the SAME code, instantiated from this one body: a code depends on the source row it is made from alone.
+template <int D, int DT, bool ROWS>
+__device__ __forceinline__ void v_prep_tiles_body(const VPrepTilesParams& p, const RowGather& g) {
     constexpr int DP = D == 96 ? 128 : D;
     constexpr int kRowChunks = D / 8, kPerThread = F8_BN * kRowChunks / 256;       // D / 32: 2, 3, 4, 6, 8 chunks per thread, no remainder
     __shared__ __attribute__((aligned(16))) uint8_t tile[F8_BN][D + 16];   // [key][d], padded rows
@@ -120,13 +132,19 @@ __global__ void __launch_bounds__(256) la_v_prep_tiles_kernel(const VPrepTilesPa
     const float inv = p.descale ? __fdiv_rn(1.f, p.descale[b * p.ds_bs + h * p.ds_hs]) : 1.f;
     const float* shift = p.shift ? p.shift + b * p.sh_bs + h * p.sh_hs : nullptr;
     const int64_t x_head = b * p.x_bs + h * p.x_hs;
+    __shared__ int src_row[ROWS ? F8_BN : 1];
+    if constexpr (ROWS) {
+        if (tid < F8_BN) src_row[tid] = n * F8_BN + tid < p.seqlen ? gather_row(g, b, n * F8_BN + tid) : 0;
+        __syncthreads();
+    }
     typename PrepLoad<DT>::raw raw[kPerThread];
 #pragma unroll
     for (int it = 0; it < kPerThread; ++it) {
         const int cid = tid + 256 * it;
         const int row = cid / kRowChunks, ch = cid % kRowChunks;
         const int key = n * F8_BN + row;
-        raw[it] = key < p.seqlen ? PrepLoad<DT>::load(p.x, x_head + static_cast<int64_t>(key) * p.x_rs + ch * 8) : PrepLoad<DT>::zero();
+        const int src = ROWS ? src_row[row] : key;
+        raw[it] = key < p.seqlen ? PrepLoad<DT>::load(p.x, x_head + static_cast<int64_t>(src) * p.x_rs + ch * 8) : PrepLoad<DT>::zero();
     }
     unsigned m = 0;
 #pragma unroll
@@ -161,6 +179,16 @@ __global__ void __launch_bounds__(256) la_v_prep_tiles_kernel(const VPrepTilesPa
         if (mw) atomicMax(reinterpret_cast<unsigned*>(p.amax + b * p.am_bs + h * p.am_hs), mw);
     }
     f8_store_vt_tile<D>(tile, p.tiles + (static_cast<int64_t>(bh) * p.k_tiles + n) * (F8_BN * DP), tid);
+}
+
+template <int D, int DT>
+__global__ void __launch_bounds__(256) la_v_prep_tiles_kernel(const VPrepTilesParams p) {
+    v_prep_tiles_body<D, DT, false>(p, RowGather{});
+}
+
+template <int D, int DT>
+__global__ void __launch_bounds__(256) la_v_prep_tiles_rows_kernel(const VPrepTilesParams p, const RowGather g) {
+    v_prep_tiles_body<D, DT, true>(p, g);
 }
 
 hipError_t launch_prep_v_fp8(const void* v, int64_t v_batch_stride, int64_t v_row_stride, int64_t v_head_stride,
@@ -205,6 +233,24 @@ hipError_t launch_v_prep_tiles(const VPrepTilesParams& p, int in_dtype, hipStrea
     if (in_dtype == 0) launch_v_prep_tiles_typed<0>(p, stream);
     else if (in_dtype == 1) launch_v_prep_tiles_typed<1>(p, stream);
     else launch_v_prep_tiles_typed<3>(p, stream);
+    return hipGetLastError();
+}
+
+template <int DT>
+static void launch_v_prep_tiles_rows_typed(const VPrepTilesParams& p, const RowGather& g, hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(p.batch) * p.num_heads * p.k_tiles);
+    if (p.head_dim == 256) hipLaunchKernelGGL((la_v_prep_tiles_rows_kernel<256, DT>), grid, dim3(256), 0, stream, p, g);
+    else if (p.head_dim == 192) hipLaunchKernelGGL((la_v_prep_tiles_rows_kernel<192, DT>), grid, dim3(256), 0, stream, p, g);
+    else if (p.head_dim == 96) hipLaunchKernelGGL((la_v_prep_tiles_rows_kernel<96, DT>), grid, dim3(256), 0, stream, p, g);
+    else if (p.head_dim == 64) hipLaunchKernelGGL((la_v_prep_tiles_rows_kernel<64, DT>), grid, dim3(256), 0, stream, p, g);
+    else hipLaunchKernelGGL((la_v_prep_tiles_rows_kernel<128, DT>), grid, dim3(256), 0, stream, p, g);
+}
+
+hipError_t launch_v_prep_tiles_rows(const VPrepTilesParams& p, const RowGather& g, int in_dtype, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (in_dtype == 0) launch_v_prep_tiles_rows_typed<0>(p, g, stream);
+    else if (in_dtype == 1) launch_v_prep_tiles_rows_typed<1>(p, g, stream);
+    else launch_v_prep_tiles_rows_typed<3>(p, g, stream);
     return hipGetLastError();
 }
 

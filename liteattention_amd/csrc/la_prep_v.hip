@@ -24,6 +24,9 @@
 //  * la_attn_unshift_lse_kernel<O, OUT>: the same with lse. A row whose lse is +-inf is the forward's empty sum (no weights carry the
 //    shift): zeros, lse copied. o runs (s, h), lse runs (h, s): a workgroup takes a tile of 32 s x 8 heads, moves the tile's lse /
 //    lse_dot / lse_out along s in whole cache lines (one element per thread, through LDS), then walks o in its own memory order.
+//  * the _rows kernels (la_v_colstats_rows_kernel, la_attn_unshift_rows_kernel, la_attn_unshift_lse_rows_kernel,
+//    la_attn_out_fp8_rows_kernel): each of the above instantiated from the same body with a RowGather (la_kernel_params.h) - a token
+//    order's gather of V or restore of O and of the LSE taken into the pass that reads the tensor anyway. Each body says what its map costs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,8 +49,12 @@ __device__ __forceinline__ void take_row(const float (&v)[8], float (&sum)[8], f
     }
 }
 
-template <int DT>
-__global__ void __launch_bounds__(256) la_v_colstats_kernel(const VColstatsParams p) {
+// ROWS (la_v_colstats_rows): row s of the statistics is row g.rows[b][s] of x. The parts are cut from p.seqlen, the table's length, and a
+// thread adds its part's rows in TABLE order: the partials are those of the gathered tensor bit for bit (a permutation's mean is order
+// free only up to fp32 rounding, a selection's is another mean), and la_v_colstats_finish runs unchanged. The kRowsInFlight indices of
+// a step are loaded in front of its row loads; every thread of a (part, batch) asks for the same words - a wave's loads of one.
+template <int DT, bool ROWS>
+__device__ __forceinline__ void v_colstats_body(const VColstatsParams& p, const RowGather& g) {
     const int chunks = p.head_dim / 8;
     const int64_t items = static_cast<int64_t>(p.n_parts) * p.batch * p.num_heads * chunks;
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -67,8 +74,11 @@ __global__ void __launch_bounds__(256) la_v_colstats_kernel(const VColstatsParam
     int64_t r = r0;
     for (; r + kRowsInFlight <= r1; r += kRowsInFlight) {
         typename PrepLoad<DT>::raw w[kRowsInFlight];
+        int64_t src[kRowsInFlight];
 #pragma unroll
-        for (int u = 0; u < kRowsInFlight; ++u) w[u] = PrepLoad<DT>::load(p.x, col0 + (r + u) * p.x_rs);
+        for (int u = 0; u < kRowsInFlight; ++u) src[u] = ROWS ? gather_row(g, b, r + u) : r + u;
+#pragma unroll
+        for (int u = 0; u < kRowsInFlight; ++u) w[u] = PrepLoad<DT>::load(p.x, col0 + src[u] * p.x_rs);
 #pragma unroll
         for (int u = 0; u < kRowsInFlight; ++u) {
             float v[8];
@@ -78,7 +88,7 @@ __global__ void __launch_bounds__(256) la_v_colstats_kernel(const VColstatsParam
     }
     for (; r < r1; ++r) {
         float v[8];
-        PrepLoad<DT>::to_float(PrepLoad<DT>::load(p.x, col0 + r * p.x_rs), v);
+        PrepLoad<DT>::to_float(PrepLoad<DT>::load(p.x, col0 + (ROWS ? gather_row(g, b, r) : r) * p.x_rs), v);
         take_row(v, sum, lo, hi);
     }
     const int64_t cols = static_cast<int64_t>(p.batch) * p.num_heads * p.head_dim;
@@ -86,6 +96,16 @@ __global__ void __launch_bounds__(256) la_v_colstats_kernel(const VColstatsParam
     PrepStore<3>::store8(dst, 0, sum);
     PrepStore<3>::store8(dst, cols, lo);
     PrepStore<3>::store8(dst, 2 * cols, hi);
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) la_v_colstats_kernel(const VColstatsParams p) {
+    v_colstats_body<DT, false>(p, RowGather{});
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) la_v_colstats_rows_kernel(const VColstatsParams p, const RowGather g) {
+    v_colstats_body<DT, true>(p, g);
 }
 
 __global__ void __launch_bounds__(256) la_v_colstats_finish_kernel(const float* __restrict__ part, int n_parts, int64_t cols, int head_dim,
@@ -123,11 +143,11 @@ __global__ void __launch_bounds__(256) la_v_colstats_finish_kernel(const float* 
         amax[b * a_bs + h * a_hs] = __uint_as_float(umax(umax(wave_max[0], wave_max[1]), umax(wave_max[2], wave_max[3])));
 }
 
-// 8 elements of a row: load, add the shift of the row's kv head, zero when the row is empty, round and store
+// 8 elements of a row: load (row src of o), add the shift of the row's kv head, zero when the row is empty, round and store (row s of out)
 template <int DT_O, int DT_OUT>
-__device__ __forceinline__ void unshift_chunk(const AttnUnshiftParams& p, int b, int s, int h, int ch, bool empty) {
+__device__ __forceinline__ void unshift_chunk(const AttnUnshiftParams& p, int b, int src, int s, int h, int ch, bool empty) {
     float v[8];
-    PrepLoad<DT_O>::to_float(PrepLoad<DT_O>::load(p.o, b * p.o_bs + s * p.o_rs + h * p.o_hs + ch * 8), v);
+    PrepLoad<DT_O>::to_float(PrepLoad<DT_O>::load(p.o, b * p.o_bs + src * p.o_rs + h * p.o_hs + ch * 8), v);
     if (p.shift != nullptr) {
         float c[8];
         load_f32x8(p.shift + b * p.sh_bs + (h / p.heads_per_vec) * p.sh_hs + ch * 8, c);
@@ -142,8 +162,10 @@ __device__ __forceinline__ void unshift_chunk(const AttnUnshiftParams& p, int b,
 }
 
 // Without lse: one thread = 8 consecutive d of one (b, s, h) row, grid stride over the rows in memory order.
-template <int DT_O, int DT_OUT>
-__global__ void __launch_bounds__(256) la_attn_unshift_kernel(const AttnUnshiftParams p) {
+// ROWS (la_attn_unshift_rows): out row s is made from row g.rows[b][s] of o - `restore` fused; p.seqlen counts the rows of out. The
+// H D / 8 threads of a row ask for the same index word, the reads of o stay whole rows, the writes keep their memory order.
+template <int DT_O, int DT_OUT, bool ROWS>
+__device__ __forceinline__ void attn_unshift_body(const AttnUnshiftParams& p, const RowGather& g) {
     const int chunks = p.head_dim / 8;
     const int64_t total = static_cast<int64_t>(p.batch) * p.seqlen * p.num_heads * chunks;
     for (int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total;
@@ -152,8 +174,17 @@ __global__ void __launch_bounds__(256) la_attn_unshift_kernel(const AttnUnshiftP
         const int64_t row = idx / chunks;      // (b * S + s) * H + h
         const int h = static_cast<int>(row % p.num_heads);
         const int64_t bs = row / p.num_heads;
-        unshift_chunk<DT_O, DT_OUT>(p, static_cast<int>(bs / p.seqlen), static_cast<int>(bs % p.seqlen), h, ch, false);
+        const int b = static_cast<int>(bs / p.seqlen), s = static_cast<int>(bs % p.seqlen);
+        unshift_chunk<DT_O, DT_OUT>(p, b, ROWS ? gather_row(g, b, s) : s, s, h, ch, false);
     }
+}
+template <int DT_O, int DT_OUT>
+__global__ void __launch_bounds__(256) la_attn_unshift_kernel(const AttnUnshiftParams p) {
+    attn_unshift_body<DT_O, DT_OUT, false>(p, RowGather{});
+}
+template <int DT_O, int DT_OUT>
+__global__ void __launch_bounds__(256) la_attn_unshift_rows_kernel(const AttnUnshiftParams p, const RowGather g) {
+    attn_unshift_body<DT_O, DT_OUT, true>(p, g);
 }
 
 // With lse: o is (b, s, h, d) and lse (b, h, s), so the flat map above would read 4 bytes of a different cache line per head. A
@@ -161,10 +192,15 @@ __global__ void __launch_bounds__(256) la_attn_unshift_kernel(const AttnUnshiftP
 // lse along s (whole lines), keeps it in LDS, writes lse_out = fmaf(scale, lse_dot, lse) the same way - each element is read and
 // written by ONE thread, so lse_out may be lse - and then walks the tile's chunks in the memory order of o (per s a contiguous run of
 // kUnshiftHeads heads), taking the empty-row flag from LDS. Tiles by grid stride.
+// ROWS: the tile is one of OUT rows. Its kUnshiftRows source rows are read once, by the first lanes of the workgroup, clamped and kept in
+// LDS (tile_src). lse and lse_dot (src_seqlen long along s) are then read at the source rows - scattered 4-byte reads, the one thing a
+// map costs here: 8 heads x 32 words against 32 whole rows of o -, lse_out (seqlen long) is written along s in whole lines as before, and
+// the walk over o reads whole source rows and writes out in its memory order. lse_out may NOT be lse, nor out o: la_api.hip refuses both.
 constexpr int kUnshiftRows = 32, kUnshiftHeads = 8;
-template <int DT_O, int DT_OUT>
-__global__ void __launch_bounds__(256) la_attn_unshift_lse_kernel(const AttnUnshiftParams p) {
+template <int DT_O, int DT_OUT, bool ROWS>
+__device__ __forceinline__ void attn_unshift_lse_body(const AttnUnshiftParams& p, const RowGather& g) {
     __shared__ float lse_tile[kUnshiftHeads * kUnshiftRows];
+    __shared__ int tile_src[ROWS ? kUnshiftRows : 1];
     const int chunks = p.head_dim / 8;
     const int s_tiles = (p.seqlen + kUnshiftRows - 1) / kUnshiftRows, h_tiles = (p.num_heads + kUnshiftHeads - 1) / kUnshiftHeads;
     const int64_t tiles = static_cast<int64_t>(p.batch) * s_tiles * h_tiles;
@@ -175,14 +211,20 @@ __global__ void __launch_bounds__(256) la_attn_unshift_lse_kernel(const AttnUnsh
         const int s0 = st * kUnshiftRows, h0 = ht * kUnshiftHeads;
         const int ns = p.seqlen - s0 < kUnshiftRows ? p.seqlen - s0 : kUnshiftRows;
         const int nh = p.num_heads - h0 < kUnshiftHeads ? p.num_heads - h0 : kUnshiftHeads;
+        if constexpr (ROWS) {
+            if (threadIdx.x < ns) tile_src[threadIdx.x] = gather_row(g, b, s0 + threadIdx.x);
+            __syncthreads();
+        }
         {
             const int hh = threadIdx.x / kUnshiftRows, ss = threadIdx.x % kUnshiftRows;      // 256 threads = 8 heads x 32 rows
             if (hh < nh && ss < ns) {
-                const int64_t idx = (static_cast<int64_t>(b) * p.num_heads + h0 + hh) * p.seqlen + s0 + ss;
-                const float l = p.lse[idx];
+                const int64_t bh = static_cast<int64_t>(b) * p.num_heads + h0 + hh;
+                const int64_t idx = bh * p.seqlen + s0 + ss, from = ROWS ? bh * g.src_seqlen + tile_src[ss] : idx;
+                const float l = p.lse[from];
                 lse_tile[threadIdx.x] = l;
                 if (p.lse_out != nullptr)                              // an empty row keeps its lse; a NaN takes the normal path
-                    p.lse_out[idx] = (l == INFINITY || l == -INFINITY) ? l : fmaf(p.softmax_scale, p.lse_dot[idx], l);
+                    p.lse_out[idx] = (l == INFINITY || l == -INFINITY || (ROWS && p.lse_dot == nullptr))      // ROWS, no lse_dot: the
+                                         ? l : fmaf(p.softmax_scale, p.lse_dot[from], l);                     // gathered lse alone
             }
         }
         __syncthreads();
@@ -190,23 +232,34 @@ __global__ void __launch_bounds__(256) la_attn_unshift_lse_kernel(const AttnUnsh
         for (int i = threadIdx.x; i < items; i += 256) {
             const int ss = i / per_row, rest = i - ss * per_row, hh = rest / chunks, ch = rest - hh * chunks;
             const float l = lse_tile[hh * kUnshiftRows + ss];
-            unshift_chunk<DT_O, DT_OUT>(p, b, s0 + ss, h0 + hh, ch, l == INFINITY || l == -INFINITY);
+            unshift_chunk<DT_O, DT_OUT>(p, b, ROWS ? tile_src[ss] : s0 + ss, s0 + ss, h0 + hh, ch, l == INFINITY || l == -INFINITY);
         }
         __syncthreads();                                               // the tile is free for the next one
     }
 }
-
 template <int DT_O, int DT_OUT>
-void launch_unshift_typed(const AttnUnshiftParams& p, hipStream_t stream) {
+__global__ void __launch_bounds__(256) la_attn_unshift_lse_kernel(const AttnUnshiftParams p) {
+    attn_unshift_lse_body<DT_O, DT_OUT, false>(p, RowGather{});
+}
+template <int DT_O, int DT_OUT>
+__global__ void __launch_bounds__(256) la_attn_unshift_lse_rows_kernel(const AttnUnshiftParams p, const RowGather g) {
+    attn_unshift_lse_body<DT_O, DT_OUT, true>(p, g);
+}
+
+// g: the row map of a _rows entry point, nullptr for the unmapped ones - the same grids, the kernels of each
+template <int DT_O, int DT_OUT>
+void launch_unshift_typed(const AttnUnshiftParams& p, const RowGather* g, hipStream_t stream) {
     if (p.lse != nullptr) {
         const int64_t tiles = static_cast<int64_t>(p.batch) * ((p.seqlen + kUnshiftRows - 1) / kUnshiftRows) *
                               ((p.num_heads + kUnshiftHeads - 1) / kUnshiftHeads);
         const unsigned grid = static_cast<unsigned>(tiles < kUnshiftMaxTiles ? tiles : kUnshiftMaxTiles);
-        hipLaunchKernelGGL((la_attn_unshift_lse_kernel<DT_O, DT_OUT>), dim3(grid), dim3(256), 0, stream, p);
+        if (g) hipLaunchKernelGGL((la_attn_unshift_lse_rows_kernel<DT_O, DT_OUT>), dim3(grid), dim3(256), 0, stream, p, *g);
+        else hipLaunchKernelGGL((la_attn_unshift_lse_kernel<DT_O, DT_OUT>), dim3(grid), dim3(256), 0, stream, p);
     } else {
         const int64_t blocks = (static_cast<int64_t>(p.batch) * p.seqlen * p.num_heads * (p.head_dim / 8) + 255) / 256;
         const unsigned grid = static_cast<unsigned>(blocks < kUnshiftMaxGrid ? blocks : kUnshiftMaxGrid);
-        hipLaunchKernelGGL((la_attn_unshift_kernel<DT_O, DT_OUT>), dim3(grid), dim3(256), 0, stream, p);
+        if (g) hipLaunchKernelGGL((la_attn_unshift_rows_kernel<DT_O, DT_OUT>), dim3(grid), dim3(256), 0, stream, p, *g);
+        else hipLaunchKernelGGL((la_attn_unshift_kernel<DT_O, DT_OUT>), dim3(grid), dim3(256), 0, stream, p);
     }
 }
 
@@ -222,24 +275,35 @@ void launch_unshift_typed(const AttnUnshiftParams& p, hipStream_t stream) {
 // maximum of the workgroup goes through four words of LDS into ONE atomicMax on the bit pattern.
 // STAGE: the batch's shift rows lie in LDS behind the flags (the launcher decides: a shift that fits). A unit reads its shift twice,
 // 32 bytes for every 16 of o, chunk after chunk: from LDS that is a short wait each, from the L2 a trip each.
-template <int DT_O, int C, bool STAGE>
-__global__ void __launch_bounds__(256) la_attn_out_fp8_kernel(const AttnUnshiftParams p, const int team) {
+// ROWS (la_attn_unshift_fp8_rows): the tile is one of OUT rows; its kAttnOutFp8Rows source rows are read once into LDS (tile_src). The
+// flags and lse_out are made from lse / lse_dot at the source rows (scattered 4-byte reads, lse_out still written along s), a team loads
+// its unit from the source row of o - still one contiguous run per head - and stores bytes and descale at the out row. The team
+// reduction per (token, scale group) and the ONE atomicMax of a workgroup are the same instructions.
+template <int DT_O, int C, bool STAGE, bool ROWS>
+__device__ __forceinline__ void attn_out_fp8_body(const AttnUnshiftParams& p, const int team, const RowGather& g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char empty_tile[];     // [num_heads][kAttnOutFp8Rows] flags (read only with lse)
     __shared__ unsigned wave_max[4];
+    __shared__ int tile_src[ROWS ? kAttnOutFp8Rows : 1];
     float* const shift_tile = reinterpret_cast<float*>(empty_tile + p.num_heads * kAttnOutFp8Rows);     // [H / heads_per_vec][D]
     const int cph = p.head_dim / 8, n = p.heads_per_scale * cph, groups = p.num_heads / p.heads_per_scale;
     const int s_tiles = (p.seqlen + kAttnOutFp8Rows - 1) / kAttnOutFp8Rows;
     const int b = static_cast<int>(blockIdx.x / s_tiles), s0 = static_cast<int>(blockIdx.x % s_tiles) * kAttnOutFp8Rows;
     const int ns = p.seqlen - s0 < kAttnOutFp8Rows ? p.seqlen - s0 : kAttnOutFp8Rows;
+    if constexpr (ROWS) {
+        if (threadIdx.x < ns) tile_src[threadIdx.x] = gather_row(g, b, s0 + threadIdx.x);
+        __syncthreads();
+    }
     if (p.lse != nullptr) {
         for (int i = threadIdx.x; i < p.num_heads * kAttnOutFp8Rows; i += 256) {
             const int hh = i / kAttnOutFp8Rows, ss = i % kAttnOutFp8Rows;
             if (ss < ns) {
-                const int64_t idx = (static_cast<int64_t>(b) * p.num_heads + hh) * p.seqlen + s0 + ss;
-                const float l = p.lse[idx];
+                const int64_t bh = static_cast<int64_t>(b) * p.num_heads + hh;
+                const int64_t idx = bh * p.seqlen + s0 + ss, from = ROWS ? bh * g.src_seqlen + tile_src[ss] : idx;
+                const float l = p.lse[from];
                 const bool empty = l == INFINITY || l == -INFINITY;    // a NaN takes the normal path
                 empty_tile[i] = empty;
-                if (p.lse_out != nullptr) p.lse_out[idx] = empty ? l : fmaf(p.softmax_scale, p.lse_dot[idx], l);
+                if (p.lse_out != nullptr)                              // ROWS, no lse_dot: the gathered lse alone
+                    p.lse_out[idx] = (empty || (ROWS && p.lse_dot == nullptr)) ? l : fmaf(p.softmax_scale, p.lse_dot[from], l);
             }
         }
     }
@@ -258,7 +322,7 @@ __global__ void __launch_bounds__(256) la_attn_out_fp8_kernel(const AttnUnshiftP
     unsigned run_max = 0;
     for (int u = threadIdx.x / team; u < ns * groups; u += teams) {
         const int ss = u / groups, g = u - ss * groups, s = s0 + ss;
-        const int64_t o_row = b * p.o_bs + s * p.o_rs, out_row = b * p.out_bs + s * p.out_rs;
+        const int64_t o_row = b * p.o_bs + (ROWS ? tile_src[ss] : s) * p.o_rs, out_row = b * p.out_bs + s * p.out_rs;
         typename PrepLoad<DT_O>::raw w[C];
         {
             int hh = hh0, ch = ch0;
@@ -339,6 +403,14 @@ __global__ void __launch_bounds__(256) la_attn_out_fp8_kernel(const AttnUnshiftP
         }
     }
 }
+template <int DT_O, int C, bool STAGE>
+__global__ void __launch_bounds__(256) la_attn_out_fp8_kernel(const AttnUnshiftParams p, const int team) {
+    attn_out_fp8_body<DT_O, C, STAGE, false>(p, team, RowGather{});
+}
+template <int DT_O, int C, bool STAGE>
+__global__ void __launch_bounds__(256) la_attn_out_fp8_rows_kernel(const AttnUnshiftParams p, const int team, const RowGather g) {
+    attn_out_fp8_body<DT_O, C, STAGE, true>(p, team, g);
+}
 
 // lanes of a team for n chunks a unit: the next power of two, at most a wave. A function of the shape alone.
 inline int unit_team(int n) {
@@ -349,31 +421,37 @@ inline int unit_team(int n) {
 
 constexpr size_t kAttnOutFp8MaxLds = 64 * 1024;      // dynamic LDS a launch may ask for without opting in to more
 
+template <int DT_O, int C, bool STAGE>
+void launch_out_fp8_sized(const AttnUnshiftParams& p, const RowGather* g, dim3 grid, size_t lds, int team, hipStream_t stream) {
+    if (g) hipLaunchKernelGGL((la_attn_out_fp8_rows_kernel<DT_O, C, STAGE>), grid, dim3(256), lds, stream, p, team, *g);
+    else hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, C, STAGE>), grid, dim3(256), lds, stream, p, team);
+}
+
 template <int DT_O, bool STAGE>
-void launch_out_fp8_staged(const AttnUnshiftParams& p, size_t lds, hipStream_t stream) {
+void launch_out_fp8_staged(const AttnUnshiftParams& p, const RowGather* g, size_t lds, hipStream_t stream) {
     const int n = p.heads_per_scale * (p.head_dim / 8), team = unit_team(n), per_lane = (n + team - 1) / team;      // <= 32: la_api.hip
     const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(p.batch) * ((p.seqlen + kAttnOutFp8Rows - 1) / kAttnOutFp8Rows)));
-    if (per_lane <= 1) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 1, STAGE>), grid, dim3(256), lds, stream, p, team);
-    else if (per_lane <= 4) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 4, STAGE>), grid, dim3(256), lds, stream, p, team);
-    else if (per_lane <= 10) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 10, STAGE>), grid, dim3(256), lds, stream, p, team);
-    else if (per_lane <= 16) hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 16, STAGE>), grid, dim3(256), lds, stream, p, team);
-    else hipLaunchKernelGGL((la_attn_out_fp8_kernel<DT_O, 32, STAGE>), grid, dim3(256), lds, stream, p, team);
+    if (per_lane <= 1) launch_out_fp8_sized<DT_O, 1, STAGE>(p, g, grid, lds, team, stream);
+    else if (per_lane <= 4) launch_out_fp8_sized<DT_O, 4, STAGE>(p, g, grid, lds, team, stream);
+    else if (per_lane <= 10) launch_out_fp8_sized<DT_O, 10, STAGE>(p, g, grid, lds, team, stream);
+    else if (per_lane <= 16) launch_out_fp8_sized<DT_O, 16, STAGE>(p, g, grid, lds, team, stream);
+    else launch_out_fp8_sized<DT_O, 32, STAGE>(p, g, grid, lds, team, stream);
 }
 
 template <int DT_O>
-void launch_out_fp8(const AttnUnshiftParams& p, hipStream_t stream) {
+void launch_out_fp8(const AttnUnshiftParams& p, const RowGather* g, hipStream_t stream) {
     const size_t flags = static_cast<size_t>(p.num_heads) * kAttnOutFp8Rows;      // a multiple of 16 bytes: the shift rows behind it are aligned
     const size_t rows = p.shift != nullptr ? static_cast<size_t>(p.num_heads / p.heads_per_vec) * p.head_dim * sizeof(float) : 0;
-    if (rows != 0 && flags + rows <= kAttnOutFp8MaxLds) launch_out_fp8_staged<DT_O, true>(p, flags + rows, stream);
-    else launch_out_fp8_staged<DT_O, false>(p, flags, stream);
+    if (rows != 0 && flags + rows <= kAttnOutFp8MaxLds) launch_out_fp8_staged<DT_O, true>(p, g, flags + rows, stream);
+    else launch_out_fp8_staged<DT_O, false>(p, g, flags, stream);
 }
 
 template <int DT_O>
-void launch_unshift_o(const AttnUnshiftParams& p, int out_dtype, hipStream_t stream) {
-    if (out_dtype == 0) launch_unshift_typed<DT_O, 0>(p, stream);
-    else if (out_dtype == 1) launch_unshift_typed<DT_O, 1>(p, stream);
-    else if (out_dtype == 2) launch_out_fp8<DT_O>(p, stream);
-    else launch_unshift_typed<DT_O, 3>(p, stream);
+void launch_unshift_o(const AttnUnshiftParams& p, const RowGather* g, int out_dtype, hipStream_t stream) {
+    if (out_dtype == 0) launch_unshift_typed<DT_O, 0>(p, g, stream);
+    else if (out_dtype == 1) launch_unshift_typed<DT_O, 1>(p, g, stream);
+    else if (out_dtype == 2) launch_out_fp8<DT_O>(p, g, stream);
+    else launch_unshift_typed<DT_O, 3>(p, g, stream);
 }
 
 }  // namespace
@@ -399,8 +477,25 @@ hipError_t launch_v_colstats_finish(const float* part, int n_parts, int batch, i
 
 hipError_t launch_attn_unshift(const AttnUnshiftParams& p, int o_dtype, int out_dtype, hipStream_t stream) {
     (void)hipGetLastError();
-    if (o_dtype == 0) launch_unshift_o<0>(p, out_dtype, stream);
-    else launch_unshift_o<1>(p, out_dtype, stream);
+    if (o_dtype == 0) launch_unshift_o<0>(p, nullptr, out_dtype, stream);
+    else launch_unshift_o<1>(p, nullptr, out_dtype, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_v_colstats_rows(const VColstatsParams& p, const RowGather& g, int in_dtype, hipStream_t stream) {
+    (void)hipGetLastError();
+    const int64_t items = static_cast<int64_t>(p.n_parts) * p.batch * p.num_heads * (p.head_dim / 8);
+    const dim3 grid(static_cast<unsigned>((items + 255) / 256)), block(256);
+    if (in_dtype == 0) hipLaunchKernelGGL(la_v_colstats_rows_kernel<0>, grid, block, 0, stream, p, g);
+    else if (in_dtype == 1) hipLaunchKernelGGL(la_v_colstats_rows_kernel<1>, grid, block, 0, stream, p, g);
+    else hipLaunchKernelGGL(la_v_colstats_rows_kernel<3>, grid, block, 0, stream, p, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_unshift_rows(const AttnUnshiftParams& p, const RowGather& g, int o_dtype, int out_dtype, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (o_dtype == 0) launch_unshift_o<0>(p, &g, out_dtype, stream);
+    else launch_unshift_o<1>(p, &g, out_dtype, stream);
     return hipGetLastError();
 }
 

@@ -564,7 +564,7 @@ class E4m3Scales:
 
     def __call__(self, x, weight=None, eps=1e-6, tables=None, norm="token", pos_offset=0, *, rows=None, positions=None, rotate=None):
         """``rows`` / ``positions`` / ``rotate``: as ``qk_prep_fp8``, for both passes. ``tiles=True`` takes no map: gather V first
-        (``TokenOrder.gather``) - and no rotation: V is not rotated."""
+        (``TokenOrder.gather``), or use ``v_prep.v_prep_tiles_rows`` / ``SmoothedV`` - and no rotation: V is not rotated."""
         B, S, H, D = x.shape
         hps = self.heads_per_scale
         mapped = rows is not None or positions is not None
@@ -580,7 +580,8 @@ class E4m3Scales:
             if norm is not None or weight is not None or tables is not None:
                 raise ValueError("tiles=True quantizes V as its projection wrote it: norm=None, no weight, no tables")
             if mapped:
-                raise ValueError("tiles=True (v_prep_tiles) takes no row map: bring V into the order first with TokenOrder.gather")
+                raise ValueError("E4m3Scales(tiles=True) takes no row map: bring V into the order first with TokenOrder.gather, or "
+                                 "quantize with v_prep_tiles_rows / SmoothedV(tiles=True)(x, rows=), whose passes gather as they read")
         first = self.amax is None or tuple(self.out.shape) != (B, S, H, D) or self.out.device != x.device
         if first:
             self.amax = torch.zeros((B, H // hps), dtype=torch.float32, device=x.device)

@@ -10,10 +10,13 @@ raster order a 256-row q-tile of a wide frame is a stripe a few rows high; ``bri
     ...
     hidden = order.restore(hidden)                                             # once, at the exit
 
-or, where the hidden states cannot be permuted, per layer: ``qk_prep(q_proj, ..., rows=order)`` (the gather fused into the prologue),
-``order.gather(v)``, ``order.restore(o)``.
+or, where the hidden states cannot be permuted, per layer, with no pass of its own anywhere: ``qk_prep(q_proj, ..., rows=order)`` (the
+gather fused into the prologue); ``v_prep_tiles_rows(v, order)`` / ``v_colstats(v, rows=order)`` / ``SmoothedV()(v, rows=order)`` (into
+the passes that read V); ``order.restore_output(o, lse)`` = ``attn_unshift(o, ..., rows=order.dst_rows)`` or ``attn_out_fp8(...,
+rows=order.dst_rows)`` (the restore of O and of the LSE, into the pass that reads O). A V that nothing prepares (16-bit attention) is
+still gathered by ``order.gather(v)``.
 
-Limits. ``PreparedV`` / ``v_prep_tiles`` and packed variable-length calls take no map: gather V first. Skip lists, ``must_do_list`` and
+Limits. Packed variable-length calls take no map. Skip lists, ``must_do_list`` and
 ``must_skip_list`` speak of rows in the order of the CALL; changing the order of a layer needs ``reset_skip_state()``. With ``bt = 1``
 in every brick level a frame's tokens stay one contiguous row range, so frame-range must-do lists carry over unchanged.
 What a brick order gains on a real model has not been measured; ``tools/token_order_bench.py`` measures a synthetic field."""
@@ -84,6 +87,17 @@ class TokenOrder:
     def restore(self, o: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The inverse of ``gather``: ``out[:, src_rows[s]] = o[:, s]``, as the gather by ``dst_rows``. For O and for hidden states."""
         return self._move(o, self.dst_rows, len(self), out, "restore")
+
+    def restore_output(self, o: torch.Tensor, lse: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, **kwargs):
+        """``restore(o)`` and ``restore_lse(lse)`` in one pass over O: ``attn_unshift(o, shift, lse=lse, rows=self.dst_rows, **kwargs)``
+        (``v_prep.attn_unshift`` has the arguments: ``shift`` of a smoothed V, ``lse_dot``, ``out``, ``out_dtype``, ...). Returns ``out``
+        in raster order, or ``(out, lse_out)`` when ``lse`` is given; a row whose lse is +-inf comes back as zeros."""
+        from .v_prep import attn_unshift                             # (v_prep imports the prologue this module imports)
+        if self.dst_rows is None:
+            raise ValueError("restore_output: this order is no permutation (it has no dst_rows)")
+        if o.dim() != 4 or o.shape[1] != len(self):
+            raise ValueError(f"restore_output: o must be (B, {len(self)}, H, D), got {tuple(o.shape)}")
+        return attn_unshift(o, shift, lse=lse, rows=self.dst_rows, **kwargs)
 
     def restore_lse(self, lse: torch.Tensor) -> torch.Tensor:
         """``lse`` (..., S) of a call in this order -> raster order. A torch index on the last dimension: small, off the hot path."""

@@ -23,7 +23,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _cabi
-from .qk_prep import _IN_DTYPES, _call, _check_scales, _check_x, _f32, descale_from_amax, qk_prep_smooth
+from .qk_prep import _IN_DTYPES, _call, _check_scales, _check_x, _f32, _row_map, descale_from_amax, qk_prep_smooth
 
 _UNSHIFT_OUT_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16, torch.float32: _cabi.LA_DTYPE_FP32}
 _UNSHIFT_IN_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16}
@@ -41,8 +41,26 @@ def v_colstats_parts(seqlen: int, num_heads: int, head_dim: int) -> Tuple[int, i
     return n, r
 
 
+def _call_rows(entry, x, detail, a, row_map):
+    """``_call`` of a V or O pass: its ``_rows`` entry point, with the map behind the arguments, when the call has a ``row_map``."""
+    if row_map is None:
+        return _call(entry, x, detail, ctypes.byref(a))
+    _call(entry + "_rows", x, lambda: f"{detail()}, row map: {a.seqlen} rows of {row_map.src_seqlen}, batch stride {row_map.batch_stride}",
+          ctypes.byref(a), ctypes.byref(row_map))
+
+
+def _index_rows(t, rows, dim):
+    """``t`` with ``rows`` ([S], [B, S] or a ``TokenOrder``) applied along ``dim`` by plain indexing: what the references do with ``rows=``."""
+    if rows is None:
+        return t
+    rows = getattr(rows, "src_rows", rows).long().to(t.device)
+    if rows.dim() == 1:
+        return t.index_select(dim, rows)
+    return torch.stack([t[b].index_select(dim - 1, rows[b]) for b in range(t.shape[0])])
+
+
 def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mean_out: Optional[torch.Tensor] = None,
-               amax_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               amax_out: Optional[torch.Tensor] = None, rows=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(mean, amax)`` of ``x`` (B, S, H, D) bf16 / fp16 / fp32 on the GPU in one read of it: ``mean`` fp32 (B, H, D) over the rows,
     ``amax`` fp32 (B, H) = the largest ``|fl(x - mean)|`` of the head - bit for bit what ``qk_prep_smooth(x, norm=None, shift=mean,
     amax_out=zeros, quantize=False)`` reports, without the second read. ``x`` may be any view whose last dimension is contiguous and
@@ -51,6 +69,8 @@ def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mea
 
     stat_part    fp32 (n_parts, 3, B, H, D) contiguous work buffer, ``n_parts`` from ``v_colstats_parts``; None: allocated.
     mean_out / amax_out   buffers to write (amax is WRITTEN, not accumulated); None: allocated.
+    rows         a ``TokenOrder`` or an int32 ``[S]`` / ``[B, S]`` table: the statistics of ``x[:, rows]`` - the gather fused into the
+                 read (``la_v_colstats_rows``), bit for bit what ``v_colstats(order.gather(x))`` gives; ``n_parts`` is then that of S.
     No host sync; with the three buffers given, no allocation; captures into a HIP graph."""
     _check_x(x, "v_colstats_reference")
     if x.stride(-1) != 1:
@@ -58,6 +78,7 @@ def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mea
     B, S, H, D = x.shape
     if B * S * H * D == 0:
         raise ValueError(f"x must not be empty, got {tuple(x.shape)}")
+    row_map, S = _row_map(x, rows, None)
     n_parts, _ = v_colstats_parts(S, H, D)
     if stat_part is None:
         stat_part = torch.empty((n_parts, 3, B, H, D), dtype=torch.float32, device=x.device)
@@ -78,24 +99,25 @@ def v_colstats(x: torch.Tensor, *, stat_part: Optional[torch.Tensor] = None, mea
     a.x, a.stat_part = x.data_ptr(), stat_part.data_ptr()
     a.x_batch_stride, a.x_row_stride, a.x_head_stride = x.stride(0), x.stride(1), x.stride(2)
     a.batch, a.seqlen, a.num_heads, a.head_dim = B, S, H, D
-    _call("la_v_colstats", x, lambda: f"x {tuple(x.shape)} strides {x.stride()}", ctypes.byref(a))
+    _call_rows("la_v_colstats", x, lambda: f"x {tuple(x.shape)} strides {x.stride()}", a, row_map)
     _call("la_v_colstats_finish", x, lambda: f"parts {tuple(stat_part.shape)}, seqlen {S}", stat_part.data_ptr(), n_parts, B, H, D, S,
           mean_out.data_ptr(), mean_out.stride(0), mean_out.stride(1), amax_out.data_ptr(), amax_out.stride(0), amax_out.stride(1))
     return mean_out, amax_out
 
 
-def v_colstats_reference(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def v_colstats_reference(x: torch.Tensor, rows=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The formula of ``v_colstats`` in torch fp64, on whatever device ``x`` lives on: ``(mean`` (B, H, D) over the rows, ``amax`` (B, H)
-    of ``|x - mean|)``."""
+    of ``|x - mean|)``; ``rows``: of ``x[:, rows]``."""
     if x.dim() != 4:
         raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
-    y = x.double()
+    y = _index_rows(x, rows, 1).double()
     mean = y.mean(dim=1)
     return mean, (y - mean[:, None]).abs().amax(dim=(1, 3))
 
 
 def _check_unshift(o, shift, lse, lse_dot):
-    """Shapes and dtypes of the restoring pass (device-free: LiteAttention checks with it before the forward). Returns heads_per_vec."""
+    """Shapes and dtypes of the restoring pass (device-free: LiteAttention checks with it before the forward). Returns heads_per_vec.
+    ``lse`` and ``lse_dot`` have the rows of ``o`` - under a row map too, where both are read at the source rows."""
     if o.dim() != 4:
         raise ValueError(f"o must be (B, S, H, D), got {tuple(o.shape)}")
     B, S, H, D = o.shape
@@ -115,9 +137,30 @@ def _check_unshift(o, shift, lse, lse_dot):
     return hpv
 
 
+def _lse_result(o, S, lse, lse_dot, lse_out, mapped):
+    """``lse_out`` of a restoring pass with S result rows (allocated when None), or None when the call returns no LSE. It returns one
+    with ``lse_dot``, and under a row map with ``lse`` alone: the LSE at the rows."""
+    B, _, H, _ = o.shape
+    if lse_dot is not None or (mapped and lse is not None):
+        if lse_out is None:
+            lse_out = torch.empty((B, H, S), dtype=torch.float32, device=o.device)
+        _f32("lse_out", lse_out, (B, H, S), o.device)
+    elif lse_out is not None:
+        raise ValueError("lse_out needs lse_dot")
+    return lse_out
+
+
+def _fill_lse_out(a, D, lse_dot, lse_out, softmax_scale):
+    if lse_out is not None:
+        a.lse_out = lse_out.data_ptr()
+    if lse_dot is not None:
+        a.lse_dot = lse_dot.data_ptr()
+        a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
+
+
 def attn_unshift(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
                  lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
-                 out_dtype: Optional[torch.dtype] = None, lse_out: Optional[torch.Tensor] = None):
+                 out_dtype: Optional[torch.dtype] = None, lse_out: Optional[torch.Tensor] = None, rows=None):
     """The restoring pass of V (and K) smoothing in one read of the attention output (``la_attn_unshift``):
 
         out[b, s, h]     = round(float(o[b, s, h]) + shift[b, h // (H_q // H_kv)])        one fp32 addition, one rounding
@@ -133,35 +176,35 @@ def attn_unshift(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
     out        bf16, fp16 or fp32 by its own strides - e.g. a ``(B, S, H, D)`` view of the (B, S, H * D) fp32 tensor the output
                projection reads; may be ``o`` itself (in place); None: a new contiguous tensor of ``out_dtype`` (default ``o.dtype``).
                Any other overlap of ``out`` and ``o`` is an error nobody detects.
-    Returns ``out``, or ``(out, lse_out)`` with ``lse_dot``. No host sync; no allocation when ``out`` (and ``lse_out``) are given;
-    captures into a HIP graph."""
+    rows       an int32 ``[S]`` / ``[B, S]`` table (or a ``TokenOrder``: its ``src_rows``): ``out[:, s]`` and ``lse_out[..., s]`` are
+               made from row ``rows[s]`` of ``o``, ``lse`` and ``lse_dot`` (``la_attn_unshift_rows``) - the result has S rows. With
+               ``rows=order.dst_rows`` this is ``order.restore`` and ``order.restore_lse`` fused into the pass, bit for bit. With
+               ``lse`` and ``rows`` the gathered LSE is always returned (``lse_dot`` None: ``lse`` at the rows). Never in place.
+    Returns ``out``, or ``(out, lse_out)`` with ``lse_dot`` (or with ``lse`` and ``rows``). No host sync; no allocation when ``out``
+    (and ``lse_out``) are given; captures into a HIP graph."""
     hpv = _check_unshift(o, shift, lse, lse_dot)
     _check_x(o, "attn_unshift_reference", "o", _UNSHIFT_IN_DTYPES, "bf16 or fp16")
     B, S, H, D = o.shape
+    row_map, S = _row_map(o, rows, None)
     if out is None:
         out = torch.empty((B, S, H, D), dtype=o.dtype if out_dtype is None else out_dtype, device=o.device)
     elif out_dtype is not None and out.dtype != out_dtype:
         raise TypeError(f"out is {out.dtype}, out_dtype says {out_dtype}")
     if out.dtype not in _UNSHIFT_OUT_DTYPES:
         raise TypeError(f"out: bf16, fp16 or fp32, got {out.dtype}")
-    if out.shape != o.shape or out.device != o.device:
-        raise ValueError(f"out must be {tuple(o.shape)} on {o.device}, got {tuple(out.shape)} on {out.device}")
+    if tuple(out.shape) != (B, S, H, D) or out.device != o.device:
+        raise ValueError(f"out must be {(B, S, H, D)} on {o.device}, got {tuple(out.shape)} on {out.device}")
     if o.stride(-1) != 1 or out.stride(-1) != 1:
         raise ValueError("the last dimension of o and out must be contiguous")
     for name, t in (("shift", shift), ("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out)):
         if t is not None and t.device != o.device:
             raise ValueError(f"{name} lives on {t.device}, o on {o.device}")
-    if lse_dot is not None:
-        if lse_out is None:
-            lse_out = torch.empty((B, H, S), dtype=torch.float32, device=o.device)
-        _f32("lse_out", lse_out, (B, H, S), o.device)
-    elif lse_out is not None:
-        raise ValueError("lse_out needs lse_dot")
+    lse_out = _lse_result(o, S, lse, lse_dot, lse_out, row_map is not None)
     for name, t in (("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out)):
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
     if B * S * H * D == 0:
-        return out if lse_dot is None else (out, lse_out.copy_(lse))
+        return out if lse_out is None else (out, lse_out.copy_(lse) if row_map is None else lse_out)
     a = _cabi.LaAttnUnshiftArgs()
     a.struct_size = ctypes.sizeof(_cabi.LaAttnUnshiftArgs)
     a.o_dtype, a.out_dtype, a.heads_per_vec = _UNSHIFT_IN_DTYPES[o.dtype], _UNSHIFT_OUT_DTYPES[out.dtype], hpv
@@ -173,19 +216,20 @@ def attn_unshift(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
         a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
     if lse is not None:
         a.lse = lse.data_ptr()
-    if lse_dot is not None:
-        a.lse_dot, a.lse_out = lse_dot.data_ptr(), lse_out.data_ptr()
-        a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
-    _call("la_attn_unshift", o, lambda: f"o {tuple(o.shape)} strides {o.stride()}, out {out.dtype} strides {out.stride()}, shift "
-                                        f"{None if shift is None else (tuple(shift.shape), shift.stride())}", ctypes.byref(a))
-    return out if lse_dot is None else (out, lse_out)
+    _fill_lse_out(a, D, lse_dot, lse_out, softmax_scale)
+    _call_rows("la_attn_unshift", o, lambda: f"o {tuple(o.shape)} strides {o.stride()}, out {out.dtype} strides {out.stride()}, shift "
+                                             f"{None if shift is None else (tuple(shift.shape), shift.stride())}", a, row_map)
+    return out if lse_out is None else (out, lse_out)
 
 
 def attn_unshift_reference(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
-                           lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+                           lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, rows=None):
     """The formula of ``attn_unshift`` in torch fp64, UNROUNDED, on whatever device ``o`` lives on: ``out``, or ``(out, lse_out)`` with
-    ``lse_dot``. The product ``softmax_scale * lse_dot`` takes the scale as the fp32 the kernel is handed."""
+    ``lse_dot``. The product ``softmax_scale * lse_dot`` takes the scale as the fp32 the kernel is handed. ``rows``: the formula on
+    ``o[:, rows]``, ``lse[..., rows]`` and ``lse_dot[..., rows]`` (``lse_out`` with ``lse_dot`` only)."""
     hpv = _check_unshift(o, shift, lse, lse_dot)
+    o, lse, lse_dot = _index_rows(o, rows, 1), None if lse is None else _index_rows(lse, rows, 2), \
+        None if lse_dot is None else _index_rows(lse_dot, rows, 2)
     out = o.double()
     if shift is not None:
         out = out + shift.double().to(o.device).repeat_interleave(hpv, dim=1)[:, None]
@@ -255,7 +299,7 @@ def _check_out_fp8(o, heads_per_scale, descale, amax_out):
 def attn_out_fp8(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
                  lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, heads_per_scale: Optional[int] = None,
                  descale: Optional[torch.Tensor] = None, amax_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                 descale_out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None):
+                 descale_out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, rows=None):
     """``attn_unshift`` with a row-scaled e4m3 result: the activation of an fp8 output projection in one read of O and one 1-byte
     write (``la_attn_unshift_fp8``). ``o``, ``shift``, ``lse``, ``lse_dot``, ``softmax_scale`` and ``lse_out`` are ``attn_unshift``'s;
     with y the fp32 value that pass would round:
@@ -270,19 +314,22 @@ def attn_out_fp8(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
     out               float8_e4m3fn (B, S, H, D) by its own strides, e.g. a view of a (B, S, H * D) buffer; never ``o`` (there is no
                       in-place form); None: allocated.
     descale_out       fp32 (B, S, H / heads_per_scale) by its own strides (dynamic mode); None: allocated.
+    rows              ``attn_unshift``'s: row s of the result, of its descale and of ``lse_out`` is made from row ``rows[s]`` of ``o``,
+                      ``lse`` and ``lse_dot`` (``la_attn_unshift_fp8_rows``); S is then the table's length.
     A NaN in a group makes that group's descale and bytes NaN and no other's. Returns ``RowScaledE4m3(data, descale)``, or
     ``(that, lse_out)`` with ``lse_dot``. No host sync; no allocation when the outputs are given; captures into a HIP graph."""
     hpv = _check_unshift(o, shift, lse, lse_dot)
     hps = _check_out_fp8(o, heads_per_scale, descale, amax_out)
     _check_x(o, "attn_out_fp8_reference", "o", _UNSHIFT_IN_DTYPES, "bf16 or fp16")
     B, S, H, D = o.shape
+    row_map, S = _row_map(o, rows, None)
     G = H // hps
     if out is None:
         out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=o.device)
     if out.dtype != torch.float8_e4m3fn:
         raise TypeError(f"out: float8_e4m3fn, got {out.dtype}")
-    if out.shape != o.shape or out.device != o.device:
-        raise ValueError(f"out must be {tuple(o.shape)} on {o.device}, got {tuple(out.shape)} on {out.device}")
+    if tuple(out.shape) != (B, S, H, D) or out.device != o.device:
+        raise ValueError(f"out must be {(B, S, H, D)} on {o.device}, got {tuple(out.shape)} on {out.device}")
     if o.stride(-1) != 1 or out.stride(-1) != 1:
         raise ValueError("the last dimension of o and out must be contiguous")
     if descale is None:
@@ -294,18 +341,13 @@ def attn_out_fp8(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
     for name, t in (("shift", shift), ("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out), ("descale", descale), ("amax_out", amax_out)):
         if t is not None and t.device != o.device:
             raise ValueError(f"{name} lives on {t.device}, o on {o.device}")
-    if lse_dot is not None:
-        if lse_out is None:
-            lse_out = torch.empty((B, H, S), dtype=torch.float32, device=o.device)
-        _f32("lse_out", lse_out, (B, H, S), o.device)
-    elif lse_out is not None:
-        raise ValueError("lse_out needs lse_dot")
+    lse_out = _lse_result(o, S, lse, lse_dot, lse_out, row_map is not None)
     for name, t in (("lse", lse), ("lse_dot", lse_dot), ("lse_out", lse_out)):
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
     res = RowScaledE4m3(out, descale_out if descale is None else descale)
     if B * S * H * D == 0:
-        return res if lse_dot is None else (res, lse_out.copy_(lse))
+        return res if lse_out is None else (res, lse_out.copy_(lse) if row_map is None else lse_out)
     a = _cabi.LaAttnUnshiftFp8Args()
     a.struct_size = ctypes.sizeof(_cabi.LaAttnUnshiftFp8Args)
     a.o_dtype, a.heads_per_vec, a.heads_per_scale = _UNSHIFT_IN_DTYPES[o.dtype], hpv, hps
@@ -317,9 +359,7 @@ def attn_out_fp8(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
         a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
     if lse is not None:
         a.lse = lse.data_ptr()
-    if lse_dot is not None:
-        a.lse_dot, a.lse_out = lse_dot.data_ptr(), lse_out.data_ptr()
-        a.softmax_scale = float(D ** -0.5 if softmax_scale is None else softmax_scale)
+    _fill_lse_out(a, D, lse_dot, lse_out, softmax_scale)
     if descale is None:
         a.row_descale = descale_out.data_ptr()
         a.row_descale_batch_stride, a.row_descale_row_stride, a.row_descale_group_stride = descale_out.stride()
@@ -328,18 +368,19 @@ def attn_out_fp8(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: 
         a.descale_in_batch_stride = descale.stride(0) if descale.numel() > 1 else 0
         if amax_out is not None:
             a.amax, a.amax_batch_stride = amax_out.data_ptr(), amax_out.stride(0)
-    _call("la_attn_unshift_fp8", o, lambda: f"o {tuple(o.shape)} strides {o.stride()}, out strides {out.stride()}, heads_per_scale {hps}, "
-                                            f"shift {None if shift is None else (tuple(shift.shape), shift.stride())}", ctypes.byref(a))
-    return res if lse_dot is None else (res, lse_out)
+    _call_rows("la_attn_unshift_fp8", o, lambda: f"o {tuple(o.shape)} strides {o.stride()}, out strides {out.stride()}, heads_per_scale "
+                                                 f"{hps}, shift {None if shift is None else (tuple(shift.shape), shift.stride())}", a, row_map)
+    return res if lse_out is None else (res, lse_out)
 
 
 def attn_out_fp8_reference(o: torch.Tensor, shift: Optional[torch.Tensor] = None, *, lse: Optional[torch.Tensor] = None,
                            lse_dot: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None,
-                           heads_per_scale: Optional[int] = None, descale: Optional[torch.Tensor] = None):
+                           heads_per_scale: Optional[int] = None, descale: Optional[torch.Tensor] = None, rows=None):
     """The formula of ``attn_out_fp8`` in torch fp64, UNROUNDED, on whatever device ``o`` lives on: ``(z, descale)`` with ``z = clamp(y /
     descale, -448, 448)`` fp64 (B, S, H, D) - the values the kernel rounds to e4m3 - and ``descale`` fp64 (B, S, H / heads_per_scale)
-    = ``max(max |y|, 2^-100) / 448``, or the given one as fp64 (B, 1, 1); with ``lse_dot``, ``((z, descale), lse_out)``."""
-    res = attn_unshift_reference(o, shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale)
+    = ``max(max |y|, 2^-100) / 448``, or the given one as fp64 (B, 1, 1); with ``lse_dot``, ``((z, descale), lse_out)``. ``rows``: as
+    ``attn_unshift_reference``."""
+    res = attn_unshift_reference(o, shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, rows=rows)
     y, lse_new = res if lse_dot is not None else (res, None)
     hps = _check_out_fp8(o, heads_per_scale, descale, None)
     B, S, H, D = y.shape
@@ -466,7 +507,24 @@ def v_prep_tiles(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None, shi
                aligned), to write into; None: allocated.
     ``x`` may be any view whose last dimension is contiguous and whose rows, heads and batches start on 16-byte boundaries (the V
     slice of a fused projection); head_dim 64, 96, 128, 192 or 256. No host sync; with ``out`` given, no allocation; captures into
-    a HIP graph; two calls write the same bytes."""
+    a HIP graph; two calls write the same bytes. This call takes no row map: ``v_prep_tiles_rows`` is the form with one."""
+    return _v_prep_tiles(x, descale, shift, amax_out, out, None)
+
+
+def v_prep_tiles_rows(x: torch.Tensor, rows, *, descale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                      amax_out: Optional[torch.Tensor] = None, out=None) -> PreparedV:
+    """``v_prep_tiles`` with a token order's gather of V taken into its loads (``la_v_prep_tiles_rows``): key s of the tiles is made
+    from row ``rows[s]`` of ``x`` - the tiles of ``v_prep_tiles(order.gather(x), ...)`` byte for byte, without that pass.
+
+    rows       a ``TokenOrder`` or an int32 ``[S]`` / ``[B, S]`` table on ``x``'s device. Sk, the keys of the returned ``PreparedV``
+               and of ``out``, is S: a permutation, a pruned selection or one with repeats.
+    Everything else is ``v_prep_tiles``'s."""
+    if rows is None:
+        raise TypeError("rows: a TokenOrder or an int32 tensor, got None (v_prep_tiles is the call without a map)")
+    return _v_prep_tiles(x, descale, shift, amax_out, out, rows)
+
+
+def _v_prep_tiles(x, descale, shift, amax_out, out, rows):
     _check_x(x, "v_prep_tiles_reference")
     if x.stride(-1) != 1:
         raise ValueError("the last dimension of x must be contiguous")
@@ -478,9 +536,13 @@ def v_prep_tiles(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None, shi
         _f32("shift", shift, (B, H, D), x.device)
         if shift.stride(2) != 1:
             raise ValueError("the last dimension of shift must be contiguous")
+    row_map, S = _row_map(x, rows, None)
+    if S == 0:
+        raise ValueError("rows must not be empty")
+    shape = torch.Size((B, S, H, D))
     if isinstance(out, PreparedV):
-        if out.shape != x.shape or out.device != x.device:
-            raise ValueError(f"out was made for {tuple(out.shape)} on {out.device}, x is {tuple(x.shape)} on {x.device}")
+        if out.shape != shape or out.device != x.device:
+            raise ValueError(f"out was made for {tuple(out.shape)} on {out.device}, the result is {tuple(shape)} on {x.device}")
         out.descale = descale
         pv = out
     else:
@@ -488,7 +550,7 @@ def v_prep_tiles(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None, shi
             out = torch.empty(v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=x.device)
         elif out.device != x.device:
             raise ValueError(f"out lives on {out.device}, x on {x.device}")
-        pv = PreparedV(out, x.shape, descale)
+        pv = PreparedV(out, shape, descale)
     a = _cabi.LaVPrepTilesArgs()
     a.struct_size = ctypes.sizeof(_cabi.LaVPrepTilesArgs)
     a.in_dtype = _IN_DTYPES[x.dtype]
@@ -501,18 +563,19 @@ def v_prep_tiles(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None, shi
         a.shift, a.shift_batch_stride, a.shift_head_stride = shift.data_ptr(), shift.stride(0), shift.stride(1)
     if amax_out is not None:
         a.amax, a.amax_batch_stride, a.amax_head_stride = amax_out.data_ptr(), amax_out.stride(0), amax_out.stride(1)
-    _call("la_v_prep_tiles", x, lambda: f"x {tuple(x.shape)} strides {x.stride()}, shift "
-                                        f"{None if shift is None else shift.stride()}", ctypes.byref(a))
+    _call_rows("la_v_prep_tiles", x, lambda: f"x {tuple(x.shape)} strides {x.stride()}, shift "
+                                             f"{None if shift is None else shift.stride()}", a, row_map)
     return pv
 
 
 def v_prep_tiles_reference(x: torch.Tensor, *, descale: Optional[torch.Tensor] = None,
-                           shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           shift: Optional[torch.Tensor] = None, rows=None) -> torch.Tensor:
     """The e4m3 codes ``v_prep_tiles`` puts into the tiles, in (B, Sk, Hk, D) order, by the same fp32 steps in torch on whatever device
-    ``x`` lives on: one subtraction, one multiplication by the fp32 ``1 / descale``, the clamp, torch's round-to-nearest-even cast."""
+    ``x`` lives on: one subtraction, one multiplication by the fp32 ``1 / descale``, the clamp, torch's round-to-nearest-even cast.
+    ``rows``: of ``x[:, rows]``."""
     if x.dim() != 4:
         raise ValueError(f"x must be (B, S, H, D), got {tuple(x.shape)}")
-    y = x.float()
+    y = _index_rows(x, rows, 1).float()
     if shift is not None:
         y = y - shift.to(y.device)[:, None]
     if descale is not None:
@@ -532,6 +595,8 @@ class SmoothedV:
                      documents. The first call has no history and runs as "current".
     tiles=True       the quantizing pass is ``v_prep_tiles``: ``v8`` is a ``PreparedV`` (the V^T tiles of the e4m3 forward, no e4m3
                      tensor), which the attention call takes as ``v``. Head_dim 64, 96, 128, 192 or 256.
+    ``sv(xv, rows=order)`` brings V into a token order on the way: the statistics and the codes are those of ``order.gather(xv)``, both
+    passes gather as they read. ``sv.finish(o, ..., rows=order.dst_rows)`` restores O (and the LSE) to raster order in the same pass.
     Buffers are allocated by the first call and reused: no host sync, no allocation after it; a call overwrites the last results,
     ``shift`` included - call ``finish`` before the next ``sv(xv)``."""
 
@@ -541,82 +606,92 @@ class SmoothedV:
         if not margin > 0:
             raise ValueError("margin must be positive")
         self.mode, self.margin, self.tiles = mode, float(margin), bool(tiles)
-        self.v8 = self.shift = self.out = self.out8 = self.out_descale = None
+        self.v8 = self.shift = self.out = self.out8 = self.out_descale = self.out_lse = None
         self.calls = 0
 
-    def _allocate(self, xv):
-        B, S, H, D = xv.shape
+    def _allocate(self, xv, S):
+        B, _, H, D = xv.shape
         f32 = dict(dtype=torch.float32, device=xv.device)
         if self.tiles:
-            self.v8 = PreparedV(torch.empty(v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=xv.device), xv.shape)
+            self.v8 = PreparedV(torch.empty(v_tiles_bytes(B, H, S, D)[1], dtype=torch.uint8, device=xv.device), (B, S, H, D))
         else:
-            self.v8 = torch.empty(xv.shape, dtype=torch.float8_e4m3fn, device=xv.device)
+            self.v8 = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=xv.device)
         self.part = torch.empty((v_colstats_parts(S, H, D)[0], 3, B, H, D), **f32)
         self.shift, self.amax, self.dv = torch.empty((B, H, D), **f32), torch.empty((B, H), **f32), torch.empty((B, H), **f32)
         if self.mode == "delayed":                               # this step's statistics, for the next step
             self.next_mean, self.next_amax = torch.empty_like(self.shift), torch.empty_like(self.amax)
         self.out = None
 
-    def __call__(self, xv: torch.Tensor):
+    def __call__(self, xv: torch.Tensor, rows=None):
         if xv.dim() != 4:
             raise ValueError(f"xv must be (B, S, H, D), got {tuple(xv.shape)}")
-        first = self.v8 is None or self.v8.shape != xv.shape or self.v8.device != xv.device
+        S = _row_map(xv, rows, None)[1]                          # rows of the result; the table is checked here, before anything launches
+        shape = (xv.shape[0], S, xv.shape[2], xv.shape[3])
+        first = self.v8 is None or tuple(self.v8.shape) != shape or self.v8.device != xv.device
         if first:
-            self._allocate(xv)
+            self._allocate(xv, S)
         if self.mode == "current":
-            v_colstats(xv, stat_part=self.part, mean_out=self.shift, amax_out=self.amax)
+            v_colstats(xv, stat_part=self.part, mean_out=self.shift, amax_out=self.amax, rows=rows)
         else:
             if first:
-                v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax)
+                v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax, rows=rows)
             self.shift.copy_(self.next_mean)
             self.amax.copy_(self.next_amax)
         descale_from_amax(self.amax, self.margin, out=self.dv)
         if self.tiles:
-            v_prep_tiles(xv, shift=self.shift, descale=self.dv, out=self.v8)
+            _v_prep_tiles(xv, self.dv, self.shift, None, self.v8, rows)
         else:
-            qk_prep_smooth(xv, norm=None, shift=self.shift, descale=self.dv, out=self.v8)
+            qk_prep_smooth(xv, norm=None, shift=self.shift, descale=self.dv, out=self.v8, rows=rows)
         if self.mode == "delayed":
-            v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax)
+            v_colstats(xv, stat_part=self.part, mean_out=self.next_mean, amax_out=self.next_amax, rows=rows)
         self.calls += 1
         return self.v8, self.dv, self.shift
 
     def finish(self, o: torch.Tensor, lse: Optional[torch.Tensor] = None, lse_dot: Optional[torch.Tensor] = None,
                softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
-               *, fp8: bool = False, heads_per_scale: Optional[int] = None, descale: Optional[torch.Tensor] = None):
+               *, fp8: bool = False, heads_per_scale: Optional[int] = None, descale: Optional[torch.Tensor] = None, rows=None):
         """``attn_unshift(o, shift, ...)`` with the shift of the last call. ``out`` None: ``o`` itself when ``out_dtype`` is None or
         ``o.dtype`` (in place: the attention call's result is overwritten), else a buffer of ``out_dtype`` this object keeps. With
         ``lse_dot`` (K smoothed too) the LSE is restored in place and ``(out, lse)`` is returned. Pass ``lse`` whenever the call may
         have had no keys.
         ``fp8=True``: ``attn_out_fp8(o, shift, ..., heads_per_scale=, descale=)`` instead - a ``RowScaledE4m3`` whose buffers this
-        object keeps (``out``: the e4m3 tensor to write; ``out_dtype`` must be None)."""
+        object keeps (``out``: the e4m3 tensor to write; ``out_dtype`` must be None).
+        ``rows``: as ``attn_unshift`` - e.g. ``order.dst_rows``, O and the LSE back in raster order. Never in place: the result and,
+        with ``lse``, the LSE are buffers this object keeps (or ``out``), and ``(out, lse)`` is returned whenever ``lse`` is given."""
         if self.shift is None:
             raise RuntimeError("finish() before the first call: there is no shift yet")
+        S = _row_map(o, rows, None)[1]
+        shape, lse_out = (o.shape[0], S, o.shape[2], o.shape[3]), lse if lse_dot is not None else None
+        if rows is not None and lse is not None:
+            if self.out_lse is None or tuple(self.out_lse.shape) != (shape[0], shape[2], S) or self.out_lse.device != o.device:
+                self.out_lse = torch.empty((shape[0], shape[2], S), dtype=torch.float32, device=o.device)
+            lse_out = self.out_lse
         if fp8:
             if out_dtype is not None:
                 raise ValueError("fp8=True writes e4m3: out_dtype must be None")
             _check_unshift(o, self.shift, lse, lse_dot)
             hps = _check_out_fp8(o, heads_per_scale, descale, None)
             if out is None:
-                if self.out8 is None or self.out8.shape != o.shape or self.out8.device != o.device:
-                    self.out8 = torch.empty(o.shape, dtype=torch.float8_e4m3fn, device=o.device)
+                if self.out8 is None or tuple(self.out8.shape) != shape or self.out8.device != o.device:
+                    self.out8 = torch.empty(shape, dtype=torch.float8_e4m3fn, device=o.device)
                 out = self.out8
-            want = (o.shape[0], o.shape[1], o.shape[2] // hps)
+            want = (o.shape[0], S, o.shape[2] // hps)
             if descale is None and (self.out_descale is None or tuple(self.out_descale.shape) != want or self.out_descale.device != o.device):
                 self.out_descale = torch.empty(want, dtype=torch.float32, device=o.device)
             return attn_out_fp8(o, self.shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, heads_per_scale=hps, descale=descale,
-                                out=out, descale_out=self.out_descale if descale is None else None,
-                                lse_out=lse if lse_dot is not None else None)
+                                out=out, descale_out=self.out_descale if descale is None else None, lse_out=lse_out, rows=rows)
         if heads_per_scale is not None or descale is not None:
             raise ValueError("heads_per_scale and descale belong to fp8=True")
         if out is None:
-            if out_dtype is None or out_dtype == o.dtype:
+            if rows is None and (out_dtype is None or out_dtype == o.dtype):
                 out = o
             else:
-                if self.out is None or self.out.shape != o.shape or self.out.dtype != out_dtype or self.out.device != o.device:
-                    self.out = torch.empty(o.shape, dtype=out_dtype, device=o.device)
+                dtype = o.dtype if out_dtype is None else out_dtype
+                if self.out is None or tuple(self.out.shape) != shape or self.out.dtype != dtype or self.out.device != o.device:
+                    self.out = torch.empty(shape, dtype=dtype, device=o.device)
                 out = self.out
         return attn_unshift(o, self.shift, lse=lse, lse_dot=lse_dot, softmax_scale=softmax_scale, out=out, out_dtype=out_dtype,
-                            lse_out=lse if lse_dot is not None else None)
+                            lse_out=lse_out, rows=rows)
 
 
 # ---- op registration: torch.ops.lite_attention.v_colstats / attn_unshift / v_prep_tiles, beside qk_prep_smooth ------------------------------------------
