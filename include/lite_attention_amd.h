@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads, la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows and la_qk_prep_rot / la_qk_prep_fp8_rot / la_qk_prep_smooth_rot were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads, la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows la_qk_prep_rot / la_qk_prep_fp8_rot / la_qk_prep_smooth_rot and la_vote_margins were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -363,6 +363,54 @@ int la_output_error(const void* out, int32_t out_dtype, int64_t out_batch_stride
                     const void* ref, int32_t ref_dtype, int64_t ref_batch_stride, int64_t ref_row_stride, int64_t ref_head_stride,
                     int32_t batch, int32_t seqlen, int32_t num_heads, int32_t head_dim, int32_t rows_per_bin,
                     double* stats, void* stream);
+
+/* The margins of the skip vote, for every key tile a walk visits, in one pass over Q K^T (added under ABI 9: a host detects it by symbol).
+ * la_fwd keeps tile n of a q-tile in the list it writes when
+ *   margin[n] = max over the q-tile's rows i of (m_loc(i, n) - m_prev(i)) * (softmax_scale * log2 e)  >  thr
+ * with m_loc the largest score q_i . k_j over the keys j of tile n and m_prev the row's running maximum over the tiles walked BEFORE n.
+ * The written list is a pure function of these numbers and thr, so the threshold that leaves a target fraction of the walked tiles is a
+ * quantile of this entry point's output - no forward call, no bisection. The pass does the Q K^T half of the forward's matrix work and no
+ * exponential; it reads no V and writes no list.
+ *   q (B, Sq, H, D), k (B, Sk, Hk, D): bf16 or fp16, both of `dtype`; last dimension contiguous, strides in ELEMENTS; H % Hk == 0, query
+ *     head h reads K head h / (H / Hk); D = 64, 96, 128, 192 or 256.
+ *   flags: LA_FLAG_HALF_VOTE, LA_FLAG_KERNEL_128ROW and LA_FLAG_LIST_INT16 are read, every other bit is ignored. The q-tile is the one
+ *     la_get_tile_sizes_ex(head_dim, 2, flags) reports - the geometry of the lists la_fwd reads and writes under these flags (256 x 64,
+ *     or 128 x 64 above head_dim 128 and under the two 128-row flags); the caller passes no block sizes. Qt = ceil(Sq / block_m),
+ *     Kt = ceil(Sk / 64).
+ *   read_list: NULL = the dense walk Kt - 1 ... 0; else rows [B_alloc >= B, H, Qt, Kt + 1] of int32_t (int16_t under LA_FLAG_LIST_INT16),
+ *     la_fwd's row format, read with la_fwd's clamps (indices into [0, Kt), at most (Kt + 1) / 2 ranges, Kt tiles in all, the first tile
+ *     of the first range always walked). The walk is in list order, key tiles descending inside a range.
+ *   margins: fp32 [B, H, Qt, Kt] contiguous, EVERY element written: margin[n] of the walked tiles; NaN for the first tile walked (it
+ *     has no m_prev and is never flagged) and for every tile the walk does not visit. A tile a malformed list names twice holds the
+ *     margin of its last visit.
+ * Conventions - those of the forward's vote: rows of the last q-tile at or past Sq are ZERO rows of q and take part (their scores are
+ * 0 in every tile, so every margin of a padded q-tile is >= 0: at a negative threshold the forward never flags one of its tiles
+ * either); keys at or past Sk in tile Kt - 1 are -inf; scores are fp32 accumulators of the 16-bit products.
+ * Under LA_FLAG_HALF_VOTE la_fwd reads a list as a SET of tiles and this entry point in list order: the same walk for every well-formed
+ * list (descending, disjoint ranges). Must-do and must-skip ranges act on the written list, not on the margins, and are not arguments.
+ * Inputs are assumed finite. One workgroup per (batch, head, q-tile), no workspace, no atomics on global memory and a reduction order
+ * the shape alone fixes: two launches give bit-identical output. Asynchronous on `stream`.
+ * Errors (all before any HIP call): NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; a dtype other than bf16 / fp16
+ * LA_ERR_DTYPE; NULL q / k / margins LA_ERR_NULL_ARG; a non-positive size or H % Hk != 0 LA_ERR_SHAPE; a head_dim without tiles
+ * LA_ERR_HEAD_DIM (also 96 / 192 under LA_FLAG_KERNEL_128ROW, as la_get_tile_sizes_ex answers); a negative stride, a q / k pointer or
+ * used stride that takes a row start off a 16-byte boundary, margins off 4 bytes or read_list off its element size LA_ERR_STRIDE;
+ * LA_FLAG_LIST_INT16 with Kt + 1 > 32767, or more key tiles than the walk storage of a workgroup holds (about 24 000 at head_dim 256,
+ * 32 000 at 128: 4 bytes per tile beside the K ring in 160 KiB of LDS) LA_ERR_SEQLEN; more than 2^31 - 1 workgroups LA_ERR_SHAPE. */
+typedef struct la_vote_margins_args {
+    uint32_t struct_size;        /* = sizeof(la_vote_margins_args)                                */
+    int32_t  dtype;              /* la_dtype of q and k: LA_DTYPE_BF16 or LA_DTYPE_FP16           */
+    const void* q;               /* (B, Sq, H, D)                                                 */
+    const void* k;               /* (B, Sk, Hk, D)                                                */
+    int64_t q_batch_stride, q_row_stride, q_head_stride;          /* in elements                  */
+    int64_t k_batch_stride, k_row_stride, k_head_stride;
+    int32_t batch, seqlen_q, seqlen_k;
+    int32_t num_heads, num_heads_k, head_dim;
+    float    softmax_scale;
+    uint32_t flags;              /* LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16; other bits ignored */
+    const void* read_list;       /* int32_t / int16_t [B_alloc, H, Qt, Kt + 1]; NULL = dense walk */
+    float*      margins;         /* fp32 [B, H, Qt, Kt] contiguous                                */
+} la_vote_margins_args;
+int la_vote_margins(const la_vote_margins_args* args, void* stream);
 
 /* The q / k prologue of a Wan2.x-style attention block in one pass: RMSNorm, 3-axis RoPE on INTERLEAVED pairs, the cast to bf16 / fp16.
  * Per token (b, s) of x (B, S, H, D), in fp32 with ONE rounding at the store:

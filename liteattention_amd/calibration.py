@@ -7,6 +7,7 @@ bound per step - the reference's "assign different error bounds to different tim
 with the error measured on the device by ``output_error`` (C-ABI ``la_output_error``: one pass, fp64)."""
 from __future__ import annotations
 
+import ctypes
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
@@ -310,3 +311,240 @@ def calibrate_head_thresholds(qkv_at, n_steps: int, bounds, metric: str = "rel_l
     rows.append(rows[-1])
     trace.append(entry(rows[-1], be.step(t, rows[-1]), dense_t, t, skip_t))
     return torch.stack(rows), trace
+
+
+# ---- vote margins: the threshold of a target sparsity from one pass over Q K^T ----------------------------------------------------
+_MARGIN_DTYPES = {torch.bfloat16: _cabi.LA_DTYPE_BF16, torch.float16: _cabi.LA_DTYPE_FP16}
+MARGIN_HEAD_DIMS = (64, 96, 128, 192, 256)
+_LOG2E = 1.4426950408889634
+
+
+def _cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def _check_margin_list(read_list: torch.Tensor, q: torch.Tensor, qt: int, kt: int):
+    B, H = q.shape[0], q.shape[2]
+    if read_list.dtype not in (torch.int32, torch.int16) or read_list.dim() != 4 or not read_list.is_contiguous():
+        raise ValueError("read_list must be a contiguous int32 or int16 tensor [batch, heads, q_tiles, k_tiles + 1]")
+    if read_list.device != q.device:
+        raise ValueError("read_list must be on the device of q")
+    if read_list.shape[0] < B or tuple(read_list.shape[1:]) != (H, qt, kt + 1):
+        raise ValueError(f"read_list must be [>= {B}, {H}, {qt}, {kt + 1}] for these operands and flags, got {tuple(read_list.shape)}")
+
+
+def vote_margins(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float] = None, read_list: Optional[torch.Tensor] = None,
+                 flags: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The margin of the skip vote for every key tile a walk visits: fp32 ``(B, H, Qt, Kt)`` from one launch of ``la_vote_margins``
+    (its contract is in include/lite_attention_amd.h). A forward call at threshold ``thr`` over the same walk keeps exactly the
+    tiles with ``margin > thr`` and each row's first tile; entries are NaN for that first tile and for tiles the walk does not visit.
+    ``q`` (B, Sq, H, D), ``k`` (B, Sk, Hk, D): bf16 or fp16 device tensors with a contiguous last dimension and 16-byte aligned rows,
+    D one of 64 / 96 / 128 / 192 / 256. ``read_list``: int32 or int16 ``[>= B, H, Qt, Kt + 1]`` in the geometry of ``flags``; None walks
+    every tile, Kt - 1 ... 0. ``flags``: the geometry flags (LA_FLAG_HALF_VOTE, LA_FLAG_KERNEL_128ROW) of the forward the margins are
+    for; None takes the host defaults, as a forward call does. ``out``: a contiguous fp32 ``(B, H, Qt, Kt)`` tensor to write into (every
+    element is written). Asynchronous on the current stream."""
+    if q.dim() != 4 or k.dim() != 4 or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3]:
+        raise ValueError(f"q (B, Sq, H, D) and k (B, Sk, Hk, D) of one batch and head dim, got {tuple(q.shape)} and {tuple(k.shape)}")
+    if not (q.is_cuda and k.device == q.device):
+        raise ValueError("q and k must live on the same GPU (there is no CPU path; vote_margins_reference is the plain form)")
+    if q.dtype not in _MARGIN_DTYPES or k.dtype != q.dtype:
+        raise TypeError(f"bf16 or fp16 operands of one dtype, got {q.dtype} and {k.dtype}")
+    if q.stride(-1) != 1 or k.stride(-1) != 1:
+        raise ValueError("the last dimension must be contiguous")
+    B, Sq, H, D = q.shape
+    Sk, Hk = k.shape[1], k.shape[2]
+    if D not in MARGIN_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {MARGIN_HEAD_DIMS}, got {D}")
+    if min(B, Sq, Sk, Hk) < 1 or H % Hk != 0:
+        raise ValueError(f"sizes must be positive and the heads of k must divide those of q, got {tuple(q.shape)} and {tuple(k.shape)}")
+    f = (_cabi.default_flags() if flags is None else int(flags)) & _cabi.GEOMETRY_FLAGS
+    bm, bn = _cabi.get_tile_sizes(D, 2, f)
+    qt, kt = _cdiv(Sq, bm), _cdiv(Sk, bn)
+    if read_list is not None:
+        _check_margin_list(read_list, q, qt, kt)
+        if read_list.dtype == torch.int16:
+            f |= _cabi.LA_FLAG_LIST_INT16
+    if out is None:
+        out = torch.empty(B, H, qt, kt, dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, qt, kt) or not out.is_contiguous() or out.device != q.device:
+        raise ValueError(f"out must be a contiguous fp32 ({B}, {H}, {qt}, {kt}) tensor on the device of q")
+    a = _cabi.LaVoteMarginsArgs()
+    a.struct_size, a.dtype = ctypes.sizeof(_cabi.LaVoteMarginsArgs), _MARGIN_DTYPES[q.dtype]
+    a.q, a.k = q.data_ptr(), k.data_ptr()
+    a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
+    a.k_batch_stride, a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1), k.stride(2)
+    a.batch, a.seqlen_q, a.seqlen_k, a.num_heads, a.num_heads_k, a.head_dim = B, Sq, Sk, H, Hk, D
+    a.softmax_scale = D ** -0.5 if softmax_scale is None else float(softmax_scale)
+    a.flags = f
+    a.read_list = None if read_list is None else read_list.data_ptr()
+    a.margins = out.data_ptr()
+    with torch.cuda.device(q.device):
+        rc = _cabi.load().la_vote_margins(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_vote_margins: {_cabi.status_string(rc)}")
+    return out
+
+
+def _walk_of_row(row: Sequence[int], kt: int) -> List[int]:
+    """The key tiles one read-list row walks, in order, under the clamps of the kernels' list expansion."""
+    n_ranges = min(max(row[0], 2) // 2, (kt + 1) // 2)
+    walk: List[int] = []
+    for r in range(n_ranges):
+        in_row = 2 + 2 * r <= kt                 # a pair whose end lies behind the row reads as (0, 0); the first start is always in it
+        start = min(max(row[1 + 2 * r], 0), kt - 1) if in_row or r == 0 else 0
+        end = min(max(row[2 + 2 * r], 0), kt - 1) if in_row else 0
+        tiles = list(range(start, end - 1, -1))
+        if r == 0 and not tiles:
+            tiles = [start]                      # the first tile of the first range is always walked
+        walk += tiles
+    return walk[:kt]
+
+
+def vote_margins_reference(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float] = None,
+                           read_list: Optional[torch.Tensor] = None, block_m: int = 256, block_n: int = 64) -> torch.Tensor:
+    """``vote_margins`` written plainly in fp64 torch, on any device: fp64 ``(B, H, Qt, Kt)``. Scores of all rows against all keys,
+    the largest per (row, key tile), then per q-tile the walk of its list row with one running maximum per row. Rows at or past Sq
+    are zero rows, keys at or past Sk are -inf; the first tile walked and the tiles not walked are NaN."""
+    B, Sq, H, D = q.shape
+    Sk, Hk = k.shape[1], k.shape[2]
+    qt, kt = _cdiv(Sq, block_m), _cdiv(Sk, block_n)
+    c = (D ** -0.5 if softmax_scale is None else float(softmax_scale)) * _LOG2E
+    q64 = torch.zeros(B, qt * block_m, H, D, dtype=torch.float64, device=q.device)
+    q64[:, :Sq] = q.to(torch.float64)
+    k64 = k.to(torch.float64).repeat_interleave(H // Hk, dim=2)
+    s = torch.full((B, H, qt * block_m, kt * block_n), float("-inf"), dtype=torch.float64, device=q.device)
+    s[..., :Sk] = torch.einsum("bqhd,bkhd->bhqk", q64, k64)
+    m_loc = s.view(B, H, qt, block_m, kt, block_n).amax(dim=-1)             # (B, H, Qt, rows, Kt)
+    out = torch.full((B, H, qt, kt), float("nan"), dtype=torch.float64, device=q.device)
+    rows = None if read_list is None else read_list[:B].cpu().tolist()
+    for b in range(B):
+        for h in range(H):
+            for m in range(qt):
+                walk = list(range(kt - 1, -1, -1)) if rows is None else _walk_of_row(rows[b][h][m], kt)
+                run = m_loc[b, h, m, :, walk[0]]
+                for n in walk[1:]:
+                    out[b, h, m, n] = (m_loc[b, h, m, :, n] - run).amax() * c
+                    run = torch.maximum(run, m_loc[b, h, m, :, n])
+    return out
+
+
+def _sorted_margins(margins: torch.Tensor, per_head: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(G, N)`` ascending with +inf behind the finite entries, and their number ``(G,)``; G = H groups of one head each, or 1."""
+    if margins.dim() != 4:
+        raise ValueError(f"margins must be (B, H, Qt, Kt), got {tuple(margins.shape)}")
+    m = margins.permute(1, 0, 2, 3).reshape(margins.shape[1], -1) if per_head else margins.reshape(1, -1)
+    finite = torch.isfinite(m)
+    return torch.where(finite, m, torch.full_like(m, float("inf"))).sort(dim=-1).values, finite.sum(dim=-1)
+
+
+def _threshold_at_count(srt: torch.Tensor, n: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+    """fp32, of the shape of ``k`` - ``(G,)`` or ``(G, J)``: per group a value with exactly ``k`` of its ``n`` finite sorted margins at
+    or below it - the midpoint of the k-th and the (k + 1)-th, one below the smallest for k = 0, one above the largest for k = n,
+    -inf for a group without margins."""
+    n2 = n.unsqueeze(-1)
+    k2 = torch.minimum(k.reshape(k.shape[0], -1).clamp(min=0), n2)
+    lo = srt.gather(-1, (k2 - 1).clamp(min=0))
+    hi = srt.gather(-1, k2.clamp(max=srt.shape[-1] - 1))
+    mid = (0.5 * (lo.double() + hi.double())).to(torch.float32)
+    mid = torch.where(mid >= hi, lo, mid)              # neighbours one ulp apart: the midpoint rounds onto one of them
+    thr = torch.where(k2 == 0, hi - 1.0, torch.where(k2 >= n2, lo + 1.0, mid))
+    return torch.where(n2 == 0, torch.full_like(thr, float("-inf")), thr).to(torch.float32).reshape(k.shape)
+
+
+def _descents(margins: torch.Tensor, read_list: Optional[torch.Tensor], per_head: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The list writer names one tile more than the vote keeps wherever, inside one range of the walk, a kept tile is followed by a
+    dropped one: the dropped tile closes the range it writes (INCLUSIVE end). Tile n follows tile n + 1 when both are walked and n + 1
+    does not end a range of the read list; such a pair adds a tile at every thr with margin[n] <= thr < margin[n + 1] (+inf for a
+    row's first tile, which is always kept). Returns the two ends of these pairs, ``(G, N)`` each, sorted, +inf where there is none."""
+    B, H, Qt, Kt = margins.shape
+    fin = torch.isfinite(margins)
+    first, ends = torch.zeros_like(fin), torch.zeros_like(fin)
+    if read_list is None:
+        first[..., Kt - 1] = True
+    else:
+        rl = read_list[:B].long()
+        first.scatter_(-1, rl[..., 1:2].clamp(0, Kt - 1), True)
+        at = rl[..., 2::2]
+        used = torch.arange(at.shape[-1], device=rl.device) < rl[..., :1].clamp(min=2) // 2
+        ends = torch.zeros(B, H, Qt, Kt, dtype=torch.int32, device=rl.device).scatter_add_(-1, at.clamp(0, Kt - 1), used.int()) > 0
+    inf = torch.full_like(margins[..., 1:], float("inf"))
+    before = torch.where(fin[..., 1:], margins[..., 1:], inf)
+    pair = fin[..., :-1] & (fin | first)[..., 1:] & ~ends[..., 1:] & (before > margins[..., :-1])
+    out = []
+    for x in (torch.where(pair, margins[..., :-1], inf), torch.where(pair, before, inf)):
+        out.append((x.permute(1, 0, 2, 3).reshape(H, -1) if per_head else x.reshape(1, -1)).sort(dim=-1).values.contiguous())
+    return out[0], out[1]
+
+
+def _threshold_for_listed(margins: torch.Tensor, read_list: Optional[torch.Tensor], keep: float, per_head: bool):
+    """``(thr, listed, walked)``, ``(G,)`` each: the threshold - a midpoint between neighbouring margins - at which the list written
+    over this walk names the number of tiles nearest to ``keep * walked``, that number, and the tiles walked. Every candidate is
+    priced exactly, listed(thr) = rows + #{margin > thr} + #{descents that straddle thr}, by two sorts and two searches: no host
+    synchronisation, no forward call."""
+    srt, n = _sorted_margins(margins, per_head)
+    G, N = srt.shape
+    rows = margins[..., 0].numel() // G                                  # every row has one first tile, always kept
+    j = torch.arange(N + 1, device=srt.device).expand(G, -1)
+    cand = _threshold_at_count(srt, n, j).contiguous()
+    lows, highs = _descents(margins, read_list, per_head)
+    listed = rows + (n.unsqueeze(-1) - j) + torch.searchsorted(lows, cand, right=True) - torch.searchsorted(highs, cand, right=True)
+    walked = n + rows
+    cost = (listed.double() - keep * walked.double().unsqueeze(-1)).abs()
+    best = torch.where(j > n.unsqueeze(-1), torch.full_like(cost, float("inf")), cost).argmin(dim=-1, keepdim=True)
+    return cand.gather(-1, best).squeeze(-1), listed.gather(-1, best).squeeze(-1), walked
+
+
+def threshold_for_skip(margins: torch.Tensor, target_skip: float, per_head: bool = False):
+    """The threshold at which ``target_skip`` of the walked non-first tiles - the finite entries of ``margins`` - have ``margin <=
+    thr`` and are dropped from the list a forward call over the same walk writes: a quantile on the device, ``round(target_skip *
+    n)`` of the n finite entries. The value returned is the MIDPOINT between the two neighbouring margins, so that the fp32 rounding
+    of the forward's own vote cannot move a tile across it. ``per_head``: an fp32 ``(H,)`` device tensor, one quantile per head over
+    the batch (for ``LiteAttention.set_head_thresholds``), computed without synchronising; else one float over everything."""
+    if not 0.0 <= target_skip <= 1.0:
+        raise ValueError("target_skip must lie in [0, 1]")
+    srt, n = _sorted_margins(margins, per_head)
+    thr = _threshold_at_count(srt, n, torch.round(target_skip * n.double()).long())
+    return thr if per_head else float(thr[0])
+
+
+def calibrate_skip_schedule(qkv_at, n_steps: int, targets: Sequence[float], per_head: bool = False, hi: float = -1e-3,
+                            max_batch_size: int = 1, list_dtype: Optional[torch.dtype] = None):
+    """A threshold per step - per (step, head) with ``per_head`` - such that the list step t WRITES keeps ``1 - targets[t]`` of the
+    tiles step t walked, without bisection: per step one margin pass over the list the step reads (``LiteAttention.vote_margins``),
+    the threshold from the margins on the device, one forward call at it. What a written list names is a pure function of the
+    margins and the threshold - each row's first tile, the tiles with ``margin > thr``, and the dropped tile that closes a range
+    (the writer's inclusive end) - so every midpoint between neighbouring margins is priced exactly and the nearest is taken. A
+    threshold is capped at ``hi`` (``set_threshold`` takes negative values only: a tile with a positive margin raised a row's maximum
+    and is never dropped); the trace shows what was reached.
+
+    Returns ``(thresholds, trace)`` as ``calibrate_error_schedule`` does: a list of floats for ``set_threshold_schedule``, or an fp32
+    ``(n_steps, H)`` device tensor for ``set_head_thresholds``. ``trace[t]``: ``threshold``, ``target``, ``skip_fraction`` (of the
+    list step t read), ``walked`` and ``kept`` (tiles step t walked / its written list names: floats, or ``(H,)`` device tensors
+    with ``per_head``, which never synchronises)."""
+    from .flash_attn_interface import skip_list_stats_heads
+    if len(targets) != n_steps:
+        raise ValueError(f"one target per step: got {len(targets)} for {n_steps} steps")
+    if hi >= 0:
+        raise ValueError("hi must be negative")
+    att = LiteAttention(threshold=-1.0, max_batch_size=max_batch_size, list_dtype=list_dtype)
+    thresholds, trace = [], []
+    for t in range(n_steps):
+        q, k, v = qkv_at(t)
+        skip_heads = att.get_skip_fraction_heads(q.shape[0])
+        margins = att.vote_margins(q, k)
+        thr, _, walked = _threshold_for_listed(margins, att.current_read_list(), 1.0 - float(targets[t]), per_head)
+        thr = thr.clamp(max=hi)
+        if per_head:
+            att.set_head_thresholds(thr)
+        else:
+            thr = float(thr[0])
+            att.set_threshold(thr)
+        att(q, k, v)
+        kept = skip_list_stats_heads(att.current_read_list(), q.shape[0]).sum(dim=0)
+        if per_head:
+            skip = torch.zeros_like(thr) if skip_heads is None else skip_heads.mean(dim=0)
+        else:
+            walked, kept, skip = float(walked[0]), float(kept.sum()), 0.0 if skip_heads is None else float(skip_heads.mean())
+        thresholds.append(thr)
+        trace.append(dict(threshold=thr, target=float(targets[t]), skip_fraction=skip, walked=walked, kept=kept))
+    return (torch.stack(thresholds) if per_head else thresholds), trace

@@ -942,3 +942,45 @@ int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream) { return v_prep
 int la_v_prep_tiles_rows(const la_v_prep_tiles_args* a, const la_row_map* map, void* stream) { return v_prep_tiles_run(a, true, map, stream); }
 
 }  // extern "C"
+
+// la_vote_margins: the margins of the skip vote in one pass over Q K^T (la_vote_margins.hip). The launcher is a weak reference, as the
+// rotating prologue's is: a host-only link of this file without la_vote_margins.hip stays complete and answers LA_ERR_UNSUPPORTED.
+namespace la {
+hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream) __attribute__((weak));
+}
+
+extern "C" {
+
+int la_vote_margins(const la_vote_margins_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_vote_margins_args)) return LA_ERR_STRUCT_SIZE;
+    if (a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
+    if (!a->q || !a->k || !a->margins) return LA_ERR_NULL_ARG;
+    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->head_dim <= 0 ||
+        a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;
+    // the q-tile of the lists la_fwd reads and writes under the same flags: one table (la_tiles.h), the other flags of la_fwd are not read
+    const uint32_t flags = a->flags & (LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16);
+    int bm = 0, bn = 0;
+    if (const int rc = la_get_tile_sizes_ex(a->head_dim, 2, flags, &bm, &bn); rc != LA_OK) return rc;
+    if (!rows_aligned(a->q, a->dtype, a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->batch, a->seqlen_q, a->num_heads) ||
+        !rows_aligned(a->k, a->dtype, a->k_batch_stride, a->k_row_stride, a->k_head_stride, a->batch, a->seqlen_k, a->num_heads_k) ||
+        (reinterpret_cast<uintptr_t>(a->margins) & 3u) ||
+        (reinterpret_cast<uintptr_t>(a->read_list) & ((flags & LA_FLAG_LIST_INT16) ? 1u : 3u))) return LA_ERR_STRIDE;
+    const int64_t q_tiles = (static_cast<int64_t>(a->seqlen_q) + bm - 1) / bm, k_tiles = (static_cast<int64_t>(a->seqlen_k) + bn - 1) / bn;
+    if ((flags & LA_FLAG_LIST_INT16) && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    if (la::vote_margins_lds_bytes(a->head_dim, static_cast<int>(k_tiles)) > la::kVoteMarginsLdsLimit) return LA_ERR_SEQLEN;   // the walk lives in LDS
+    if (static_cast<int64_t>(a->batch) * a->num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per q-tile
+    la::VoteMarginsParams p = {};
+    p.q = a->q; p.k = a->k; p.read_list = a->read_list; p.margins = a->margins;
+    p.q_bs = a->q_batch_stride; p.q_rs = a->q_row_stride; p.q_hs = a->q_head_stride;
+    p.k_bs = a->k_batch_stride; p.k_rs = a->k_row_stride; p.k_hs = a->k_head_stride;
+    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
+    p.heads_per_k = a->num_heads / a->num_heads_k;
+    p.q_tiles = static_cast<int>(q_tiles); p.k_tiles = static_cast<int>(k_tiles); p.block_m = bm;
+    p.list_int16 = (flags & LA_FLAG_LIST_INT16) ? 1 : 0;
+    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);
+    if (!la::launch_vote_margins) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_vote_margins(p, a->dtype, a->head_dim, static_cast<hipStream_t>(stream_)));
+}
+
+}  // extern "C"

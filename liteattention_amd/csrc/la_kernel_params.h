@@ -259,4 +259,26 @@ hipError_t launch_v_prep_tiles_rows(const VPrepTilesParams& p, const RowGather& 
 hipError_t launch_v_colstats_rows(const VColstatsParams& p, const RowGather& g, int in_dtype, hipStream_t stream);
 hipError_t launch_attn_unshift_rows(const AttnUnshiftParams& p, const RowGather& g, int o_dtype, int out_dtype, hipStream_t stream);
 
+// la_vote_margins (la_vote_margins.hip): checked and filled by la_api.hip. Strides in elements.
+struct VoteMarginsParams {
+    const void* q;               // (B, Sq, H, D) by q_bs / q_rs / q_hs
+    const void* k;               // (B, Sk, Hk, D) by k_bs / k_rs / k_hs
+    const void* read_list;       // [B_alloc, H, q_tiles, k_tiles + 1] int32 or int16 rows; NULL = the dense walk k_tiles - 1 ... 0
+    float* margins;              // [B, H, q_tiles, k_tiles] contiguous, every element written
+    int64_t q_bs, q_rs, q_hs, k_bs, k_rs, k_hs;
+    int batch, seqlen_q, seqlen_k, num_heads, heads_per_k;      // heads_per_k = H / Hk: query head h reads K head h / heads_per_k
+    int q_tiles, k_tiles, block_m;                       // block_m: 256 or 128 rows of a q-tile; a key tile is 64 keys
+    int list_int16;
+    float scale_log2;            // softmax_scale * log2(e), rounded to fp32 once on the host
+};
+// Dynamic LDS of one workgroup: two stages of 64 keys at a pitch of 2 D + 16 bytes, the four waves' part maxima of two tiles and the
+// tile count (64 bytes), the walk (one int per key tile) and two bitmaps over the key tiles (range ends for the list expansion, walked
+// tiles). The one place it is sized: la_api.hip holds it against kVoteMarginsLdsLimit (LA_ERR_SEQLEN), the launcher asks for it.
+constexpr size_t kVoteMarginsLdsLimit = 160 * 1024;
+inline size_t vote_margins_lds_bytes(int head_dim, int k_tiles) {
+    const size_t seq_cap = (static_cast<size_t>(k_tiles) + 3) & ~static_cast<size_t>(3), words = (static_cast<size_t>(k_tiles) + 31) / 32;
+    return 2 * 64 * (static_cast<size_t>(head_dim) * 2 + 16) + 64 + 4 * seq_cap + 8 * words;
+}
+hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream);      // dtype: 0 bf16, 1 fp16
+
 }  // namespace la

@@ -468,6 +468,22 @@ class LiteAttention:
         listed = skip_list_stats_heads(rl, batch)
         return 1.0 - listed.to(torch.float32) / float(rl.shape[2] * (rl.shape[3] - 1))
 
+    def vote_margins(self, query: Tensor, key: Tensor, scale: Optional[float] = None) -> Tensor:
+        """The margins of the skip vote (``calibration.vote_margins``: fp32 ``(B, H, Qt, Kt)``) for the call that would come next on
+        these operands: over the list that call reads, in its tile geometry and list element type - the dense walk when skipping is
+        off, before the first call or when the shapes differ from the lists' (that call would start from "all tiles listed").
+        Reads the skip state and changes none of it: no list is written, no phase flipped, no step counted."""
+        from .calibration import vote_margins
+        read_list = None
+        shape_key = (query.shape[1], key.shape[1], query.shape[2], query.shape[3], query.dtype, query.device,
+                     get_tile_sizes(query.shape[3], query.dtype.itemsize), self.list_dtype)
+        if self.enable_skipping and self._skip_list is not None and shape_key == self._shape_key:
+            read_list = self._skip_list[self._phase]
+            if query.shape[0] > read_list.shape[0]:        # sequences not tracked yet start from "all tiles listed"
+                fresh = self._init_skip_list(query, key, batch=query.shape[0] - read_list.shape[0])[0]
+                read_list = torch.cat([read_list, fresh])
+        return vote_margins(query, key, scale, read_list)
+
     def snapshot(self) -> dict:
         """Both ping-pong lists, the phase and the step counter, copied ON THE DEVICE (no host round trip, no sync: ``state_dict()``
         takes 112 MB per layer through the host at S = 75 600, H = 40). For ``restore``; thresholds are not part of it."""
