@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads, la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows la_qk_prep_rot / la_qk_prep_fp8_rot / la_qk_prep_smooth_rot and la_vote_margins were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
+#define LA_ABI_VERSION 9   /* la_output_error, la_qk_prep, la_qk_prep_fp8, la_qk_prep_smooth (+ _parts, _part_rows), la_colsum_finish, la_v_colstats (+ _parts, _part_rows, _finish), la_attn_unshift, la_v_prep_tiles, la_v_tiles_bytes, la_v_tiles_workspace_bytes, la_fwd_head_thr, la_skip_list_stats_heads, la_qk_prep_rows / la_qk_prep_fp8_rows / la_qk_prep_smooth_rows la_qk_prep_rot / la_qk_prep_fp8_rot / la_qk_prep_smooth_rot, la_vote_margins and la_vote_margins_fp8 were ADDED under 9: an added entry point is compatible (la_fwd_args and every older signature are unchanged), a host detects it by symbol;
                             * 9 = 8 + LA_FLAG_LIST_INT16, la_skip_list_stats_ex, la_blockmask_to_lists_ex (la_fwd_args unchanged); 8 = 7 with the sense of the two fp8 flags turned round (the reference's arithmetic is the default form of P) + LA_FLAG_HALF_VOTE + la_combine_list;
                             * 7 = 6 + la_build_info; 6 = 5 + la_blockmask_to_lists, la_device_slots (5 = 4 + skip lists and fp8 with cu_seqlens, LA_FLAG_EXACT_ROWSUM /
                             * LA_FLAG_EXACT_EXP (renamed and inverted in 8), LA_DTYPE_FP32 for la_combine); la_fwd_args unchanged since 4 */
@@ -411,6 +411,45 @@ typedef struct la_vote_margins_args {
     float*      margins;         /* fp32 [B, H, Qt, Kt] contiguous                                */
 } la_vote_margins_args;
 int la_vote_margins(const la_vote_margins_args* args, void* stream);
+
+/* The same map for the e4m3 forward (added under ABI 9: a host detects it by symbol): q and k are the LA_DTYPE_FP8_E4M3 operands la_fwd
+ * is given, with the descales la_fwd is given, and no 16-bit copy of either is made. The e4m3 la_fwd takes its vote on the fp32
+ * accumulators of the block-scaled fp8 MFMA at unit block scales, with the descales folded into the score scale:
+ *   margin[n] = max over the q-tile's rows i of (m_loc(i, n) - m_prev(i)) * c,   c = ((softmax_scale * log2 e) * qd) * kd   in fp32
+ * with m_loc and m_prev over the products of the e4m3 CODES, qd = q_descale[b][h / (H / Hk)] and kd = k_descale[b][h / (H / Hk)]. This
+ * entry point computes the same numbers with the same instruction. Everything la_vote_margins says holds, except:
+ *   q (B, Sq, H, D), k (B, Sk, Hk, D): e4m3 (1-byte elements: strides in elements are strides in bytes); D = 64, 96, 128, 192 or 256.
+ *   q_descale, k_descale: fp32 [B, Hk] by their batch / head strides (in elements, as in la_fwd_args); NULL = 1.0.
+ *   flags: only LA_FLAG_LIST_INT16 is read. The e4m3 forward has one q-tile per head dim - la_get_tile_sizes_ex(head_dim, 1, 0): 256 x 64
+ *     up to head_dim 128, 128 x 64 above - and LA_FLAG_HALF_VOTE / LA_FLAG_KERNEL_128ROW do not change it.
+ *   scores are fp32 accumulators of the fp8 MFMA's products; contraction positions past a head_dim of 96 are zeros in both operands.
+ * K smoothing (la_qk_prep_smooth: k - mean over the keys) shifts every score of a query row by the same amount, so m_loc - m_prev and
+ * with it every margin is that of the unshifted K: the smoothed codes and their descale are passed as they are.
+ * Errors (all before any HIP call), in this order: NULL args LA_ERR_NULL_ARG; struct_size LA_ERR_STRUCT_SIZE; NULL q / k / margins
+ * LA_ERR_NULL_ARG; a non-positive size or H % Hk != 0 LA_ERR_SHAPE; a head_dim without an e4m3 tile LA_ERR_HEAD_DIM; a negative
+ * stride, a q / k pointer or used stride that takes a row start off a 16-byte boundary, margins or a descale pointer off 4 bytes,
+ * read_list off its element size LA_ERR_STRIDE; LA_FLAG_LIST_INT16 with Kt + 1 > 32767, or more key tiles than the walk storage of a
+ * workgroup holds (4 bytes per tile beside the K ring in 160 KiB of LDS) LA_ERR_SEQLEN; more than 2^31 - 1 workgroups LA_ERR_SHAPE; a
+ * library linked without the kernel LA_ERR_UNSUPPORTED. */
+typedef struct la_vote_margins_fp8_args {
+    uint32_t struct_size;        /* = sizeof(la_vote_margins_fp8_args)                            */
+    uint32_t flags;              /* LA_FLAG_LIST_INT16; other bits ignored                        */
+    const void* q;               /* (B, Sq, H, D) e4m3                                            */
+    const void* k;               /* (B, Sk, Hk, D) e4m3                                           */
+    int64_t q_batch_stride, q_row_stride, q_head_stride;          /* in elements (= bytes)        */
+    int64_t k_batch_stride, k_row_stride, k_head_stride;
+    int32_t batch, seqlen_q, seqlen_k;
+    int32_t num_heads, num_heads_k, head_dim;
+    const float* q_descale;      /* fp32 [B, Hk] by the strides below; NULL = 1.0                 */
+    const float* k_descale;
+    int64_t q_descale_batch_stride, q_descale_head_stride;        /* in elements                  */
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    float    softmax_scale;
+    uint32_t reserved0;          /* padding; not read                                             */
+    const void* read_list;       /* int32_t / int16_t [B_alloc, H, Qt, Kt + 1]; NULL = dense walk */
+    float*      margins;         /* fp32 [B, H, Qt, Kt] contiguous                                */
+} la_vote_margins_fp8_args;
+int la_vote_margins_fp8(const la_vote_margins_fp8_args* args, void* stream);
 
 /* The q / k prologue of a Wan2.x-style attention block in one pass: RMSNorm, 3-axis RoPE on INTERLEAVED pairs, the cast to bf16 / fp16.
  * Per token (b, s) of x (B, S, H, D), in fp32 with ONE rounding at the store:

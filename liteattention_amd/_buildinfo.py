@@ -12,14 +12,16 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 PUBLIC_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "lite_attention_amd.h")
 SOURCES = ["la_fwd_kernel_v2.hip", "la_fwd_kernel_x64.hip", "la_prep_fp8.hip", "la_fwd_kernel_x64_fp8.hip", "la_aux_kernels.hip",
-           "la_prep_qk.hip", "la_prep_qk_rot.hip", "la_prep_v.hip", "la_vote_margins.hip", "la_api.hip"]
+           "la_prep_qk.hip", "la_prep_qk_rot.hip", "la_prep_v.hip", "la_vote_margins.hip", "la_vote_margins_fp8.hip",
+           "la_api.hip"]
 # What a source is compiled with beside the common flags. The rotated prologue is built without the packed fp32 forms (v_pk_add / mul /
 # fma_f32): its butterflies gain nothing from them, and without them the compiler needs fewer registers - the headline form,
 # token_kernel<bf16, e4m3, NCH 10, mode 1>, 279 -> 227 VGPRs, one wave per SIMD -> two (profiles/qk_rotate.md has the times of both
 # flag sets). la_prep_qk.hip keeps the flags the unrotated kernels have always had, so that their instructions stay the parent's;
 # `-DLA_QK_PREP_SAME_FLAGS=1` on a variant build (build.py) puts it under these flags too, for the comparison.
 SOURCE_FLAGS = {"la_prep_qk_rot.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
-HEADERS = ["la_kernel_params.h", "la_tiles.h", "la_fwd_common.h", "la_fwd_shell.h", "la_prep_common.h", "gen_fwd_x64.py", "gen_fwd_x64_fp8.py",
+HEADERS = ["la_kernel_params.h", "la_tiles.h", "la_fwd_common.h", "la_fwd_shell.h", "la_prep_common.h", "la_vote_margins_common.h",
+           "gen_fwd_x64.py", "gen_fwd_x64_fp8.py",
            "gen_epilogue.py", "gen_asm.py", "gen_blocks.py"]
 
 

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = (
     "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows", "la_attn_unshift_fp8",
     "la_qk_prep_rot", "la_qk_prep_fp8_rot", "la_qk_prep_smooth_rot",
     "la_v_colstats_rows", "la_v_prep_tiles_rows", "la_attn_unshift_rows", "la_attn_unshift_fp8_rows",
-    "la_vote_margins",
+    "la_vote_margins", "la_vote_margins_fp8",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -165,6 +165,23 @@ class LaVoteMarginsArgs(ctypes.Structure):
         ("batch", ctypes.c_int32), ("seqlen_q", ctypes.c_int32), ("seqlen_k", ctypes.c_int32),
         ("num_heads", ctypes.c_int32), ("num_heads_k", ctypes.c_int32), ("head_dim", ctypes.c_int32),
         ("softmax_scale", ctypes.c_float), ("flags", ctypes.c_uint32),
+        ("read_list", ctypes.c_void_p), ("margins", ctypes.c_void_p),
+    ]
+
+
+class LaVoteMarginsFp8Args(ctypes.Structure):
+    """Mirror of ``la_vote_margins_fp8_args`` (field order and types must match the header)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p),
+        ("q_batch_stride", ctypes.c_int64), ("q_row_stride", ctypes.c_int64), ("q_head_stride", ctypes.c_int64),
+        ("k_batch_stride", ctypes.c_int64), ("k_row_stride", ctypes.c_int64), ("k_head_stride", ctypes.c_int64),
+        ("batch", ctypes.c_int32), ("seqlen_q", ctypes.c_int32), ("seqlen_k", ctypes.c_int32),
+        ("num_heads", ctypes.c_int32), ("num_heads_k", ctypes.c_int32), ("head_dim", ctypes.c_int32),
+        ("q_descale", ctypes.c_void_p), ("k_descale", ctypes.c_void_p),
+        ("q_descale_batch_stride", ctypes.c_int64), ("q_descale_head_stride", ctypes.c_int64),
+        ("k_descale_batch_stride", ctypes.c_int64), ("k_descale_head_stride", ctypes.c_int64),
+        ("softmax_scale", ctypes.c_float), ("reserved0", ctypes.c_uint32),
         ("read_list", ctypes.c_void_p), ("margins", ctypes.c_void_p),
     ]
 
@@ -340,6 +357,8 @@ def load() -> ctypes.CDLL:
     lib.la_v_prep_tiles.restype = ctypes.c_int
     lib.la_vote_margins.argtypes = [ctypes.POINTER(LaVoteMarginsArgs), ctypes.c_void_p]
     lib.la_vote_margins.restype = ctypes.c_int
+    lib.la_vote_margins_fp8.argtypes = [ctypes.POINTER(LaVoteMarginsFp8Args), ctypes.c_void_p]
+    lib.la_vote_margins_fp8.restype = ctypes.c_int
     for fn in (lib.la_v_tiles_bytes, lib.la_v_tiles_workspace_bytes):
         fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
         fn.restype = ctypes.c_int64

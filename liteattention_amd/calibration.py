@@ -333,10 +333,22 @@ def _check_margin_list(read_list: torch.Tensor, q: torch.Tensor, qt: int, kt: in
         raise ValueError(f"read_list must be [>= {B}, {H}, {qt}, {kt + 1}] for these operands and flags, got {tuple(read_list.shape)}")
 
 
+def _descale_fields(name: str, d: Optional[torch.Tensor], q: torch.Tensor, Hk: int):
+    """(pointer, batch stride, head stride) of an fp32 ``(B, Hk)`` descale on q's device, any strides; None reads as 1.0."""
+    if d is None:
+        return None, 0, 0
+    if d.dtype != torch.float32 or tuple(d.shape) != (q.shape[0], Hk) or d.device != q.device:
+        raise ValueError(f"{name} must be an fp32 ({q.shape[0]}, {Hk}) tensor on the device of q, got {d.dtype} {tuple(d.shape)}")
+    return d.data_ptr(), d.stride(0), d.stride(1)
+
+
 def vote_margins(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float] = None, read_list: Optional[torch.Tensor] = None,
-                 flags: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 flags: Optional[int] = None, out: Optional[torch.Tensor] = None, *, q_descale: Optional[torch.Tensor] = None,
+                 k_descale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The margin of the skip vote for every key tile a walk visits: fp32 ``(B, H, Qt, Kt)`` from one launch of ``la_vote_margins``
-    (its contract is in include/lite_attention_amd.h). A forward call at threshold ``thr`` over the same walk keeps exactly the
+    - of ``la_vote_margins_fp8`` for ``float8_e4m3fn`` operands, which are read as they are, with the fp32 ``(B, Hk)`` ``q_descale`` /
+    ``k_descale`` of the e4m3 forward (any strides, None = 1.0; the q-tile is the e4m3 forward's, which no flag changes). The
+    contracts are in include/lite_attention_amd.h. A forward call at threshold ``thr`` over the same walk keeps exactly the
     tiles with ``margin > thr`` and each row's first tile; entries are NaN for that first tile and for tiles the walk does not visit.
     ``q`` (B, Sq, H, D), ``k`` (B, Sk, Hk, D): bf16 or fp16 device tensors with a contiguous last dimension and 16-byte aligned rows,
     D one of 64 / 96 / 128 / 192 / 256. ``read_list``: int32 or int16 ``[>= B, H, Qt, Kt + 1]`` in the geometry of ``flags``; None walks
@@ -347,8 +359,11 @@ def vote_margins(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float
         raise ValueError(f"q (B, Sq, H, D) and k (B, Sk, Hk, D) of one batch and head dim, got {tuple(q.shape)} and {tuple(k.shape)}")
     if not (q.is_cuda and k.device == q.device):
         raise ValueError("q and k must live on the same GPU (there is no CPU path; vote_margins_reference is the plain form)")
-    if q.dtype not in _MARGIN_DTYPES or k.dtype != q.dtype:
-        raise TypeError(f"bf16 or fp16 operands of one dtype, got {q.dtype} and {k.dtype}")
+    fp8 = q.dtype == torch.float8_e4m3fn
+    if (q.dtype not in _MARGIN_DTYPES and not fp8) or k.dtype != q.dtype:
+        raise TypeError(f"bf16, fp16 or float8_e4m3fn operands of one dtype, got {q.dtype} and {k.dtype}")
+    if not fp8 and (q_descale is not None or k_descale is not None):
+        raise ValueError("q_descale / k_descale belong to float8_e4m3fn operands")
     if q.stride(-1) != 1 or k.stride(-1) != 1:
         raise ValueError("the last dimension must be contiguous")
     B, Sq, H, D = q.shape
@@ -358,7 +373,8 @@ def vote_margins(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float
     if min(B, Sq, Sk, Hk) < 1 or H % Hk != 0:
         raise ValueError(f"sizes must be positive and the heads of k must divide those of q, got {tuple(q.shape)} and {tuple(k.shape)}")
     f = (_cabi.default_flags() if flags is None else int(flags)) & _cabi.GEOMETRY_FLAGS
-    bm, bn = _cabi.get_tile_sizes(D, 2, f)
+    bm, bn = _cabi.get_tile_sizes(D, 1, f) if fp8 else _cabi.get_tile_sizes(D, 2, f)
+    f = 0 if fp8 else f
     qt, kt = _cdiv(Sq, bm), _cdiv(Sk, bn)
     if read_list is not None:
         _check_margin_list(read_list, q, qt, kt)
@@ -368,8 +384,14 @@ def vote_margins(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float
         out = torch.empty(B, H, qt, kt, dtype=torch.float32, device=q.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, qt, kt) or not out.is_contiguous() or out.device != q.device:
         raise ValueError(f"out must be a contiguous fp32 ({B}, {H}, {qt}, {kt}) tensor on the device of q")
-    a = _cabi.LaVoteMarginsArgs()
-    a.struct_size, a.dtype = ctypes.sizeof(_cabi.LaVoteMarginsArgs), _MARGIN_DTYPES[q.dtype]
+    if fp8:
+        a, entry = _cabi.LaVoteMarginsFp8Args(), "la_vote_margins_fp8"
+        a.struct_size = ctypes.sizeof(_cabi.LaVoteMarginsFp8Args)
+        a.q_descale, a.q_descale_batch_stride, a.q_descale_head_stride = _descale_fields("q_descale", q_descale, q, Hk)
+        a.k_descale, a.k_descale_batch_stride, a.k_descale_head_stride = _descale_fields("k_descale", k_descale, q, Hk)
+    else:
+        a, entry = _cabi.LaVoteMarginsArgs(), "la_vote_margins"
+        a.struct_size, a.dtype = ctypes.sizeof(_cabi.LaVoteMarginsArgs), _MARGIN_DTYPES[q.dtype]
     a.q, a.k = q.data_ptr(), k.data_ptr()
     a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
     a.k_batch_stride, a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1), k.stride(2)
@@ -379,9 +401,9 @@ def vote_margins(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float
     a.read_list = None if read_list is None else read_list.data_ptr()
     a.margins = out.data_ptr()
     with torch.cuda.device(q.device):
-        rc = _cabi.load().la_vote_margins(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = getattr(_cabi.load(), entry)(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc != _cabi.LA_OK:
-        raise RuntimeError(f"la_vote_margins: {_cabi.status_string(rc)}")
+        raise RuntimeError(f"{entry}: {_cabi.status_string(rc)}")
     return out
 
 
@@ -401,14 +423,20 @@ def _walk_of_row(row: Sequence[int], kt: int) -> List[int]:
 
 
 def vote_margins_reference(q: torch.Tensor, k: torch.Tensor, softmax_scale: Optional[float] = None,
-                           read_list: Optional[torch.Tensor] = None, block_m: int = 256, block_n: int = 64) -> torch.Tensor:
+                           read_list: Optional[torch.Tensor] = None, block_m: int = 256, block_n: int = 64, *,
+                           q_descale: Optional[torch.Tensor] = None, k_descale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``vote_margins`` written plainly in fp64 torch, on any device: fp64 ``(B, H, Qt, Kt)``. Scores of all rows against all keys,
     the largest per (row, key tile), then per q-tile the walk of its list row with one running maximum per row. Rows at or past Sq
-    are zero rows, keys at or past Sk are -inf; the first tile walked and the tiles not walked are NaN."""
+    are zero rows, keys at or past Sk are -inf; the first tile walked and the tiles not walked are NaN. ``q_descale`` / ``k_descale``
+    (``(B, Hk)``, None = 1.0): the margins of (batch, head) are scaled by ``c = softmax_scale log2 e qd kd`` of its K/V head, in fp64."""
     B, Sq, H, D = q.shape
     Sk, Hk = k.shape[1], k.shape[2]
     qt, kt = _cdiv(Sq, block_m), _cdiv(Sk, block_n)
-    c = (D ** -0.5 if softmax_scale is None else float(softmax_scale)) * _LOG2E
+    c = torch.full((B, Hk), (D ** -0.5 if softmax_scale is None else float(softmax_scale)) * _LOG2E, dtype=torch.float64)
+    for d in (q_descale, k_descale):
+        if d is not None:
+            c = c * d.to(device="cpu", dtype=torch.float64)
+    c = c.repeat_interleave(H // Hk, dim=1).tolist()
     q64 = torch.zeros(B, qt * block_m, H, D, dtype=torch.float64, device=q.device)
     q64[:, :Sq] = q.to(torch.float64)
     k64 = k.to(torch.float64).repeat_interleave(H // Hk, dim=2)
@@ -423,7 +451,7 @@ def vote_margins_reference(q: torch.Tensor, k: torch.Tensor, softmax_scale: Opti
                 walk = list(range(kt - 1, -1, -1)) if rows is None else _walk_of_row(rows[b][h][m], kt)
                 run = m_loc[b, h, m, :, walk[0]]
                 for n in walk[1:]:
-                    out[b, h, m, n] = (m_loc[b, h, m, :, n] - run).amax() * c
+                    out[b, h, m, n] = (m_loc[b, h, m, :, n] - run).amax() * c[b][h]
                     run = torch.maximum(run, m_loc[b, h, m, :, n])
     return out
 
@@ -508,12 +536,14 @@ def threshold_for_skip(margins: torch.Tensor, target_skip: float, per_head: bool
 
 
 def calibrate_skip_schedule(qkv_at, n_steps: int, targets: Sequence[float], per_head: bool = False, hi: float = -1e-3,
-                            max_batch_size: int = 1, list_dtype: Optional[torch.dtype] = None):
+                            max_batch_size: int = 1, list_dtype: Optional[torch.dtype] = None, descales_at=None):
     """A threshold per step - per (step, head) with ``per_head`` - such that the list step t WRITES keeps ``1 - targets[t]`` of the
     tiles step t walked, without bisection: per step one margin pass over the list the step reads (``LiteAttention.vote_margins``),
     the threshold from the margins on the device, one forward call at it. What a written list names is a pure function of the
     margins and the threshold - each row's first tile, the tiles with ``margin > thr``, and the dropped tile that closes a range
     (the writer's inclusive end) - so every midpoint between neighbouring margins is priced exactly and the nearest is taken. A
+    ``descales_at``: for ``float8_e4m3fn`` operands, a callable ``t -> dict`` of ``q_descale`` / ``k_descale`` / ``v_descale``; what it
+    returns is handed to both the margin pass (which reads q's and k's) and the forward call of step t. A
     threshold is capped at ``hi`` (``set_threshold`` takes negative values only: a tile with a positive margin raised a row's maximum
     and is never dropped); the trace shows what was reached.
 
@@ -531,7 +561,8 @@ def calibrate_skip_schedule(qkv_at, n_steps: int, targets: Sequence[float], per_
     for t in range(n_steps):
         q, k, v = qkv_at(t)
         skip_heads = att.get_skip_fraction_heads(q.shape[0])
-        margins = att.vote_margins(q, k)
+        descales = {} if descales_at is None else dict(descales_at(t))
+        margins = att.vote_margins(q, k, **{name: d for name, d in descales.items() if name != "v_descale"})
         thr, _, walked = _threshold_for_listed(margins, att.current_read_list(), 1.0 - float(targets[t]), per_head)
         thr = thr.clamp(max=hi)
         if per_head:
@@ -539,7 +570,7 @@ def calibrate_skip_schedule(qkv_at, n_steps: int, targets: Sequence[float], per_
         else:
             thr = float(thr[0])
             att.set_threshold(thr)
-        att(q, k, v)
+        att(q, k, v, **descales)
         kept = skip_list_stats_heads(att.current_read_list(), q.shape[0]).sum(dim=0)
         if per_head:
             skip = torch.zeros_like(thr) if skip_heads is None else skip_heads.mean(dim=0)

@@ -984,3 +984,50 @@ int la_vote_margins(const la_vote_margins_args* a, void* stream_) {
 }
 
 }  // extern "C"
+
+// la_vote_margins_fp8: the same map for e4m3 operands (la_vote_margins_fp8.hip); its launcher is a weak reference for the same reason.
+namespace la {
+hipError_t launch_vote_margins_fp8(const VoteMarginsFp8Params& p, int head_dim, hipStream_t stream) __attribute__((weak));
+}
+
+extern "C" {
+
+int la_vote_margins_fp8(const la_vote_margins_fp8_args* a, void* stream_) {
+    if (!a) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(la_vote_margins_fp8_args)) return LA_ERR_STRUCT_SIZE;
+    if (!a->q || !a->k || !a->margins) return LA_ERR_NULL_ARG;
+    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->head_dim <= 0 ||
+        a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;
+    // the q-tile of the lists the e4m3 la_fwd reads and writes: it has one geometry per head dim, the 16-bit geometry flags are not read
+    const la::TileShape ts = la::tile_shape(a->head_dim, 1);
+    if (ts.block_m == 0) return LA_ERR_HEAD_DIM;
+    const bool int16 = (a->flags & LA_FLAG_LIST_INT16) != 0;
+    // rows of 1-byte elements are read 16 bytes at a time: every row start on a 16-byte boundary
+    if (!rows_aligned(a->q, 16u, 16, a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->batch, a->seqlen_q, a->num_heads) ||
+        !rows_aligned(a->k, 16u, 16, a->k_batch_stride, a->k_row_stride, a->k_head_stride, a->batch, a->seqlen_k, a->num_heads_k) ||
+        (reinterpret_cast<uintptr_t>(a->margins) & 3u) || (reinterpret_cast<uintptr_t>(a->read_list) & (int16 ? 1u : 3u)) ||
+        ((reinterpret_cast<uintptr_t>(a->q_descale) | reinterpret_cast<uintptr_t>(a->k_descale)) & 3u) ||
+        a->q_descale_batch_stride < 0 || a->q_descale_head_stride < 0 || a->k_descale_batch_stride < 0 || a->k_descale_head_stride < 0)
+        return LA_ERR_STRIDE;
+    const int64_t q_tiles = (static_cast<int64_t>(a->seqlen_q) + ts.block_m - 1) / ts.block_m;
+    const int64_t k_tiles = (static_cast<int64_t>(a->seqlen_k) + ts.block_n - 1) / ts.block_n;
+    if (int16 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    if (la::vote_margins_fp8_lds_bytes(a->head_dim, static_cast<int>(k_tiles)) > la::kVoteMarginsLdsLimit) return LA_ERR_SEQLEN;   // the walk lives in LDS
+    if (static_cast<int64_t>(a->batch) * a->num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per q-tile
+    la::VoteMarginsFp8Params pf = {};
+    la::VoteMarginsParams& p = pf.m;
+    p.q = a->q; p.k = a->k; p.read_list = a->read_list; p.margins = a->margins;
+    p.q_bs = a->q_batch_stride; p.q_rs = a->q_row_stride; p.q_hs = a->q_head_stride;
+    p.k_bs = a->k_batch_stride; p.k_rs = a->k_row_stride; p.k_hs = a->k_head_stride;
+    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
+    p.heads_per_k = a->num_heads / a->num_heads_k;
+    p.q_tiles = static_cast<int>(q_tiles); p.k_tiles = static_cast<int>(k_tiles); p.block_m = ts.block_m;
+    p.list_int16 = int16 ? 1 : 0;
+    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);
+    pf.q_descale = a->q_descale; pf.qd_bs = a->q_descale_batch_stride; pf.qd_hs = a->q_descale_head_stride;
+    pf.k_descale = a->k_descale; pf.kd_bs = a->k_descale_batch_stride; pf.kd_hs = a->k_descale_head_stride;
+    if (!la::launch_vote_margins_fp8) return LA_ERR_UNSUPPORTED;
+    return launch_status(la::launch_vote_margins_fp8(pf, a->head_dim, static_cast<hipStream_t>(stream_)));
+}
+
+}  // extern "C"

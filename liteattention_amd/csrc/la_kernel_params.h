@@ -281,4 +281,19 @@ inline size_t vote_margins_lds_bytes(int head_dim, int k_tiles) {
 }
 hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream);      // dtype: 0 bf16, 1 fp16
 
+// la_vote_margins_fp8 (la_vote_margins_fp8.hip): the same block for e4m3 q and k (strides in elements = bytes; block_m is the e4m3
+// forward's q-tile), and the descales the e4m3 forward folds into its score scale, per (batch, K/V head), NULL = 1.0.
+struct VoteMarginsFp8Params {
+    VoteMarginsParams m;
+    const float* q_descale;
+    const float* k_descale;
+    int64_t qd_bs, qd_hs, kd_bs, kd_hs;      // elements
+};
+// ... with two stages of 64 keys at a pitch of 64 ceil(D / 64) + 16 bytes; the rest as above, held against the same limit.
+inline size_t vote_margins_fp8_lds_bytes(int head_dim, int k_tiles) {
+    const size_t seq_cap = (static_cast<size_t>(k_tiles) + 3) & ~static_cast<size_t>(3), words = (static_cast<size_t>(k_tiles) + 31) / 32;
+    return 2 * 64 * ((static_cast<size_t>(head_dim) + 63) / 64 * 64 + 16) + 64 + 4 * seq_cap + 8 * words;
+}
+hipError_t launch_vote_margins_fp8(const VoteMarginsFp8Params& p, int head_dim, hipStream_t stream);
+
 }  // namespace la

@@ -27,28 +27,13 @@
 
 #include <cmath>
 
-#include "la_fwd_common.h"
+#include "la_vote_margins_common.h"
 
 namespace la {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kBN = 64;           // keys per tile (la_tiles.h: every 16-bit geometry)
-
-// One step of a maximum over lanes on the DPP datapath: lanes without a source keep their own value.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_max(float v) {
-    const int x = __float_as_int(v);
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(x, x, CTRL, ROW_MASK, 0xf, false)));
-}
-// Maximum over lanes 0 .. 31, valid in lane 31 (four row_shr steps scan each row of 16, row_bcast:15 carries row 0 into row 1).
-__device__ __forceinline__ float max_into_lane31(float v) {
-    v = dpp_max<0x111, 0xf>(v);
-    v = dpp_max<0x112, 0xf>(v);
-    v = dpp_max<0x114, 0xf>(v);
-    v = dpp_max<0x118, 0xf>(v);
-    return dpp_max<0x142, 0xa>(v);
-}
 
 template <bool F16, int D, int NQ>
 __global__ __launch_bounds__(kThreads, 2) void la_vote_margins_kernel(const VoteMarginsParams p) {
@@ -63,12 +48,10 @@ __global__ __launch_bounds__(kThreads, 2) void la_vote_margins_kernel(const Vote
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const ring = smem;
-    float* const part = reinterpret_cast<float*>(smem + 2 * STAGE);          // [2][4] part maxima, by tile parity
-    int* const n_tiles_slot = reinterpret_cast<int*>(part + 8);
-    int* const seq = reinterpret_cast<int*>(smem + 2 * STAGE + 64);
-    const int k_tiles = p.k_tiles, words = (k_tiles + 31) >> 5;
-    unsigned* const endflags = reinterpret_cast<unsigned*>(seq + ((k_tiles + 3) & ~3));
-    unsigned* const walked = endflags + words;
+    const int k_tiles = p.k_tiles;
+    const VoteWalk w = vote_walk_at(smem + 2 * STAGE, k_tiles);               // part maxima, tile count, walk, two bitmaps
+    float* const part = w.part;
+    int* const seq = w.seq;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int vid = xcd_work_id<64>();               // consecutive q-tiles of a head share an XCD's L2: they walk the same K
@@ -79,17 +62,7 @@ __global__ __launch_bounds__(kThreads, 2) void la_vote_margins_kernel(const Vote
     const u32x4 zero = {0u, 0u, 0u, 0u};
 
     // ---- the walk: seq[0 .. n_tiles), and the bitmap of the tiles that get a margin
-    for (int i = tid; i < 2 * words; i += kThreads) endflags[i] = 0u;          // endflags and walked are adjacent
-    __syncthreads();
-    if (p.read_list == nullptr) {
-        for (int i = tid; i < k_tiles; i += kThreads) seq[i] = k_tiles - 1 - i;
-        if (tid == 0) *n_tiles_slot = k_tiles;
-    } else if (wave == 0) {
-        const int64_t row = (static_cast<int64_t>(bh) * p.q_tiles + m_block) * (k_tiles + 1);
-        int n = 0;
-        LA_WITH_LIST_TYPE(p.list_int16, n = expand_read_list(static_cast<const ListT*>(p.read_list) + row, seq, endflags, k_tiles, lane));
-        if (lane == 0) *n_tiles_slot = n;
-    }
+    vote_walk_build<kThreads>(w, p.read_list, p.list_int16, static_cast<int64_t>(bh) * p.q_tiles + m_block, k_tiles, tid);
 
     // ---- Q: the wave's rows, once. Rows at or past Sq are zero rows and vote (the forward's convention).
     X8 qf[NQ][KS];
@@ -104,11 +77,7 @@ __global__ __launch_bounds__(kThreads, 2) void la_vote_margins_kernel(const Vote
         }
     }
     __syncthreads();
-    const int n_tiles = *n_tiles_slot;
-    for (int i = 1 + tid; i < n_tiles; i += kThreads) atomicOr(&walked[seq[i] >> 5], 1u << (seq[i] & 31));
-    __syncthreads();
-    for (int n = tid; n < k_tiles; n += kThreads)
-        if (!((walked[n >> 5] >> (n & 31)) & 1u)) out[n] = __builtin_nanf("");
+    const int n_tiles = vote_walk_finish<kThreads>(w, out, k_tiles, tid);
 
     // ---- K tiles: global -> registers -> LDS stage
     u32x4 kr[CH];

@@ -468,10 +468,12 @@ class LiteAttention:
         listed = skip_list_stats_heads(rl, batch)
         return 1.0 - listed.to(torch.float32) / float(rl.shape[2] * (rl.shape[3] - 1))
 
-    def vote_margins(self, query: Tensor, key: Tensor, scale: Optional[float] = None) -> Tensor:
+    def vote_margins(self, query: Tensor, key: Tensor, scale: Optional[float] = None, *, q_descale: Optional[Tensor] = None,
+                     k_descale: Optional[Tensor] = None) -> Tensor:
         """The margins of the skip vote (``calibration.vote_margins``: fp32 ``(B, H, Qt, Kt)``) for the call that would come next on
         these operands: over the list that call reads, in its tile geometry and list element type - the dense walk when skipping is
         off, before the first call or when the shapes differ from the lists' (that call would start from "all tiles listed").
+        ``q_descale`` / ``k_descale``: the fp32 ``(B, Hk)`` descales of ``float8_e4m3fn`` operands, as the forward call takes them.
         Reads the skip state and changes none of it: no list is written, no phase flipped, no step counted."""
         from .calibration import vote_margins
         read_list = None
@@ -482,7 +484,8 @@ class LiteAttention:
             if query.shape[0] > read_list.shape[0]:        # sequences not tracked yet start from "all tiles listed"
                 fresh = self._init_skip_list(query, key, batch=query.shape[0] - read_list.shape[0])[0]
                 read_list = torch.cat([read_list, fresh])
-        return vote_margins(query, key, scale, read_list)
+        descales = {name: d for name, d in (("q_descale", q_descale), ("k_descale", k_descale)) if d is not None}
+        return vote_margins(query, key, scale, read_list, **descales)
 
     def snapshot(self) -> dict:
         """Both ping-pong lists, the phase and the step counter, copied ON THE DEVICE (no host round trip, no sync: ``state_dict()``
