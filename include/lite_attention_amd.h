@@ -429,8 +429,7 @@ int la_vote_margins(const la_vote_margins_args* args, void* stream);
  * LA_ERR_NULL_ARG; a non-positive size or H % Hk != 0 LA_ERR_SHAPE; a head_dim without an e4m3 tile LA_ERR_HEAD_DIM; a negative
  * stride, a q / k pointer or used stride that takes a row start off a 16-byte boundary, margins or a descale pointer off 4 bytes,
  * read_list off its element size LA_ERR_STRIDE; LA_FLAG_LIST_INT16 with Kt + 1 > 32767, or more key tiles than the walk storage of a
- * workgroup holds (4 bytes per tile beside the K ring in 160 KiB of LDS) LA_ERR_SEQLEN; more than 2^31 - 1 workgroups LA_ERR_SHAPE; a
- * library linked without the kernel LA_ERR_UNSUPPORTED. */
+ * workgroup holds (4 bytes per tile beside the K ring in 160 KiB of LDS) LA_ERR_SEQLEN; more than 2^31 - 1 workgroups LA_ERR_SHAPE. */
 typedef struct la_vote_margins_fp8_args {
     uint32_t struct_size;        /* = sizeof(la_vote_margins_fp8_args)                            */
     uint32_t flags;              /* LA_FLAG_LIST_INT16; other bits ignored                        */

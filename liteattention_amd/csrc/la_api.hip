@@ -609,26 +609,25 @@ static int qk_prep_e4m3_check_and_fill(const A* a, const la_row_map* map, const 
     return LA_OK;
 }
 
-// The three passes, each behind its unmapped entry point (mapped false, map NULL), its _rows one (mapped true: a map is required; it is
-// checked for presence with the arguments and for its size behind theirs, its fields inside the shared checker) and its _rot one
-// (rotated true: a la_head_rotation is required and checked the same way, behind the map; the map is there when it is given).
-// The rotating launcher is a weak reference HERE only: a host-only link of this file against stand-ins for the older launchers
-// (tests/cabi_launches) stays complete without one for it; a link that lacks la_prep_qk_rot.hip answers LA_ERR_UNSUPPORTED.
-namespace la {
-hipError_t launch_qk_prep_rot(const QkPrepParams& p, const QkPrepRot& rot, int in_dtype, int out_dtype, int mode, hipStream_t stream)
-    __attribute__((weak));
+// The head of every entry point below: its argument struct A, a la_row_map where one is required (mapped) and a la_head_rotation where
+// one is required (rotated) are checked for presence together, then for their sizes together; their fields inside the checkers.
+template <class A>
+static int args_status(const A* a, bool mapped = false, const la_row_map* map = nullptr, bool rotated = false, const la_head_rotation* rot = nullptr) {
+    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
+    if (a->struct_size != sizeof(A) || (mapped && map->struct_size != sizeof(la_row_map)) ||
+        (rotated && rot->struct_size != sizeof(la_head_rotation))) return LA_ERR_STRUCT_SIZE;
+    return LA_OK;
 }
+
+// The three passes, each behind its unmapped entry point (mapped false, map NULL), its _rows one (mapped true: a map is required) and
+// its _rot one (rotated true: a la_head_rotation is required; the map is there when it is given).
 static int launch_prep(const la::QkPrepParams& p, const la::QkPrepRot& pr, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
-    if (pr.log2_lanes == 0) return launch_status(la::launch_qk_prep(p, in_dtype, out_dtype, mode, stream));
-    if (!la::launch_qk_prep_rot) return LA_ERR_UNSUPPORTED;
-    return launch_status(la::launch_qk_prep_rot(p, pr, in_dtype, out_dtype, mode, stream));
+    return launch_status(pr.log2_lanes == 0 ? la::launch_qk_prep(p, in_dtype, out_dtype, mode, stream)
+                                            : la::launch_qk_prep_rot(p, pr, in_dtype, out_dtype, mode, stream));
 }
-static bool row_map_size_ok(bool mapped, const la_row_map* map) { return !mapped || map->struct_size == sizeof(la_row_map); }
-static bool head_rot_size_ok(bool rotated, const la_head_rotation* rot) { return !rotated || rot->struct_size == sizeof(la_head_rotation); }
 
 static int qk_prep_run(const la_qk_prep_args* a, bool mapped, const la_row_map* map, bool rotated, const la_head_rotation* rot, void* stream_) {
-    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_args) || !row_map_size_ok(mapped, map) || !head_rot_size_ok(rotated, rot)) return LA_ERR_STRUCT_SIZE;
+    if (const int rc = args_status(a, mapped, map, rotated, rot); rc != LA_OK) return rc;
     if (!a->x || !a->out) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype) || (a->out_dtype != LA_DTYPE_BF16 && a->out_dtype != LA_DTYPE_FP16)) return LA_ERR_DTYPE;
     la::QkPrepParams p;
@@ -639,8 +638,7 @@ static int qk_prep_run(const la_qk_prep_args* a, bool mapped, const la_row_map* 
 }
 
 static int qk_prep_fp8_run(const la_qk_prep_fp8_args* a, bool mapped, const la_row_map* map, bool rotated, const la_head_rotation* rot, void* stream_) {
-    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_fp8_args) || !row_map_size_ok(mapped, map) || !head_rot_size_ok(rotated, rot)) return LA_ERR_STRUCT_SIZE;
+    if (const int rc = args_status(a, mapped, map, rotated, rot); rc != LA_OK) return rc;
     if (!a->x || (!a->out && !a->amax)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (!qk_prep_scale_groups_ok(a)) return LA_ERR_SHAPE;
@@ -653,8 +651,7 @@ static int qk_prep_fp8_run(const la_qk_prep_fp8_args* a, bool mapped, const la_r
 }
 
 static int qk_prep_smooth_run(const la_qk_prep_smooth_args* a, bool mapped, const la_row_map* map, bool rotated, const la_head_rotation* rot, void* stream_) {
-    if (!a || (mapped && !map) || (rotated && !rot)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_qk_prep_smooth_args) || !row_map_size_ok(mapped, map) || !head_rot_size_ok(rotated, rot)) return LA_ERR_STRUCT_SIZE;
+    if (const int rc = args_status(a, mapped, map, rotated, rot); rc != LA_OK) return rc;
     if (!a->x || (!a->out && !a->amax && !a->colsum_part && !a->dot_out)) return LA_ERR_NULL_ARG;
     if ((a->dot_out != nullptr) != (a->dot_vec != nullptr)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
@@ -735,23 +732,22 @@ int la_colsum_finish(const float* part, int32_t n_parts, int32_t batch, int32_t 
 // la_attn_unshift_fp8_rows), in the three places their order of checks has, each beside the unmapped rules of its kind: presence (with the
 // pointers), src_seqlen (with the sizes), the table's alignment and batch stride (behind the strides of the tensors). args->seqlen
 // counts the table's entries, src_seqlen the rows of the tensor that is read: its row stride is a used stride when src_seqlen > 1.
-// The launchers of the mapped kernels are weak references, as the rotating prologue's above and for its reason.
-namespace la {
-hipError_t launch_v_prep_tiles_rows(const VPrepTilesParams& p, const RowGather& g, int in_dtype, hipStream_t stream) __attribute__((weak));
-hipError_t launch_v_colstats_rows(const VColstatsParams& p, const RowGather& g, int in_dtype, hipStream_t stream) __attribute__((weak));
-hipError_t launch_attn_unshift_rows(const AttnUnshiftParams& p, const RowGather& g, int o_dtype, int out_dtype, hipStream_t stream)
-    __attribute__((weak));
-}
-static bool vo_map_present(bool mapped, const la_row_map* map) { return !mapped || (map->src_rows != nullptr); }
+// Behind args_status a map is there exactly when the entry point is a _rows one.
+static bool vo_map_present(const la_row_map* map) { return !map || map->src_rows != nullptr; }
 static bool vo_map_strides_ok(const la_row_map* map) {
     return !map || (map->batch_stride >= 0 && (reinterpret_cast<uintptr_t>(map->src_rows) & 3u) == 0);
 }
-static la::RowGather vo_gather(const la_row_map* map) { return la::RowGather{map->src_rows, map->batch_stride, map->src_seqlen}; }
+// The tail of the four passes: the launcher of the unmapped kernels, else that of the mapped ones with the map as their RowGather
+template <class P, class... T>
+static int launch_vo(const la_row_map* map, hipError_t (*plain)(const P&, T...), hipError_t (*rows)(const P&, const la::RowGather&, T...),
+                     const P& p, T... t) {
+    if (!map) return launch_status(plain(p, t...));
+    return launch_status(rows(p, la::RowGather{map->src_rows, map->batch_stride, map->src_seqlen}, t...));
+}
 
 static int v_colstats_run(const la_v_colstats_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_v_colstats_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
-    if (!a->x || !a->stat_part || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
+    if (const int rc = args_status(a, mapped, map); rc != LA_OK) return rc;
+    if (!a->x || !a->stat_part || !vo_map_present(map)) return LA_ERR_NULL_ARG;
     if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
     if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
     if (a->head_dim % 8 != 0 || a->head_dim > 256) return LA_ERR_HEAD_DIM;
@@ -766,9 +762,147 @@ static int v_colstats_run(const la_v_colstats_args* a, bool mapped, const la_row
     p.part_rows = la::v_colstats_part_rows(a->seqlen, a->num_heads, a->head_dim);
     // one thread per (part, batch, head, chunk of 8 columns), 256 per workgroup
     if (static_cast<int64_t>(p.n_parts) * a->batch * a->num_heads * (a->head_dim / 8) > 0x7fffffffLL * 256) return LA_ERR_SHAPE;
-    if (!map) return launch_status(la::launch_v_colstats(p, a->in_dtype, static_cast<hipStream_t>(stream_)));
-    if (!la::launch_v_colstats_rows) return LA_ERR_UNSUPPORTED;
-    return launch_status(la::launch_v_colstats_rows(p, vo_gather(map), a->in_dtype, static_cast<hipStream_t>(stream_)));
+    return launch_vo(map, la::launch_v_colstats, la::launch_v_colstats_rows, p, a->in_dtype, static_cast<hipStream_t>(stream_));
+}
+
+// What la_attn_unshift and la_attn_unshift_fp8 check alike behind args_status, and the kernel parameters they share. A: either argument
+// struct (the same field names). out_dtype: la_dtype of out. map: the la_row_map of a _rows entry point, NULL for the unmapped ones: o,
+// lse and lse_dot then have map->src_seqlen rows, out, lse_out and row_descale args->seqlen, and nothing may be written over what is
+// read. The rules only one of the two has come as `own`, each answered beside the shared rules of its code.
+struct UnshiftOwnRules {
+    bool ptrs_ok;        // with the pointers (LA_ERR_NULL_ARG)
+    bool dtype_ok;       // with o_dtype (LA_ERR_DTYPE)
+    bool shapes_ok;      // with the sizes and heads_per_vec (LA_ERR_SHAPE)
+    bool strides_ok;     // with the strides and alignments (LA_ERR_STRIDE)
+    bool in_place;       // out may be o (without a map: a gather in place is not defined)
+};
+template <class A>
+static int attn_unshift_check_and_fill(const A* a, int32_t out_dtype, const la_row_map* map, const UnshiftOwnRules& own, la::AttnUnshiftParams& p) {
+    if (!a->o || !a->out || !own.ptrs_ok || !vo_map_present(map)) return LA_ERR_NULL_ARG;
+    // (under a map lse_out may come without lse_dot: the LSE at the rows)
+    if ((a->lse_dot && !a->lse_out) || (a->lse_out && !a->lse_dot && !map) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
+    if ((a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) || !own.dtype_ok) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
+    if ((a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) || !own.shapes_ok) return LA_ERR_SHAPE;
+    if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
+    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
+                      a->num_heads) ||
+        !rows_aligned(a->out, out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen, a->num_heads))
+        return LA_ERR_STRIDE;
+    if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
+                            a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
+    if (((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out)) & 3u) ||
+        !own.strides_ok || !vo_map_strides_ok(map)) return LA_ERR_STRIDE;
+    // a gather in place is not defined (rows would be read after they were overwritten), and nothing here has a position
+    if ((a->out == a->o && (map || !own.in_place)) || (map && ((a->lse_out && a->lse_out == a->lse) || map->positions))) return LA_ERR_UNSUPPORTED;
+    p = {};
+    p.o = a->o; p.out = a->out; p.shift = a->shift; p.lse = a->lse; p.lse_dot = a->lse_dot; p.lse_out = a->lse_out;
+    p.o_bs = a->o_batch_stride; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
+    p.out_bs = a->out_batch_stride; p.out_rs = a->out_row_stride; p.out_hs = a->out_head_stride;
+    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
+    p.softmax_scale = a->softmax_scale;
+    return LA_OK;
+}
+
+static int attn_unshift_run(const la_attn_unshift_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (const int rc = args_status(a, mapped, map); rc != LA_OK) return rc;
+    la::AttnUnshiftParams p;
+    const UnshiftOwnRules own = {true, is_input_dtype(a->out_dtype), true, true, true};
+    if (const int rc = attn_unshift_check_and_fill(a, a->out_dtype, map, own, p); rc != LA_OK) return rc;
+    return launch_vo(map, la::launch_attn_unshift, la::launch_attn_unshift_rows, p, a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_));
+}
+
+static int attn_unshift_fp8_run(const la_attn_unshift_fp8_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (const int rc = args_status(a, mapped, map); rc != LA_OK) return rc;
+    la::AttnUnshiftParams p;
+    UnshiftOwnRules own;
+    own.ptrs_ok = a->descale_in || a->row_descale;
+    own.dtype_ok = true;
+    own.shapes_ok = a->heads_per_scale >= 1 && a->num_heads % a->heads_per_scale == 0;
+    own.strides_ok = ((reinterpret_cast<uintptr_t>(a->row_descale) | reinterpret_cast<uintptr_t>(a->descale_in) | reinterpret_cast<uintptr_t>(a->amax)) & 3u) == 0 &&
+                     a->row_descale_batch_stride >= 0 && a->row_descale_row_stride >= 0 && a->row_descale_group_stride >= 0 &&
+                     a->descale_in_batch_stride >= 0 && a->amax_batch_stride >= 0;
+    own.in_place = false;            // one byte for two: a chunk's bytes lie over another chunk's elements
+    const int32_t out_dtype = LA_DTYPE_FP8_E4M3;
+    if (const int rc = attn_unshift_check_and_fill(a, out_dtype, map, own, p); rc != LA_OK) return rc;
+    // a wave keeps a scale group in registers; a workgroup the empty-row flags of every head of its rows in LDS
+    if (static_cast<int64_t>(a->heads_per_scale) * a->head_dim > la::kAttnOutFp8MaxGroup || a->num_heads > la::kAttnOutFp8MaxHeads)
+        return LA_ERR_UNSUPPORTED;
+    // one workgroup per tile of rows of a batch
+    if (static_cast<int64_t>(a->batch) * ((static_cast<int64_t>(a->seqlen) + la::kAttnOutFp8Rows - 1) / la::kAttnOutFp8Rows) > 0x7fffffffLL)
+        return LA_ERR_SHAPE;
+    p.heads_per_scale = a->heads_per_scale;
+    if (a->descale_in) {                                             // static: the batch's scale, an optional running maximum
+        p.descale_in = a->descale_in; p.di_bs = a->descale_in_batch_stride;
+        p.amax = a->amax; p.am_bs = a->amax_batch_stride;
+    } else {                                                         // dynamic: a scale per (token, group), written
+        p.row_descale = a->row_descale;
+        p.rd_bs = a->row_descale_batch_stride; p.rd_rs = a->row_descale_row_stride; p.rd_gs = a->row_descale_group_stride;
+    }
+    return launch_vo(map, la::launch_attn_unshift, la::launch_attn_unshift_rows, p, a->o_dtype, out_dtype, static_cast<hipStream_t>(stream_));
+}
+
+// behind la_v_prep_tiles (mapped false, map NULL) and la_v_prep_tiles_rows: x then has map->src_seqlen rows, the tiles args->seqlen keys
+static int v_prep_tiles_run(const la_v_prep_tiles_args* a, bool mapped, const la_row_map* map, void* stream_) {
+    if (const int rc = args_status(a, mapped, map); rc != LA_OK) return rc;
+    if (!a->x || !a->tiles || !vo_map_present(map)) return LA_ERR_NULL_ARG;
+    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
+    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
+    if (la::tile_shape(a->head_dim, 1).block_m == 0) return LA_ERR_HEAD_DIM;     // the head dims the e4m3 forward has
+    if (a->reserved0 != 0 || (map && map->positions)) return LA_ERR_UNSUPPORTED;
+    if (!vo_map_strides_ok(map) ||
+        !rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
+                      a->num_heads) ||
+        (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1, a->num_heads)) ||
+        !aligned16(a->tiles) || a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 ||
+        a->amax_head_stride < 0 || ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u))
+        return LA_ERR_STRIDE;
+    la::VPrepTilesParams p = {};
+    p.k_tiles = (a->seqlen + 63) / 64;
+    if (static_cast<int64_t>(a->batch) * a->num_heads * p.k_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;      // one workgroup per tile
+    p.x = a->x; p.tiles = static_cast<uint8_t*>(a->tiles); p.descale = a->descale; p.shift = a->shift; p.amax = a->amax;
+    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
+    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
+    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
+    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
+    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
+    return launch_vo(map, la::launch_v_prep_tiles, la::launch_v_prep_tiles_rows, p, a->in_dtype, static_cast<hipStream_t>(stream_));
+}
+
+// What la_vote_margins (la_vote_margins.hip) and la_vote_margins_fp8 (la_vote_margins_fp8.hip) check alike behind args_status, and the
+// parameter block they share. A: either argument struct (the same field names). ts: the q-tile of the lists la_fwd reads and writes for
+// these operands, and tile_rc what its lookup answered (behind the sizes, as the lookups were); unit: elements of 16 bytes - every row
+// of q and k starts on a 16-byte boundary; lds_bytes: the LDS of a workgroup for (head_dim, k_tiles); own_strides_ok: the strides and
+// alignments only one of the two has.
+template <class A>
+static int vote_margins_check_and_fill(const A* a, int tile_rc, la::TileShape ts, int64_t unit, size_t (*lds_bytes)(int, int), bool own_strides_ok,
+                                       la::VoteMarginsParams& p) {
+    if (!a->q || !a->k || !a->margins) return LA_ERR_NULL_ARG;
+    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->head_dim <= 0 ||
+        a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;
+    if (tile_rc != LA_OK) return tile_rc;
+    const bool int16 = (a->flags & LA_FLAG_LIST_INT16) != 0;
+    if (!rows_aligned(a->q, 16u, unit, a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->batch, a->seqlen_q, a->num_heads) ||
+        !rows_aligned(a->k, 16u, unit, a->k_batch_stride, a->k_row_stride, a->k_head_stride, a->batch, a->seqlen_k, a->num_heads_k) ||
+        (reinterpret_cast<uintptr_t>(a->margins) & 3u) || (reinterpret_cast<uintptr_t>(a->read_list) & (int16 ? 1u : 3u)) || !own_strides_ok)
+        return LA_ERR_STRIDE;
+    const int64_t q_tiles = (static_cast<int64_t>(a->seqlen_q) + ts.block_m - 1) / ts.block_m;
+    const int64_t k_tiles = (static_cast<int64_t>(a->seqlen_k) + ts.block_n - 1) / ts.block_n;
+    if (int16 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
+    if (lds_bytes(a->head_dim, static_cast<int>(k_tiles)) > la::kVoteMarginsLdsLimit) return LA_ERR_SEQLEN;   // the walk lives in LDS
+    if (static_cast<int64_t>(a->batch) * a->num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per q-tile
+    p = {};
+    p.q = a->q; p.k = a->k; p.read_list = a->read_list; p.margins = a->margins;
+    p.q_bs = a->q_batch_stride; p.q_rs = a->q_row_stride; p.q_hs = a->q_head_stride;
+    p.k_bs = a->k_batch_stride; p.k_rs = a->k_row_stride; p.k_hs = a->k_head_stride;
+    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
+    p.heads_per_k = a->num_heads / a->num_heads_k;
+    p.q_tiles = static_cast<int>(q_tiles); p.k_tiles = static_cast<int>(k_tiles); p.block_m = ts.block_m;
+    p.list_int16 = int16 ? 1 : 0;
+    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);
+    return LA_OK;
 }
 
 extern "C" {
@@ -803,95 +937,8 @@ int la_v_colstats_finish(const float* part, int32_t n_parts, int32_t batch, int3
     return launch_status(err);
 }
 
-// la_attn_unshift and la_attn_unshift_fp8 behind their unmapped entry points (mapped false, map NULL) and their _rows ones: o, lse and
-// lse_dot then have map->src_seqlen rows, out, lse_out and row_descale args->seqlen, and nothing may be written over what is read
-static int attn_unshift_run(const la_attn_unshift_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_attn_unshift_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
-    if (!a->o || !a->out || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
-    // (under a map lse_out may come without lse_dot: the LSE at the rows)
-    if ((a->lse_dot && !a->lse_out) || (a->lse_out && !a->lse_dot && !map) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
-    if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
-    if (!is_input_dtype(a->out_dtype)) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
-    if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
-    if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
-                      a->num_heads) ||
-        !rows_aligned(a->out, a->out_dtype, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen, a->num_heads))
-        return LA_ERR_STRIDE;
-    if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
-                            a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
-    if ((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out)) & 3u)
-        return LA_ERR_STRIDE;
-    if (!vo_map_strides_ok(map)) return LA_ERR_STRIDE;
-    // a gather in place is not defined (rows would be read after they were overwritten), and nothing here has a position
-    if (map && (a->out == a->o || (a->lse_out && a->lse_out == a->lse) || map->positions)) return LA_ERR_UNSUPPORTED;
-    la::AttnUnshiftParams p = {};
-    p.o = a->o; p.out = a->out; p.shift = a->shift; p.lse = a->lse; p.lse_dot = a->lse_dot; p.lse_out = a->lse_out;
-    p.o_bs = a->o_batch_stride; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
-    p.out_bs = a->out_batch_stride; p.out_rs = a->out_row_stride; p.out_hs = a->out_head_stride;
-    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
-    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
-    p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
-    p.softmax_scale = a->softmax_scale;
-    if (!map) return launch_status(la::launch_attn_unshift(p, a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_)));
-    if (!la::launch_attn_unshift_rows) return LA_ERR_UNSUPPORTED;
-    return launch_status(la::launch_attn_unshift_rows(p, vo_gather(map), a->o_dtype, a->out_dtype, static_cast<hipStream_t>(stream_)));
-}
 int la_attn_unshift(const la_attn_unshift_args* a, void* stream) { return attn_unshift_run(a, false, nullptr, stream); }
 int la_attn_unshift_rows(const la_attn_unshift_args* a, const la_row_map* map, void* stream) { return attn_unshift_run(a, true, map, stream); }
-
-static int attn_unshift_fp8_run(const la_attn_unshift_fp8_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_attn_unshift_fp8_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
-    if (!a->o || !a->out || (!a->descale_in && !a->row_descale) || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
-    // (under a map lse_out may come without lse_dot: the LSE at the rows)
-    if ((a->lse_dot && !a->lse_out) || (a->lse_out && !a->lse_dot && !map) || (a->lse_out && !a->lse)) return LA_ERR_NULL_ARG;
-    if (a->o_dtype != LA_DTYPE_BF16 && a->o_dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
-    if (a->shift && (a->heads_per_vec < 1 || a->num_heads % a->heads_per_vec != 0)) return LA_ERR_SHAPE;
-    if (a->heads_per_scale < 1 || a->num_heads % a->heads_per_scale != 0) return LA_ERR_SHAPE;
-    if (a->head_dim % 8 != 0) return LA_ERR_HEAD_DIM;
-    if (!rows_aligned(a->o, a->o_dtype, a->o_batch_stride, a->o_row_stride, a->o_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
-                      a->num_heads) ||
-        !rows_aligned(a->out, LA_DTYPE_FP8_E4M3, a->out_batch_stride, a->out_row_stride, a->out_head_stride, a->batch, a->seqlen,
-                      a->num_heads)) return LA_ERR_STRIDE;
-    if (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1,
-                            a->num_heads / a->heads_per_vec)) return LA_ERR_STRIDE;
-    if ((reinterpret_cast<uintptr_t>(a->lse) | reinterpret_cast<uintptr_t>(a->lse_dot) | reinterpret_cast<uintptr_t>(a->lse_out) |
-         reinterpret_cast<uintptr_t>(a->row_descale) | reinterpret_cast<uintptr_t>(a->descale_in) | reinterpret_cast<uintptr_t>(a->amax)) & 3u)
-        return LA_ERR_STRIDE;
-    if (a->row_descale_batch_stride < 0 || a->row_descale_row_stride < 0 || a->row_descale_group_stride < 0 ||
-        a->descale_in_batch_stride < 0 || a->amax_batch_stride < 0 || !vo_map_strides_ok(map)) return LA_ERR_STRIDE;
-    if (a->out == a->o) return LA_ERR_UNSUPPORTED;                   // one byte for two: a chunk's bytes lie over another chunk's elements
-    if (map && ((a->lse_out && a->lse_out == a->lse) || map->positions)) return LA_ERR_UNSUPPORTED;      // as la_attn_unshift_rows
-    // a wave keeps a scale group in registers; a workgroup the empty-row flags of every head of its rows in LDS
-    if (static_cast<int64_t>(a->heads_per_scale) * a->head_dim > la::kAttnOutFp8MaxGroup || a->num_heads > la::kAttnOutFp8MaxHeads)
-        return LA_ERR_UNSUPPORTED;
-    // one workgroup per tile of rows of a batch
-    if (static_cast<int64_t>(a->batch) * ((static_cast<int64_t>(a->seqlen) + la::kAttnOutFp8Rows - 1) / la::kAttnOutFp8Rows) > 0x7fffffffLL)
-        return LA_ERR_SHAPE;
-    la::AttnUnshiftParams p = {};
-    p.o = a->o; p.out = a->out; p.shift = a->shift; p.lse = a->lse; p.lse_dot = a->lse_dot; p.lse_out = a->lse_out;
-    p.o_bs = a->o_batch_stride; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
-    p.out_bs = a->out_batch_stride; p.out_rs = a->out_row_stride; p.out_hs = a->out_head_stride;
-    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
-    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
-    p.heads_per_vec = a->shift ? a->heads_per_vec : 1;
-    p.softmax_scale = a->softmax_scale;
-    p.heads_per_scale = a->heads_per_scale;
-    if (a->descale_in) {                                             // static: the batch's scale, an optional running maximum
-        p.descale_in = a->descale_in; p.di_bs = a->descale_in_batch_stride;
-        p.amax = a->amax; p.am_bs = a->amax_batch_stride;
-    } else {                                                         // dynamic: a scale per (token, group), written
-        p.row_descale = a->row_descale;
-        p.rd_bs = a->row_descale_batch_stride; p.rd_rs = a->row_descale_row_stride; p.rd_gs = a->row_descale_group_stride;
-    }
-    if (!map) return launch_status(la::launch_attn_unshift(p, a->o_dtype, LA_DTYPE_FP8_E4M3, static_cast<hipStream_t>(stream_)));
-    if (!la::launch_attn_unshift_rows) return LA_ERR_UNSUPPORTED;
-    return launch_status(la::launch_attn_unshift_rows(p, vo_gather(map), a->o_dtype, LA_DTYPE_FP8_E4M3, static_cast<hipStream_t>(stream_)));
-}
 int la_attn_unshift_fp8(const la_attn_unshift_fp8_args* a, void* stream) { return attn_unshift_fp8_run(a, false, nullptr, stream); }
 int la_attn_unshift_fp8_rows(const la_attn_unshift_fp8_args* a, const la_row_map* map, void* stream) {
     return attn_unshift_fp8_run(a, true, map, stream);
@@ -909,125 +956,37 @@ int64_t la_v_tiles_workspace_bytes(int32_t batch, int32_t num_heads_k, int32_t s
     return tiles < 0 ? tiles : tiles + static_cast<int64_t>(kSchedWorkspaceBytes);      // FwdWorkspace's first two terms: an e4m3 la_fwd that is one launch
 }
 
-// behind la_v_prep_tiles (mapped false, map NULL) and la_v_prep_tiles_rows: x then has map->src_seqlen rows, the tiles args->seqlen keys
-static int v_prep_tiles_run(const la_v_prep_tiles_args* a, bool mapped, const la_row_map* map, void* stream_) {
-    if (!a || (mapped && !map)) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_v_prep_tiles_args) || !row_map_size_ok(mapped, map)) return LA_ERR_STRUCT_SIZE;
-    if (!a->x || !a->tiles || !vo_map_present(mapped, map)) return LA_ERR_NULL_ARG;
-    if (!is_input_dtype(a->in_dtype)) return LA_ERR_DTYPE;
-    if (a->batch <= 0 || a->seqlen <= 0 || a->num_heads <= 0 || a->head_dim <= 0 || (map && map->src_seqlen < 1)) return LA_ERR_SHAPE;
-    if (la::tile_shape(a->head_dim, 1).block_m == 0) return LA_ERR_HEAD_DIM;     // the head dims the e4m3 forward has
-    if (a->reserved0 != 0 || (map && map->positions)) return LA_ERR_UNSUPPORTED;
-    if (!vo_map_strides_ok(map) ||
-        !rows_aligned(a->x, a->in_dtype, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->batch, map ? map->src_seqlen : a->seqlen,
-                      a->num_heads) ||
-        (a->shift && !rows_aligned(a->shift, LA_DTYPE_FP32, a->shift_batch_stride, 0, a->shift_head_stride, a->batch, 1, a->num_heads)) ||
-        !aligned16(a->tiles) || a->descale_batch_stride < 0 || a->descale_head_stride < 0 || a->amax_batch_stride < 0 ||
-        a->amax_head_stride < 0 || ((reinterpret_cast<uintptr_t>(a->descale) | reinterpret_cast<uintptr_t>(a->amax)) & 3u))
-        return LA_ERR_STRIDE;
-    la::VPrepTilesParams p = {};
-    p.k_tiles = (a->seqlen + 63) / 64;
-    if (static_cast<int64_t>(a->batch) * a->num_heads * p.k_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;      // one workgroup per tile
-    p.x = a->x; p.tiles = static_cast<uint8_t*>(a->tiles); p.descale = a->descale; p.shift = a->shift; p.amax = a->amax;
-    p.x_bs = a->x_batch_stride; p.x_rs = a->x_row_stride; p.x_hs = a->x_head_stride;
-    p.ds_bs = a->descale_batch_stride; p.ds_hs = a->descale_head_stride;
-    p.sh_bs = a->shift_batch_stride; p.sh_hs = a->shift_head_stride;
-    p.am_bs = a->amax_batch_stride; p.am_hs = a->amax_head_stride;
-    p.batch = a->batch; p.seqlen = a->seqlen; p.num_heads = a->num_heads; p.head_dim = a->head_dim;
-    if (!map) return launch_status(la::launch_v_prep_tiles(p, a->in_dtype, static_cast<hipStream_t>(stream_)));
-    if (!la::launch_v_prep_tiles_rows) return LA_ERR_UNSUPPORTED;
-    return launch_status(la::launch_v_prep_tiles_rows(p, vo_gather(map), a->in_dtype, static_cast<hipStream_t>(stream_)));
-}
 int la_v_prep_tiles(const la_v_prep_tiles_args* a, void* stream) { return v_prep_tiles_run(a, false, nullptr, stream); }
 int la_v_prep_tiles_rows(const la_v_prep_tiles_args* a, const la_row_map* map, void* stream) { return v_prep_tiles_run(a, true, map, stream); }
 
-}  // extern "C"
-
-// la_vote_margins: the margins of the skip vote in one pass over Q K^T (la_vote_margins.hip). The launcher is a weak reference, as the
-// rotating prologue's is: a host-only link of this file without la_vote_margins.hip stays complete and answers LA_ERR_UNSUPPORTED.
-namespace la {
-hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream) __attribute__((weak));
-}
-
-extern "C" {
-
+// ---- the margins of the skip vote in one pass over Q K^T ---------------------------------------------------------------------------
 int la_vote_margins(const la_vote_margins_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_vote_margins_args)) return LA_ERR_STRUCT_SIZE;
+    if (const int rc = args_status(a); rc != LA_OK) return rc;
     if (a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
-    if (!a->q || !a->k || !a->margins) return LA_ERR_NULL_ARG;
-    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->head_dim <= 0 ||
-        a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;
     // the q-tile of the lists la_fwd reads and writes under the same flags: one table (la_tiles.h), the other flags of la_fwd are not read
-    const uint32_t flags = a->flags & (LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16);
-    int bm = 0, bn = 0;
-    if (const int rc = la_get_tile_sizes_ex(a->head_dim, 2, flags, &bm, &bn); rc != LA_OK) return rc;
-    if (!rows_aligned(a->q, a->dtype, a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->batch, a->seqlen_q, a->num_heads) ||
-        !rows_aligned(a->k, a->dtype, a->k_batch_stride, a->k_row_stride, a->k_head_stride, a->batch, a->seqlen_k, a->num_heads_k) ||
-        (reinterpret_cast<uintptr_t>(a->margins) & 3u) ||
-        (reinterpret_cast<uintptr_t>(a->read_list) & ((flags & LA_FLAG_LIST_INT16) ? 1u : 3u))) return LA_ERR_STRIDE;
-    const int64_t q_tiles = (static_cast<int64_t>(a->seqlen_q) + bm - 1) / bm, k_tiles = (static_cast<int64_t>(a->seqlen_k) + bn - 1) / bn;
-    if ((flags & LA_FLAG_LIST_INT16) && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
-    if (la::vote_margins_lds_bytes(a->head_dim, static_cast<int>(k_tiles)) > la::kVoteMarginsLdsLimit) return LA_ERR_SEQLEN;   // the walk lives in LDS
-    if (static_cast<int64_t>(a->batch) * a->num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per q-tile
-    la::VoteMarginsParams p = {};
-    p.q = a->q; p.k = a->k; p.read_list = a->read_list; p.margins = a->margins;
-    p.q_bs = a->q_batch_stride; p.q_rs = a->q_row_stride; p.q_hs = a->q_head_stride;
-    p.k_bs = a->k_batch_stride; p.k_rs = a->k_row_stride; p.k_hs = a->k_head_stride;
-    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
-    p.heads_per_k = a->num_heads / a->num_heads_k;
-    p.q_tiles = static_cast<int>(q_tiles); p.k_tiles = static_cast<int>(k_tiles); p.block_m = bm;
-    p.list_int16 = (flags & LA_FLAG_LIST_INT16) ? 1 : 0;
-    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);
-    if (!la::launch_vote_margins) return LA_ERR_UNSUPPORTED;
+    la::TileShape ts = {0, 0};
+    const int tile_rc = la_get_tile_sizes_ex(a->head_dim, 2, a->flags & (LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16),
+                                             &ts.block_m, &ts.block_n);
+    la::VoteMarginsParams p;
+    if (const int rc = vote_margins_check_and_fill(a, tile_rc, ts, 8, la::vote_margins_lds_bytes, true, p); rc != LA_OK) return rc;
     return launch_status(la::launch_vote_margins(p, a->dtype, a->head_dim, static_cast<hipStream_t>(stream_)));
 }
 
-}  // extern "C"
-
-// la_vote_margins_fp8: the same map for e4m3 operands (la_vote_margins_fp8.hip); its launcher is a weak reference for the same reason.
-namespace la {
-hipError_t launch_vote_margins_fp8(const VoteMarginsFp8Params& p, int head_dim, hipStream_t stream) __attribute__((weak));
-}
-
-extern "C" {
-
 int la_vote_margins_fp8(const la_vote_margins_fp8_args* a, void* stream_) {
-    if (!a) return LA_ERR_NULL_ARG;
-    if (a->struct_size != sizeof(la_vote_margins_fp8_args)) return LA_ERR_STRUCT_SIZE;
-    if (!a->q || !a->k || !a->margins) return LA_ERR_NULL_ARG;
-    if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->head_dim <= 0 ||
-        a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;
+    if (const int rc = args_status(a); rc != LA_OK) return rc;
     // the q-tile of the lists the e4m3 la_fwd reads and writes: it has one geometry per head dim, the 16-bit geometry flags are not read
     const la::TileShape ts = la::tile_shape(a->head_dim, 1);
-    if (ts.block_m == 0) return LA_ERR_HEAD_DIM;
-    const bool int16 = (a->flags & LA_FLAG_LIST_INT16) != 0;
-    // rows of 1-byte elements are read 16 bytes at a time: every row start on a 16-byte boundary
-    if (!rows_aligned(a->q, 16u, 16, a->q_batch_stride, a->q_row_stride, a->q_head_stride, a->batch, a->seqlen_q, a->num_heads) ||
-        !rows_aligned(a->k, 16u, 16, a->k_batch_stride, a->k_row_stride, a->k_head_stride, a->batch, a->seqlen_k, a->num_heads_k) ||
-        (reinterpret_cast<uintptr_t>(a->margins) & 3u) || (reinterpret_cast<uintptr_t>(a->read_list) & (int16 ? 1u : 3u)) ||
-        ((reinterpret_cast<uintptr_t>(a->q_descale) | reinterpret_cast<uintptr_t>(a->k_descale)) & 3u) ||
-        a->q_descale_batch_stride < 0 || a->q_descale_head_stride < 0 || a->k_descale_batch_stride < 0 || a->k_descale_head_stride < 0)
-        return LA_ERR_STRIDE;
-    const int64_t q_tiles = (static_cast<int64_t>(a->seqlen_q) + ts.block_m - 1) / ts.block_m;
-    const int64_t k_tiles = (static_cast<int64_t>(a->seqlen_k) + ts.block_n - 1) / ts.block_n;
-    if (int16 && k_tiles + 1 > kListInt16MaxRow) return LA_ERR_SEQLEN;
-    if (la::vote_margins_fp8_lds_bytes(a->head_dim, static_cast<int>(k_tiles)) > la::kVoteMarginsLdsLimit) return LA_ERR_SEQLEN;   // the walk lives in LDS
-    if (static_cast<int64_t>(a->batch) * a->num_heads * q_tiles > 0x7fffffffLL) return LA_ERR_SHAPE;       // one workgroup per q-tile
+    const bool descales_ok = ((reinterpret_cast<uintptr_t>(a->q_descale) | reinterpret_cast<uintptr_t>(a->k_descale)) & 3u) == 0 &&
+                             a->q_descale_batch_stride >= 0 && a->q_descale_head_stride >= 0 && a->k_descale_batch_stride >= 0 &&
+                             a->k_descale_head_stride >= 0;
     la::VoteMarginsFp8Params pf = {};
-    la::VoteMarginsParams& p = pf.m;
-    p.q = a->q; p.k = a->k; p.read_list = a->read_list; p.margins = a->margins;
-    p.q_bs = a->q_batch_stride; p.q_rs = a->q_row_stride; p.q_hs = a->q_head_stride;
-    p.k_bs = a->k_batch_stride; p.k_rs = a->k_row_stride; p.k_hs = a->k_head_stride;
-    p.batch = a->batch; p.seqlen_q = a->seqlen_q; p.seqlen_k = a->seqlen_k; p.num_heads = a->num_heads;
-    p.heads_per_k = a->num_heads / a->num_heads_k;
-    p.q_tiles = static_cast<int>(q_tiles); p.k_tiles = static_cast<int>(k_tiles); p.block_m = ts.block_m;
-    p.list_int16 = int16 ? 1 : 0;
-    p.scale_log2 = static_cast<float>(static_cast<double>(a->softmax_scale) * 1.4426950408889634);
+    // rows of 1-byte elements are read 16 bytes at a time: every row start on a 16-byte boundary
+    if (const int rc = vote_margins_check_and_fill(a, ts.block_m == 0 ? LA_ERR_HEAD_DIM : LA_OK, ts, 16, la::vote_margins_fp8_lds_bytes,
+                                                   descales_ok, pf.m); rc != LA_OK) return rc;
     pf.q_descale = a->q_descale; pf.qd_bs = a->q_descale_batch_stride; pf.qd_hs = a->q_descale_head_stride;
     pf.k_descale = a->k_descale; pf.kd_bs = a->k_descale_batch_stride; pf.kd_hs = a->k_descale_head_stride;
-    if (!la::launch_vote_margins_fp8) return LA_ERR_UNSUPPORTED;
     return launch_status(la::launch_vote_margins_fp8(pf, a->head_dim, static_cast<hipStream_t>(stream_)));
 }
 
 }  // extern "C"
+

@@ -61,12 +61,19 @@ std::string val(hipStream_t p) { return val(static_cast<const void*>(p)); }
 #define LA_QKPREP_FIELDS(X) X(x) X(out) X(weight) X(table[0]) X(table[1]) X(table[2]) X(x_bs) X(x_rs) X(x_hs) X(o_bs) X(o_rs) X(o_hs) \
     X(tokens) X(seqlen) X(num_heads) X(head_dim) X(norm_mode) X(rotate) X(ext1) X(ext2) X(pairs[0]) X(pairs[1]) X(pairs[2]) \
     X(pos_offset) X(eps) X(descale) X(amax) X(ds_bs) X(ds_hs) X(am_bs) X(am_hs) X(heads_per_scale) X(shift) X(colsum_part) X(dot_vec) \
-    X(dot_out) X(sh_bs) X(sh_hs) X(dv_bs) X(dv_hs) X(heads_per_dot) X(batch) X(part_rows) X(part_blocks)
+    X(dot_out) X(sh_bs) X(sh_hs) X(dv_bs) X(dv_hs) X(heads_per_dot) X(batch) X(part_rows) X(part_blocks) X(src_rows) X(positions) \
+    X(map_bs) X(src_seqlen) X(pos_limit)
+#define LA_QKROT_FIELDS(X) X(signs) X(log2_lanes) X(scale)
 #define LA_VPREP_FIELDS(X) X(x) X(tiles) X(descale) X(shift) X(amax) X(x_bs) X(x_rs) X(x_hs) X(ds_bs) X(ds_hs) X(sh_bs) X(sh_hs) \
     X(am_bs) X(am_hs) X(batch) X(seqlen) X(num_heads) X(head_dim) X(k_tiles)
 #define LA_VCOL_FIELDS(X) X(x) X(stat_part) X(x_bs) X(x_rs) X(x_hs) X(batch) X(seqlen) X(num_heads) X(head_dim) X(n_parts) X(part_rows)
 #define LA_UNSHIFT_FIELDS(X) X(o) X(out) X(shift) X(lse) X(lse_dot) X(lse_out) X(o_bs) X(o_rs) X(o_hs) X(out_bs) X(out_rs) X(out_hs) \
-    X(sh_bs) X(sh_hs) X(batch) X(seqlen) X(num_heads) X(head_dim) X(heads_per_vec) X(softmax_scale)
+    X(sh_bs) X(sh_hs) X(batch) X(seqlen) X(num_heads) X(head_dim) X(heads_per_vec) X(softmax_scale) X(row_descale) X(descale_in) \
+    X(amax) X(rd_bs) X(rd_rs) X(rd_gs) X(di_bs) X(am_bs) X(heads_per_scale)
+#define LA_GATHER_FIELDS(X) X(rows) X(map_bs) X(src_seqlen)
+#define LA_VOTE_FIELDS(X) X(q) X(k) X(read_list) X(margins) X(q_bs) X(q_rs) X(q_hs) X(k_bs) X(k_rs) X(k_hs) X(batch) X(seqlen_q) X(seqlen_k) \
+    X(num_heads) X(heads_per_k) X(q_tiles) X(k_tiles) X(block_m) X(list_int16) X(scale_log2)
+#define LA_VOTE_FP8_FIELDS(X) X(m) X(q_descale) X(k_descale) X(qd_bs) X(qd_hs) X(kd_bs) X(kd_hs)      // m: the nested VoteMarginsParams, a record of its own
 #define LA_VAL(f) s += val(p.f); s += ',';
 #define LA_NAME(f) #f ","
 #define LA_STRUCT_VAL(T, FIELDS)                                                          \
@@ -82,6 +89,10 @@ LA_STRUCT_VAL(QkPrepParams, LA_QKPREP_FIELDS)
 LA_STRUCT_VAL(VPrepTilesParams, LA_VPREP_FIELDS)
 LA_STRUCT_VAL(VColstatsParams, LA_VCOL_FIELDS)
 LA_STRUCT_VAL(AttnUnshiftParams, LA_UNSHIFT_FIELDS)
+LA_STRUCT_VAL(QkPrepRot, LA_QKROT_FIELDS)
+LA_STRUCT_VAL(RowGather, LA_GATHER_FIELDS)
+LA_STRUCT_VAL(VoteMarginsParams, LA_VOTE_FIELDS)
+LA_STRUCT_VAL(VoteMarginsFp8Params, LA_VOTE_FP8_FIELDS)
 
 template <class... A>
 hipError_t record(const char* name, const char* arg_names, const A&... a) {
@@ -163,6 +174,9 @@ hipError_t launch_output_error(const void* out, int out_dtype, int64_t o_bs, int
 hipError_t launch_qk_prep(const QkPrepParams& p, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
     return REC("launch_qk_prep", p, in_dtype, out_dtype, mode, stream);
 }
+hipError_t launch_qk_prep_rot(const QkPrepParams& p, const QkPrepRot& rot, int in_dtype, int out_dtype, int mode, hipStream_t stream) {
+    return REC("launch_qk_prep_rot", p, rot, in_dtype, out_dtype, mode, stream);
+}
 hipError_t launch_colsum_finish(const float* part, int n_parts, int batch, int num_heads, int head_dim, int seqlen, float* mean, int64_t m_bs,
                                 int64_t m_hs, hipStream_t stream) {
     return REC("launch_colsum_finish", part, n_parts, batch, num_heads, head_dim, seqlen, mean, m_bs, m_hs, stream);
@@ -174,6 +188,21 @@ hipError_t launch_v_colstats_finish(const float* part, int n_parts, int batch, i
 }
 hipError_t launch_attn_unshift(const AttnUnshiftParams& p, int o_dtype, int out_dtype, hipStream_t stream) {
     return REC("launch_attn_unshift", p, o_dtype, out_dtype, stream);
+}
+hipError_t launch_v_prep_tiles_rows(const VPrepTilesParams& p, const RowGather& g, int in_dtype, hipStream_t stream) {
+    return REC("launch_v_prep_tiles_rows", p, g, in_dtype, stream);
+}
+hipError_t launch_v_colstats_rows(const VColstatsParams& p, const RowGather& g, int in_dtype, hipStream_t stream) {
+    return REC("launch_v_colstats_rows", p, g, in_dtype, stream);
+}
+hipError_t launch_attn_unshift_rows(const AttnUnshiftParams& p, const RowGather& g, int o_dtype, int out_dtype, hipStream_t stream) {
+    return REC("launch_attn_unshift_rows", p, g, o_dtype, out_dtype, stream);
+}
+hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream) {
+    return REC("launch_vote_margins", p, dtype, head_dim, stream);
+}
+hipError_t launch_vote_margins_fp8(const VoteMarginsFp8Params& p, int head_dim, hipStream_t stream) {
+    return REC("launch_vote_margins_fp8", p, head_dim, stream);
 }
 }  // namespace la
 extern "C" hipError_t hipMemsetD32Async(hipDeviceptr_t dst, int value, size_t count, hipStream_t stream) {
@@ -625,6 +654,33 @@ template <class A> void scale_fields(A& a) {
     a.descale = fake<float>(0x54000000); a.descale_batch_stride = 2; a.descale_head_stride = 1;
     a.amax = fake<float>(0x55000000); a.amax_batch_stride = 2; a.amax_head_stride = 1;
 }
+la_v_colstats_args colstats_base() {
+    la_v_colstats_args vc;
+    memset(&vc, 0, sizeof vc);
+    vc.struct_size = sizeof vc; vc.in_dtype = BF16; vc.x = fake<void>(X); vc.stat_part = fake<float>(0x57000000);
+    vc.batch = 2; vc.seqlen = 100; vc.num_heads = 4; vc.head_dim = 128; vc.x_head_stride = 128; vc.x_row_stride = 512; vc.x_batch_stride = 51200;
+    return vc;
+}
+template <class A> A unshift_base() {           // what la_attn_unshift_args and la_attn_unshift_fp8_args share
+    A au;
+    memset(&au, 0, sizeof au);
+    au.struct_size = sizeof au; au.o_dtype = BF16; au.heads_per_vec = 2; au.o = fake<void>(O); au.out = fake<void>(OUT);
+    au.batch = 2; au.seqlen = 100; au.num_heads = 4; au.head_dim = 128;
+    au.o_head_stride = au.out_head_stride = 128; au.o_row_stride = au.out_row_stride = 512; au.o_batch_stride = au.out_batch_stride = 51200;
+    au.shift = fake<float>(0x56000000); au.shift_batch_stride = 256; au.shift_head_stride = 128;
+    au.lse = fake<float>(LSE); au.lse_dot = fake<float>(0x59000000); au.lse_out = fake<float>(0x5c000000); au.softmax_scale = 0.125f;
+    return au;
+}
+la_v_prep_tiles_args tiles_base() {
+    la_v_prep_tiles_args vt;
+    memset(&vt, 0, sizeof vt);
+    vt.struct_size = sizeof vt; vt.in_dtype = BF16; vt.x = fake<void>(X); vt.tiles = fake<void>(WS);
+    vt.batch = 2; vt.seqlen = 500; vt.num_heads = 2; vt.head_dim = 128; vt.x_head_stride = 128; vt.x_row_stride = 256; vt.x_batch_stride = 128000;
+    vt.descale = fake<float>(0x54000000); vt.descale_batch_stride = 2; vt.descale_head_stride = 1;
+    vt.shift = fake<float>(0x56000000); vt.shift_batch_stride = 256; vt.shift_head_stride = 128;
+    vt.amax = fake<float>(0x55000000); vt.amax_batch_stride = 2; vt.amax_head_stride = 1;
+    return vt;
+}
 // the returns of qk_prep_check_and_fill, reached through entry point `fn` with the base block `b`
 template <class A, class Fn>
 void cases_prep_shared(const std::string& e, const A& b, Fn fn) {
@@ -916,10 +972,7 @@ void cases_other_entry_points() {
 
     // la_v_colstats (+ _finish), la_attn_unshift
     using AV = la_v_colstats_args;
-    AV vc;
-    memset(&vc, 0, sizeof vc);
-    vc.struct_size = sizeof vc; vc.in_dtype = BF16; vc.x = fake<void>(X); vc.stat_part = fake<float>(0x57000000);
-    vc.batch = 2; vc.seqlen = 100; vc.num_heads = 4; vc.head_dim = 128; vc.x_head_stride = 128; vc.x_row_stride = 512; vc.x_batch_stride = 51200;
+    const AV vc = colstats_base();
     const std::string e3 = "la_v_colstats";
     run_case(e3 + ": NULL args -> LA_ERR_NULL_ARG", [&]() -> int64_t { return la_v_colstats(nullptr, STREAM); });
     args_case(e3 + ": bf16", vc, la_v_colstats, keep);
@@ -950,13 +1003,7 @@ void cases_other_entry_points() {
     vcf("amax_out + 2 bytes -> LA_ERR_STRIDE", part, 4, 2, 4, 128, 100, mean, 512, 128, fake<float>(0x5b000002), 4, 1);
     vcf("65536 x 32768 heads -> LA_ERR_SHAPE", part, 4, 65536, 32768, 128, 100, mean, 512, 128, amax, 4, 1);
     using AU = la_attn_unshift_args;
-    AU au;
-    memset(&au, 0, sizeof au);
-    au.struct_size = sizeof au; au.o_dtype = BF16; au.out_dtype = FP32; au.heads_per_vec = 2; au.o = fake<void>(O); au.out = fake<void>(OUT);
-    au.batch = 2; au.seqlen = 100; au.num_heads = 4; au.head_dim = 128;
-    au.o_head_stride = au.out_head_stride = 128; au.o_row_stride = au.out_row_stride = 512; au.o_batch_stride = au.out_batch_stride = 51200;
-    au.shift = fake<float>(0x56000000); au.shift_batch_stride = 256; au.shift_head_stride = 128;
-    au.lse = fake<float>(LSE); au.lse_dot = fake<float>(0x59000000); au.lse_out = fake<float>(0x5c000000); au.softmax_scale = 0.125f;
+    const AU au = with(unshift_base<AU>(), [](AU& a) { a.out_dtype = FP32; });
     const std::string e4 = "la_attn_unshift";
     run_case(e4 + ": NULL args -> LA_ERR_NULL_ARG", [&]() -> int64_t { return la_attn_unshift(nullptr, STREAM); });
     args_case(e4 + ": bf16 -> fp32 with shift and LSE", au, la_attn_unshift, keep);
@@ -991,13 +1038,7 @@ void cases_other_entry_points() {
         run_case(e + ": head_dim 80 -> LA_ERR_HEAD_DIM", [&]() -> int64_t { return fn(2, 2, 500, 80); });
     }
     using AT = la_v_prep_tiles_args;
-    AT vt;
-    memset(&vt, 0, sizeof vt);
-    vt.struct_size = sizeof vt; vt.in_dtype = BF16; vt.x = fake<void>(X); vt.tiles = fake<void>(WS);
-    vt.batch = 2; vt.seqlen = 500; vt.num_heads = 2; vt.head_dim = 128; vt.x_head_stride = 128; vt.x_row_stride = 256; vt.x_batch_stride = 128000;
-    vt.descale = fake<float>(0x54000000); vt.descale_batch_stride = 2; vt.descale_head_stride = 1;
-    vt.shift = fake<float>(0x56000000); vt.shift_batch_stride = 256; vt.shift_head_stride = 128;
-    vt.amax = fake<float>(0x55000000); vt.amax_batch_stride = 2; vt.amax_head_stride = 1;
+    const AT vt = tiles_base();
     const std::string e5 = "la_v_prep_tiles";
     run_case(e5 + ": NULL args -> LA_ERR_NULL_ARG", [&]() -> int64_t { return la_v_prep_tiles(nullptr, STREAM); });
     args_case(e5 + ": bf16 with descale, shift and amax", vt, la_v_prep_tiles, keep);
@@ -1022,6 +1063,466 @@ void cases_other_entry_points() {
     run_case("la_abi_version", [&]() -> int64_t { return la_abi_version(); });
     for (int st = 1; st >= -14; --st)
         run_case("la_status_string(" + std::to_string(st) + ")", [&]() -> int64_t { return st; }, {}, ",\"text\":\"" + std::string(la_status_string(st)) + "\"");
+}
+
+// ---- the _rows and _rot entry points, la_attn_unshift_fp8 and the vote maps --------------------------------------------------------------
+// A case holds a block, a row map and a head rotation, and an entry point is a function of the three. An ORDER case breaks two checks
+// that answer with different codes and names the one that answers: the first failing check decides.
+constexpr uintptr_t ROWS = 0x63000000, POS = 0x64000000, SIGNS = 0x65000000, MARG = 0x66000000, RD = 0x67000000, DI = 0x68000000, AM = 0x69000000;
+template <class A> struct Mapped {
+    A a; la_row_map map; la_head_rotation rot;
+    bool has_args, has_map, has_rot;                  // false: the entry point is handed NULL
+    const A* args() const { return has_args ? &a : nullptr; }
+    const la_row_map* m() const { return has_map ? &map : nullptr; }
+    const la_head_rotation* r() const { return has_rot ? &rot : nullptr; }
+};
+// block `a` with a table of source rows (one for every batch) over src_seqlen rows, and a rotation with signs
+template <class A> Mapped<A> mapped(const A& a, int src_seqlen) {
+    Mapped<A> c;
+    memset(&c, 0, sizeof c);
+    c.a = a; c.has_args = c.has_map = c.has_rot = true;
+    c.map.struct_size = sizeof c.map; c.map.src_seqlen = src_seqlen; c.map.src_rows = fake<int32_t>(ROWS);
+    c.rot.struct_size = sizeof c.rot; c.rot.signs = fake<float>(SIGNS);
+    return c;
+}
+template <class A, class Fn, class M>
+void map_case(const std::string& name, const Mapped<A>& base, Fn fn, M&& m, const Knobs& kn = {}) {
+    Mapped<A> c = base;
+    m(c);
+    run_case(name, [&]() -> int64_t { return fn(c); }, kn);
+}
+template <class A> void prep_dim(A& a, int d) {       // head_dim d of a prep_base block: contiguous strides, d / 2 pairs
+    a.head_dim = d; a.x_head_stride = a.out_head_stride = d; a.x_row_stride = a.out_row_stride = 4 * d;
+    a.x_batch_stride = a.out_batch_stride = 400 * d;
+    a.axis_pairs[0] = d / 8; a.axis_pairs[1] = a.axis_pairs[2] = 3 * d / 16;
+}
+
+// what the three passes of the q/k prologue share under a map (`rows`: the _rows entry point) and a rotation (`rot`: the _rot one);
+// b: the base block of the unmapped cases (100 rows, 100 positions)
+template <class A, class Rows, class Rot>
+void cases_prep_mapped(const std::string& e, const A& b, Rows rows, Rot rot) {
+    using C = Mapped<A>;
+    const C c = mapped(b, 100);
+    const std::string er = e + "_rows", et = e + "_rot";
+    Knobs fail; fail.fail_at = 0; fail.fail_err = hipErrorLaunchFailure;
+    // the preamble
+    map_case(er + ": NULL args -> LA_ERR_NULL_ARG", c, rows, [](C& x) { x.has_args = false; });
+    map_case(er + ": NULL map -> LA_ERR_NULL_ARG", c, rows, [](C& x) { x.has_map = false; });
+    map_case(er + ": NULL map and struct_size 0 -> LA_ERR_NULL_ARG first", c, rows, [](C& x) { x.has_map = false; x.a.struct_size = 0; });
+    map_case(er + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", c, rows, [](C& x) { x.a.struct_size = 0; });
+    map_case(er + ": map struct_size + 8 -> LA_ERR_STRUCT_SIZE", c, rows, [](C& x) { x.map.struct_size += 8; });
+    map_case(er + ": map struct_size + 8 and x NULL -> LA_ERR_STRUCT_SIZE first", c, rows, [](C& x) { x.map.struct_size += 8; x.a.x = nullptr; });
+    map_case(er + ": x NULL -> LA_ERR_NULL_ARG", c, rows, [](C& x) { x.a.x = nullptr; });
+    map_case(er + ": in_dtype e4m3 -> LA_ERR_DTYPE", c, rows, [](C& x) { x.a.in_dtype = E4M3; });
+    map_case(er + ": in_dtype e4m3 and src_seqlen 0 -> LA_ERR_DTYPE first", c, rows, [](C& x) { x.a.in_dtype = E4M3; x.map.src_seqlen = 0; });
+    // the map's rules inside the shared checks, each beside the unmapped rules of its kind
+    map_case(er + ": norm_mode 3 and src_seqlen 0 -> LA_ERR_UNSUPPORTED first", c, rows, [](C& x) { x.a.norm_mode = 3; x.map.src_seqlen = 0; });
+    map_case(er + ": src_seqlen 0 -> LA_ERR_SHAPE", c, rows, [](C& x) { x.map.src_seqlen = 0; });
+    map_case(er + ": no src_rows, 99 source rows for 100 -> LA_ERR_SHAPE", c, rows, [](C& x) { x.map.src_rows = nullptr; x.map.src_seqlen = 99; });
+    map_case(er + ": src_rows, 50 source rows for 100 -> passes", c, rows, [](C& x) { x.map.src_seqlen = 50; });
+    map_case(er + ": src_seqlen 0 and head_dim 100 -> LA_ERR_SHAPE first", c, rows, [](C& x) { x.map.src_seqlen = 0; x.a.head_dim = 100; });
+    map_case(er + ": x_row_stride + 4 with 1 row of 100 source rows -> LA_ERR_STRIDE (a used stride)", c, rows, [](C& x) { x.a.seqlen = 1; x.a.x_row_stride += 4; });
+    map_case(er + ": x_row_stride + 4 with 1 source row -> passes (unused stride)", c, rows, [](C& x) { x.map.src_seqlen = 1; x.a.x_row_stride += 4; });
+    map_case(er + ": map batch_stride -100 -> LA_ERR_STRIDE", c, rows, [](C& x) { x.map.batch_stride = -100; });
+    map_case(er + ": src_rows + 2 bytes -> LA_ERR_STRIDE", c, rows, [](C& x) { x.map.src_rows = fake<int32_t>(ROWS + 2); });
+    map_case(er + ": positions + 2 bytes -> LA_ERR_STRIDE", c, rows, [](C& x) { x.map.positions = fake<int32_t>(POS + 2); });
+    map_case(er + ": src_rows with out == x -> LA_ERR_UNSUPPORTED (a gather in place)", c, rows, [](C& x) { x.a.out = const_cast<void*>(x.a.x); });
+    map_case(er + ": map batch_stride -100 and out == x -> LA_ERR_STRIDE first", c, rows, [](C& x) { x.map.batch_stride = -100; x.a.out = const_cast<void*>(x.a.x); });
+    map_case(er + ": src_rows with out == x and weight + 8 bytes -> LA_ERR_UNSUPPORTED first", c, rows, [](C& x) { x.a.out = const_cast<void*>(x.a.x); x.a.weight = fake<float>(0x50000008); });
+    map_case(er + ": positions alone with out == x -> passes", c, rows, [](C& x) { x.map.src_rows = nullptr; x.map.positions = fake<int32_t>(POS); x.a.out = const_cast<void*>(x.a.x); });
+    map_case(er + ": no positions, 200 source rows on 100 positions -> LA_ERR_SHAPE", c, rows, [](C& x) { x.map.src_seqlen = 200; });
+    map_case(er + ": positions, 200 source rows on 100 positions -> passes (clamped by the kernel)", c, rows, [](C& x) { x.map.src_seqlen = 200; x.map.positions = fake<int32_t>(POS); });
+    // the fills
+    map_case(er + ": src_rows alone, one table for every batch", c, rows, keep);
+    map_case(er + ": positions alone", c, rows, [](C& x) { x.map.src_rows = nullptr; x.map.positions = fake<int32_t>(POS); });
+    map_case(er + ": both tables, one per batch (batch_stride 100)", c, rows, [](C& x) { x.map.positions = fake<int32_t>(POS); x.map.batch_stride = 100; });
+    map_case(er + ": neither table, src_seqlen == seqlen (the unmapped call)", c, rows, [](C& x) { x.map.src_rows = nullptr; });
+    map_case(er + ": all rope tables NULL under a map -> pos_limit 1", c, rows, [](C& x) { x.a.rope_table[0] = x.a.rope_table[1] = x.a.rope_table[2] = nullptr; x.map.src_seqlen = 300; });
+    // the rotation: the preamble ...
+    map_case(et + ": NULL args -> LA_ERR_NULL_ARG", c, rot, [](C& x) { x.has_args = false; });
+    map_case(et + ": NULL rot -> LA_ERR_NULL_ARG", c, rot, [](C& x) { x.has_rot = false; });
+    map_case(et + ": NULL map and NULL rot -> LA_ERR_NULL_ARG", c, rot, [](C& x) { x.has_map = x.has_rot = false; });
+    map_case(et + ": NULL rot and map struct_size + 8 -> LA_ERR_NULL_ARG first", c, rot, [](C& x) { x.has_rot = false; x.map.struct_size += 8; });
+    map_case(et + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", c, rot, [](C& x) { x.a.struct_size = 0; });
+    map_case(et + ": map struct_size + 8 -> LA_ERR_STRUCT_SIZE", c, rot, [](C& x) { x.map.struct_size += 8; });
+    map_case(et + ": rot struct_size 0 -> LA_ERR_STRUCT_SIZE", c, rot, [](C& x) { x.rot.struct_size = 0; });
+    map_case(et + ": rot struct_size 0 and x NULL -> LA_ERR_STRUCT_SIZE first", c, rot, [](C& x) { x.rot.struct_size = 0; x.a.x = nullptr; });
+    map_case(et + ": NULL map, map struct_size not looked at, d128 -> passes (log2_lanes 4)", c, rot, [](C& x) { x.has_map = false; x.map.struct_size = 0; });
+    // ... its rules inside the shared checks, and the fills
+    map_case(et + ": map, d64 -> passes (log2_lanes 3)", c, rot, [](C& x) { prep_dim(x.a, 64); });
+    map_case(et + ": map with positions, d256 -> passes (log2_lanes 5)", c, rot, [](C& x) { prep_dim(x.a, 256); x.map.positions = fake<int32_t>(POS); });
+    map_case(et + ": signs NULL, rot reserved 1 (not read) -> passes", c, rot, [](C& x) { x.rot.signs = nullptr; x.rot.reserved = 1; });
+    map_case(et + ": head_dim 96 -> LA_ERR_HEAD_DIM (a rotated head)", c, rot, [](C& x) { prep_dim(x.a, 96); });
+    map_case(et + ": head_dim 96 with 172 heads under LA_NORM_TOKEN -> LA_ERR_HEAD_DIM first", c, rot, [](C& x) { prep_dim(x.a, 96); x.a.num_heads = 172; });
+    map_case(et + ": signs + 2 bytes -> LA_ERR_STRIDE", c, rot, [](C& x) { x.rot.signs = fake<float>(SIGNS + 2); });
+    map_case(et + ": signs + 2 bytes and axis_pairs[2] -1 -> LA_ERR_STRIDE first", c, rot, [](C& x) { x.rot.signs = fake<float>(SIGNS + 2); x.a.axis_pairs[2] = -1; });
+    map_case(et + ": src_rows with out == x and signs + 2 bytes -> LA_ERR_UNSUPPORTED first", c, rot, [](C& x) { x.a.out = const_cast<void*>(x.a.x); x.rot.signs = fake<float>(SIGNS + 2); });
+    map_case(et + ": the launch fails -> LA_ERR_LAUNCH", c, rot, keep, fail);
+}
+// ... and what la_qk_prep_fp8 and la_qk_prep_smooth add: their own checks sit before the shared ones, the limit of heads behind
+template <class A, class Rows, class Rot>
+void cases_prep_e4m3_mapped(const std::string& e, const A& b, Rows rows, Rot rot) {
+    using C = Mapped<A>;
+    const C c = mapped(b, 100);
+    map_case(e + "_rows: map struct_size + 8 and heads_per_scale 3 -> LA_ERR_STRUCT_SIZE first", c, rows, [](C& x) { x.map.struct_size += 8; x.a.heads_per_scale = 3; });
+    map_case(e + "_rows: descale_batch_stride -2 and src_seqlen 0 -> LA_ERR_STRIDE first", c, rows, [](C& x) { x.a.descale_batch_stride = -2; x.map.src_seqlen = 0; });
+    map_case(e + "_rows: src_rows with out == x and 1026 heads -> LA_ERR_UNSUPPORTED", c, rows, [](C& x) { x.a.out = const_cast<void*>(x.a.x); x.a.num_heads = 1026; x.a.norm_mode = LA_NORM_HEAD; });
+    map_case(e + "_rows: 1026 heads -> LA_ERR_UNSUPPORTED (scale slots)", c, rows, [](C& x) { x.a.num_heads = 1026; x.a.norm_mode = LA_NORM_HEAD; });
+    map_case(e + "_rows: out NULL under a map (no quantized output)", c, rows, [](C& x) { x.a.out = nullptr; });
+    map_case(e + "_rot: out NULL, no map (no quantized output)", c, rot, [](C& x) { x.a.out = nullptr; x.has_map = false; });
+}
+
+void cases_maps_rotations_margins() {
+    Knobs fail; fail.fail_at = 0; fail.fail_err = hipErrorLaunchFailure;
+    // la_qk_prep / la_qk_prep_fp8 / la_qk_prep_smooth: _rows and _rot
+    using AP = la_qk_prep_args; using A8 = la_qk_prep_fp8_args; using AS = la_qk_prep_smooth_args;
+    const AP qp = with(prep_base<AP>(), [](AP& a) { a.out_dtype = FP16; });
+    cases_prep_mapped("la_qk_prep", qp, [](const Mapped<AP>& c) { return la_qk_prep_rows(c.args(), c.m(), STREAM); },
+                      [](const Mapped<AP>& c) { return la_qk_prep_rot(c.args(), c.m(), c.r(), STREAM); });
+    map_case("la_qk_prep_rows: out NULL -> LA_ERR_NULL_ARG", mapped(qp, 100), [](const Mapped<AP>& c) { return la_qk_prep_rows(c.args(), c.m(), STREAM); },
+             [](Mapped<AP>& x) { x.a.out = nullptr; });
+    map_case("la_qk_prep_rot: out_dtype fp32 -> LA_ERR_DTYPE", mapped(qp, 100), [](const Mapped<AP>& c) { return la_qk_prep_rot(c.args(), c.m(), c.r(), STREAM); },
+             [](Mapped<AP>& x) { x.a.out_dtype = FP32; });
+    const A8 q8 = with(prep_base<A8>(), [](A8& a) { scale_fields(a); });
+    const auto rows8 = [](const Mapped<A8>& c) { return la_qk_prep_fp8_rows(c.args(), c.m(), STREAM); };
+    const auto rot8 = [](const Mapped<A8>& c) { return la_qk_prep_fp8_rot(c.args(), c.m(), c.r(), STREAM); };
+    cases_prep_mapped("la_qk_prep_fp8", q8, rows8, rot8);
+    cases_prep_e4m3_mapped("la_qk_prep_fp8", q8, rows8, rot8);
+    const AS qs = with(prep_base<AS>(), [](AS& a) {
+        scale_fields(a);
+        a.shift = fake<float>(0x56000000); a.shift_batch_stride = 512; a.shift_head_stride = 128;
+        a.colsum_part = fake<float>(0x57000000);
+        a.dot_vec = fake<float>(0x58000000); a.dot_vec_batch_stride = 256; a.dot_vec_head_stride = 128; a.heads_per_dot = 2;
+        a.dot_out = fake<float>(0x59000000);
+    });
+    const auto rowss = [](const Mapped<AS>& c) { return la_qk_prep_smooth_rows(c.args(), c.m(), STREAM); };
+    const auto rots = [](const Mapped<AS>& c) { return la_qk_prep_smooth_rot(c.args(), c.m(), c.r(), STREAM); };
+    cases_prep_mapped("la_qk_prep_smooth", qs, rowss, rots);
+    cases_prep_e4m3_mapped("la_qk_prep_smooth", qs, rowss, rots);
+    Knobs s17; s17.sum_slots = 17;
+    map_case("la_qk_prep_smooth_rows: dot_out without dot_vec and src_seqlen 0 -> LA_ERR_NULL_ARG first", mapped(qs, 100), rowss, [](Mapped<AS>& x) { x.a.dot_vec = nullptr; x.map.src_seqlen = 0; });
+    map_case("la_qk_prep_smooth_rows: shift + 8 bytes and src_seqlen 0 -> LA_ERR_STRIDE first", mapped(qs, 100), rowss, [](Mapped<AS>& x) { x.a.shift = fake<float>(0x56000008); x.map.src_seqlen = 0; });
+    map_case("la_qk_prep_smooth_rot: 17 column-sum slots -> LA_ERR_UNSUPPORTED", mapped(qs, 100), rots, keep, s17);
+    map_case("la_qk_prep_smooth_rot: nothing added, no map -> la_qk_prep_fp8's mode 1, rotated", mapped(qs, 100), rots,
+             [](Mapped<AS>& x) { x.has_map = false; x.a.shift = nullptr; x.a.colsum_part = nullptr; x.a.dot_vec = nullptr; x.a.dot_out = nullptr; });
+
+    // la_v_colstats_rows: 100 table entries over 150 source rows
+    using AV = la_v_colstats_args; using CV = Mapped<AV>;
+    const CV cv = mapped(colstats_base(), 150);
+    const auto vcr = [](const CV& c) { return la_v_colstats_rows(c.args(), c.m(), STREAM); };
+    const std::string e0 = "la_v_colstats_rows";
+    map_case(e0 + ": bf16, 100 entries over 150 rows", cv, vcr, keep);
+    map_case(e0 + ": a table per batch (batch_stride 100), 1 source row", cv, vcr, [](CV& x) { x.map.batch_stride = 100; x.map.src_seqlen = 1; });
+    map_case(e0 + ": the launch fails -> LA_ERR_LAUNCH", cv, vcr, keep, fail);
+    map_case(e0 + ": NULL args -> LA_ERR_NULL_ARG", cv, vcr, [](CV& x) { x.has_args = false; });
+    map_case(e0 + ": NULL map -> LA_ERR_NULL_ARG", cv, vcr, [](CV& x) { x.has_map = false; });
+    map_case(e0 + ": NULL map and struct_size 0 -> LA_ERR_NULL_ARG first", cv, vcr, [](CV& x) { x.has_map = false; x.a.struct_size = 0; });
+    map_case(e0 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", cv, vcr, [](CV& x) { x.a.struct_size = 0; });
+    map_case(e0 + ": map struct_size + 8 -> LA_ERR_STRUCT_SIZE", cv, vcr, [](CV& x) { x.map.struct_size += 8; });
+    map_case(e0 + ": map struct_size + 8 and x NULL -> LA_ERR_STRUCT_SIZE first", cv, vcr, [](CV& x) { x.map.struct_size += 8; x.a.x = nullptr; });
+    map_case(e0 + ": stat_part NULL -> LA_ERR_NULL_ARG", cv, vcr, [](CV& x) { x.a.stat_part = nullptr; });
+    map_case(e0 + ": src_rows NULL -> LA_ERR_NULL_ARG", cv, vcr, [](CV& x) { x.map.src_rows = nullptr; });
+    map_case(e0 + ": src_rows NULL and in_dtype e4m3 -> LA_ERR_NULL_ARG first", cv, vcr, [](CV& x) { x.map.src_rows = nullptr; x.a.in_dtype = E4M3; });
+    map_case(e0 + ": in_dtype e4m3 -> LA_ERR_DTYPE", cv, vcr, [](CV& x) { x.a.in_dtype = E4M3; });
+    map_case(e0 + ": in_dtype e4m3 and src_seqlen 0 -> LA_ERR_DTYPE first", cv, vcr, [](CV& x) { x.a.in_dtype = E4M3; x.map.src_seqlen = 0; });
+    map_case(e0 + ": src_seqlen 0 -> LA_ERR_SHAPE", cv, vcr, [](CV& x) { x.map.src_seqlen = 0; });
+    map_case(e0 + ": src_seqlen 0 and head_dim 100 -> LA_ERR_SHAPE first", cv, vcr, [](CV& x) { x.map.src_seqlen = 0; x.a.head_dim = 100; });
+    map_case(e0 + ": head_dim 264 -> LA_ERR_HEAD_DIM", cv, vcr, [](CV& x) { x.a.head_dim = 264; });
+    map_case(e0 + ": head_dim 100 and positions -> LA_ERR_HEAD_DIM first", cv, vcr, [](CV& x) { x.a.head_dim = 100; x.map.positions = fake<int32_t>(POS); });
+    map_case(e0 + ": positions -> LA_ERR_UNSUPPORTED", cv, vcr, [](CV& x) { x.map.positions = fake<int32_t>(POS); });
+    map_case(e0 + ": positions and x_row_stride + 4 -> LA_ERR_UNSUPPORTED first", cv, vcr, [](CV& x) { x.map.positions = fake<int32_t>(POS); x.a.x_row_stride += 4; });
+    map_case(e0 + ": x_row_stride + 4 with 1 entry over 150 rows -> LA_ERR_STRIDE (a used stride)", cv, vcr, [](CV& x) { x.a.seqlen = 1; x.a.x_row_stride += 4; });
+    map_case(e0 + ": x_row_stride + 4 with 1 source row -> passes (unused stride)", cv, vcr, [](CV& x) { x.map.src_seqlen = 1; x.a.x_row_stride += 4; });
+    map_case(e0 + ": map batch_stride -100 -> LA_ERR_STRIDE", cv, vcr, [](CV& x) { x.map.batch_stride = -100; });
+    map_case(e0 + ": src_rows + 2 bytes -> LA_ERR_STRIDE", cv, vcr, [](CV& x) { x.map.src_rows = fake<int32_t>(ROWS + 2); });
+    map_case(e0 + ": map batch_stride -100 and 2^31 x 2^9 threads -> LA_ERR_STRIDE first", cv, vcr, [](CV& x) { x.map.batch_stride = -100; x.a.batch = 1 << 20; x.a.num_heads = 1 << 16; x.a.head_dim = 256; x.a.seqlen = 16; });
+    map_case(e0 + ": 2^31 x 2^9 threads -> LA_ERR_SHAPE", cv, vcr, [](CV& x) { x.a.batch = 1 << 20; x.a.num_heads = 1 << 16; x.a.head_dim = 256; x.a.seqlen = 16; });
+
+    // la_v_prep_tiles_rows: 500 keys from 700 source rows
+    using AT = la_v_prep_tiles_args; using CT = Mapped<AT>;
+    const CT ct = mapped(tiles_base(), 700);
+    const auto vtr = [](const CT& c) { return la_v_prep_tiles_rows(c.args(), c.m(), STREAM); };
+    const std::string e1 = "la_v_prep_tiles_rows";
+    map_case(e1 + ": bf16 with descale, shift and amax, 500 keys from 700 rows", ct, vtr, keep);
+    map_case(e1 + ": fp32, nothing optional, a table per batch", ct, vtr, [](CT& x) { x.a.in_dtype = FP32; x.a.descale = nullptr; x.a.shift = nullptr; x.a.amax = nullptr; x.map.batch_stride = 500; });
+    map_case(e1 + ": the launch fails -> LA_ERR_LAUNCH", ct, vtr, keep, fail);
+    map_case(e1 + ": NULL args -> LA_ERR_NULL_ARG", ct, vtr, [](CT& x) { x.has_args = false; });
+    map_case(e1 + ": NULL map -> LA_ERR_NULL_ARG", ct, vtr, [](CT& x) { x.has_map = false; });
+    map_case(e1 + ": NULL map and struct_size 0 -> LA_ERR_NULL_ARG first", ct, vtr, [](CT& x) { x.has_map = false; x.a.struct_size = 0; });
+    map_case(e1 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", ct, vtr, [](CT& x) { x.a.struct_size = 0; });
+    map_case(e1 + ": map struct_size + 8 -> LA_ERR_STRUCT_SIZE", ct, vtr, [](CT& x) { x.map.struct_size += 8; });
+    map_case(e1 + ": map struct_size + 8 and tiles NULL -> LA_ERR_STRUCT_SIZE first", ct, vtr, [](CT& x) { x.map.struct_size += 8; x.a.tiles = nullptr; });
+    map_case(e1 + ": tiles NULL -> LA_ERR_NULL_ARG", ct, vtr, [](CT& x) { x.a.tiles = nullptr; });
+    map_case(e1 + ": src_rows NULL -> LA_ERR_NULL_ARG", ct, vtr, [](CT& x) { x.map.src_rows = nullptr; });
+    map_case(e1 + ": src_rows NULL and in_dtype e4m3 -> LA_ERR_NULL_ARG first", ct, vtr, [](CT& x) { x.map.src_rows = nullptr; x.a.in_dtype = E4M3; });
+    map_case(e1 + ": in_dtype e4m3 and src_seqlen 0 -> LA_ERR_DTYPE first", ct, vtr, [](CT& x) { x.a.in_dtype = E4M3; x.map.src_seqlen = 0; });
+    map_case(e1 + ": src_seqlen 0 -> LA_ERR_SHAPE", ct, vtr, [](CT& x) { x.map.src_seqlen = 0; });
+    map_case(e1 + ": src_seqlen 0 and head_dim 80 -> LA_ERR_SHAPE first", ct, vtr, [](CT& x) { x.map.src_seqlen = 0; x.a.head_dim = 80; });
+    map_case(e1 + ": head_dim 80 and positions -> LA_ERR_HEAD_DIM first", ct, vtr, [](CT& x) { x.a.head_dim = 80; x.map.positions = fake<int32_t>(POS); });
+    map_case(e1 + ": reserved0 1 -> LA_ERR_UNSUPPORTED", ct, vtr, [](CT& x) { x.a.reserved0 = 1; });
+    map_case(e1 + ": positions -> LA_ERR_UNSUPPORTED", ct, vtr, [](CT& x) { x.map.positions = fake<int32_t>(POS); });
+    map_case(e1 + ": positions and x_head_stride + 4 -> LA_ERR_UNSUPPORTED first", ct, vtr, [](CT& x) { x.map.positions = fake<int32_t>(POS); x.a.x_head_stride += 4; });
+    map_case(e1 + ": map batch_stride -500 -> LA_ERR_STRIDE", ct, vtr, [](CT& x) { x.map.batch_stride = -500; });
+    map_case(e1 + ": src_rows + 2 bytes -> LA_ERR_STRIDE", ct, vtr, [](CT& x) { x.map.src_rows = fake<int32_t>(ROWS + 2); });
+    map_case(e1 + ": x_row_stride + 4 with 1 key from 700 rows -> LA_ERR_STRIDE (a used stride)", ct, vtr, [](CT& x) { x.a.seqlen = 1; x.a.x_row_stride += 4; });
+    map_case(e1 + ": x_row_stride + 4 with 1 source row -> passes (unused stride)", ct, vtr, [](CT& x) { x.map.src_seqlen = 1; x.a.x_row_stride += 4; });
+    map_case(e1 + ": map batch_stride -500 and 65536 x 32768 tiles -> LA_ERR_STRIDE first", ct, vtr, [](CT& x) { x.map.batch_stride = -500; x.a.batch = 65536; x.a.num_heads = 32768; x.a.seqlen = 64; });
+    map_case(e1 + ": 65536 x 32768 tiles -> LA_ERR_SHAPE", ct, vtr, [](CT& x) { x.a.batch = 65536; x.a.num_heads = 32768; x.a.seqlen = 64; });
+
+    // la_attn_unshift: what its table lacked, then la_attn_unshift_rows (100 out rows from 150 rows of o / lse / lse_dot)
+    using AU = la_attn_unshift_args; using CU = Mapped<AU>;
+    const AU au = with(unshift_base<AU>(), [](AU& a) { a.out_dtype = FP32; });
+    const std::string e2 = "la_attn_unshift";
+    args_case(e2 + ": lse_out without lse_dot, no map -> LA_ERR_NULL_ARG", au, la_attn_unshift, [](AU& a) { a.lse_dot = nullptr; });
+    args_case(e2 + ": bf16 in place (out == o, lse_out == lse) -> passes", au, la_attn_unshift, [](AU& a) { a.out_dtype = BF16; a.out = const_cast<void*>(a.o); a.lse_out = const_cast<float*>(a.lse); });
+    args_case(e2 + ": lse_out without lse and o_dtype fp32 -> LA_ERR_NULL_ARG first", au, la_attn_unshift, [](AU& a) { a.lse = nullptr; a.o_dtype = FP32; });
+    args_case(e2 + ": out_dtype e4m3 and seqlen 0 -> LA_ERR_DTYPE first", au, la_attn_unshift, [](AU& a) { a.out_dtype = E4M3; a.seqlen = 0; });
+    args_case(e2 + ": heads_per_vec 3 and head_dim 100 -> LA_ERR_SHAPE first", au, la_attn_unshift, [](AU& a) { a.heads_per_vec = 3; a.head_dim = 100; });
+    args_case(e2 + ": head_dim 100 and o_row_stride + 4 -> LA_ERR_HEAD_DIM first", au, la_attn_unshift, [](AU& a) { a.head_dim = 100; a.o_row_stride += 4; });
+    args_case(e2 + ": no lse at all", au, la_attn_unshift, [](AU& a) { a.lse = a.lse_dot = nullptr; a.lse_out = nullptr; });
+    const CU cu = mapped(au, 150);
+    const auto aur = [](const CU& c) { return la_attn_unshift_rows(c.args(), c.m(), STREAM); };
+    const std::string e3 = "la_attn_unshift_rows";
+    map_case(e3 + ": bf16 -> fp32 with shift and LSE, 100 rows from 150", cu, aur, keep);
+    map_case(e3 + ": lse_out without lse_dot under a map -> passes (the LSE at the rows)", cu, aur, [](CU& x) { x.a.lse_dot = nullptr; });
+    map_case(e3 + ": no shift, no lse, a table per batch", cu, aur, [](CU& x) { x.a.shift = nullptr; x.a.heads_per_vec = 0; x.a.lse = x.a.lse_dot = nullptr; x.a.lse_out = nullptr; x.map.batch_stride = 100; });
+    map_case(e3 + ": the launch fails -> LA_ERR_LAUNCH", cu, aur, keep, fail);
+    map_case(e3 + ": NULL args -> LA_ERR_NULL_ARG", cu, aur, [](CU& x) { x.has_args = false; });
+    map_case(e3 + ": NULL map -> LA_ERR_NULL_ARG", cu, aur, [](CU& x) { x.has_map = false; });
+    map_case(e3 + ": NULL map and struct_size 0 -> LA_ERR_NULL_ARG first", cu, aur, [](CU& x) { x.has_map = false; x.a.struct_size = 0; });
+    map_case(e3 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", cu, aur, [](CU& x) { x.a.struct_size = 0; });
+    map_case(e3 + ": map struct_size + 8 -> LA_ERR_STRUCT_SIZE", cu, aur, [](CU& x) { x.map.struct_size += 8; });
+    map_case(e3 + ": map struct_size + 8 and o NULL -> LA_ERR_STRUCT_SIZE first", cu, aur, [](CU& x) { x.map.struct_size += 8; x.a.o = nullptr; });
+    map_case(e3 + ": out NULL -> LA_ERR_NULL_ARG", cu, aur, [](CU& x) { x.a.out = nullptr; });
+    map_case(e3 + ": src_rows NULL -> LA_ERR_NULL_ARG", cu, aur, [](CU& x) { x.map.src_rows = nullptr; });
+    map_case(e3 + ": lse_dot without lse_out -> LA_ERR_NULL_ARG", cu, aur, [](CU& x) { x.a.lse_out = nullptr; });
+    map_case(e3 + ": lse_out without lse -> LA_ERR_NULL_ARG", cu, aur, [](CU& x) { x.a.lse = nullptr; });
+    map_case(e3 + ": lse_out without lse and o_dtype fp32 -> LA_ERR_NULL_ARG first", cu, aur, [](CU& x) { x.a.lse = nullptr; x.a.o_dtype = FP32; });
+    map_case(e3 + ": o_dtype fp32 -> LA_ERR_DTYPE", cu, aur, [](CU& x) { x.a.o_dtype = FP32; });
+    map_case(e3 + ": out_dtype e4m3 and src_seqlen 0 -> LA_ERR_DTYPE first", cu, aur, [](CU& x) { x.a.out_dtype = E4M3; x.map.src_seqlen = 0; });
+    map_case(e3 + ": src_seqlen 0 -> LA_ERR_SHAPE", cu, aur, [](CU& x) { x.map.src_seqlen = 0; });
+    map_case(e3 + ": heads_per_vec 3 and head_dim 100 -> LA_ERR_SHAPE first", cu, aur, [](CU& x) { x.a.heads_per_vec = 3; x.a.head_dim = 100; });
+    map_case(e3 + ": head_dim 100 and out == o -> LA_ERR_HEAD_DIM first", cu, aur, [](CU& x) { x.a.head_dim = 100; x.a.out = const_cast<void*>(x.a.o); });
+    map_case(e3 + ": o_row_stride + 4 with 1 out row from 150 -> LA_ERR_STRIDE (a used stride)", cu, aur, [](CU& x) { x.a.seqlen = 1; x.a.o_row_stride += 4; });
+    map_case(e3 + ": o_row_stride + 4 with 1 source row -> passes (unused stride)", cu, aur, [](CU& x) { x.map.src_seqlen = 1; x.a.o_row_stride += 4; });
+    map_case(e3 + ": map batch_stride -100 -> LA_ERR_STRIDE", cu, aur, [](CU& x) { x.map.batch_stride = -100; });
+    map_case(e3 + ": src_rows + 2 bytes -> LA_ERR_STRIDE", cu, aur, [](CU& x) { x.map.src_rows = fake<int32_t>(ROWS + 2); });
+    map_case(e3 + ": map batch_stride -100 and out == o -> LA_ERR_STRIDE first", cu, aur, [](CU& x) { x.map.batch_stride = -100; x.a.out = const_cast<void*>(x.a.o); });
+    map_case(e3 + ": positions and o_row_stride + 4 -> LA_ERR_STRIDE first", cu, aur, [](CU& x) { x.map.positions = fake<int32_t>(POS); x.a.o_row_stride += 4; });
+    map_case(e3 + ": out == o -> LA_ERR_UNSUPPORTED (a gather in place)", cu, aur, [](CU& x) { x.a.out_dtype = BF16; x.a.out = const_cast<void*>(x.a.o); });
+    map_case(e3 + ": lse_out == lse -> LA_ERR_UNSUPPORTED (a gather in place)", cu, aur, [](CU& x) { x.a.lse_out = const_cast<float*>(x.a.lse); });
+    map_case(e3 + ": positions -> LA_ERR_UNSUPPORTED", cu, aur, [](CU& x) { x.map.positions = fake<int32_t>(POS); });
+
+    // la_attn_unshift_fp8 (dynamic: row_descale written; static: descale_in read), then la_attn_unshift_fp8_rows
+    using AF = la_attn_unshift_fp8_args; using CF = Mapped<AF>;
+    const AF af = with(unshift_base<AF>(), [](AF& a) {
+        a.heads_per_scale = 2; a.row_descale = fake<float>(RD); a.row_descale_batch_stride = 200; a.row_descale_row_stride = 2; a.row_descale_group_stride = 1;
+    });
+    const auto make_static = [](AF& a) {
+        a.row_descale = nullptr; a.descale_in = fake<float>(DI); a.descale_in_batch_stride = 1; a.amax = fake<float>(AM); a.amax_batch_stride = 1;
+    };
+    const AF afs = with(af, make_static);
+    const std::string e4 = "la_attn_unshift_fp8";
+    run_case(e4 + ": NULL args -> LA_ERR_NULL_ARG", [&]() -> int64_t { return la_attn_unshift_fp8(nullptr, STREAM); });
+    args_case(e4 + ": dynamic, a scale per (token, 2 heads), shift and LSE", af, la_attn_unshift_fp8, keep);
+    args_case(e4 + ": static with a running maximum", afs, la_attn_unshift_fp8, keep);
+    args_case(e4 + ": static without amax, one descale for every batch", afs, la_attn_unshift_fp8, [](AF& a) { a.amax = nullptr; a.descale_in_batch_stride = 0; });
+    args_case(e4 + ": row_descale and descale_in both given -> static, row_descale not handed on", afs, la_attn_unshift_fp8, [](AF& a) { a.row_descale = fake<float>(RD); });
+    args_case(e4 + ": no shift, no lse -> heads_per_vec 1", af, la_attn_unshift_fp8, [](AF& a) { a.shift = nullptr; a.heads_per_vec = 0; a.lse = a.lse_dot = nullptr; a.lse_out = nullptr; });
+    args_case(e4 + ": lse_out == lse, no map -> passes", af, la_attn_unshift_fp8, [](AF& a) { a.lse_out = const_cast<float*>(a.lse); });
+    args_case(e4 + ": the launch fails -> LA_ERR_LAUNCH", af, la_attn_unshift_fp8, keep, fail);
+    args_case(e4 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", af, la_attn_unshift_fp8, [](AF& a) { a.struct_size = 0; });
+    args_case(e4 + ": la_attn_unshift's struct_size and o NULL -> LA_ERR_STRUCT_SIZE first", af, la_attn_unshift_fp8, [](AF& a) { a.struct_size = sizeof(la_attn_unshift_args); a.o = nullptr; });
+    args_case(e4 + ": o NULL -> LA_ERR_NULL_ARG", af, la_attn_unshift_fp8, [](AF& a) { a.o = nullptr; });
+    args_case(e4 + ": out NULL -> LA_ERR_NULL_ARG", af, la_attn_unshift_fp8, [](AF& a) { a.out = nullptr; });
+    args_case(e4 + ": row_descale and descale_in both NULL -> LA_ERR_NULL_ARG", af, la_attn_unshift_fp8, [](AF& a) { a.row_descale = nullptr; });
+    args_case(e4 + ": lse_dot without lse_out -> LA_ERR_NULL_ARG", af, la_attn_unshift_fp8, [](AF& a) { a.lse_out = nullptr; });
+    args_case(e4 + ": lse_out without lse_dot, no map -> LA_ERR_NULL_ARG", af, la_attn_unshift_fp8, [](AF& a) { a.lse_dot = nullptr; });
+    args_case(e4 + ": lse_out without lse -> LA_ERR_NULL_ARG", af, la_attn_unshift_fp8, [](AF& a) { a.lse = nullptr; });
+    args_case(e4 + ": lse_out without lse and o_dtype fp32 -> LA_ERR_NULL_ARG first", af, la_attn_unshift_fp8, [](AF& a) { a.lse = nullptr; a.o_dtype = FP32; });
+    args_case(e4 + ": o_dtype fp32 -> LA_ERR_DTYPE", af, la_attn_unshift_fp8, [](AF& a) { a.o_dtype = FP32; });
+    args_case(e4 + ": o_dtype fp32 and seqlen 0 -> LA_ERR_DTYPE first", af, la_attn_unshift_fp8, [](AF& a) { a.o_dtype = FP32; a.seqlen = 0; });
+    args_case(e4 + ": seqlen 0 -> LA_ERR_SHAPE", af, la_attn_unshift_fp8, [](AF& a) { a.seqlen = 0; });
+    args_case(e4 + ": heads_per_vec 3 -> LA_ERR_SHAPE", af, la_attn_unshift_fp8, [](AF& a) { a.heads_per_vec = 3; });
+    args_case(e4 + ": heads_per_scale 0 -> LA_ERR_SHAPE", af, la_attn_unshift_fp8, [](AF& a) { a.heads_per_scale = 0; });
+    args_case(e4 + ": heads_per_scale 3 of 4 heads -> LA_ERR_SHAPE", af, la_attn_unshift_fp8, [](AF& a) { a.heads_per_scale = 3; });
+    args_case(e4 + ": heads_per_scale 3 and head_dim 100 -> LA_ERR_SHAPE first", af, la_attn_unshift_fp8, [](AF& a) { a.heads_per_scale = 3; a.head_dim = 100; });
+    args_case(e4 + ": head_dim 100 -> LA_ERR_HEAD_DIM", af, la_attn_unshift_fp8, [](AF& a) { a.head_dim = 100; });
+    args_case(e4 + ": head_dim 100 and o_row_stride + 4 -> LA_ERR_HEAD_DIM first", af, la_attn_unshift_fp8, [](AF& a) { a.head_dim = 100; a.o_row_stride += 4; });
+    args_case(e4 + ": o_row_stride + 4 -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.o_row_stride += 4; });
+    args_case(e4 + ": out_row_stride + 4 -> LA_ERR_STRIDE (8-byte rows of e4m3)", af, la_attn_unshift_fp8, [](AF& a) { a.out_row_stride += 4; });
+    args_case(e4 + ": out + 8 bytes, out_row_stride + 8 -> passes (8-byte rows of e4m3)", af, la_attn_unshift_fp8, [](AF& a) { a.out = fake<void>(OUT + 8); a.out_row_stride += 8; });
+    args_case(e4 + ": out + 4 bytes -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.out = fake<void>(OUT + 4); });
+    args_case(e4 + ": shift_batch_stride + 2 -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.shift_batch_stride += 2; });
+    args_case(e4 + ": lse_dot + 2 bytes -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.lse_dot = fake<float>(0x59000002); });
+    args_case(e4 + ": row_descale + 2 bytes -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.row_descale = fake<float>(RD + 2); });
+    args_case(e4 + ": descale_in + 2 bytes -> LA_ERR_STRIDE", afs, la_attn_unshift_fp8, [](AF& a) { a.descale_in = fake<float>(DI + 2); });
+    args_case(e4 + ": amax + 2 bytes -> LA_ERR_STRIDE", afs, la_attn_unshift_fp8, [](AF& a) { a.amax = fake<float>(AM + 2); });
+    args_case(e4 + ": row_descale_row_stride -2 -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.row_descale_row_stride = -2; });
+    args_case(e4 + ": row_descale_group_stride -1 -> LA_ERR_STRIDE", af, la_attn_unshift_fp8, [](AF& a) { a.row_descale_group_stride = -1; });
+    args_case(e4 + ": descale_in_batch_stride -1 -> LA_ERR_STRIDE", afs, la_attn_unshift_fp8, [](AF& a) { a.descale_in_batch_stride = -1; });
+    args_case(e4 + ": amax_batch_stride -1 -> LA_ERR_STRIDE", afs, la_attn_unshift_fp8, [](AF& a) { a.amax_batch_stride = -1; });
+    args_case(e4 + ": amax_batch_stride -1 and out == o -> LA_ERR_STRIDE first", afs, la_attn_unshift_fp8, [](AF& a) { a.amax_batch_stride = -1; a.out = const_cast<void*>(a.o); });
+    args_case(e4 + ": out == o -> LA_ERR_UNSUPPORTED (no in-place form)", af, la_attn_unshift_fp8, [](AF& a) { a.out = const_cast<void*>(a.o); });
+    args_case(e4 + ": a scale group of 256 x 128 elements -> LA_ERR_UNSUPPORTED", af, la_attn_unshift_fp8, [](AF& a) { a.num_heads = 256; a.heads_per_scale = 256; a.heads_per_vec = 128; });
+    args_case(e4 + ": a scale group of 128 x 128 elements -> passes", af, la_attn_unshift_fp8, [](AF& a) { a.num_heads = 256; a.heads_per_scale = 128; a.heads_per_vec = 128; });
+    args_case(e4 + ": 1032 heads -> LA_ERR_UNSUPPORTED (empty-row flags)", af, la_attn_unshift_fp8, [](AF& a) { a.num_heads = 1032; a.heads_per_scale = 1; a.heads_per_vec = 1; });
+    args_case(e4 + ": 1024 heads -> passes", af, la_attn_unshift_fp8, [](AF& a) { a.num_heads = 1024; a.heads_per_scale = 1; a.heads_per_vec = 1; });
+    args_case(e4 + ": 1032 heads and 65536 x 32768 tiles -> LA_ERR_UNSUPPORTED first", af, la_attn_unshift_fp8, [](AF& a) { a.num_heads = 1032; a.heads_per_scale = 1; a.heads_per_vec = 1; a.batch = 65536; a.seqlen = 32768 * 32; });
+    args_case(e4 + ": 65536 x 32768 tiles -> LA_ERR_SHAPE", af, la_attn_unshift_fp8, [](AF& a) { a.batch = 65536; a.seqlen = 32768 * 32; });
+    args_case(e4 + ": 65536 x 32767 tiles -> passes", af, la_attn_unshift_fp8, [](AF& a) { a.batch = 65536; a.seqlen = 32767 * 32; });
+    const CF cf = mapped(af, 150), cfs = mapped(afs, 150);
+    const auto afr = [](const CF& c) { return la_attn_unshift_fp8_rows(c.args(), c.m(), STREAM); };
+    const std::string e5 = "la_attn_unshift_fp8_rows";
+    map_case(e5 + ": dynamic, 100 rows from 150", cf, afr, keep);
+    map_case(e5 + ": static with a running maximum, a table per batch", cfs, afr, [](CF& x) { x.map.batch_stride = 100; });
+    map_case(e5 + ": lse_out without lse_dot under a map -> passes (the LSE at the rows)", cf, afr, [](CF& x) { x.a.lse_dot = nullptr; });
+    map_case(e5 + ": the launch fails -> LA_ERR_LAUNCH", cf, afr, keep, fail);
+    map_case(e5 + ": NULL args -> LA_ERR_NULL_ARG", cf, afr, [](CF& x) { x.has_args = false; });
+    map_case(e5 + ": NULL map -> LA_ERR_NULL_ARG", cf, afr, [](CF& x) { x.has_map = false; });
+    map_case(e5 + ": NULL map and struct_size 0 -> LA_ERR_NULL_ARG first", cf, afr, [](CF& x) { x.has_map = false; x.a.struct_size = 0; });
+    map_case(e5 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", cf, afr, [](CF& x) { x.a.struct_size = 0; });
+    map_case(e5 + ": map struct_size + 8 -> LA_ERR_STRUCT_SIZE", cf, afr, [](CF& x) { x.map.struct_size += 8; });
+    map_case(e5 + ": map struct_size + 8 and o NULL -> LA_ERR_STRUCT_SIZE first", cf, afr, [](CF& x) { x.map.struct_size += 8; x.a.o = nullptr; });
+    map_case(e5 + ": row_descale and descale_in both NULL -> LA_ERR_NULL_ARG", cf, afr, [](CF& x) { x.a.row_descale = nullptr; });
+    map_case(e5 + ": src_rows NULL -> LA_ERR_NULL_ARG", cf, afr, [](CF& x) { x.map.src_rows = nullptr; });
+    map_case(e5 + ": src_rows NULL and o_dtype fp32 -> LA_ERR_NULL_ARG first", cf, afr, [](CF& x) { x.map.src_rows = nullptr; x.a.o_dtype = FP32; });
+    map_case(e5 + ": lse_dot without lse_out -> LA_ERR_NULL_ARG", cf, afr, [](CF& x) { x.a.lse_out = nullptr; });
+    map_case(e5 + ": o_dtype fp32 and src_seqlen 0 -> LA_ERR_DTYPE first", cf, afr, [](CF& x) { x.a.o_dtype = FP32; x.map.src_seqlen = 0; });
+    map_case(e5 + ": src_seqlen 0 -> LA_ERR_SHAPE", cf, afr, [](CF& x) { x.map.src_seqlen = 0; });
+    map_case(e5 + ": heads_per_scale 3 and head_dim 100 -> LA_ERR_SHAPE first", cf, afr, [](CF& x) { x.a.heads_per_scale = 3; x.a.head_dim = 100; });
+    map_case(e5 + ": head_dim 100 and out == o -> LA_ERR_HEAD_DIM first", cf, afr, [](CF& x) { x.a.head_dim = 100; x.a.out = const_cast<void*>(x.a.o); });
+    map_case(e5 + ": o_row_stride + 4 with 1 out row from 150 -> LA_ERR_STRIDE (a used stride)", cf, afr, [](CF& x) { x.a.seqlen = 1; x.a.o_row_stride += 4; });
+    map_case(e5 + ": o_row_stride + 4 with 1 source row -> passes (unused stride)", cf, afr, [](CF& x) { x.map.src_seqlen = 1; x.a.o_row_stride += 4; });
+    map_case(e5 + ": map batch_stride -100 -> LA_ERR_STRIDE", cf, afr, [](CF& x) { x.map.batch_stride = -100; });
+    map_case(e5 + ": src_rows + 2 bytes -> LA_ERR_STRIDE", cf, afr, [](CF& x) { x.map.src_rows = fake<int32_t>(ROWS + 2); });
+    map_case(e5 + ": map batch_stride -100 and out == o -> LA_ERR_STRIDE first", cf, afr, [](CF& x) { x.map.batch_stride = -100; x.a.out = const_cast<void*>(x.a.o); });
+    map_case(e5 + ": positions and row_descale + 2 bytes -> LA_ERR_STRIDE first", cf, afr, [](CF& x) { x.map.positions = fake<int32_t>(POS); x.a.row_descale = fake<float>(RD + 2); });
+    map_case(e5 + ": out == o and a map with positions -> LA_ERR_UNSUPPORTED", cf, afr, [](CF& x) { x.a.out = const_cast<void*>(x.a.o); x.map.positions = fake<int32_t>(POS); });
+    map_case(e5 + ": out == o -> LA_ERR_UNSUPPORTED", cf, afr, [](CF& x) { x.a.out = const_cast<void*>(x.a.o); });
+    map_case(e5 + ": lse_out == lse -> LA_ERR_UNSUPPORTED (a gather in place)", cf, afr, [](CF& x) { x.a.lse_out = const_cast<float*>(x.a.lse); });
+    map_case(e5 + ": positions -> LA_ERR_UNSUPPORTED", cf, afr, [](CF& x) { x.map.positions = fake<int32_t>(POS); });
+    map_case(e5 + ": positions and 65536 x 32768 tiles -> LA_ERR_UNSUPPORTED first", cf, afr, [](CF& x) { x.map.positions = fake<int32_t>(POS); x.a.batch = 65536; x.a.seqlen = 32768 * 32; });
+    map_case(e5 + ": 1032 heads -> LA_ERR_UNSUPPORTED (empty-row flags)", cf, afr, [](CF& x) { x.a.num_heads = 1032; x.a.heads_per_scale = 1; x.a.heads_per_vec = 1; });
+    map_case(e5 + ": 65536 x 32768 tiles -> LA_ERR_SHAPE", cf, afr, [](CF& x) { x.a.batch = 65536; x.a.seqlen = 32768 * 32; });
+
+    // la_vote_margins and la_vote_margins_fp8: (batch 2, 300 queries, 500 keys, 4 heads on 2 K heads, head_dim 128), dense walk
+    const auto vote_dims = [](auto& a, int d, int sq, int sk) {
+        a.head_dim = d; a.seqlen_q = sq; a.seqlen_k = sk;
+        a.q_head_stride = d; a.q_row_stride = int64_t(d) * a.num_heads; a.q_batch_stride = a.q_row_stride * sq;
+        a.k_head_stride = d; a.k_row_stride = int64_t(d) * a.num_heads_k; a.k_batch_stride = a.k_row_stride * sk;
+    };
+    using VM = la_vote_margins_args;
+    VM vm;
+    memset(&vm, 0, sizeof vm);
+    vm.struct_size = sizeof vm; vm.dtype = BF16; vm.q = fake<void>(Q); vm.k = fake<void>(K); vm.margins = fake<float>(MARG);
+    vm.batch = 2; vm.num_heads = 4; vm.num_heads_k = 2; vm.softmax_scale = 0.125f;
+    vote_dims(vm, 128, 300, 500);
+    const std::string e6 = "la_vote_margins";
+    run_case(e6 + ": NULL args -> LA_ERR_NULL_ARG", [&]() -> int64_t { return la_vote_margins(nullptr, STREAM); });
+    args_case(e6 + ": bf16 d128, dense walk", vm, la_vote_margins, keep);
+    args_case(e6 + ": fp16 d128, int32 list", vm, la_vote_margins, [](VM& a) { a.dtype = FP16; a.read_list = fake<void>(RL); });
+    args_case(e6 + ": bf16 d128, int16 list -> list_int16 1", vm, la_vote_margins, [](VM& a) { a.read_list = fake<void>(RL); a.flags = LA_FLAG_LIST_INT16; });
+    args_case(e6 + ": LA_FLAG_HALF_VOTE -> block_m 128, 3 q-tiles", vm, la_vote_margins, [](VM& a) { a.flags = LA_FLAG_HALF_VOTE; a.read_list = fake<void>(RL); });
+    args_case(e6 + ": LA_FLAG_KERNEL_128ROW -> block_m 128", vm, la_vote_margins, [](VM& a) { a.flags = LA_FLAG_KERNEL_128ROW; });
+    args_case(e6 + ": LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16", vm, la_vote_margins, [](VM& a) { a.flags = LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16; a.read_list = fake<void>(RL); });
+    for (int d : {64, 96, 192, 256})
+        args_case(e6 + ": bf16 d" + std::to_string(d) + ", dense walk", vm, la_vote_margins, [&](VM& a) { vote_dims(a, d, 300, 500); });
+    args_case(e6 + ": d256 LA_FLAG_HALF_VOTE (no effect at this head dim)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 256, 300, 500); a.flags = LA_FLAG_HALF_VOTE; });
+    args_case(e6 + ": the other flags of la_fwd and unknown bits are not read -> passes", vm, la_vote_margins, [](VM& a) { a.flags = LA_FLAG_V_PREPARED | LA_FLAG_STATIC_SCHED | LA_FLAG_EXACT_RESCALE | 256u | 0x80000000u; });
+    args_case(e6 + ": MHA 4 on 4, softmax_scale 0", vm, la_vote_margins, [&](VM& a) { a.num_heads_k = 4; vote_dims(a, 128, 300, 500); a.softmax_scale = 0.0f; });
+    args_case(e6 + ": the launch fails -> LA_ERR_LAUNCH", vm, la_vote_margins, keep, fail);
+    args_case(e6 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", vm, la_vote_margins, [](VM& a) { a.struct_size = 0; });
+    args_case(e6 + ": struct_size 0 and dtype fp32 -> LA_ERR_STRUCT_SIZE first", vm, la_vote_margins, [](VM& a) { a.struct_size = 0; a.dtype = FP32; });
+    args_case(e6 + ": dtype e4m3 -> LA_ERR_DTYPE", vm, la_vote_margins, [](VM& a) { a.dtype = E4M3; });
+    args_case(e6 + ": dtype fp32 and q NULL -> LA_ERR_DTYPE first", vm, la_vote_margins, [](VM& a) { a.dtype = FP32; a.q = nullptr; });
+    args_case(e6 + ": q NULL -> LA_ERR_NULL_ARG", vm, la_vote_margins, [](VM& a) { a.q = nullptr; });
+    args_case(e6 + ": k NULL -> LA_ERR_NULL_ARG", vm, la_vote_margins, [](VM& a) { a.k = nullptr; });
+    args_case(e6 + ": margins NULL -> LA_ERR_NULL_ARG", vm, la_vote_margins, [](VM& a) { a.margins = nullptr; });
+    args_case(e6 + ": margins NULL and batch 0 -> LA_ERR_NULL_ARG first", vm, la_vote_margins, [](VM& a) { a.margins = nullptr; a.batch = 0; });
+    args_case(e6 + ": seqlen_k 0 -> LA_ERR_SHAPE", vm, la_vote_margins, [](VM& a) { a.seqlen_k = 0; });
+    args_case(e6 + ": num_heads_k 0 -> LA_ERR_SHAPE", vm, la_vote_margins, [](VM& a) { a.num_heads_k = 0; });
+    args_case(e6 + ": 4 heads on 3 K heads -> LA_ERR_SHAPE", vm, la_vote_margins, [](VM& a) { a.num_heads_k = 3; });
+    args_case(e6 + ": 4 heads on 3 K heads and head_dim 80 -> LA_ERR_SHAPE first", vm, la_vote_margins, [](VM& a) { a.num_heads_k = 3; a.head_dim = 80; });
+    args_case(e6 + ": head_dim 80 -> LA_ERR_HEAD_DIM", vm, la_vote_margins, [](VM& a) { a.head_dim = 80; });
+    args_case(e6 + ": head_dim 96 under LA_FLAG_KERNEL_128ROW -> LA_ERR_HEAD_DIM", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 96, 300, 500); a.flags = LA_FLAG_KERNEL_128ROW; });
+    args_case(e6 + ": head_dim 80 and q + 8 bytes -> LA_ERR_HEAD_DIM first", vm, la_vote_margins, [](VM& a) { a.head_dim = 80; a.q = fake<void>(Q + 8); });
+    args_case(e6 + ": q + 8 bytes -> LA_ERR_STRIDE", vm, la_vote_margins, [](VM& a) { a.q = fake<void>(Q + 8); });
+    args_case(e6 + ": q_row_stride + 4 -> LA_ERR_STRIDE", vm, la_vote_margins, [](VM& a) { a.q_row_stride += 4; });
+    args_case(e6 + ": k_batch_stride negative -> LA_ERR_STRIDE", vm, la_vote_margins, [](VM& a) { a.k_batch_stride = -a.k_batch_stride; });
+    args_case(e6 + ": k_head_stride + 4 with one K head -> passes (unused stride)", vm, la_vote_margins, [](VM& a) { a.num_heads_k = 1; a.k_head_stride += 4; });
+    args_case(e6 + ": margins + 2 bytes -> LA_ERR_STRIDE", vm, la_vote_margins, [](VM& a) { a.margins = fake<float>(MARG + 2); });
+    args_case(e6 + ": int32 read_list + 2 bytes -> LA_ERR_STRIDE", vm, la_vote_margins, [](VM& a) { a.read_list = fake<void>(RL + 2); });
+    args_case(e6 + ": int16 read_list + 2 bytes -> passes", vm, la_vote_margins, [](VM& a) { a.read_list = fake<void>(RL + 2); a.flags = LA_FLAG_LIST_INT16; });
+    args_case(e6 + ": int16 read_list + 1 byte -> LA_ERR_STRIDE", vm, la_vote_margins, [](VM& a) { a.read_list = fake<void>(RL + 1); a.flags = LA_FLAG_LIST_INT16; });
+    args_case(e6 + ": margins + 2 bytes and 40000 key tiles -> LA_ERR_STRIDE first", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 128, 300, 40000 * 64); a.margins = fake<float>(MARG + 2); });
+    args_case(e6 + ": d64 int16 list, 32767 key tiles -> LA_ERR_SEQLEN (row too long)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 64, 300, 32767 * 64); a.flags = LA_FLAG_LIST_INT16; a.read_list = fake<void>(RL); });
+    args_case(e6 + ": d64 int16 list, 32766 key tiles -> passes", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 64, 300, 32766 * 64); a.flags = LA_FLAG_LIST_INT16; a.read_list = fake<void>(RL); });
+    args_case(e6 + ": d64 int32 list, 32767 key tiles -> passes", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 64, 300, 32767 * 64); a.read_list = fake<void>(RL); });
+    args_case(e6 + ": d64, 34196 key tiles -> passes (the walk storage is full)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 64, 300, 34196 * 64); });
+    args_case(e6 + ": d64, 34197 key tiles -> LA_ERR_SEQLEN (walk storage)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 64, 300, 34197 * 64); });
+    args_case(e6 + ": d128, 30340 key tiles -> passes (the walk storage is full)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 128, 300, 30340 * 64); });
+    args_case(e6 + ": d128, 30341 key tiles -> LA_ERR_SEQLEN (walk storage)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 128, 300, 30341 * 64); });
+    args_case(e6 + ": d256, 22632 key tiles -> passes (the walk storage is full)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 256, 300, 22632 * 64); });
+    args_case(e6 + ": d256, 22633 key tiles -> LA_ERR_SEQLEN (walk storage)", vm, la_vote_margins, [&](VM& a) { vote_dims(a, 256, 300, 22633 * 64); });
+    args_case(e6 + ": 40000 key tiles and 65536 x 32768 q-tiles -> LA_ERR_SEQLEN first", vm, la_vote_margins, [&](VM& a) { a.batch = 65536; a.num_heads = 32768; vote_dims(a, 128, 256, 40000 * 64); });
+    args_case(e6 + ": 65536 x 32768 q-tiles -> LA_ERR_SHAPE", vm, la_vote_margins, [&](VM& a) { a.batch = 65536; a.num_heads = 32768; vote_dims(a, 128, 256, 500); });
+    args_case(e6 + ": 65536 x 16384 rows of 256 under LA_FLAG_HALF_VOTE (2 q-tiles each) -> LA_ERR_SHAPE", vm, la_vote_margins, [&](VM& a) { a.batch = 65536; a.num_heads = 16384; vote_dims(a, 128, 256, 500); a.flags = LA_FLAG_HALF_VOTE; });
+    args_case(e6 + ": 65536 x 16384 q-tiles -> passes", vm, la_vote_margins, [&](VM& a) { a.batch = 65536; a.num_heads = 16384; vote_dims(a, 128, 256, 500); });
+
+    using V8 = la_vote_margins_fp8_args;
+    V8 v8;
+    memset(&v8, 0, sizeof v8);
+    v8.struct_size = sizeof v8; v8.q = fake<void>(Q); v8.k = fake<void>(K); v8.margins = fake<float>(MARG);
+    v8.batch = 2; v8.num_heads = 4; v8.num_heads_k = 2; v8.softmax_scale = 0.125f;
+    v8.q_descale = fake<float>(QD); v8.k_descale = fake<float>(KD);
+    v8.q_descale_batch_stride = v8.k_descale_batch_stride = 2; v8.q_descale_head_stride = v8.k_descale_head_stride = 1;
+    vote_dims(v8, 128, 300, 500);
+    const std::string e7 = "la_vote_margins_fp8";
+    run_case(e7 + ": NULL args -> LA_ERR_NULL_ARG", [&]() -> int64_t { return la_vote_margins_fp8(nullptr, STREAM); });
+    args_case(e7 + ": d128 with descales, dense walk", v8, la_vote_margins_fp8, keep);
+    args_case(e7 + ": d128 without descales, int32 list", v8, la_vote_margins_fp8, [](V8& a) { a.q_descale = a.k_descale = nullptr; a.read_list = fake<void>(RL); });
+    args_case(e7 + ": d128 int16 list -> list_int16 1", v8, la_vote_margins_fp8, [](V8& a) { a.read_list = fake<void>(RL); a.flags = LA_FLAG_LIST_INT16; });
+    for (int d : {64, 96, 192, 256})
+        args_case(e7 + ": d" + std::to_string(d) + ", dense walk", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, d, 300, 500); });
+    args_case(e7 + ": LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW and unknown bits are not read -> passes", v8, la_vote_margins_fp8, [](V8& a) { a.flags = LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | 256u; });
+    args_case(e7 + ": reserved0 1 (not read) -> passes", v8, la_vote_margins_fp8, [](V8& a) { a.reserved0 = 1; });
+    args_case(e7 + ": the launch fails -> LA_ERR_LAUNCH", v8, la_vote_margins_fp8, keep, fail);
+    args_case(e7 + ": struct_size 0 -> LA_ERR_STRUCT_SIZE", v8, la_vote_margins_fp8, [](V8& a) { a.struct_size = 0; });
+    args_case(e7 + ": la_vote_margins' struct_size and q NULL -> LA_ERR_STRUCT_SIZE first", v8, la_vote_margins_fp8, [](V8& a) { a.struct_size = sizeof(la_vote_margins_args); a.q = nullptr; });
+    args_case(e7 + ": q NULL -> LA_ERR_NULL_ARG", v8, la_vote_margins_fp8, [](V8& a) { a.q = nullptr; });
+    args_case(e7 + ": k NULL -> LA_ERR_NULL_ARG", v8, la_vote_margins_fp8, [](V8& a) { a.k = nullptr; });
+    args_case(e7 + ": margins NULL and batch 0 -> LA_ERR_NULL_ARG first", v8, la_vote_margins_fp8, [](V8& a) { a.margins = nullptr; a.batch = 0; });
+    args_case(e7 + ": seqlen_q 0 -> LA_ERR_SHAPE", v8, la_vote_margins_fp8, [](V8& a) { a.seqlen_q = 0; });
+    args_case(e7 + ": 4 heads on 3 K heads -> LA_ERR_SHAPE", v8, la_vote_margins_fp8, [](V8& a) { a.num_heads_k = 3; });
+    args_case(e7 + ": 4 heads on 3 K heads and head_dim 80 -> LA_ERR_SHAPE first", v8, la_vote_margins_fp8, [](V8& a) { a.num_heads_k = 3; a.head_dim = 80; });
+    args_case(e7 + ": head_dim 80 -> LA_ERR_HEAD_DIM", v8, la_vote_margins_fp8, [](V8& a) { a.head_dim = 80; });
+    args_case(e7 + ": head_dim 80 and k + 8 bytes -> LA_ERR_HEAD_DIM first", v8, la_vote_margins_fp8, [](V8& a) { a.head_dim = 80; a.k = fake<void>(K + 8); });
+    args_case(e7 + ": k + 8 bytes -> LA_ERR_STRIDE (16-byte rows)", v8, la_vote_margins_fp8, [](V8& a) { a.k = fake<void>(K + 8); });
+    args_case(e7 + ": q_row_stride + 8 -> LA_ERR_STRIDE (16-byte rows)", v8, la_vote_margins_fp8, [](V8& a) { a.q_row_stride += 8; });
+    args_case(e7 + ": q_row_stride + 16 -> passes", v8, la_vote_margins_fp8, [](V8& a) { a.q_row_stride += 16; });
+    args_case(e7 + ": k_head_stride negative -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.k_head_stride = -128; });
+    args_case(e7 + ": margins + 2 bytes -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.margins = fake<float>(MARG + 2); });
+    args_case(e7 + ": int32 read_list + 2 bytes -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.read_list = fake<void>(RL + 2); });
+    args_case(e7 + ": int16 read_list + 2 bytes -> passes", v8, la_vote_margins_fp8, [](V8& a) { a.read_list = fake<void>(RL + 2); a.flags = LA_FLAG_LIST_INT16; });
+    args_case(e7 + ": int16 read_list + 1 byte -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.read_list = fake<void>(RL + 1); a.flags = LA_FLAG_LIST_INT16; });
+    args_case(e7 + ": q_descale + 2 bytes -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.q_descale = fake<float>(QD + 2); });
+    args_case(e7 + ": k_descale + 2 bytes -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.k_descale = fake<float>(KD + 2); });
+    args_case(e7 + ": q_descale_head_stride -1 -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.q_descale_head_stride = -1; });
+    args_case(e7 + ": k_descale_batch_stride -2 -> LA_ERR_STRIDE", v8, la_vote_margins_fp8, [](V8& a) { a.k_descale_batch_stride = -2; });
+    args_case(e7 + ": k_descale_batch_stride -2 and 40000 key tiles -> LA_ERR_STRIDE first", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 128, 300, 40000 * 64); a.k_descale_batch_stride = -2; });
+    args_case(e7 + ": d128 int16 list, 32767 key tiles -> LA_ERR_SEQLEN (row too long)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 128, 300, 32767 * 64); a.flags = LA_FLAG_LIST_INT16; a.read_list = fake<void>(RL); });
+    args_case(e7 + ": d128 int16 list, 32766 key tiles -> passes", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 128, 300, 32766 * 64); a.flags = LA_FLAG_LIST_INT16; a.read_list = fake<void>(RL); });
+    args_case(e7 + ": d128 int32 list, 32767 key tiles -> passes", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 128, 300, 32767 * 64); a.read_list = fake<void>(RL); });
+    args_case(e7 + ": d64, 36124 key tiles -> passes (the walk storage is full)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 64, 300, 36124 * 64); });
+    args_case(e7 + ": d64, 36125 key tiles -> LA_ERR_SEQLEN (walk storage)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 64, 300, 36125 * 64); });
+    args_case(e7 + ": d128, 34196 key tiles -> passes (the walk storage is full)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 128, 300, 34196 * 64); });
+    args_case(e7 + ": d128, 34197 key tiles -> LA_ERR_SEQLEN (walk storage)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 128, 300, 34197 * 64); });
+    args_case(e7 + ": d256, 30340 key tiles -> passes (the walk storage is full)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 256, 300, 30340 * 64); });
+    args_case(e7 + ": d256, 30341 key tiles -> LA_ERR_SEQLEN (walk storage)", v8, la_vote_margins_fp8, [&](V8& a) { vote_dims(a, 256, 300, 30341 * 64); });
+    args_case(e7 + ": 40000 key tiles and 65536 x 32768 q-tiles -> LA_ERR_SEQLEN first", v8, la_vote_margins_fp8, [&](V8& a) { a.batch = 65536; a.num_heads = 32768; vote_dims(a, 128, 256, 40000 * 64); });
+    args_case(e7 + ": 65536 x 32768 q-tiles -> LA_ERR_SHAPE", v8, la_vote_margins_fp8, [&](V8& a) { a.batch = 65536; a.num_heads = 32768; vote_dims(a, 128, 256, 500); });
+    args_case(e7 + ": d256: 65536 x 16384 rows of 256 (2 q-tiles each) -> LA_ERR_SHAPE", v8, la_vote_margins_fp8, [&](V8& a) { a.batch = 65536; a.num_heads = 16384; vote_dims(a, 256, 256, 500); });
 }
 
 // ---- --time N: host nanoseconds of one la_fwd call on the one-launch listed cases ------------------------------------------------------
@@ -1049,6 +1550,7 @@ int main(int argc, char** argv) {
     cases_launch_shapes();
     cases_split();
     cases_other_entry_points();
+    cases_maps_rotations_margins();
     printf("],\n\"legend\":{");
     bool first = true;
     for (const auto& [name, fields] : g_legend) {
