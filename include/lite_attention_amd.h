@@ -412,6 +412,31 @@ typedef struct la_vote_margins_args {
 } la_vote_margins_args;
 int la_vote_margins(const la_vote_margins_args* args, void* stream);
 
+/* The softmax MASS of every key tile a walk visits, in one pass over Q K^T (added under ABI 9: a host detects it by symbol). For query
+ * row i and walked tile n,
+ *   mass_i[n] = sum over the keys j of tile n of exp2(s_ij * c - lse_i * log2 e),   c = softmax_scale * log2 e
+ * is the share of row i's softmax that the tile carries under the normaliser `lse` names. If the tiles a sparse call drops hold mass
+ * delta of a row, its output moves by at most 2 delta max|V| (O = (1 - delta) A + delta B with A, B convex combinations of rows of V,
+ * and the sparse result is A): this map, beside the margins, turns a mass budget into a vote threshold without a forward call per
+ * probe. Per (q-tile, walked tile) it writes
+ *   mass_max[n]  = max over the q-tile's rows of mass_i[n]
+ *   mass_mean[n] = (sum over the q-tile's rows of mass_i[n]) / rows,   rows = min(block_m, Sq - m_block * block_m)
+ * and, when args->margins is given, la_vote_margins' margins of the same walk: the same bits, from the same scores.
+ *   args: la_vote_margins_args with everything it means for la_vote_margins (operands, flags and q-tile, read_list and its clamps, the
+ *     padded-row and masked-key conventions), except that args->margins may be NULL.
+ *   lse: fp32 [B, H, Sq] contiguous - la_fwd's LSE layout, natural log - of the launch whose probabilities are wanted. A row whose lse
+ *     is not finite (la_fwd's -inf of an empty row included) and the rows of the last q-tile at or past Sq contribute exactly 0 to both
+ *     outputs; keys at or past Sk contribute 0.
+ *   mass_max, mass_mean: fp32 [B, H, Qt, Kt] contiguous; either may be NULL. EVERY element of every output given is written: NaN for
+ *     every tile the walk does not visit. The FIRST tile walked has a mass; it is NaN in margins only.
+ * One workgroup per (batch, head, q-tile), one v_exp_f32 per score, no workspace, no atomics on global memory and a fixed order of every
+ * sum: two launches give bit-identical output. e4m3 operands are not served (la_vote_margins_fp8 is the only e4m3 map). Asynchronous on
+ * `stream`.
+ * Errors (all before any HIP call): every check of la_vote_margins in its order with its codes, except that a NULL args->margins passes;
+ * then NULL lse, or margins, mass_max and mass_mean all NULL, LA_ERR_NULL_ARG; lse, mass_max or mass_mean off 4 bytes LA_ERR_STRIDE;
+ * more key tiles than the walk storage holds beside the parts of three outputs (64 bytes fewer than la_vote_margins has) LA_ERR_SEQLEN. */
+int la_tile_mass(const la_vote_margins_args* args, const float* lse, float* mass_max, float* mass_mean, void* stream);
+
 /* The same map for the e4m3 forward (added under ABI 9: a host detects it by symbol): q and k are the LA_DTYPE_FP8_E4M3 operands la_fwd
  * is given, with the descales la_fwd is given, and no 16-bit copy of either is made. The e4m3 la_fwd takes its vote on the fp32
  * accumulators of the block-scaled fp8 MFMA at unit block scales, with the descales folded into the score scale:

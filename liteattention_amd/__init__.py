@@ -24,6 +24,7 @@ if not _BUILDING:
     from .calibration import (ErrorStats, calibrate_error_schedule, calibrate_head_thresholds, calibrate_threshold,  # noqa: E402
                               output_error)
     from .calibration import threshold_for_skip, vote_margins, vote_margins_reference  # noqa: E402
+    from .calibration import TileMass, calibrate_mass_schedule, threshold_for_mass, tile_mass, tile_mass_reference  # noqa: E402
     from .qk_prep import RopeTables, qk_prep, qk_prep_reference, rope_tables, wan_rope_parts  # noqa: E402
     from .qk_prep import HeadRotation, head_rotation  # noqa: E402
     from .qk_prep import E4m3Scales, descale_from_amax, qk_prep_amax, qk_prep_fp8, qk_prep_fp8_reference  # noqa: E402
@@ -42,6 +43,7 @@ __all__ = ["LiteAttention", "SeqParallelLiteAttention", "flash_attn_func", "flas
            "flash_blocksparse_attn_func", "flash_blocksparse_attn_qkvpacked_func", "blockmask_to_skip_lists", "calibrate_threshold",
            "calibrate_error_schedule", "output_error", "ErrorStats", "skip_list_stats_heads", "calibrate_head_thresholds",
            "vote_margins", "vote_margins_reference", "threshold_for_skip",
+           "tile_mass", "tile_mass_reference", "threshold_for_mass", "calibrate_mass_schedule", "TileMass",
            "qk_prep", "qk_prep_reference", "rope_tables", "wan_rope_parts", "RopeTables", "head_rotation", "HeadRotation",
            "qk_prep_fp8", "qk_prep_amax", "descale_from_amax", "qk_prep_fp8_reference", "E4m3Scales",
            "qk_prep_smooth", "qk_prep_colmean", "colsum_finish", "qk_prep_smooth_parts", "qk_prep_smooth_reference", "lse_unshift", "SmoothedQK",

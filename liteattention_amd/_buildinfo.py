@@ -13,7 +13,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 PUBLIC_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "lite_attention_amd.h")
 SOURCES = ["la_fwd_kernel_v2.hip", "la_fwd_kernel_x64.hip", "la_prep_fp8.hip", "la_fwd_kernel_x64_fp8.hip", "la_aux_kernels.hip",
            "la_prep_qk.hip", "la_prep_qk_rot.hip", "la_prep_v.hip", "la_vote_margins.hip", "la_vote_margins_fp8.hip",
-           "la_api.hip"]
+           "la_tile_mass.hip", "la_api.hip"]
 # What a source is compiled with beside the common flags. The rotated prologue is built without the packed fp32 forms (v_pk_add / mul /
 # fma_f32): its butterflies gain nothing from them, and without them the compiler needs fewer registers - the headline form,
 # token_kernel<bf16, e4m3, NCH 10, mode 1>, 279 -> 227 VGPRs, one wave per SIMD -> two (profiles/qk_rotate.md has the times of both

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = (
     "la_qk_prep_rows", "la_qk_prep_fp8_rows", "la_qk_prep_smooth_rows", "la_attn_unshift_fp8",
     "la_qk_prep_rot", "la_qk_prep_fp8_rot", "la_qk_prep_smooth_rot",
     "la_v_colstats_rows", "la_v_prep_tiles_rows", "la_attn_unshift_rows", "la_attn_unshift_fp8_rows",
-    "la_vote_margins", "la_vote_margins_fp8",
+    "la_vote_margins", "la_vote_margins_fp8", "la_tile_mass",
 )
 (LA_STAT_ABS_DIFF, LA_STAT_ABS_REF, LA_STAT_SQ_DIFF, LA_STAT_SQ_REF, LA_STAT_MAX_ABS_DIFF, LA_STAT_NONFINITE) = range(6)    # la_error_stat
 LA_STAT_COUNT = 6
@@ -359,6 +359,8 @@ def load() -> ctypes.CDLL:
     lib.la_vote_margins.restype = ctypes.c_int
     lib.la_vote_margins_fp8.argtypes = [ctypes.POINTER(LaVoteMarginsFp8Args), ctypes.c_void_p]
     lib.la_vote_margins_fp8.restype = ctypes.c_int
+    lib.la_tile_mass.argtypes = [ctypes.POINTER(LaVoteMarginsArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.la_tile_mass.restype = ctypes.c_int
     for fn in (lib.la_v_tiles_bytes, lib.la_v_tiles_workspace_bytes):
         fn.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
         fn.restype = ctypes.c_int64

@@ -8,7 +8,7 @@ with the error measured on the device by ``output_error`` (C-ABI ``la_output_err
 from __future__ import annotations
 
 import ctypes
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -578,4 +578,209 @@ def calibrate_skip_schedule(qkv_at, n_steps: int, targets: Sequence[float], per_
             walked, kept, skip = float(walked[0]), float(kept.sum()), 0.0 if skip_heads is None else float(skip_heads.mean())
         thresholds.append(thr)
         trace.append(dict(threshold=thr, target=float(targets[t]), skip_fraction=skip, walked=walked, kept=kept))
+    return (torch.stack(thresholds) if per_head else thresholds), trace
+
+
+# ---- tile mass: the softmax mass of every walked key tile, and the threshold of a mass budget ----------------------------------
+class TileMass(NamedTuple):
+    """What ``tile_mass`` returns: fp32 ``(B, H, Qt, Kt)`` each (fp64 from ``tile_mass_reference``); ``margins`` is None unless asked."""
+    mass_max: torch.Tensor
+    mass_mean: torch.Tensor
+    margins: Optional[torch.Tensor] = None
+
+
+def _lse_bhs(lse: torch.Tensor, B: int, H: int, Sq: int) -> torch.Tensor:
+    """``lse`` as ``(B, H, Sq)``: given so, or as the ``(B, Sq, H)`` view of it."""
+    if tuple(lse.shape) == (B, H, Sq):
+        return lse
+    if tuple(lse.shape) == (B, Sq, H):
+        return lse.transpose(1, 2)
+    raise ValueError(f"lse must be ({B}, {H}, {Sq}) or its ({B}, {Sq}, {H}) view, got {tuple(lse.shape)}")
+
+
+def tile_mass(q: torch.Tensor, k: torch.Tensor, lse: torch.Tensor, softmax_scale: Optional[float] = None,
+              read_list: Optional[torch.Tensor] = None, flags: Optional[int] = None, *, margins: bool = False,
+              out: Optional[TileMass] = None) -> TileMass:
+    """The share of a query row's softmax that every key tile of a walk carries, reduced over the rows of a q-tile: ``mass_max``
+    (the largest of a row) and ``mass_mean`` (the mean over the q-tile's rows), fp32 ``(B, H, Qt, Kt)`` each, from one launch of
+    ``la_tile_mass`` (contract in include/lite_attention_amd.h). ``lse``: fp32 ``(B, H, Sq)``, or the ``(B, Sq, H)`` view of it, the
+    natural-log LSE of the attention call whose probabilities are meant (``return_softmax_lse=True``); rows whose lse is not finite
+    count as 0. ``margins=True``: the same launch also writes ``vote_margins`` of the same arguments, bit for bit. Every tile the walk
+    does not visit is NaN in all outputs; the first walked tile has a mass and is NaN in the margins only. If the tiles dropped from
+    a row hold mass delta, its output moves by at most ``2 delta max|V|``. ``q``, ``k``, ``softmax_scale``, ``read_list`` and ``flags``
+    as ``vote_margins`` takes them; bf16 and fp16 only (e4m3 operands have ``vote_margins`` alone). ``out``: a ``TileMass`` of
+    contiguous fp32 tensors to write into. Asynchronous on the current stream."""
+    if q.dim() != 4 or k.dim() != 4 or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3]:
+        raise ValueError(f"q (B, Sq, H, D) and k (B, Sk, Hk, D) of one batch and head dim, got {tuple(q.shape)} and {tuple(k.shape)}")
+    if not (q.is_cuda and k.device == q.device and lse.device == q.device):
+        raise ValueError("q, k and lse must live on the same GPU (there is no CPU path; tile_mass_reference is the plain form)")
+    if q.dtype not in _MARGIN_DTYPES or k.dtype != q.dtype:
+        raise TypeError(f"bf16 or fp16 operands of one dtype, got {q.dtype} and {k.dtype}")
+    if q.stride(-1) != 1 or k.stride(-1) != 1:
+        raise ValueError("the last dimension must be contiguous")
+    B, Sq, H, D = q.shape
+    Sk, Hk = k.shape[1], k.shape[2]
+    if D not in MARGIN_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {MARGIN_HEAD_DIMS}, got {D}")
+    if min(B, Sq, Sk, Hk) < 1 or H % Hk != 0:
+        raise ValueError(f"sizes must be positive and the heads of k must divide those of q, got {tuple(q.shape)} and {tuple(k.shape)}")
+    if lse.dtype != torch.float32:
+        raise TypeError(f"lse must be fp32, got {lse.dtype}")
+    lse = _lse_bhs(lse, B, H, Sq).contiguous()
+    f = (_cabi.default_flags() if flags is None else int(flags)) & _cabi.GEOMETRY_FLAGS
+    bm, bn = _cabi.get_tile_sizes(D, 2, f)
+    qt, kt = _cdiv(Sq, bm), _cdiv(Sk, bn)
+    if read_list is not None:
+        _check_margin_list(read_list, q, qt, kt)
+        if read_list.dtype == torch.int16:
+            f |= _cabi.LA_FLAG_LIST_INT16
+    if out is None:
+        maps = [torch.empty(B, H, qt, kt, dtype=torch.float32, device=q.device) for _ in range(3 if margins else 2)]
+        out = TileMass(*maps)
+    for t in (out.mass_max, out.mass_mean) + ((out.margins,) if margins else ()):
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != (B, H, qt, kt) or not t.is_contiguous() or t.device != q.device:
+            raise ValueError(f"out must hold contiguous fp32 ({B}, {H}, {qt}, {kt}) tensors on the device of q")
+    a = _cabi.LaVoteMarginsArgs()
+    a.struct_size, a.dtype = ctypes.sizeof(_cabi.LaVoteMarginsArgs), _MARGIN_DTYPES[q.dtype]
+    a.q, a.k = q.data_ptr(), k.data_ptr()
+    a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
+    a.k_batch_stride, a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1), k.stride(2)
+    a.batch, a.seqlen_q, a.seqlen_k, a.num_heads, a.num_heads_k, a.head_dim = B, Sq, Sk, H, Hk, D
+    a.softmax_scale = D ** -0.5 if softmax_scale is None else float(softmax_scale)
+    a.flags = f
+    a.read_list = None if read_list is None else read_list.data_ptr()
+    a.margins = out.margins.data_ptr() if margins else None
+    with torch.cuda.device(q.device):
+        rc = _cabi.load().la_tile_mass(ctypes.byref(a), lse.data_ptr(), out.mass_max.data_ptr(), out.mass_mean.data_ptr(),
+                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != _cabi.LA_OK:
+        raise RuntimeError(f"la_tile_mass: {_cabi.status_string(rc)}")
+    return out if margins else TileMass(out.mass_max, out.mass_mean, None)
+
+
+def tile_mass_reference(q: torch.Tensor, k: torch.Tensor, lse: torch.Tensor, softmax_scale: Optional[float] = None,
+                        read_list: Optional[torch.Tensor] = None, block_m: int = 256, block_n: int = 64, *,
+                        margins: bool = False) -> TileMass:
+    """``tile_mass`` written plainly in fp64 torch, on any device (``block_m`` / ``block_n`` in the place of ``flags``, as
+    ``vote_margins_reference`` has them): ``p = exp(s softmax_scale - lse)`` for all rows against all keys, summed per (row, key
+    tile), then the maximum and the mean over each q-tile's rows. Rows at or past Sq and rows whose lse is not finite count as 0 (the
+    mean divides by the rows the q-tile has), keys at or past Sk are -inf; tiles the walk of the q-tile's list row does not visit are
+    NaN."""
+    B, Sq, H, D = q.shape
+    Sk, Hk = k.shape[1], k.shape[2]
+    qt, kt = _cdiv(Sq, block_m), _cdiv(Sk, block_n)
+    scale = D ** -0.5 if softmax_scale is None else float(softmax_scale)
+    k64 = k.to(torch.float64).repeat_interleave(H // Hk, dim=2)
+    s = torch.full((B, H, qt * block_m, kt * block_n), float("-inf"), dtype=torch.float64, device=q.device)
+    s[:, :, :Sq, :Sk] = torch.einsum("bqhd,bkhd->bhqk", q.to(torch.float64), k64) * scale
+    l64 = torch.full((B, H, qt * block_m), float("inf"), dtype=torch.float64, device=q.device)
+    given = _lse_bhs(lse, B, H, Sq).to(torch.float64)
+    l64[:, :, :Sq] = torch.where(torch.isfinite(given), given, torch.full_like(given, float("inf")))
+    mass = torch.exp(s - l64[..., None]).view(B, H, qt, block_m, kt, block_n).sum(dim=-1)          # (B, H, Qt, rows, Kt)
+    rows = torch.tensor([min(block_m, Sq - m * block_m) for m in range(qt)], dtype=torch.float64, device=q.device)
+    mass_max, mass_mean = mass.amax(dim=3), mass.sum(dim=3) / rows[:, None]
+    walked = torch.ones(B, H, qt, kt, dtype=torch.bool)
+    if read_list is not None:
+        lists = read_list[:B].cpu().tolist()
+        walked = torch.zeros(B, H, qt, kt, dtype=torch.bool)
+        for b in range(B):
+            for h in range(H):
+                for m in range(qt):
+                    walked[b, h, m, _walk_of_row(lists[b][h][m], kt)] = True
+    nan = torch.full_like(mass_max, float("nan"))
+    walked = walked.to(q.device)
+    ref = vote_margins_reference(q, k, softmax_scale, read_list, block_m, block_n) if margins else None
+    return TileMass(torch.where(walked, mass_max, nan), torch.where(walked, mass_mean, nan), ref)
+
+
+def _group(x: torch.Tensor, per_head: bool) -> torch.Tensor:
+    """``(B, H, ...)`` -> ``(G, N)``: one group per head over the batch, or one group of everything."""
+    return x.transpose(0, 1).reshape(x.shape[1], -1) if per_head else x.reshape(1, -1)
+
+
+def _dropped_mass(margins: torch.Tensor, mass: torch.Tensor, thr: torch.Tensor, reduce: str, per_head: bool) -> torch.Tensor:
+    """``(G,)`` fp64: the mass of the dropped set {finite margin <= thr} as ``threshold_for_mass`` counts it - the worst q-tile's sum
+    (``max``) or the mean over the q-tiles of their sums (``mean``)."""
+    t = thr.reshape(1, -1, 1, 1) if per_head else thr.reshape(1, 1, 1, 1)
+    per_tile = torch.where(torch.isfinite(margins) & (margins <= t), mass.double(), torch.zeros_like(mass, dtype=torch.float64)).sum(dim=-1)
+    return _group(per_tile, per_head).amax(dim=-1) if reduce == "max" else _group(per_tile, per_head).mean(dim=-1)
+
+
+def threshold_for_mass(margins: torch.Tensor, mass: torch.Tensor, budget: float, reduce: str = "max", per_head: bool = False,
+                       hi: float = -1e-3):
+    """The largest threshold whose dropped set - the tiles with a finite ``margin <= thr`` - stays inside a mass ``budget``, from
+    the two maps of one ``tile_mass(..., margins=True)`` pass: no forward call, no bisection, no host synchronisation.
+    ``reduce="max"`` with ``mass = mass_max``: for EVERY q-tile the ``mass_max`` of its dropped tiles sums to at most ``budget`` - a
+    bound on the dropped mass of every row (a sum of maxima is at least the maximum of the sums), hence ``|O' - O| <= 2 budget
+    max|V|`` for every row. ``reduce="mean"`` with ``mass = mass_mean``: the mean over the q-tiles of the summed ``mass_mean`` of
+    their dropped tiles is at most ``budget``. The value is the MIDPOINT between the last margin dropped and the first one kept, as
+    ``threshold_for_skip`` returns it, capped at ``hi``. ``per_head``: an fp32 ``(H,)`` device tensor, one threshold per head over
+    the batch; else one float. The forward's list writer also KEEPS the dropped tile that closes a range (its inclusive end), so the
+    forward drops a subset of the set priced here: the budget is conservative."""
+    if reduce not in ("max", "mean"):
+        raise ValueError("reduce: max or mean")
+    if margins.dim() != 4 or mass.shape != margins.shape:
+        raise ValueError(f"margins and mass must be (B, H, Qt, Kt) of one shape, got {tuple(margins.shape)} and {tuple(mass.shape)}")
+    if budget < 0 or hi >= 0:
+        raise ValueError("budget must not be negative and hi must be negative")
+    fin = torch.isfinite(margins)
+    m = torch.where(fin, margins, torch.full_like(margins, float("inf")))
+    w = torch.where(fin, mass.double(), torch.zeros_like(mass, dtype=torch.float64))
+    srt, n = _sorted_margins(margins, per_head)
+    inf = torch.full((1,), float("inf"), dtype=srt.dtype, device=srt.device)
+    if reduce == "max":
+        row_m, order = m.sort(dim=-1)                                      # per q-tile: its tiles in the order a rising threshold drops them
+        over = (w.gather(-1, order).cumsum(dim=-1) > budget) & torch.isfinite(row_m)
+        limit = _group(torch.where(over, row_m, inf).amin(dim=-1), per_head).amin(dim=-1)          # the first margin that breaks a q-tile's budget
+    else:
+        grp_m, order = _group(m, per_head).sort(dim=-1)
+        q_tiles = margins[..., 0].numel() // srt.shape[0]
+        fits = (_group(w, per_head).gather(-1, order).cumsum(dim=-1) / q_tiles <= budget) & torch.isfinite(grp_m)
+        k0 = fits.sum(dim=-1, keepdim=True)
+        limit = torch.where(k0 < n.unsqueeze(-1), grp_m.gather(-1, k0.clamp(max=grp_m.shape[-1] - 1)), inf).squeeze(-1)
+    k = torch.searchsorted(srt, limit.unsqueeze(-1).contiguous(), right=False).squeeze(-1)       # margins strictly below the limit: ties drop together
+    thr = _threshold_at_count(srt, n, torch.minimum(k, n)).clamp(max=hi)
+    return thr if per_head else float(thr[0])
+
+
+def calibrate_mass_schedule(qkv_at, n_steps: int, budgets: Sequence[float], reduce: str = "max", per_head: bool = False,
+                            hi: float = -1e-3, max_batch_size: int = 1, list_dtype: Optional[torch.dtype] = None):
+    """A threshold per step - per (step, head) with ``per_head`` - under a MASS budget per step, without bisection. Step t: one
+    forward call over the list the step reads, for its LSE (a threshold does not touch the output or the LSE of its own call, only
+    the list it writes; that list is discarded by restoring the snapshot taken before); one ``tile_mass(..., margins=True)`` pass
+    under the same list; ``threshold_for_mass`` of ``budgets[t]``; and the committed forward call at that threshold, which writes the
+    list step t + 1 reads. Two forward calls and one map pass per step, against the 2 ``iters`` + 1 forward calls per step of
+    ``calibrate_error_schedule``, and a bound instead of a probe: with ``reduce="max"`` every row of step t loses at most
+    ``budgets[t]`` of the softmax mass step t computed, so its output moves by at most ``2 budgets[t] max|V|`` against that.
+    ``budgets[t]`` is INCREMENTAL: relative to what step t computed over the list it read, not to the dense softmax; a cumulative
+    audit against the dense result is not made here (``calibrate_error_schedule`` measures one).
+
+    Returns ``(thresholds, trace)``: a list of floats for ``set_threshold_schedule``, or an fp32 ``(n_steps, H)`` device tensor for
+    ``set_head_thresholds``. ``trace[t]``: ``threshold``, ``budget``, ``predicted_mass`` (the mass of the dropped set as
+    ``threshold_for_mass`` counts it) and ``skip_fraction`` (of the list step t read); floats, or ``(H,)`` device tensors with
+    ``per_head``, which never synchronises."""
+    if len(budgets) != n_steps:
+        raise ValueError(f"one budget per step: got {len(budgets)} for {n_steps} steps")
+    att = LiteAttention(threshold=-1.0, max_batch_size=max_batch_size, list_dtype=list_dtype)
+    thresholds, trace = [], []
+    for t in range(n_steps):
+        q, k, v = qkv_at(t)
+        skip_heads = att.get_skip_fraction_heads(q.shape[0])
+        snap = att.snapshot()
+        _, lse = att(q, k, v, return_softmax_lse=True)
+        att.restore(snap)
+        maps = att.tile_mass(q, k, lse, margins=True)
+        mass = maps.mass_max if reduce == "max" else maps.mass_mean
+        thr = threshold_for_mass(maps.margins, mass, float(budgets[t]), reduce, per_head, hi)
+        predicted = _dropped_mass(maps.margins, mass, torch.as_tensor(thr, dtype=torch.float32, device=q.device), reduce, per_head)
+        if per_head:
+            att.set_head_thresholds(thr)
+            skip = torch.zeros_like(thr) if skip_heads is None else skip_heads.mean(dim=0)
+        else:
+            predicted = float(predicted)
+            att.set_threshold(thr)
+            skip = 0.0 if skip_heads is None else float(skip_heads.mean())
+        att(q, k, v)
+        thresholds.append(thr)
+        trace.append(dict(threshold=thr, budget=float(budgets[t]), predicted_mass=predicted, skip_fraction=skip))
     return (torch.stack(thresholds) if per_head else thresholds), trace

@@ -875,11 +875,11 @@ static int v_prep_tiles_run(const la_v_prep_tiles_args* a, bool mapped, const la
 // parameter block they share. A: either argument struct (the same field names). ts: the q-tile of the lists la_fwd reads and writes for
 // these operands, and tile_rc what its lookup answered (behind the sizes, as the lookups were); unit: elements of 16 bytes - every row
 // of q and k starts on a 16-byte boundary; lds_bytes: the LDS of a workgroup for (head_dim, k_tiles); own_strides_ok: the strides and
-// alignments only one of the two has.
+// alignments only one of the two has; need_margins: false for la_tile_mass, whose margins are one output of three and may be NULL.
 template <class A>
 static int vote_margins_check_and_fill(const A* a, int tile_rc, la::TileShape ts, int64_t unit, size_t (*lds_bytes)(int, int), bool own_strides_ok,
-                                       la::VoteMarginsParams& p) {
-    if (!a->q || !a->k || !a->margins) return LA_ERR_NULL_ARG;
+                                       la::VoteMarginsParams& p, bool need_margins = true) {
+    if (!a->q || !a->k || (need_margins && !a->margins)) return LA_ERR_NULL_ARG;
     if (a->batch <= 0 || a->seqlen_q <= 0 || a->seqlen_k <= 0 || a->num_heads <= 0 || a->num_heads_k <= 0 || a->head_dim <= 0 ||
         a->num_heads % a->num_heads_k != 0) return LA_ERR_SHAPE;
     if (tile_rc != LA_OK) return tile_rc;
@@ -969,6 +969,22 @@ int la_vote_margins(const la_vote_margins_args* a, void* stream_) {
                                              &ts.block_m, &ts.block_n);
     la::VoteMarginsParams p;
     if (const int rc = vote_margins_check_and_fill(a, tile_rc, ts, 8, la::vote_margins_lds_bytes, true, p); rc != LA_OK) return rc;
+    return launch_status(la::launch_vote_margins(p, a->dtype, a->head_dim, static_cast<hipStream_t>(stream_)));
+}
+
+// ---- the softmax mass of every walked key tile, and on request the margins, in one pass (la_tile_mass.hip) ---------------------------
+int la_tile_mass(const la_vote_margins_args* a, const float* lse, float* mass_max, float* mass_mean, void* stream_) {
+    if (const int rc = args_status(a); rc != LA_OK) return rc;
+    if (a->dtype != LA_DTYPE_BF16 && a->dtype != LA_DTYPE_FP16) return LA_ERR_DTYPE;
+    la::TileShape ts = {0, 0};
+    const int tile_rc = la_get_tile_sizes_ex(a->head_dim, 2, a->flags & (LA_FLAG_HALF_VOTE | LA_FLAG_KERNEL_128ROW | LA_FLAG_LIST_INT16),
+                                             &ts.block_m, &ts.block_n);
+    la::VoteMarginsParams p;
+    if (const int rc = vote_margins_check_and_fill(a, tile_rc, ts, 8, la::vote_margins_lds_bytes, true, p, false); rc != LA_OK) return rc;
+    if (!lse || (!a->margins && !mass_max && !mass_mean)) return LA_ERR_NULL_ARG;
+    if ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(mass_max) | reinterpret_cast<uintptr_t>(mass_mean)) & 3u) return LA_ERR_STRIDE;
+    if (la::tile_mass_lds_bytes(a->head_dim, p.k_tiles) > la::kVoteMarginsLdsLimit) return LA_ERR_SEQLEN;      // 64 bytes more than the margins' walk
+    p.lse = lse; p.mass_max = mass_max; p.mass_mean = mass_mean;       // lse set: launch_vote_margins goes to la_tile_mass_kernel
     return launch_status(la::launch_vote_margins(p, a->dtype, a->head_dim, static_cast<hipStream_t>(stream_)));
 }
 

@@ -270,6 +270,10 @@ struct VoteMarginsParams {
     int q_tiles, k_tiles, block_m;                       // block_m: 256 or 128 rows of a q-tile; a key tile is 64 keys
     int list_int16;
     float scale_log2;            // softmax_scale * log2(e), rounded to fp32 once on the host
+    // la_tile_mass only (la_vote_margins leaves them NULL): lse set = the launch goes to la_tile_mass_kernel, and margins may be NULL
+    const float* lse = nullptr;  // [B, H, Sq] contiguous, natural log: the LSE of the launch whose probabilities are wanted
+    float* mass_max = nullptr;   // [B, H, q_tiles, k_tiles] contiguous, every element written; NULL = not wanted
+    float* mass_mean = nullptr;  // the same
 };
 // Dynamic LDS of one workgroup: two stages of 64 keys at a pitch of 2 D + 16 bytes, the four waves' part maxima of two tiles and the
 // tile count (64 bytes), the walk (one int per key tile) and two bitmaps over the key tiles (range ends for the list expansion, walked
@@ -280,6 +284,14 @@ inline size_t vote_margins_lds_bytes(int head_dim, int k_tiles) {
     return 2 * 64 * (static_cast<size_t>(head_dim) * 2 + 16) + 64 + 4 * seq_cap + 8 * words;
 }
 hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream);      // dtype: 0 bf16, 1 fp16
+// la_tile_mass (la_tile_mass.hip): the same ring and walk, with the four waves' parts of three outputs (margins, mass_max, mass_mean)
+// for two tile parities and the tile count in 128 bytes instead of 64; held against the same limit. launch_vote_margins forwards to
+// launch_tile_mass when p.lse is set.
+inline size_t tile_mass_lds_bytes(int head_dim, int k_tiles) {
+    const size_t seq_cap = (static_cast<size_t>(k_tiles) + 3) & ~static_cast<size_t>(3), words = (static_cast<size_t>(k_tiles) + 31) / 32;
+    return 2 * 64 * (static_cast<size_t>(head_dim) * 2 + 16) + 128 + 4 * seq_cap + 8 * words;
+}
+hipError_t launch_tile_mass(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream);
 
 // la_vote_margins_fp8 (la_vote_margins_fp8.hip): the same block for e4m3 q and k (strides in elements = bytes; block_m is the e4m3
 // forward's q-tile), and the descales the e4m3 forward folds into its score scale, per (batch, K/V head), NULL = 1.0.

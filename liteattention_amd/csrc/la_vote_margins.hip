@@ -192,6 +192,7 @@ hipError_t launch_dim(const VoteMarginsParams& p, int head_dim, hipStream_t stre
 }  // namespace
 
 hipError_t launch_vote_margins(const VoteMarginsParams& p, int dtype, int head_dim, hipStream_t stream) {
+    if (p.lse != nullptr) return launch_tile_mass(p, dtype, head_dim, stream);      // la_tile_mass: the kernel of la_tile_mass.hip
     (void)hipGetLastError();   // drop any stale sticky error of this thread: only OUR launch is reported
     return dtype == 1 ? launch_dim<true>(p, head_dim, stream) : launch_dim<false>(p, head_dim, stream);
 }

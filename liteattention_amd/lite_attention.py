@@ -476,6 +476,19 @@ class LiteAttention:
         ``q_descale`` / ``k_descale``: the fp32 ``(B, Hk)`` descales of ``float8_e4m3fn`` operands, as the forward call takes them.
         Reads the skip state and changes none of it: no list is written, no phase flipped, no step counted."""
         from .calibration import vote_margins
+        descales = {name: d for name, d in (("q_descale", q_descale), ("k_descale", k_descale)) if d is not None}
+        return vote_margins(query, key, scale, self._next_read_list(query, key), **descales)
+
+    def tile_mass(self, query: Tensor, key: Tensor, lse: Tensor, scale: Optional[float] = None, margins: bool = False):
+        """The softmax mass of every key tile (``calibration.tile_mass``: a ``TileMass`` of fp32 ``(B, H, Qt, Kt)`` maps, with the
+        margins of the same walk when asked) for the call that would come next on these operands, over the list, tile geometry and
+        list element type ``vote_margins`` takes. ``lse``: the LSE of that call, ``(B, H, S)`` as ``return_softmax_lse=True`` gives
+        it. bf16 and fp16 operands. Reads the skip state and changes none of it."""
+        from .calibration import tile_mass
+        return tile_mass(query, key, lse, scale, self._next_read_list(query, key), margins=margins)
+
+    def _next_read_list(self, query: Tensor, key: Tensor) -> Optional[Tensor]:
+        """The list the next call on these operands reads, None = every tile (``vote_margins`` says when)."""
         read_list = None
         shape_key = (query.shape[1], key.shape[1], query.shape[2], query.shape[3], query.dtype, query.device,
                      get_tile_sizes(query.shape[3], query.dtype.itemsize), self.list_dtype)
@@ -484,8 +497,7 @@ class LiteAttention:
             if query.shape[0] > read_list.shape[0]:        # sequences not tracked yet start from "all tiles listed"
                 fresh = self._init_skip_list(query, key, batch=query.shape[0] - read_list.shape[0])[0]
                 read_list = torch.cat([read_list, fresh])
-        descales = {name: d for name, d in (("q_descale", q_descale), ("k_descale", k_descale)) if d is not None}
-        return vote_margins(query, key, scale, read_list, **descales)
+        return read_list
 
     def snapshot(self) -> dict:
         """Both ping-pong lists, the phase and the step counter, copied ON THE DEVICE (no host round trip, no sync: ``state_dict()``
